@@ -1,14 +1,24 @@
 #!/usr/bin/env python
 """bench.py — images/sec of ResNet-50-FPN forward+backward at "1333x800" (zero-padded to 800x1344) on MI355X.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 is launched by the driver with torch.distributed.run (one rank per GPU, RCCL); this file reads
   RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment.
 One step = one pass of the hot path over one synthetic batch: stage image -> ResNet-50 -> FPN (5 levels)
 forward, backward from fixed cotangents g_l = randn_like(P_l)/numel(P_l) (the reference has no head / loss,
 SURVEY §8(d) C4), all parameter gradients (conv weights, BN gamma/beta, FPN biases), and for N > 1 the bucketed
 RCCL all-reduce of the 26.85 M gradients overlapped with backward.  Weak scaling: 2 images per GPU.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line; `ms_per_step` is the wall time of one of the K timed steps.
+
+A plain run sets up, runs W warm-up and K timed steps and prints the line.  --full adds the side measurements, each
+after the timed region: the dominant launch timed with HIP events (`roofline`), the same step with the weight
+repack inside the graph (`ms_per_step_with_repack`), the box ops (`secondary`) and the CPU oracle (`cpu_baseline`);
+--no-kernel-timer / --no-secondary / --no-cpu-baseline leave single ones out again.
+--dump-outputs DIR: after the timed steps, what the last one computed is written as DIR/<name>.npy in float32 —
+the FPN outputs P2..P6 (N, 256, H, W) and every parameter gradient (grad.backbone.<param>, grad.neck.<param>).
+An array with more elements than its cap (DUMP_CAP) is written as a fixed sample of its row-major flattening: the
+positions drawn without replacement by numpy.random.default_rng(0), in increasing order.  Weights, images and
+cotangents are seeded, so the same arguments give the same inputs and the same sample positions in every run.
 """
 import argparse
 import json
@@ -28,6 +38,24 @@ FWD_GFLOP = {50: 296.96, 101: 456.06}     # per image, SURVEY §8(d)
 FWDBWD_GFLOP = {50: 885.8, 101: 1363.1}   # 3*fwd - dgrad(conv1)
 MFMA_PEAK_TFLOPS = 2500.0          # bf16 dense, MI355X_MICROARCH.md
 DOM = dict(Cin=256, Cout=256, k=3, stride=1, H=200, W=336)   # neck.fpn_convs.0: 79.27 GFLOP / image
+DUMP_CAP = {"level": 1 << 20, "grad": 1 << 15}   # elements kept per FPN output / per parameter gradient
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes (name, tensor, cap) triples as out_dir/<name>.npy in float32: whole tensors up to `cap` elements, above
+    that the fixed sample described in the module docstring.  Refuses to write more than DUMP_MAX_BYTES in all."""
+    import numpy as np
+    total = 4 * sum(min(t.numel(), cap) for _, t, cap in arrays)
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t, cap in arrays:
+        t = t.detach()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().contiguous().cpu().numpy())
 
 
 def dominant_traffic():
@@ -317,15 +345,23 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"],
                     help="operand type; f16 + --depth 101 --batch-per-gpu 4 = SURVEY §8(d) config C5 "
                          "(cotangents x1024: static loss scale)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the box-op and repack side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements: dominant-kernel timer, repack step, "
+                         "box ops, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's FPN outputs and parameter gradients as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="with --full: skip the dominant-kernel timer")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the box-op and repack side measurements")
     ap.add_argument("--bucket-mb", type=int, default=32)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--force-reducer", action="store_true",
                     help="world size 1 only: run the N>1 code path (RCCL process group, bucketed reducer inside the "
                          "captured step) on a single GPU — a rehearsal of what --gpus N executes")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -383,8 +419,13 @@ def main():
     reducer = dp.attach_reducer([neck, backbone], bucket_bytes=args.bucket_mb << 20, dtype=cdtype) \
         if use_dist else None
     params = list(backbone.parameters()) + list(neck.parameters())
+    param_names = [("backbone", n) for n, _ in backbone.named_parameters()] + \
+        [("neck", n) for n, _ in neck.named_parameters()]
+    # what the timed path's last step computed: its outputs and gradients are the static tensors of the graph / launch
+    # plan once captured / prepared (each replay overwrites them), the newest eager step's otherwise
+    held = {}
 
-    def step():
+    def step(keep=None):
         if reducer is None:
             for p in params:
                 p.grad = None
@@ -392,6 +433,12 @@ def main():
         torch.autograd.backward(outs, cots)
         if reducer is not None:
             reducer.finish()
+        if keep is not None:
+            keep["outs"] = [o.detach() for o in outs]
+            keep["grads"] = [p.grad for p in params]
+
+    def main_step():
+        step(held)
 
     def sync():
         if world > 1:
@@ -405,9 +452,9 @@ def main():
     if not args.no_graph:
         from torch_detection_amd.graph import GraphedStep
         # headline: forward + backward with STATIC weights (the metric BASELINE.json names) — the packed 16-bit operands
-        # are derived once; config.weights_static says so and ms_per_step_with_repack (below) is the same step with
-        # the fold + pack launches of a real training step (weights change every iteration) inside the graph
-        gs = GraphedStep(step, params=params, repack=False)
+        # are derived once; config.weights_static says so and ms_per_step_with_repack (below, --full) is the same step
+        # with the fold + pack launches of a real training step (weights change every iteration) inside the graph
+        gs = GraphedStep(main_step, params=params, repack=False)
         ok = 1 if gs.captured else 0
         if use_dist:
             # every rank must run the same mode: a graph on some ranks and eager launches on others would still be
@@ -422,7 +469,7 @@ def main():
             graph = gs
             mode = "hipGraph replay (one captured fwd+bwd step; wgrad kernels on forked side streams%s)" % (
                 "; bucketed RCCL all-reduce nodes on a comm stream inside the graph" if use_dist else "")
-            if world == 1 and not args.no_secondary:
+            if args.full and world == 1 and not args.no_secondary:
                 rg = GraphedStep(step, params=params, repack=True)
                 repack_graph = rg if rg.captured else None
         else:
@@ -433,7 +480,7 @@ def main():
         # no hipGraph (refused, or --no-graph): the library's own executor — the launches of one recorded step,
         # enqueued again by one C call per step (torch_detection_amd.graph.PreparedStep, tdn_plan_* in include/tdn.h)
         from torch_detection_amd.graph import PreparedStep
-        ps = PreparedStep(step, params=params, repack=False)
+        ps = PreparedStep(main_step, params=params, repack=False)
         if ps.prepared:
             plan = ps
             mode = "launch plan replay (libtdn executor: %d launches, %d events per step, one C call)" % ps.stats()[:2]
@@ -449,11 +496,12 @@ def main():
         elif plan is not None:
             plan()
         else:
-            step()
+            main_step()
 
     for _ in range(args.warmup):
         run_step()
-    timer = None if (args.no_kernel_timer or graph is not None or plan is not None) else KernelTimer(ops, DOM)
+    timer = None if (not args.full or args.no_kernel_timer or graph is not None or plan is not None) \
+        else KernelTimer(ops, DOM)
     sync()
     t0 = time.perf_counter()
     if timer is not None:
@@ -467,8 +515,13 @@ def main():
             run_step()
         sync()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     [("P%d" % (i + 2), o, DUMP_CAP["level"]) for i, o in enumerate(held["outs"])] +
+                     [("grad.%s.%s" % (part, n), gr, DUMP_CAP["grad"])
+                      for (part, n), gr in zip(param_names, held["grads"]) if gr is not None])
     timed_in = "the timed region"
-    if (graph is not None or plan is not None) and not args.no_kernel_timer:
+    if args.full and (graph is not None or plan is not None) and not args.no_kernel_timer:
         # HIP events cannot be read back from inside a replayed graph: time the dominant launch in eager steps of
         # the same process / tensors right after the timed region (same kernel, same stream, full-step context)
         timer = KernelTimer(ops, DOM)
@@ -549,9 +602,9 @@ def main():
         # what torch.distributed reported after init (1 = no process group): lets the driver's N-rank check read the
         # world size the collectives actually ran over
         line["rccl_world"] = dist.get_world_size() if (use_dist and dist.is_initialized()) else 1
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             line["secondary"] = box_secondary(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.depth)
         print(json.dumps(line), flush=True)
     if use_dist:

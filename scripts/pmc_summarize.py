@@ -43,7 +43,7 @@ def weight(fam):
 WANT = sorted(agg, key=lambda f_: (not is_tagged(f_), -weight(f_)))[:14]
 
 print("# rocprofv3 --pmc passes (separate runs per counter group, kernel-trace only) of:")
-print("#   python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-graph   (scripts/pmc_bench.sh)")
+print("#   python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-graph   (scripts/pmc_bench.sh)")
 print("# one MI355X, R50-FPN fwd+bwd, 2 x 3x800x1344 per step. Values are per launch (mean over launches).")
 print("# The first entry is the dominant launch (3x3 256->256, M = 134400: neck.fpn_convs.0 forward and its dgrad):")
 print("# the launches bench.py brackets with HIP events run under their own symbol (TDN_TAG_DOMINANT).  Then every")
