@@ -125,3 +125,33 @@ def test_full_size_in_situ(T, depth, batch, dtype):
     for kind in ("dgrad", "dw", "dgamma", "dbeta_or_dbias"):
         assert b[kind][0] <= parity_util.BWD_IN_SITU_TOL, (kind, b[kind])
     assert b["launches"]["dgrad"] >= (52 if depth == 50 else 103) and b["launches"]["wgrad"] >= 61
+
+
+def test_full_size_schedule(T, monkeypatch):
+    """The routes the forward chooses for R50 at 2 x 3x800x1344 in training (functional.seq_schedule, kept on the
+    autograd node for its backward): layer1.0 a head block, layer1.1-1.2 and layer2.1-2.3 one-launch blocks whose saved
+    h1 carries their ReLU bit planes, every other block per-conv launches; per-image chains from the first block on,
+    the stem per image range.  TDN_BLOCK_FUSE=0: per-conv launches throughout.  A forward under no_grad keeps no bit
+    planes (nothing would read them)."""
+    from torch_detection_amd import functional as HF
+    rb, _ = _net(T, 50, torch.bfloat16)
+    x = det_tensor((2, 3, H, W), 700, -2, 2).cuda()
+    node = rb(x)[0].grad_fn
+    sch = node.schedule
+    assert sch.routes == [HF.HEAD] + [HF.BLOCK if i in (1, 2, 4, 5, 6) else HF.CONVS for i in range(1, 16)]
+    assert sch.bits == [r != HF.CONVS for r in sch.routes]
+    assert [hasattr(sv[1], "_tdn_bits") for sv in node.saved] == sch.bits
+    assert (sch.split, sch.cuts, sch.stem) == (0, [0, 1, 2], HF.STEM_SPLIT)
+    del node
+    monkeypatch.setenv("TDN_BLOCK_FUSE", "0")
+    assert rb(x)[0].grad_fn.schedule.routes == [HF.CONVS] * 16
+    monkeypatch.delenv("TDN_BLOCK_FUSE")
+    cap = {}
+    HF.DEBUG_CAPTURE = cap
+    try:
+        with torch.no_grad():
+            rb(x)
+    finally:
+        HF.DEBUG_CAPTURE = None
+    saved = cap["seq"][1]
+    assert len(saved) == 16 and not any(hasattr(sv[1], "_tdn_bits") for sv in saved)

@@ -1,6 +1,7 @@
 """The capture rule of torch_detection_amd/streams.py: inside a hipGraph capture two forked streams may not wait on
-each other (hipStreamEndCapture dies with SIGSEGV on such a capture, ROCm 7.2 — diagnosed in round 3 with the
-TDN_CHAIN_SYNC knob of functional._blocks_fwd_split); one-way waits and joins through the origin stream are fine.
+each other (hipStreamEndCapture dies with SIGSEGV on such a capture, ROCm 7.2 — diagnosed in round 3 with a
+since-removed diagnostic that cross-joined the per-image forward chains); one-way waits and joins through the origin
+stream are fine.
 The assertion turns the crash into a RuntimeError at the offending ``wait``."""
 import pytest
 import torch

@@ -26,6 +26,14 @@ from ..layers import conv1x1_group, conv3x3_group, conv7x7_group, norm_layer
 from ..registry import BACKBONES
 
 
+def _seq_apply(net, x):
+    """HF.SeqNetFunction over ``x``.  A backward pass follows when grad mode is on and the input or a parameter needs a
+    gradient: only then does the forward keep what the backward alone reads (the one-launch blocks' ReLU bit planes)."""
+    params = net.params()
+    want_bwd = torch.is_grad_enabled() and (getattr(x, 'requires_grad', False) or any(p.requires_grad for p in params))
+    return HF.SeqNetFunction.apply(net, x, want_bwd, *params)
+
+
 class _ResBlock(nn.Module):
     """Shared plumbing of BasicBlock / Bottleneck: parameter holders + the fused HIP schedule."""
     expansion = 1
@@ -47,7 +55,7 @@ class _ResBlock(nn.Module):
     def forward(self, x):
         with HF.batched_refresh():
             net = HF.SeqNet(None, [self.hip_spec(HF.pick_dtype(self, x))], [0])
-        return HF.SeqNetFunction.apply(net, x, *net.params())[0]
+        return _seq_apply(net, x)[0]
 
 
 class BasicBlock(_ResBlock):
@@ -196,7 +204,7 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         net = self.hip_net(HF.pick_dtype(self, x))
-        outs = HF.SeqNetFunction.apply(net, x, *net.params())
+        outs = _seq_apply(net, x)
         return outs[0] if len(outs) == 1 else tuple(outs)
 
     def train(self, mode=True):

@@ -93,7 +93,8 @@ class GradReducer(object):
         self.reset()
 
     def on_flush_point(self, n, nstages):
-        """functional.FLUSH_HOOKS: the backward pass has launched the weight-gradient groups of n of its nstages stages."""
+        """functional.FLUSH_HOOKS, called once at every stage boundary of a ResNet backward pass: it has launched the
+        weight-gradient groups of n of its nstages stages."""
         if not self.defer or self.launch_mode == 'finish':
             return
         at = int(self.launch_mode) if self.launch_mode.isdigit() else max(1, nstages - 1)
@@ -259,7 +260,7 @@ def attach_reducer(modules, bucket_bytes=32 << 20, group=None, average=True, dty
             for b_, ss_ in _pb:
                 _red.mark_ready_n(b_, len(ss_), stream, ss_)
         u.on_grads = _cb
-    # the backward schedule tells the reducer when a stage's weight-gradient groups have been launched (held weakly:
+    # the backward schedule tells the reducer when a stage's weight-gradient group has been launched (held weakly:
     # a dropped reducer drops out of the hook list)
     ref = weakref.ref(red)
 

@@ -812,15 +812,14 @@ class SeqNet(object):
         return ps
 
 
-def _block_fusable(b, C4):
-    """Stride-1 Bottleneck without a downsample branch, plain convs (+ folded eval-mode BN), ReLU activations, and a
-    one-launch kernel for its width in this build (csrc/conv_block.hip): conv1 -> conv2 -> conv3 + residual run as
-    ONE launch, forward (ops.bottleneck_fwd) and input-gradient chain (ops.bottleneck_dgrad).  TDN_BLOCK_FUSE=0
-    keeps the per-conv launches (A/B runs, and the reference side of tests/test_gpu_block.py)."""
-    knob = os.environ.get('TDN_BLOCK_FUSE', '1')     # 0: off; 1: every width the build has; 64 / 128: up to that width
-    if b.kind != 'bottleneck' or b.ud is not None or b.stride != 1 or knob == '0':
+def _block_fusable(b, C4, widest):
+    """Stride-1 Bottleneck without a downsample branch, plain convs (+ folded eval-mode BN), ReLU activations, at most
+    ``widest`` mid channels (None: any), and a one-launch kernel for its width in this build (csrc/conv_block.hip):
+    conv1 -> conv2 -> conv3 + residual run as ONE launch, forward (ops.bottleneck_fwd) and input-gradient chain
+    (ops.bottleneck_dgrad)."""
+    if b.kind != 'bottleneck' or b.ud is not None or b.stride != 1:
         return False
-    if knob not in ('', '1') and b.u1.Cout > int(knob):
+    if widest is not None and b.u1.Cout > widest:
         return False
     u1, u2, u3 = b.u1, b.u2, b.u3
     for u in (u1, u2, u3):
@@ -836,13 +835,10 @@ def _block_fusable(b, C4):
 def _block_head_fusable(b, Cin):
     """The stage's first Bottleneck where it keeps the resolution (layer1.0, resnet.py:130-136: a 1x1 conv + BN
     downsample because inplanes != 4 * planes): conv1 -> conv2 -> conv3 + residual run as one launch whose residual is
-    the downsample branch — computed inside the launch, forward and backward (default, TDN_BLOCK_HEAD=2; 2f: forward
-    only) or by a launch of its own (TDN_BLOCK_HEAD=1): ops.bottleneck_head_fwd / _dgrad.  TDN_BLOCK_HEAD=0 (or
-    TDN_BLOCK_FUSE=0) keeps the per-conv launches.  One box, interleaved: 0 -> 510.7, 1 -> 518.1, 2f -> 520.0,
-    2 -> 523.9 img/s."""
+    the downsample branch, computed inside the launch, forward and backward: ops.bottleneck_head_fwd / _dgrad.  One box,
+    interleaved: per-conv launches 510.7, downsample conv and its dgrad as launches of their own 518.1, downsample inside
+    the forward launch only 520.0, inside both 523.9 img/s."""
     if b.kind != 'bottleneck' or b.ud is None or b.stride != 1:
-        return False
-    if os.environ.get('TDN_BLOCK_FUSE', '1') == '0' or os.environ.get('TDN_BLOCK_HEAD', '1') == '0':
         return False
     u1, u2, u3, ud = b.u1, b.u2, b.u3, b.ud
     for u in (u1, u2, u3, ud):
@@ -855,346 +851,323 @@ def _block_head_fusable(b, Cin):
     return ops.bottleneck_head_supported(1, 1, Cin, C)
 
 
-# set by SeqNetFunction.forward for the duration of the call: will a backward pass follow (does any input / parameter of
-# the node need a gradient)?  Inside autograd.Function.forward grad mode is always off, so it cannot be asked there.
-_WANT_BWD = [False]
-
-
-def _block_bits_on():
-    """ReLU bit planes for the one-launch blocks (default on): the forward launch also writes h1 > 0, h2 > 0 and x > 0
-    as 1-bit planes and the backward launch reads those instead of the 16-bit tensors (1/16 of the mask bytes: 37 % of
-    that launch's HBM traffic).  TDN_BLOCK_BITS=0: 16-bit mask sources."""
-    return os.environ.get('TDN_BLOCK_BITS', '1') != '0'
-
-
-def _block_fwd(x, b, bufs=None):
-    """One residual block.  ``bufs`` = caller-provided (h1, h2, out, res[, bits]) outputs — one image's slices of batch
-    tensors when the images of a batch run as separate chains (ImageSplit); everything then stays on the routed
-    stream (no branch stream for the downsample conv)."""
-    res, br = x, None
-    o1 = o2 = o3 = ores = bits = None
-    if bufs is not None:
-        o1, o2, o3, ores = bufs[:4]
-        bits = bufs[4] if len(bufs) > 4 else None
-    if _block_fusable(b, x.shape[3]):
-        u1, u2, u3 = b.u1, b.u2, b.u3
-        if bufs is None and _block_bits_on() and _WANT_BWD[0]:
-            bits = ops.bottleneck_bit_planes(x.shape[0], x.shape[1], x.shape[2], u1.Cout, x.device)
-        h1, h2, out = ops.bottleneck_fwd(x, u1.w_fwd, u2.w_fwd, u3.w_fwd,
-                                         (u1.scale, u1.shift, u2.scale, u2.shift, u3.scale, u3.shift),
-                                         outs=(o1, o2, o3) if bufs is not None else None, bits=bits)
-        if bufs is None and bits is not None:
-            h1._tdn_bits = bits       # travels with the saved activation to the backward launch
-        return out, (x, h1, h2, out)
-    if _block_head_fusable(b, x.shape[3]):
-        u1, u2, u3 = b.u1, b.u2, b.u3
-        down = None
-        if os.environ.get('TDN_BLOCK_HEAD', '2') == '1':
-            res = unit_fwd(b.ud, x, relu=False, out=ores)
-        else:
-            res, down = None, (b.ud.w_fwd, b.ud.scale, b.ud.shift)
-        if bufs is None and _block_bits_on() and _WANT_BWD[0]:
-            bits = ops.bottleneck_bit_planes(x.shape[0], x.shape[1], x.shape[2], u1.Cout, x.device)[:2]
-        h1, h2, out = ops.bottleneck_head_fwd(x, u1.w_fwd, u2.w_fwd, u3.w_fwd,
-                                              (u1.scale, u1.shift, u2.scale, u2.shift, u3.scale, u3.shift), res,
-                                              outs=(o1, o2, o3) if bufs is not None else None, bits=bits, down=down)
-        if bufs is None and bits is not None:
-            h1._tdn_bits = bits
-        return out, (x, h1, h2, out)
-    if b.ud is not None:
-        if bufs is not None:
-            res = unit_fwd(b.ud, x, relu=False, out=ores)
-        else:
-            with branch(x.device, b.ud, (x,)) as br:    # the downsample conv runs beside conv1 (-> conv2)
-                res = unit_fwd(b.ud, x, relu=False)
-    if b.kind == 'bottleneck':
-        h1 = unit_fwd(b.u1, x, relu=True, out=o1)
-        h2 = unit_fwd(b.u2, h1, relu=True, out=o2)
-        if br is not None:
-            br.join()
-        out = unit_fwd(b.u3, h2, res, ADD_SAME, True, out=o3)
-        return out, (x, h1, h2, out)
-    h1 = unit_fwd(b.u1, x, relu=True, out=o1)
-    if br is not None:
-        br.join()
-    out = unit_fwd(b.u2, h1, res, ADD_SAME, True, out=o3)
-    return out, (x, h1, None, out)
-
-
-# Small-M stages (layer3 / layer4 at the BASELINE batch of 2: 8,400 and 2,100 pixels) cannot fill 256 CUs from one
-# launch — 132 ... 528 workgroups with short K loops, each launch paying its own ramp, tail and dependency gap.  The
-# images of a batch are independent (eval-mode BN), so from the first block whose batch has at most TDN_IMG_SPLIT_M
-# pixels on, the forward chain runs once per image, each chain on a stream of its own: the launches of one image fill
-# the gaps of the other's.  Outputs are the image slices of ordinary batch tensors (backward is unchanged).
-_split_streams = {}
-
-
-def _img_split_m():
-    return int(os.environ.get('TDN_IMG_SPLIT_M', '300000'))
-
-
 def _splittable(b):
     return all(not (u.gn or u.bnt) and u.groups == 1 for u in b.units())
 
 
-def _blocks_fwd_split(blocks, cur, pre=None):
-    """Forward of ``blocks`` on batch ``cur`` (N >= 2) as N per-image chains on N streams; returns (out, saved).
-    ``pre(a, e)``: optional producer of cur[a:e], launched at the head of that image range's chain (the stem)."""
-    dev = cur.device
-    N = cur.shape[0]
+def _block_out_hw(b, hw):
+    """Spatial sizes (of h1, of out) of block ``b`` for an input of ``hw`` (a Bottleneck's h2 has out's size)."""
+    h1 = tuple(ops.conv_out_size(v, b.u1.k, b.u1.stride, b.u1.pad) for v in hw)
+    if b.kind != 'bottleneck':
+        return h1, h1
+    return h1, tuple(ops.conv_out_size(v, b.u2.k, b.u2.stride, b.u2.pad) for v in h1)
+
+
+# Routes of a residual block: per-conv launches, the one-launch block (_block_fusable), the one-launch head block
+# (_block_head_fusable).  Routes of the stem: conv and max pool as two launches, one stem + pool launch for the batch,
+# one per image range at the head of the per-image forward chains.
+CONVS, BLOCK, HEAD = 'convs', 'block', 'head'
+STEM_TWO, STEM_ONE, STEM_SPLIT = 'two', 'one', 'split'
+
+
+class SeqSchedule(object):
+    """How one SeqNetFunction call runs, chosen once at the start of its forward (seq_schedule) and followed by its
+    backward.  routes[i] / bits[i]: block i's route, and whether its forward writes ReLU bit planes; split: the first
+    block of the per-image forward chains (None: no chains); cuts: the image ranges of the chains, forward and
+    backward (cuts[i] .. cuts[i + 1]; None: no chains either way); bwd_chains: the backward may run per-image dgrad
+    chains; stem: the stem's route (None: the net has no stem)."""
+
+    def __init__(self, routes, bits, split, cuts, bwd_chains, stem):
+        self.routes, self.bits, self.split, self.cuts = routes, bits, split, cuts
+        self.bwd_chains, self.stem = bwd_chains, stem
+
+
+def seq_schedule(net, shape, want_bwd):
+    """The SeqSchedule of one call whose first block gets a batch of ``shape`` = (N, H, W, C) (behind the stem);
+    ``want_bwd``: a backward pass will follow.  The only reader of the schedule's knobs, on every call:
+
+      TDN_BLOCK_FUSE=0/1/64/128  one-launch blocks off / every width the build has / up to that many mid channels
+      TDN_BLOCK_HEAD=0           head blocks as per-conv launches (also off with TDN_BLOCK_FUSE=0)
+      TDN_BLOCK_BITS=0           the one-launch blocks' backward reads 16-bit mask sources instead of bit planes
+      TDN_IMG_SPLIT_M, _WAYS     per-image forward chains (below); number of chains, forward and backward
+      TDN_BWD_SPLIT=0            no per-image dgrad chains
+      TDN_STEM_FUSED=0           stem conv and max pool as two launches
+      TDN_STEM_SPLIT=0           one stem + pool launch for the batch in front of chains that start at the first block
+
+    Bit planes (default on): the forward launch of a one-launch block also writes h1 > 0, h2 > 0 and x > 0 as 1-bit
+    planes and the backward launch reads those instead of the 16-bit tensors (1/16 of the mask bytes: 37 % of that
+    launch's HBM traffic) — only written where a backward pass will follow.
+
+    Per-image chains: small-M stages (layer3 / layer4 at the BASELINE batch of 2: 8,400 and 2,100 pixels) cannot fill
+    256 CUs from one launch — 132 ... 528 workgroups with short K loops, each launch paying its own ramp, tail and
+    dependency gap.  The images of a batch are independent (eval-mode BN), so from the first block whose output batch
+    has at most TDN_IMG_SPLIT_M pixels on, the forward runs once per image range, each chain on a stream of its own:
+    the launches of one range fill the gaps of the other's.  Two chains whatever the batch: at 4 images per GPU four
+    chains measured worse than two (R101 fp16: 311 vs 350 img/s with the backward chains on; R50: 493 vs 541)."""
+    env = os.environ.get
+    fuse = env('TDN_BLOCK_FUSE', '1')
+    widest = None if fuse in ('', '1') else int(fuse)
+    head = fuse != '0' and env('TDN_BLOCK_HEAD', '1') != '0'
+    bits = want_bwd and env('TDN_BLOCK_BITS', '1') != '0'
+    split_m = int(env('TDN_IMG_SPLIT_M', '300000'))
+    N, H, W, C = shape
+    routes, split, hw = [], None, (H, W)
+    for i, b in enumerate(net.blocks):
+        if _block_fusable(b, C, widest):
+            routes.append(BLOCK)
+        elif head and _block_head_fusable(b, C):
+            routes.append(HEAD)
+        else:
+            routes.append(CONVS)
+        hw = _block_out_hw(b, hw)[1]
+        C = (b.u3 if b.kind == 'bottleneck' else b.u2).Cout
+        if (split is None and split_m > 0 and N >= 2 and N * hw[0] * hw[1] <= split_m and
+                all(_splittable(bb) for bb in net.blocks[i:])):
+            split = i
+    stem = None
+    if net.stem is not None:
+        u = net.stem
+        # a parity test's DEBUG_CAPTURE looks at the stem activation, which the one-launch stem never writes
+        if (u.gn or u.bnt or u.Cout != 64 or u.scale is None or u.shift is None or DEBUG_CAPTURE is not None or
+                env('TDN_STEM_FUSED', '1') == '0'):
+            stem = STEM_TWO
+        elif split == 0 and env('TDN_STEM_SPLIT', '1') != '0':
+            stem = STEM_SPLIT
+        else:
+            stem = STEM_ONE
+    bwd_chains = (env('TDN_BWD_SPLIT', '1') != '0' and N >= 2 and bool(net.blocks) and
+                  all(_splittable(b) for b in net.blocks))
+    cuts = None
+    if split is not None or bwd_chains:
+        ways = max(2, min(N, int(env('TDN_IMG_SPLIT_WAYS', '2'))))
+        cuts = [N * i // ways for i in range(ways + 1)]      # contiguous image ranges, one chain each
+    return SeqSchedule(routes, [bits and r != CONVS for r in routes], split, cuts, bwd_chains, stem)
+
+
+_split_streams = {}
+
+
+def _chain_streams(dev, ways):
+    """The streams of the per-image chains, forward and backward: one pool per device and main stream."""
     key = (dev.index, torch._C._cuda_getCurrentRawStream(dev.index))
-    # two chains whatever the batch: at 4 images per GPU four chains measured worse than two (R101 fp16: 311 vs 350
-    # img/s with the backward chains on; R50: 493 vs 541)
-    ways = max(2, min(N, int(os.environ.get('TDN_IMG_SPLIT_WAYS', '2'))))
-    cuts = [N * i // ways for i in range(ways + 1)]      # contiguous image ranges, one chain each
     pool = _split_streams.get(key)
     if pool is None or len(pool) < ways:
         pool = [torch.cuda.Stream(device=dev) for _ in range(ways)]
         _split_streams[key] = pool
-    # batch tensors of every block, allocated on the current stream
-    bufs, x = [], cur
-    for b in blocks:
-        H, W = x.shape[1], x.shape[2]
+    return pool[:ways]
 
-        def new(hh, ww, c):
-            return torch.empty(N, hh, ww, c, dtype=x.dtype, device=dev)
-        if b.kind == 'bottleneck':
-            h1 = new(ops.conv_out_size(H, b.u1.k, b.u1.stride, b.u1.pad),
-                     ops.conv_out_size(W, b.u1.k, b.u1.stride, b.u1.pad), b.u1.Cout)
-            h2 = new(ops.conv_out_size(h1.shape[1], b.u2.k, b.u2.stride, b.u2.pad),
-                     ops.conv_out_size(h1.shape[2], b.u2.k, b.u2.stride, b.u2.pad), b.u2.Cout)
-            out = new(h2.shape[1], h2.shape[2], b.u3.Cout)
+
+@contextlib.contextmanager
+def _on_stream(st):
+    """The library launches inside go to stream ``st``."""
+    prev = _lib.set_stream_override(st.cuda_stream)
+    try:
+        yield
+    finally:
+        _lib.set_stream_override(prev)
+
+
+def _rows(t, a, e):
+    """Images a..e of a batch tensor, or of every tensor of a tuple (None stays None)."""
+    if isinstance(t, tuple):
+        return tuple(_rows(v, a, e) for v in t)
+    return None if t is None else t[a:e]
+
+
+def _block_outputs(b, route, bits, x):
+    """Batch tensors (h1, h2, out, res, bit planes) that block ``b`` writes for input ``x``: h2 for a Bottleneck, res
+    where the downsample branch is a launch of its own, and with ``bits`` two planes for a head block (its x is no mask
+    source) or three for a one-launch block — those travel with h1 to the backward launch.  A block with a run-time
+    norm or a grouped conv (never in a per-image chain) leaves allocation to its units: all None."""
+    if not _splittable(b):
+        return None, None, None, None, None
+    N, H, W, _ = x.shape
+    hw1, hw = _block_out_hw(b, (H, W))
+
+    def new(s, c):
+        return torch.empty(N, s[0], s[1], c, dtype=x.dtype, device=x.device)
+    bott = b.kind == 'bottleneck'
+    h1 = new(hw1, b.u1.Cout)
+    h2 = new(hw, b.u2.Cout) if bott else None
+    out = new(hw, (b.u3 if bott else b.u2).Cout)
+    res = new(hw, out.shape[3]) if b.ud is not None and route == CONVS else None
+    planes = None
+    if bits:
+        planes = ops.bottleneck_bit_planes(N, H, W, b.u1.Cout, x.device, head=route == HEAD)
+        h1._tdn_bits = planes
+    return h1, h2, out, res, planes
+
+
+def _block_fwd(b, route, x, bufs, whole=False):
+    """One residual block on one image range by ``route``: returns (out, saved = (x, h1, h2, out)).  ``bufs``: the
+    block's _block_outputs, or their slices for this range.  ``whole``: the range is the batch, and the downsample
+    conv runs beside conv1 -> conv2 on a branch stream; otherwise everything stays on the routed stream."""
+    h1, h2, out, res, bits = bufs
+    u1, u2, u3 = b.u1, b.u2, b.u3
+    if route != CONVS:
+        affine = (u1.scale, u1.shift, u2.scale, u2.shift, u3.scale, u3.shift)
+        if route == BLOCK:
+            h1, h2, out = ops.bottleneck_fwd(x, u1.w_fwd, u2.w_fwd, u3.w_fwd, affine, outs=(h1, h2, out), bits=bits)
         else:
-            h1 = new(ops.conv_out_size(H, b.u1.k, b.u1.stride, b.u1.pad),
-                     ops.conv_out_size(W, b.u1.k, b.u1.stride, b.u1.pad), b.u1.Cout)
-            h2 = None
-            out = new(h1.shape[1], h1.shape[2], b.u2.Cout)
-        res = None
-        if b.ud is not None and not (_block_head_fusable(b, x.shape[3]) and os.environ.get('TDN_BLOCK_HEAD', '2') != '1'):
-            res = new(out.shape[1], out.shape[2], out.shape[3])     # (a head block computes the branch in its launch)
-        bits = None
-        if _block_bits_on() and _WANT_BWD[0] and _block_fusable(b, x.shape[3]):
-            bits = ops.bottleneck_bit_planes(N, H, W, b.u1.Cout, dev)
-            h1._tdn_bits = bits
-        elif _block_bits_on() and _WANT_BWD[0] and _block_head_fusable(b, x.shape[3]):
-            bits = ops.bottleneck_bit_planes(N, H, W, b.u1.Cout, dev)[:2]
-            h1._tdn_bits = bits
-        bufs.append((h1, h2, out, res, bits))
-        x = out
+            h1, h2, out = ops.bottleneck_head_fwd(x, u1.w_fwd, u2.w_fwd, u3.w_fwd, affine, outs=(h1, h2, out),
+                                                  bits=bits, down=(b.ud.w_fwd, b.ud.scale, b.ud.shift))
+        return out, (x, h1, h2, out)
+    br = None
+    if b.ud is not None:
+        br = branch(x.device, b.ud, (x,)) if whole else None
+        with br or contextlib.nullcontext():
+            res = unit_fwd(b.ud, x, relu=False, out=res)
+    else:
+        res = x
+    h1 = unit_fwd(u1, x, relu=True, out=h1)
+    if b.kind == 'bottleneck':
+        h2 = unit_fwd(u2, h1, relu=True, out=h2)
+    if br is not None:
+        br.join()
+    last, inp = (u3, h2) if b.kind == 'bottleneck' else (u2, h1)
+    out = unit_fwd(last, inp, res, ADD_SAME, True, out=out)
+    return out, (x, h1, h2, out)
+
+
+def _blocks_fwd_chains(blocks, routes, bits, cur, cuts, pre=None):
+    """Forward of ``blocks`` on batch ``cur`` as one chain per image range cuts[i] .. cuts[i + 1], each on a stream of
+    its own; returns (out, saved).  Outputs are the image slices of ordinary batch tensors.  ``pre(a, e)``: optional
+    producer of cur[a:e], launched at the head of that range's chain (the stem)."""
+    dev = cur.device
+    pool = _chain_streams(dev, len(cuts) - 1)
+    bufs, x = [], cur
+    for b, route, bb in zip(blocks, routes, bits):        # batch tensors of every block, on the current stream
+        bufs.append(_block_outputs(b, route, bb, x))
+        x = bufs[-1][2]
     ev = streams.record(torch.cuda.current_stream(dev))
-    for i in range(ways):
-        streams.wait(pool[i], ev)
+    for st in pool:
+        streams.wait(st, ev)
     # Launch order: block by block, alternating between the chains — the order in which the eager path and the
     # launch-plan executor hand the launches to the GPU.  (A captured hipGraph is replayed by the runtime branch by
     # branch whatever the capture order: the second chain starts as soon as the host has submitted the first chain's
     # nodes — a few hundred microseconds unprofiled, ~0.7 ms under rocprofv3, which is what its timelines show.)
-    xs = [cur[cuts[i]:cuts[i + 1]] for i in range(ways)]
-    # TDN_CHAIN_SYNC=n (diagnostic, default off): every n blocks each chain waits for the other chains' progress up to
-    # that block (a per-block cross-join, meant to make a replayed graph interleave the chains).  Mode 'cross' (mutual
-    # waits between the two forked streams) is the pattern that crashed hipStreamEndCapture in round 2; inside a
-    # GraphedStep capture streams.wait now refuses it with a RuntimeError (the step then runs eager) — to reproduce the
-    # crash itself, capture with a plain torch.cuda.graph (not policed).
-    chain_sync = int(os.environ.get('TDN_CHAIN_SYNC', '0'))
+    ranges = list(zip(pool, cuts, cuts[1:]))
     if pre is not None:
-        for i in range(ways):
-            prev = _lib.set_stream_override(pool[i].cuda_stream)
-            try:
-                pre(cuts[i], cuts[i + 1])
-            finally:
-                _lib.set_stream_override(prev)
-    for bi_, (b, (h1, h2, out, res, bits)) in enumerate(zip(blocks, bufs)):
-        if chain_sync > 0 and bi_ > 0 and bi_ % chain_sync == 0:
-            mode = os.environ.get('TDN_CHAIN_SYNC_MODE', 'cross')
-            if mode == 'cross':        # every chain waits for every other chain's event of this point
-                toks = [streams.record(pool[i]) for i in range(ways)]
-                for i in range(ways):
-                    for j in range(ways):
-                        if i != j:
-                            streams.wait(pool[i], toks[j])
-            elif mode == 'oneway':     # chain i waits for chain i - 1 only
-                toks = [streams.record(pool[i]) for i in range(ways)]
-                for i in range(1, ways):
-                    streams.wait(pool[i], toks[i - 1])
-            else:                      # 'main': join into the main stream and fork again
-                main_ = torch.cuda.current_stream(dev)
-                for i in range(ways):
-                    streams.wait_stream(main_, pool[i])
-                ev_ = streams.record(main_)
-                for i in range(ways):
-                    streams.wait(pool[i], ev_)
-        for i in range(ways):
-            a, e_ = cuts[i], cuts[i + 1]
-            prev = _lib.set_stream_override(pool[i].cuda_stream)
-            try:
-                xs[i], _ = _block_fwd(xs[i], b, (h1[a:e_], h2[a:e_] if h2 is not None else None, out[a:e_],
-                                                 res[a:e_] if res is not None else None,
-                                                 tuple(t[a:e_] for t in bits) if bits is not None else None))
-            finally:
-                _lib.set_stream_override(prev)
+        for st, a, e in ranges:
+            with _on_stream(st):
+                pre(a, e)
+    xs = [cur[a:e] for _, a, e in ranges]
+    for b, route, bb in zip(blocks, routes, bufs):
+        for i, (st, a, e) in enumerate(ranges):
+            with _on_stream(st):
+                xs[i], _ = _block_fwd(b, route, xs[i], _rows(bb, a, e))
     main = torch.cuda.current_stream(dev)
-    for i in range(ways):
-        streams.wait_stream(main, pool[i])
+    for st in pool:
+        streams.wait_stream(main, st)
     saved, x = [], cur
-    for (h1, h2, out, res, bits) in bufs:
+    for h1, h2, out, _, _ in bufs:
         saved.append((x, h1, h2, out))
         x = out
     return x, saved
 
 
-def _block_dgrad_fused(b, saved, g, mask_src, outs=None, bits=None):
-    """The three input gradients of a fusable block in one launch (g2, g1, dx); with DEBUG_BWD set the launch is
-    recorded as the three dgrad launches it replaces — their operands and results all exist in HBM — so the in-situ
-    parity checks (tests/parity_util.py) recompute every conv of the fused launch like any other."""
-    x, h1, h2, out = saved
+def _bwd_steps(net, sch, saved, ext, need_net_dx):
+    """What only the backward pass knows, per block: (route, extra, mask_src, need_dx) — extra: the external gradient
+    w.r.t. the block's input (ext: of the block outputs the net returns), mask_src: the input's producer output, whose
+    ReLU mask dx takes; need_dx: anything needs dx.  The route is the forward's unless its kernel cannot take the block
+    here: the one-launch dgrad kernels fold in no external gradient, and the head kernel's dx carries no ReLU mask.
+    Also whether the per-image dgrad chains run: they need dx of every block and fold external gradients in through
+    a downsample conv only."""
+    steps = []
+    for bi in range(len(net.blocks)):
+        extra = ext.get(bi - 1) if bi > 0 else None
+        mask_src = saved[bi - 1][3] if bi > 0 else None
+        need_dx = bi > 0 or net.stem is not None or need_net_dx
+        route = sch.routes[bi]
+        if not need_dx or extra is not None or (route == HEAD and mask_src is not None):
+            route = CONVS
+        steps.append((route, extra, mask_src, need_dx))
+    chains = (sch.bwd_chains and (net.stem is not None or need_net_dx) and
+              all(net.blocks[k + 1].ud is not None for k in ext if k + 1 < len(net.blocks)))
+    return steps, chains
+
+
+def _block_dgrad(b, route, sv, g, extra, mask_src, bits, need_dx=True, outs=None):
+    """Input gradients (g2, g1, dx) of block ``b`` on one image range by ``route`` (_bwd_steps).  g: gradient w.r.t. the
+    block's pre-ReLU output, already masked by (out > 0); sv: the forward's (x, h1, h2, out); bits: its ReLU bit planes.
+    ``outs`` = (g2, g1, dx, t) slices of batch tensors (t: the downsample conv's dgrad where that is a launch of its
+    own), everything on the routed stream; or None: the whole batch, with the downsample conv's dgrad on a branch
+    stream beside the conv3 -> conv2 dgrads.  With DEBUG_BWD set a one-launch kernel is recorded as the three dgrad
+    launches it replaces — their operands and results all exist in HBM — so the in-situ parity checks
+    (tests/parity_util.py) recompute it like any other; the head block's downsample dgrad is then a launch of its own
+    (the recorder wants t as a tensor)."""
+    x, h1, h2 = sv[:3]
+    o2, o1, odx, ot = outs if outs is not None else (None,) * 4
     u1, u2, u3 = b.u1, b.u2, b.u3
-    if bits is None:
-        bits = getattr(h1, '_tdn_bits', None)
-    if bits is not None and mask_src is not None and mask_src.data_ptr() != x.data_ptr():
-        bits = None                    # the third plane is x > 0: only valid when the block's input is the mask source
-    if bits is not None and mask_src is None:
-        bits = None                    # no mask on dx at all (first block of a net without a stem): 16-bit path
-    g2, g1, dx = ops.bottleneck_dgrad(g, u3.w_dgrad, u2.w_dgrad, u1.w_dgrad, (h2, h1, mask_src), outs=outs, bits=bits)
-    if DEBUG_BWD is not None:
-        DEBUG_BWD.append(('dgrad', u3, g, _hw(h2), None, ADD_NONE, h2, g2))
-        DEBUG_BWD.append(('dgrad', u2, g2, _hw(h1), None, ADD_NONE, h1, g1))
-        DEBUG_BWD.append(('dgrad', u1, g1, _hw(x), g, ADD_SAME, mask_src, dx))
+    if route != CONVS:
+        if route == BLOCK:
+            t = g                                   # the identity residual
+            if mask_src is None or mask_src.data_ptr() != x.data_ptr():
+                bits = None    # the third plane is x > 0: only valid where the block's input is the mask source
+            g2, g1, dx = ops.bottleneck_dgrad(g, u3.w_dgrad, u2.w_dgrad, u1.w_dgrad, (h2, h1, mask_src),
+                                              outs=(o2, o1, odx), bits=bits)
+        else:
+            # downsample^T(g) accumulated inside the launch, beside conv3^T(g): g is read once, t never exists in HBM
+            t, down = None, b.ud.w_dgrad
+            if DEBUG_BWD is not None:
+                t, down = unit_dgrad(b.ud, g, _hw(x), out=ot), None
+            g2, g1, dx = ops.bottleneck_head_dgrad(g, u3.w_dgrad, u2.w_dgrad, u1.w_dgrad, (h2, h1), t,
+                                                   outs=(o2, o1, odx), bits=bits, down=down)
+        if DEBUG_BWD is not None:
+            DEBUG_BWD.append(('dgrad', u3, g, _hw(h2), None, ADD_NONE, h2, g2))
+            DEBUG_BWD.append(('dgrad', u2, g2, _hw(h1), None, ADD_NONE, h1, g1))
+            DEBUG_BWD.append(('dgrad', u1, g1, _hw(x), t, ADD_SAME, mask_src, dx))
+        return g2, g1, dx
+    t, br = g, None
+    if need_dx and b.ud is not None:
+        br = branch(g.device, b.ud, (g, extra) if extra is not None else (g,)) if outs is None else None
+        with br or contextlib.nullcontext():
+            t = unit_dgrad(b.ud, g, _hw(x), extra, ADD_SAME, out=ot)
+    if b.kind == 'bottleneck':
+        g2 = unit_dgrad(u3, g, _hw(h2), mask_src=h2, out=o2)
+        g1 = unit_dgrad(u2, g2, _hw(h1), mask_src=h1, out=o1)
+    else:
+        g2, g1 = None, unit_dgrad(u2, g, _hw(h1), mask_src=h1, out=o1)
+    if not need_dx:
+        return g2, g1, None
+    if br is not None:
+        br.join()
+    elif b.ud is None and extra is not None:
+        t = ops.add_relu_mask(g, extra, None)
+    return g2, g1, unit_dgrad(u1, g1, _hw(x), t, ADD_SAME, mask_src, out=odx)
+
+
+def _block_dgrad_chains(b, route, sv, g, extra, mask_src, ranges):
+    """_block_dgrad with the launches of every image range (stream, a, e) on that range's stream (see
+    SeqNetFunction._backward); returns (g2, g1, dx) as batch tensors allocated here."""
+    x, h1, h2 = sv[:3]
+    g2 = torch.empty_like(h2) if h2 is not None else None
+    g1, dx = torch.empty_like(h1), torch.empty_like(x)
+    t = torch.empty_like(x) if b.ud is not None and (route == CONVS or DEBUG_BWD is not None) else None
+    bits = getattr(h1, '_tdn_bits', None)
+    for st, a, e in ranges:
+        with _on_stream(st):
+            _block_dgrad(b, route, _rows(sv, a, e), g[a:e], _rows(extra, a, e), _rows(mask_src, a, e),
+                         _rows(bits, a, e), outs=_rows((g2, g1, dx, t), a, e))
+    # nothing of this block may be recycled before the chains have run: t is only referenced here
+    key = (x.device.index, torch._C._cuda_getCurrentRawStream(x.device.index))
+    _side_refs.setdefault(key, []).extend(v for v in (t, g, g1, g2, dx) if v is not None)
     return g2, g1, dx
 
 
-def _head_ds_in_launch():
-    """TDN_BLOCK_HEAD=2 (default): the head block's downsample branch is computed inside its launch, forward and
-    backward.  The in-situ parity recorder (DEBUG_BWD) wants the downsample dgrad's result as a tensor: separate launch."""
-    return os.environ.get('TDN_BLOCK_HEAD', '2') not in ('1', '2f') and DEBUG_BWD is None
-
-
-def _block_head_dgrad_fused(b, saved, g, outs=None, bits=None, t_out=None):
-    """Input gradients of a head block (_block_head_fusable): the downsample conv's dgrad as a launch of its own, then
-    g2, g1 and dx = conv1^T(g1) + t in one launch.  Returns (g2, g1, dx, t)."""
-    x, h1, h2, out = saved
-    u1, u2, u3 = b.u1, b.u2, b.u3
-    if bits is None:
-        bits = getattr(h1, '_tdn_bits', None)
-    if _head_ds_in_launch():
-        # downsample^T(g) accumulated inside the launch, beside conv3^T(g): g is read once, t never exists in HBM
-        t, down = None, b.ud.w_dgrad
-    else:
-        t, down = unit_dgrad(b.ud, g, _hw(x), out=t_out), None
-    g2, g1, dx = ops.bottleneck_head_dgrad(g, u3.w_dgrad, u2.w_dgrad, u1.w_dgrad, (h2, h1), t, outs=outs,
-                                           bits=bits[:2] if bits is not None else None, down=down)
-    if DEBUG_BWD is not None:
-        DEBUG_BWD.append(('dgrad', u3, g, _hw(h2), None, ADD_NONE, h2, g2))
-        DEBUG_BWD.append(('dgrad', u2, g2, _hw(h1), None, ADD_NONE, h1, g1))
-        DEBUG_BWD.append(('dgrad', u1, g1, _hw(x), t, ADD_SAME, None, dx))
-    return g2, g1, dx, t
-
-
-def _block_bwd(b, saved, g, extra, mask_src, need_dx, wq=None):
-    """g: gradient w.r.t. the block's pre-ReLU output, already masked by (out > 0).
-    extra: external gradient w.r.t. the block INPUT to fold in (e.g. the FPN's gradient of a stage output).
-    mask_src: if given, the returned dx is masked by (mask_src > 0) — i.e. it already is the masked ``g`` of the
-    block that produced this block's input.  Returns (dx | None, {unit: grads})."""
-    x, h1, h2, out = saved
+def _block_wgrads(b, sv, g, g2, g1, wq):
+    """Queue the weight gradients of block ``b`` on batch tensors (g, g2, g1: w.r.t. out, h2, h1): {unit: grads}."""
+    x, h1, h2 = sv[:3]
     grads = {}
-    t, br = None, None
-    if need_dx and extra is None and _block_fusable(b, x.shape[3]):
-        g2, g1, dx = _block_dgrad_fused(b, saved, g, mask_src)
-        grads[b.u3] = unit_wgrad(b.u3, h2, g, queue=wq)
-        grads[b.u2] = unit_wgrad(b.u2, h1, g2, queue=wq)
-        grads[b.u1] = unit_wgrad(b.u1, x, g1, queue=wq)
-        return dx, grads
-    if need_dx and extra is None and mask_src is None and _block_head_fusable(b, x.shape[3]):
-        g2, g1, dx, _ = _block_head_dgrad_fused(b, saved, g)
-        grads[b.u3] = unit_wgrad(b.u3, h2, g, queue=wq)
-        grads[b.u2] = unit_wgrad(b.u2, h1, g2, queue=wq)
-        grads[b.u1] = unit_wgrad(b.u1, x, g1, queue=wq)
-        grads[b.ud] = unit_wgrad(b.ud, x, g, queue=wq)
-        return dx, grads
-    if need_dx and b.ud is not None:
-        with branch(g.device, b.ud, (g, extra) if extra is not None else (g,)) as br:
-            t = unit_dgrad(b.ud, g, _hw(x), extra, ADD_SAME)   # beside the conv3 -> conv2 dgrads of the main path
     if b.kind == 'bottleneck':
         grads[b.u3] = unit_wgrad(b.u3, h2, g, queue=wq)
-        g2 = unit_dgrad(b.u3, g, _hw(h2), mask_src=h2)
-        grads[b.u2] = unit_wgrad(b.u2, h1, g2, queue=wq)
-        g1 = unit_dgrad(b.u2, g2, _hw(h1), mask_src=h1)
-    else:
-        grads[b.u2] = unit_wgrad(b.u2, h1, g, queue=wq)
-        g1 = unit_dgrad(b.u2, g, _hw(h1), mask_src=h1)
-    grads[b.u1] = unit_wgrad(b.u1, x, g1, queue=wq)
-    if b.ud is not None:
-        grads[b.ud] = unit_wgrad(b.ud, x, g, queue=wq)
-    dx = None
-    if need_dx:
-        if b.ud is not None:
-            br.join()
-        elif extra is not None:
-            t = ops.add_relu_mask(g, extra, None)
-        else:
-            t = g
-        dx = unit_dgrad(b.u1, g1, _hw(x), t, ADD_SAME, mask_src)
-    return dx, grads
-
-
-def _block_bwd_chains(b, saved, g, extra, mask_src, wq, pool, cuts):
-    """_block_bwd with the dgrad launches of every image range issued on that range's stream (see
-    SeqNetFunction._backward): outputs are slices of batch tensors allocated here, weight gradients are queued on the
-    batch tensors as usual.  Needs need_dx, and `extra` only where the block has a downsample conv."""
-    x, h1, h2, out = saved
-    grads = {}
-    dev = g.device
-
-    def new_like(t):
-        return torch.empty_like(t)
-
-    bott = b.kind == 'bottleneck'
-    g2 = new_like(h2) if bott else None
-    g1 = new_like(h1)
-    dx = new_like(x)
-    fused = extra is None and _block_fusable(b, x.shape[3])
-    head = extra is None and mask_src is None and _block_head_fusable(b, x.shape[3])
-    t = g
-    if b.ud is not None:
-        t = new_like(x) if not (head and _head_ds_in_launch()) else None
-    bits_all = getattr(h1, '_tdn_bits', None) if (fused or head) else None
-    for i, st in enumerate(pool[:len(cuts) - 1]):
-        a, e = cuts[i], cuts[i + 1]
-        prev = _lib.set_stream_override(st.cuda_stream)
-        try:
-            gi = g[a:e]
-            if fused:
-                _block_dgrad_fused(b, (x[a:e], h1[a:e], h2[a:e], None), gi,
-                                   mask_src[a:e] if mask_src is not None else None,
-                                   outs=(g2[a:e], g1[a:e], dx[a:e]),
-                                   bits=tuple(t[a:e] for t in bits_all) if bits_all is not None else None)
-                continue
-            if head:
-                _block_head_dgrad_fused(b, (x[a:e], h1[a:e], h2[a:e], None), gi, outs=(g2[a:e], g1[a:e], dx[a:e]),
-                                        bits=tuple(t_[a:e] for t_ in bits_all) if bits_all is not None else None,
-                                        t_out=t[a:e] if t is not None else None)
-                continue
-            if b.ud is not None:
-                unit_dgrad(b.ud, gi, _hw(x), extra[a:e] if extra is not None else None, ADD_SAME, out=t[a:e])
-            if bott:
-                unit_dgrad(b.u3, gi, _hw(h2), mask_src=h2[a:e], out=g2[a:e])
-                unit_dgrad(b.u2, g2[a:e], _hw(h1), mask_src=h1[a:e], out=g1[a:e])
-            else:
-                unit_dgrad(b.u2, gi, _hw(h1), mask_src=h1[a:e], out=g1[a:e])
-            unit_dgrad(b.u1, g1[a:e], _hw(x), t[a:e], ADD_SAME, mask_src[a:e] if mask_src is not None else None,
-                       out=dx[a:e])
-        finally:
-            _lib.set_stream_override(prev)
-    if bott:
-        grads[b.u3] = unit_wgrad(b.u3, h2, g, queue=wq)
         grads[b.u2] = unit_wgrad(b.u2, h1, g2, queue=wq)
     else:
         grads[b.u2] = unit_wgrad(b.u2, h1, g, queue=wq)
     grads[b.u1] = unit_wgrad(b.u1, x, g1, queue=wq)
     if b.ud is not None:
         grads[b.ud] = unit_wgrad(b.ud, x, g, queue=wq)
-    # nothing of this block may be recycled before the chains have run: t is only referenced here
-    key = (dev.index, torch._C._cuda_getCurrentRawStream(dev.index))
-    _side_refs.setdefault(key, []).extend(v for v in (t, g, g1, g2, dx) if v is not None)
-    return dx, grads
+    return grads
 
 
 def _stem_fwd(u, xp, hw):
@@ -1207,132 +1180,80 @@ def _stem_fwd(u, xp, hw):
     return s
 
 
-def _stem_pool_split(u, xp, hw):
-    """The one-launch stem + pool per image range, at the head of the per-image forward chains (TDN_STEM_SPLIT, default
-    1): returns (pooled output, indices, pre) with the batch tensors allocated here and ``pre(a, e)`` the launch that
-    fills images a..e — or None where the one-launch stem does not apply."""
-    if (u.gn or u.bnt or u.Cout != 64 or u.scale is None or u.shift is None or DEBUG_CAPTURE is not None or
-            os.environ.get('TDN_STEM_FUSED', '1') == '0' or os.environ.get('TDN_STEM_SPLIT', '1') == '0'):
-        return None
-    H, W = hw
-    N = xp.shape[0]
-    Ho, Wo = ops.conv_out_size(H // 2, 3, 2, 1), ops.conv_out_size(W // 2, 3, 2, 1)
-    y = torch.empty(N, Ho, Wo, u.Cout, dtype=xp.dtype, device=xp.device)
-    idx = torch.empty(N, Ho, Wo, u.Cout, dtype=torch.uint8, device=xp.device)
+def _stem_pool(u, route, xp, hw, shape):
+    """Stem + max pool (resnet.py:254-258) by ``route``: (stem activation | None, pooled output of ``shape``, window
+    indices, pre | None).  The plain stem — 64 channels, eval-mode BN folded into the conv — runs as ONE launch that
+    never writes its full-size activation (ops.stem_pool_fwd, bit-identical to the two launches): for the batch, or
+    per image range at the head of the per-image chains, where ``pre(a, e)`` is the launch that fills images a..e of
+    the batch tensors allocated here."""
+    if route == STEM_TWO:
+        s = _stem_fwd(u, xp, hw)
+        y, idx = ops.maxpool3x3s2_fwd(s)
+        return s, y, idx, None
+    if route == STEM_ONE:
+        y, idx = ops.stem_pool_fwd(xp, u.w_fwd, hw, u.scale, u.shift)
+        return None, y, idx, None
+    y = torch.empty(shape, dtype=xp.dtype, device=xp.device)
+    idx = torch.empty(shape, dtype=torch.uint8, device=xp.device)
 
     def pre(a, e):
         ops.stem_pool_fwd(xp[a:e], u.w_fwd, hw, u.scale, u.shift, out=(y[a:e], idx[a:e]))
-    return y, idx, pre
+    return None, y, idx, pre
 
 
-def _stem_pool_fwd(u, xp, hw):
-    """Stem + max pool (resnet.py:254-258): (stem activation or None, pooled output, window indices).  The plain stem —
-    64 channels, eval-mode BN folded into the conv — runs as ONE launch that never writes its full-size activation
-    (ops.stem_pool_fwd, bit-identical to the two launches); TDN_STEM_FUSED=0, a parity test's DEBUG_CAPTURE (it looks
-    at the stem activation) and every other stem variant take the two launches."""
-    if (not (u.gn or u.bnt) and u.Cout == 64 and u.scale is not None and u.shift is not None and
-            DEBUG_CAPTURE is None and os.environ.get('TDN_STEM_FUSED', '1') != '0'):
-        y, idx = ops.stem_pool_fwd(xp, u.w_fwd, hw, u.scale, u.shift)
-        return None, y, idx
-    s = _stem_fwd(u, xp, hw)
-    y, idx = ops.maxpool3x3s2_fwd(s)
-    return s, y, idx
-
-
-# Called by SeqNetFunction._backward behind every weight-gradient group launch of a stage, with the number of stages
+# Called by SeqNetFunction._backward behind the weight-gradient group launch of every stage, with the number of stages
 # whose groups have been launched so far in this pass (1: the last stage's, ...) and the number of stages:
 # dp.GradReducer hangs the launch of its deferred bucket all-reduces on it.
 FLUSH_HOOKS = []
 
 
 class SeqNetFunction(torch.autograd.Function):
-    """ResNet.forward (resnet.py:253-268) — or a single residual block — as one autograd node."""
+    """ResNet.forward (resnet.py:253-268) — or a single residual block — as one autograd node.  ``want_bwd``: will a
+    backward pass follow?  (Grad mode is always off inside autograd.Function.forward: the caller asks.)"""
 
     @staticmethod
-    def forward(ctx, net, x, *params):
+    def forward(ctx, net, x, want_bwd, *params):
         ctx.gn_saved = {}
-        prev = _WANT_BWD[0]
-        _WANT_BWD[0] = any(ctx.needs_input_grad)
-        try:
-            with gn_scope(ctx.gn_saved):
-                return SeqNetFunction._forward(ctx, net, x, *params)
-        finally:
-            _WANT_BWD[0] = prev
+        with gn_scope(ctx.gn_saved):
+            return SeqNetFunction._forward(ctx, net, x, want_bwd)
 
     @staticmethod
-    def _forward(ctx, net, x, *params):
-        st = {}
-        s = None
-        stem_pre = None
-        if net.stem is not None and isinstance(x, StagedImages):
-            if x.dtype != net.dtype:
-                raise RuntimeError('staged images are %s but the net computes in %s' % (x.dtype, net.dtype))
-            xp, (H, W) = x.xp, x.hw
-            s, cur, idx, stem_pre = SeqNetFunction._stem(net, xp, (H, W))
-            st.update(xp=xp, y=cur, idx=idx, img_hw=(H, W))   # the stem's own output is not kept: see maxpool3x3s2_bwd
-        elif net.stem is not None:
-            if x.dim() != 4 or x.shape[1] != 3:
-                raise RuntimeError('ResNet expects an (N,3,H,W) image batch, got %s' % (tuple(x.shape),))
-            img = x if x.dtype == torch.float32 else x.float()
-            H, W = img.shape[2], img.shape[3]
-            xp = ops.stage_image(img, net.dtype)
-            s, cur, idx, stem_pre = SeqNetFunction._stem(net, xp, (H, W))
-            st.update(xp=xp, y=cur, idx=idx, img_hw=(H, W))   # the stem's own output is not kept: see maxpool3x3s2_bwd
+    def _forward(ctx, net, x, want_bwd):
+        st, s, pre = {}, None, None
+        if net.stem is not None:
+            if isinstance(x, StagedImages):
+                if x.dtype != net.dtype:
+                    raise RuntimeError('staged images are %s but the net computes in %s' % (x.dtype, net.dtype))
+                xp, hw = x.xp, tuple(x.hw)
+            else:
+                if x.dim() != 4 or x.shape[1] != 3:
+                    raise RuntimeError('ResNet expects an (N,3,H,W) image batch, got %s' % (tuple(x.shape),))
+                img = x if x.dtype == torch.float32 else x.float()
+                hw = (img.shape[2], img.shape[3])
+                xp = ops.stage_image(img, net.dtype)
+            shape = (xp.shape[0], ops.conv_out_size(hw[0] // 2, 3, 2, 1), ops.conv_out_size(hw[1] // 2, 3, 2, 1),
+                     net.stem.Cout)
+            sch = seq_schedule(net, shape, want_bwd)
+            s, cur, idx, pre = _stem_pool(net.stem, sch.stem, xp, hw, shape)
+            st.update(xp=xp, y=cur, idx=idx, img_hw=hw)   # the stem's own output is not kept: see maxpool3x3s2_bwd
         else:
             cur = ops.to_nhwc_bf16(x, net.dtype)
-        saved, outs = [], []
-        nb = len(net.blocks)
-        bi = 0
-        split_m = _img_split_m()
-        while bi < nb:
-            b = net.blocks[bi]
-            # pixels of this block's output batch (stride on conv2 / conv1: the block works at the reduced size)
-            m_out = cur.shape[0] * -(-cur.shape[1] // b.stride) * -(-cur.shape[2] // b.stride)
-            if split_m > 0 and cur.shape[0] >= 2 and m_out <= split_m and \
-                    all(_splittable(bb) for bb in net.blocks[bi:]):
-                join_branches(cur.device)
-                cur, svs = _blocks_fwd_split(net.blocks[bi:], cur, pre=stem_pre)
-                stem_pre = None
-                for j, sv in enumerate(svs):
-                    saved.append(sv)
-                    if bi + j in net.out_blocks:
-                        outs.append(sv[3])
-                bi = nb
-                break
-            if stem_pre is not None:       # the chains do not start here after all: the whole batch's stem now
-                stem_pre(0, cur.shape[0])
-                stem_pre = None
-            cur, sv = _block_fwd(cur, b)
+            sch = seq_schedule(net, tuple(cur.shape), want_bwd)
+        split = len(net.blocks) if sch.split is None else sch.split
+        saved = []
+        for b, route, bits in zip(net.blocks[:split], sch.routes, sch.bits):
+            cur, sv = _block_fwd(b, route, cur, _block_outputs(b, route, bits, cur), whole=True)
             saved.append(sv)
-            if bi in net.out_blocks:
-                outs.append(cur)
-            bi += 1
-        if stem_pre is not None:
-            stem_pre(0, cur.shape[0])
-        if not net.blocks:
-            outs.append(cur)
+        if sch.split is not None:
+            join_branches(cur.device)
+            cur, svs = _blocks_fwd_chains(net.blocks[split:], sch.routes[split:], sch.bits[split:], cur, sch.cuts, pre)
+            saved += svs
+        outs = [sv[3] for bi, sv in enumerate(saved) if bi in net.out_blocks] if net.blocks else [cur]
         join_branches(cur.device)
-        ctx.net, ctx.st, ctx.saved, ctx.dev = net, st, saved, cur.device
+        ctx.net, ctx.st, ctx.saved, ctx.dev, ctx.schedule = net, st, saved, cur.device, sch
         if DEBUG_CAPTURE is not None:      # parity tests look at the stem's activation too; the step itself drops it
             DEBUG_CAPTURE['seq'] = (dict(st, s=s), saved)
         return tuple(_as_nchw(o) for o in outs)
-
-    @staticmethod
-    def _stem(net, xp, hw):
-        """(stem activation | None, pooled output, window indices, pre | None): with ``pre`` the pooled output is still
-        to be produced — per image range, at the head of the per-image chains (_blocks_fwd_split) — which is only done
-        when those chains start at the first block."""
-        N = xp.shape[0]
-        H, W = hw
-        will_split = (_img_split_m() > 0 and N >= 2 and net.blocks and
-                      N * (H // 4) * (W // 4) // (net.blocks[0].stride ** 2) <= _img_split_m() and
-                      all(_splittable(bb) for bb in net.blocks))
-        if will_split:
-            r = _stem_pool_split(net.stem, xp, hw)
-            if r is not None:
-                return None, r[0], r[1], r[2]
-        s, cur, idx = _stem_pool_fwd(net.stem, xp, hw)
-        return s, cur, idx, None
 
     @staticmethod
     def backward(ctx, *douts):
@@ -1348,79 +1269,58 @@ class SeqNetFunction(torch.autograd.Function):
                 ext[bi] = ops.to_nhwc_bf16(d, net.dtype)
         unit_grads = {}
         need_net_dx = ctx.needs_input_grad[1] and net.stem is None
+        steps, chains = _bwd_steps(net, ctx.schedule, saved, ext, need_net_dx)
         g = None
         wq = WgradQueue(ctx.dev)
-        flush_every = int(os.environ.get('TDN_WGRAD_FLUSH', '0'))
-        since_flush = 0
-        nflush = 0
-        nstages = sum(1 for b_ in net.blocks if b_.ud is not None)
+        nflush, nstages = 0, sum(1 for b in net.blocks if b.ud is not None)
         # Per-image dgrad chains (default; TDN_BWD_SPLIT=0 turns them off): like the forward's, the dgrad launches of
         # each image range go to that range's stream, block by block in alternation — the stretches of the backward
         # pass where a chain of small dgrad kernels had the GPU to itself become two half-size chains side by side
         # (443 -> 459 img/s).  The weight-gradient groups still see batch tensors, so the main stream joins the chains
         # before every group is launched.
-        chains = None
-        nimg = saved[0][0].shape[0] if saved else 0
-        if os.environ.get('TDN_BWD_SPLIT', '1') != '0' and nimg >= 2 and (net.stem is not None or need_net_dx) and \
-                all(_splittable(b_) for b_ in net.blocks) and \
-                all(net.blocks[k + 1].ud is not None for k in ext if k + 1 < len(net.blocks)):
-            dev = ctx.dev
-            key = (dev.index, torch._C._cuda_getCurrentRawStream(dev.index))
-            ways = max(2, min(nimg, int(os.environ.get('TDN_IMG_SPLIT_WAYS', '2'))))
-            pool = _split_streams.get(key)
-            if pool is None or len(pool) < ways:
-                pool = [torch.cuda.Stream(device=dev) for _ in range(ways)]
-                _split_streams[key] = pool
-            chains = (pool[:ways], [nimg * i // ways for i in range(ways + 1)])
+        pool = _chain_streams(ctx.dev, len(ctx.schedule.cuts) - 1) if chains else []
+        ranges = list(zip(pool, ctx.schedule.cuts, ctx.schedule.cuts[1:])) if chains else None
         main = torch.cuda.current_stream(ctx.dev)
+        started = False
 
         def join_chains():
-            for st_ in chains[0]:
-                streams.wait_stream(main, st_)
+            if started:
+                for st_ in pool:
+                    streams.wait_stream(main, st_)
 
-        started = False
-        if chains is not None:
-            # a flush from inside a block (TDN_WGRAD_GROUP=0 flushes per layer) must see the chains' g tensors too
-            wq.pre_flush = lambda: join_chains() if started else None
+        # a flush from inside a block (TDN_WGRAD_GROUP=0 flushes per layer) must see the chains' g tensors too
+        wq.pre_flush = join_chains
         for bi in reversed(range(len(net.blocks))):
             b, sv = net.blocks[bi], saved[bi]
+            route, extra, mask_src, need_dx = steps[bi]
             if g is None:
                 e = ext.get(bi)
                 if e is None:
                     continue  # nothing flows into this block's output
                 g = ops.add_relu_mask(e, None, sv[3])
-            extra = ext.get(bi - 1) if bi > 0 else None
-            mask_src = saved[bi - 1][3] if bi > 0 else None
-            need_dx = bi > 0 or net.stem is not None or need_net_dx
-            if chains is not None and need_dx:
+            if chains and need_dx:
                 if not started:        # the chains start behind everything the main stream has produced so far
                     ev0 = streams.record(main)
-                    for st_ in chains[0]:
+                    for st_ in pool:
                         streams.wait(st_, ev0)
                     started = True
-                g, gr = _block_bwd_chains(b, sv, g, extra, mask_src, wq, chains[0], chains[1])
+                g2, g1, dx = _block_dgrad_chains(b, route, sv, g, extra, mask_src, ranges)
             else:
-                if chains is not None and started:
-                    join_chains()      # this block runs on the main stream and reads what the chains produced
-                g, gr = _block_bwd(b, sv, g, extra, mask_src, need_dx, wq)
-            unit_grads.update(gr)
-            since_flush += 1
-            # Weight gradients are launched as groups: at the first block of a stage (resnet.py:130-136; the last one
-            # the backward pass reaches) and, inside long stages, every TDN_WGRAD_FLUSH blocks.  One group per stage
-            # is the most efficient launch, but it only becomes available when the stage's dgrad chain has ended: the
-            # timeline then alternates between stretches where a chain of small dgrad kernels has the GPU to itself
-            # (layer3: ~300 us) and bursts of weight-gradient work, and ends in a tail of weight gradients with nothing
-            # left beside them.  Half-stage groups keep both kinds of work on the GPU throughout.
-            if b.ud is not None or (flush_every > 0 and since_flush >= flush_every):
-                if chains is not None and started:
-                    join_chains()
+                join_chains()          # this block runs on the main stream and reads what the chains produced
+                g2, g1, dx = _block_dgrad(b, route, sv, g, extra, mask_src, getattr(sv[1], '_tdn_bits', None),
+                                          need_dx)
+            unit_grads.update(_block_wgrads(b, sv, g, g2, g1, wq))
+            g = dx
+            # Weight gradients are launched as one group per stage, at its first block (resnet.py:130-136; the last
+            # one the backward pass reaches).  Smaller groups (half stages) were measured: less efficient, and they
+            # slow the critical dgrad chain down.
+            if b.ud is not None:
+                join_chains()
                 wq.flush()
-                since_flush = 0
                 nflush += 1
                 for hook in FLUSH_HOOKS:
                     hook(nflush, nstages)
-        if chains is not None and started:
-            join_chains()
+        join_chains()
         dx_in = None
         if net.stem is not None:
             if g is not None:
@@ -1435,7 +1335,7 @@ class SeqNetFunction(torch.autograd.Function):
         for u in net.units():
             flat += unit_grads.get(u, [None] * len(u.params()))
         join_side_stream(ctx.dev)
-        return (None, dx_in) + tuple(flat)
+        return (None, dx_in, None) + tuple(flat)
 
 
 # ---------------------------------------------------------------------------------------------------

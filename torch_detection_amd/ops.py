@@ -264,11 +264,12 @@ def bottleneck_supported(H, W, C, stride=1, dilation=1):
     return bool(_lib.load().tdn_bottleneck_supported(int(H), int(W), int(C), int(stride), int(dilation)))
 
 
-def bottleneck_bit_planes(N, H, W, C, device):
+def bottleneck_bit_planes(N, H, W, C, device, head=False):
     """Empty ReLU bit planes of one bottleneck (1 bit per element; include/tdn.h: tdn_bottleneck_args.bits1..3):
-    (h1 > 0, h2 > 0) of C channels and (x > 0) of 4C channels, as int32 words [N][H][W][channels / 32]."""
+    (h1 > 0, h2 > 0) of C channels and (x > 0) of 4C channels, as int32 words [N][H][W][channels / 32].  ``head``:
+    only the first two (a head block's input is no mask source)."""
     mk = lambda ch: torch.empty(N, H, W, ch // 32, dtype=torch.int32, device=device)
-    return mk(C), mk(C), mk(4 * C)
+    return (mk(C), mk(C)) if head else (mk(C), mk(C), mk(4 * C))
 
 
 def _bottleneck_args(name, a, w1, w2, w3, affine, masks, outs, bits=None, head=None):

@@ -9,8 +9,9 @@ dependency with its own events.
 Capture rule (checked here, at capture time).  Inside a hipGraph capture two FORKED streams must not wait on each
 other: if side stream A has waited for an event of side stream B, B must not wait for an event of A (and vice versa)
 — synchronise them through the capture's origin stream instead (origin waits for both, both wait for the origin).
-Diagnosed on ROCm 7.2 / PyTorch 2.10 (round 3, ``TDN_CHAIN_SYNC`` in functional._blocks_fwd_split): with the two
-per-image chains each waiting for the other's per-block event the process died with SIGSEGV inside
+Diagnosed on ROCm 7.2 / PyTorch 2.10 (round 3, with a since-removed diagnostic that cross-joined the per-image forward
+chains after every few blocks): with the two per-image chains each waiting for the other's per-block event the process
+died with SIGSEGV inside
 ``hipStreamEndCapture`` (``torch.cuda.CUDAGraph.capture_end``, no message); the same dependencies expressed one-way
 (chain 1 waits for chain 0) or through the origin stream capture, instantiate and replay correctly.  The dependency
 graph is acyclic in all three cases — what differs is the runtime's bookkeeping of which capturing streams are tied to
