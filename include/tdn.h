@@ -65,19 +65,7 @@ typedef struct tdn_epilogue {
   const void* mask_src;  /* NHWC, same shape as the output, or NULL */
   int32_t out_f32;       /* 0: out is bf16 NHWC; 1: out is float32 NHWC */
   int32_t reserved;
-  /* Optional scratch for cross-workgroup split-K (small-M, long-K layers: too few output tiles for 256 CUs, so a tile's
-   * K range is cut over several workgroups and the last one to arrive sums the fp32 partials in split order —
-   * deterministic).  Layout: the first TDN_SPLITK_TICKET_BYTES bytes are per-tile arrival counters and must be ZERO
-   * before the first use (the kernels leave them zero); the rest holds partial tiles.  Must not be shared by launches
-   * that may run concurrently (one buffer per stream).  NULL / too small: the launch simply does not split. */
-  void* splitk_ws;
-  int64_t splitk_ws_bytes;
 } tdn_epilogue;
-#define TDN_SPLITK_TICKET_BYTES 65536
-/* One-time device probe (allocates and frees a few KB, synchronises the device — call it outside any stream capture;
- * torch_detection_amd._lib.load() does): do workgroups with equal blockIdx.x always run on the same XCD?  1 yes, 0 no.
- * The XCD-local form of the split-K exchange (TDN_SPLITK=1) is only used when it returned 1. */
-int tdn_probe_xcd_mapping(void);
 
 const char* tdn_last_error(void);
 int tdn_version(void);
@@ -478,7 +466,7 @@ int tdn_collate_images(const void* const* imgs, const int32_t* hw, const uint8_t
 /* ---- host-only introspection (no GPU needed; used by CPU tests) --------------------- */
 
 /* Describes the GEMM decomposition the library would launch for a conv: fills out[0..15] with
- * {M, Ngemm, Kgemm, BM, BN, BK, grid_x, grid_y, grid_z, nclasses, ntaps(class0), splitk, ...}.
+ * {M, Ngemm, Kgemm, BM, BN, BK, grid_x, grid_y, grid_z, nclasses, ntaps(class0), 1 (GEMM route), ...}.
  * kind: 0 = fwd, 1 = dgrad, 2 = wgrad.  A shape taken by the LDS-resident patch kernel (csrc/conv_halo.hip: 3x3
  * stride-1 convs) reports grid_z = 100 + its configuration id, out[11] = patch rows * 1000 + patch columns and
  * out[12] = chunk images held in LDS * 100 + output-channel passes per workgroup. */

@@ -23,10 +23,10 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert _lib.load().tdn_version() == 100
 
 
-def test_epilogue_struct_layout():
+def test_epilogue_struct_layout_without_split_k_scratch():
     from torch_detection_amd._lib import Epilogue
-    # mirror of tdn_epilogue: 3 pointers, 4 int32, pointer, 2 int32, pointer, int64 (LP64)
-    assert ctypes.sizeof(Epilogue) == 72
+    # mirror of tdn_epilogue: 3 pointers, 4 int32, pointer, 2 int32 (LP64)
+    assert ctypes.sizeof(Epilogue) == 56
     assert Epilogue.mask_src.offset == 40 and Epilogue.out_f32.offset == 48
 
 

@@ -48,14 +48,12 @@ def test_mutual_wait_between_forked_streams_is_refused_in_capture():
     torch.cuda.synchronize()
 
 
-def test_graphed_step_captures_with_split_k_scratch(monkeypatch):
-    """ADVICE (round 3): with TDN_SPLITK on, the split-K scratch is created during GraphedStep's warm-up, keyed by the
-    raw stream; the capture must run on that same stream to find it again (it may not allocate).  captured == True."""
+def test_graphed_step_captures_on_the_warm_up_stream():
+    """ADVICE (round 3): per-stream state — the side / chain stream pools — is created during GraphedStep's warm-up,
+    keyed by the raw stream; the capture must run on that same stream to find it again (it may not allocate).
+    captured == True."""
     import torch_detection_amd as T
-    from torch_detection_amd import _lib
     from torch_detection_amd.graph import GraphedStep
-    monkeypatch.setenv("TDN_SPLITK", "2")
-    _lib.load()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     net = T.BACKBONES.module_dict["ResNet"](50)

@@ -16,7 +16,6 @@ LIB_PATH = os.path.join(_HERE, os.path.basename(os.environ.get("TDN_LIB", "") or
 
 TDN_BF16 = 0
 TDN_F16 = 1
-SPLITK_TICKET_BYTES = 65536
 ADD_NONE, ADD_SAME, ADD_UP2X, ADD_SUMPOOL2 = 0, 1, 2, 3
 
 c_void_p = ctypes.c_void_p
@@ -38,8 +37,6 @@ class Epilogue(ctypes.Structure):
         ("mask_src", c_void_p),
         ("out_f32", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
-        ("splitk_ws", c_void_p),
-        ("splitk_ws_bytes", c_i64),
     ]
 
 
@@ -188,7 +185,6 @@ SIGNATURES = {
     "tdn_plan_run": (c_int, [c_void_p]),
     "tdn_plan_stats": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "tdn_plan_free": (c_int, [c_void_p]),
-    "tdn_probe_xcd_mapping": (c_int, []),
     "tdn_conv2d_plan": (c_int, [c_int] * 9 + [ctypes.POINTER(ctypes.c_int32)]),
     "tdn_debug_trace": (c_int, [c_void_p, ctypes.c_longlong]),
 }
@@ -212,8 +208,6 @@ def load():
         fn.restype = res
         fn.argtypes = args
     _lib = lib
-    if torch.cuda.is_available() and os.environ.get("TDN_SPLITK", "0") == "1":
-        lib.tdn_probe_xcd_mapping()    # once per process, before anything could be capturing a stream
     return lib
 
 

@@ -175,12 +175,3 @@ struct tdn_attr_once {
   }
   void mark() { if (dev >= 0) done[dev] = true; }
 };
-
-// XCD-aware bijective remap: blocks b, b+8, b+16.. share an XCD (observed round-robin placement,
-// speed only) -> give each XCD a contiguous chunk of tile ids so neighbours share L2 lines.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7;
-  const int xcd = bid & 7, idx = bid >> 3;
-  const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + idx;
-}

@@ -13,7 +13,6 @@
 // A "class" is a sub-lattice of output pixels sharing one tap list: forward and stride-1 dgrad have one
 // class; stride-2 dgrad has four output-parity classes (gather form, no atomics, no zero-insertion).
 #include "common.h"
-#include <vector>
 
 // conv_halo.hip: LDS-resident activation patch kernel for 3x3 / 1x1 convs (stride-1 3x3, any 1x1 forward; stride-1
 // input gradients).  Each returns 1 when it launched, 0 when the shape stays with the generic kernel below.
@@ -59,15 +58,8 @@ struct GemmParams {
   int addend_mode, addend_h, addend_w, relu, out_f32;
   int tiles_n, nwg_pad;
   unsigned tn_mul, tn_shr;   // fast_div by tiles_n
-  int ncls, krot;
+  int ncls;
   int grouped;   // block-diagonal grouped conv: the output tile's 64 channels see only the same 64 input channels
-  // cross-workgroup split-K (gridDim.z = splitk workgroups per output tile, each over a contiguous range of K-steps)
-  int splitk;
-  int split_local;               // XCD-local exchange (the dispatch-to-XCD mapping was verified), else agent scope
-  float* slab;                   // fp32 partial tiles: [class * nwg_pad + tile][split][BM * BN]
-  unsigned long long* ticket;    // per tile: arrivals (bits 0..3) + arrivals per XCD (4 bits each from bit 4); zero at rest
-  void* ws;                      // caller's split-K scratch (tdn_epilogue.splitk_ws) or NULL
-  long long ws_bytes;
   unsigned long long* trace;   // TAG 2 instantiations only: 32 timestamps per workgroup (scripts/trace_gemm.py)
   GemmClass cls[4];
 };
@@ -228,31 +220,13 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
   const int kchunks = p.grouped ? 1 : p.Ktap / BK;
   const int in_kc0 = p.grouped ? n0 / BK : 0;
   const int T = ntaps * kchunks;
-  // cross-workgroup split-K: this workgroup multiplies K-steps [t_begin, t_end) of its tile
-  const int nsplit = (KG == 1) ? p.splitk : 1;
-  const int split = (nsplit > 1) ? (int)blockIdx.z : 0;
-  int t_begin = 0, t_end = T;
-  if (nsplit > 1) {
-    const int per = (T + nsplit - 1) / nsplit;
-    t_begin = min(T, split * per);
-    t_end = min(T, t_begin + per);
-  }
-  const int Tg = KG == 1 ? (t_end - t_begin) : (T + KG - 1) / KG;   // K-steps per group (shared barriers)
+  const int Tg = KG == 1 ? T : (T + KG - 1) / KG;   // K-steps per group (shared barriers)
   // K order: channel chunk outermost, taps innermost.  All taps of a chunk touch the same input lines (shifted by
   // a pixel or a row), so within ~ntaps K-steps the workgroups of an XCD re-read a working set of
   // (pixels + halo) x 128 B instead of cycling through the whole (pixels x Cin) slab — the latter overflows the
   // 4 MB L2 for 256-channel 3x3 layers and drops the LDS-DMA stream to Infinity-Cache speed (~10 TB/s measured).
-  // Every workgroup starts its K loop at a different channel chunk (the sum over K is order-independent): tiles run
-  // in near lock-step, and with all of them on chunk c at once every row they request (pixel stride Cin*2 B,
-  // weight-row stride K*2 B — multiples of 512 B) lands on the same few L2 channels.  Opt-in: TDN_KROT=1.
-  int ld_tap = 0, ld_issued = grp;   // ld_issued: global index of the next K-step this group issues
-  int ld_kc = p.krot ? (tile_m + tile_n) % kchunks : 0;   // (tap, channel chunk) of the next K-step to be issued
-  if (nsplit > 1) {                  // start at K-step t_begin: chunk t / ntaps (from the start chunk), tap t % ntaps
-    const int c_adv = t_begin / ntaps;
-    ld_tap = t_begin - c_adv * ntaps;
-    ld_kc = (ld_kc + c_adv) % kchunks;
-    ld_issued = t_begin;
-  }
+  int ld_tap = 0, ld_kc = 0;         // (tap, channel chunk) of the next K-step to be issued
+  int ld_issued = grp;               // global index of the next K-step this group issues
   auto advance_k = [&]() {   // taps innermost
     if (++ld_tap == ntaps) { ld_tap = 0; ld_kc = (ld_kc + 1 == kchunks) ? 0 : ld_kc + 1; }
   };
@@ -264,7 +238,7 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
   auto stage_load = [&](int s) {
     char* sA = smem + s * STAGE + wave * (RPI * ROWB);
     char* sB = sA + A_BYTES;
-    if (ld_issued < t_end) {
+    if (ld_issued < T) {
       ld_issued += KG;
       const int tp = __builtin_amdgcn_readlane(tapv, ld_tap);
       const int dh = (tp & 0xff) - 64, dw = ((tp >> 8) & 0xff) - 64, widx = tp >> 16;
@@ -561,94 +535,6 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
     TDN_TRACE(27);
   }
 
-  // ---- cross-workgroup split-K: publish the partial tile; the last workgroup to arrive sums all of them ----
-  // The sum runs over the splits in index order (this workgroup's own partial taken from its registers at its
-  // position): the result does not depend on who is last.  Two ways to exchange:
-  //   * XCD-local (p.split_local): all splits of a tile share blockIdx.x, and a dispatch hands workgroup x to XCD
-  //     x mod 8 (each XCD takes its share of the packet; checked once per process by tdn_probe_xcd_mapping) — so the
-  //     peers share ONE L2, which is the coherence point of its CUs: plain stores, an L2 atomic, an L1 invalidate and
-  //     plain loads, ~1 us.  The arrival counter also counts arrivals per XCD; a peer on another XCD would never
-  //     complete the count — the probe is what rules that out.
-  //   * agent scope: write-through stores, a memory-side atomic and L2-bypassing loads — correct wherever the peers
-  //     run, but ~10 us of serial latency per tile (measured slower than not splitting on every layer).
-  if constexpr (KG == 1) {
-    if (nsplit > 1) {
-      constexpr int PART64 = BM * BN / 2;                     // 64-bit words per partial tile
-      const int tile_lin = (int)blockIdx.y * p.nwg_pad + tile;
-      unsigned long long* slab = (unsigned long long*)p.slab + (size_t)tile_lin * nsplit * PART64;
-      unsigned long long* mine = slab + (size_t)split * PART64;
-      const bool local = p.split_local != 0;
-#pragma unroll
-      for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) {
-          const size_t at = ((size_t)(i * FM + j) * (NW * 64) + tid) * 2;
-          const f32x4_t a = acc[i][j];
-          if (local) {
-            *(f32x4_t*)(mine + at) = a;
-          } else {
-            const unsigned long long lo = ((unsigned long long)__float_as_uint(a[1]) << 32) | __float_as_uint(a[0]);
-            const unsigned long long hi = ((unsigned long long)__float_as_uint(a[3]) << 32) | __float_as_uint(a[2]);
-            __hip_atomic_store(mine + at, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(mine + at + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this lane's partial has reached L2 / memory
-      __shared__ unsigned long long s_total;
-      __syncthreads();                                        // ... and every lane's
-      unsigned xcc = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-#endif
-      xcc &= 7u;
-      if (tid == 0) {
-        const unsigned long long inc = 1ull | (1ull << (4 + 4 * xcc));
-        unsigned long long old;
-        if (local) old = __hip_atomic_fetch_add(p.ticket + tile_lin, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        else old = __hip_atomic_fetch_add(p.ticket + tile_lin, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_total = old + inc;
-      }
-      __syncthreads();
-      const unsigned long long total = s_total;
-      if ((int)(total & 15ull) != nsplit) return;             // not the last one: done
-      if (tid == 0) {                                         // zero at rest
-        if (local) __hip_atomic_store(p.ticket + tile_lin, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        else __hip_atomic_store(p.ticket + tile_lin, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      const bool same_xcd = (int)((total >> (4 + 4 * xcc)) & 15ull) == nsplit;
-#if defined(__HIP_DEVICE_COMPILE__)
-      if (local) asm volatile("buffer_inv sc0" ::: "memory");   // nothing of the slab may come from this CU's L1
-#endif
-#pragma unroll
-      for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) {
-          const size_t at = ((size_t)(i * FM + j) * (NW * 64) + tid) * 2;
-          f32x4_t sum = {0.f, 0.f, 0.f, 0.f};
-          for (int sp = 0; sp < nsplit; ++sp) {
-            f32x4_t v;
-            if (sp == split) {
-              v = acc[i][j];
-            } else {
-              const unsigned long long* src = slab + (size_t)sp * PART64 + at;
-              if (local || same_xcd) {
-                v = *(const f32x4_t*)src;
-              } else {
-                const unsigned long long lo = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long hi = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                v[0] = __uint_as_float((unsigned)lo);
-                v[1] = __uint_as_float((unsigned)(lo >> 32));
-                v[2] = __uint_as_float((unsigned)hi);
-                v[3] = __uint_as_float((unsigned)(hi >> 32));
-              }
-            }
-            sum = (sp == 0) ? v : sum + v;
-          }
-          acc[i][j] = sum;
-        }
-    }
-  }
-
   // ---- split-K groups: exchange the partial accumulators through LDS (the rings are idle now) ----
   // layout: [group][wave][fragment][lane] x 16 B, conflict-free 16-byte accesses; summed in group order 0..KG-1 by
   // whichever group owns the fragment, so the result does not depend on the ownership map
@@ -916,80 +802,7 @@ static const GemmCfg kCfgs[] = {
 };
 static const int kNumCfgs = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
 
-// ---- workgroup -> XCD mapping probe -------------------------------------------------------------------------------
-// The XCD-local split-K exchange needs every workgroup with the same blockIdx.x to run on the same XCD whatever its
-// blockIdx.y / z.  That is how a dispatch is shared out (every XCD takes the workgroups whose linear id is congruent
-// to its index; grid.x is a multiple of 8 here); this probe checks it on the device once per process — three grid
-// shapes, HW_REG_XCC_ID per workgroup — and the XCD-local mode is only used if it held.
-__global__ void xcd_probe_kernel(unsigned* out) {
-  if (threadIdx.x == 0) {
-    unsigned xcc = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-#endif
-    out[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = xcc & 15u;
-  }
-}
-
-static int g_xcd_static = -1;   // -1 not probed, 0 mapping does not hold (or probe failed), 1 holds
-
-extern "C" int tdn_probe_xcd_mapping(void) {
-  if (g_xcd_static >= 0) return g_xcd_static;
-  const int shapes[3][3] = {{64, 1, 4}, {40, 4, 3}, {264, 1, 7}};
-  unsigned* dev = nullptr;
-  const size_t cap = 264 * 7 * 4;
-  if (hipMalloc(&dev, cap * sizeof(unsigned)) != hipSuccess) { g_xcd_static = 0; return 0; }
-  std::vector<unsigned> host(cap);
-  int ok = 1;
-  for (int s = 0; s < 3 && ok; ++s) {
-    const int gx = shapes[s][0], gy = shapes[s][1], gz = shapes[s][2];
-    hipLaunchKernelGGL(xcd_probe_kernel, dim3(gx, gy, gz), dim3(512), 0, nullptr, dev);
-    if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(host.data(), dev, (size_t)gx * gy * gz * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) {
-      ok = 0;
-      break;
-    }
-    for (int z = 0; z < gz && ok; ++z)
-      for (int y = 0; y < gy && ok; ++y)
-        for (int x = 0; x < gx; ++x)
-          if (host[((size_t)z * gy + y) * gx + x] != host[x % 8]) { ok = 0; break; }
-  }
-  (void)hipFree(dev);
-  g_xcd_static = ok;
-  return ok;
-}
-
-// Cross-workgroup split-K (see the kernel): for layers whose 128x128 tiles cannot fill the chip and whose K loop is
-// long enough to cut.  OFF by default: measured on MI355X (scripts/conv_bench.py, every layer3 / layer4 / top-FPN
-// shape at batch 1 and 2) it loses to the tuned unsplit tiles in both exchange modes — one image, unsplit / XCD-local
-// / agent scope: layer4 3x3 28 / 32 / 37 us, 2048->512 11 / 21 / 24, 2048->256 lateral 11 / 16 / 21, layer3 3x3
-// 19 / 22 / 29; whole step 436 / 420 / 403 img/s.  The agent-scope chain (write-through stores, memory-side atomic,
-// L2-bypassing loads) is ~10 us of serial latency per tile; the XCD-local one ~4 us — still more than the shorter
-// K loops save, because what bounds these launches is the per-workgroup fixed cost, which splitting multiplies.
-// TDN_SPLITK_WGS = workgroups aimed at (default 320), TDN_SPLITK_MINT = fewest K-steps per split.
-// TDN_SPLITK: 0 off, 1 XCD-local exchange (needs the probe to have passed, else off), 2 agent-scope exchange.
-static int splitk_mode() {
-  const char* e = getenv("TDN_SPLITK");
-  const int m = (e && *e) ? atoi(e) : 0;
-  if (m == 1) return g_xcd_static == 1 ? 1 : 0;
-  return m == 2 ? 2 : 0;
-}
-
-static int splitk_for(int tiles, int T) {
-  if (splitk_mode() == 0) return 1;
-  const int wgs = getenv("TDN_SPLITK_WGS") ? atoi(getenv("TDN_SPLITK_WGS")) : 320;
-  const int mint = getenv("TDN_SPLITK_MINT") ? atoi(getenv("TDN_SPLITK_MINT")) : 6;
-  if (tiles <= 0 || T < 2 * mint) return 1;
-  int S = wgs / tiles;
-  if (S > 8) S = 8;
-  while (S > 1 && T / S < mint) --S;
-  // every split must own at least one K-step: with per = ceil(T / S) the last one starts at (S - 1) * per
-  while (S > 1 && (S - 1) * ((T + S - 1) / S) >= T) --S;
-  return S < 1 ? 1 : S;
-}
-
-static int choose_cfg(int maxM, int ngemm, int kgemm, int grouped = 0, int ktap = 64, int ncls = 1,
-                      bool can_split = false) {
+static int choose_cfg(int maxM, int ngemm, int kgemm, int grouped = 0, int ktap = 64) {
   if (grouped) return 0;   // block-diagonal grouped conv: one 64-channel block per N tile
   if (const char* env = getenv("TDN_GEMM_CFG")) {
     const int id = atoi(env);
@@ -1019,14 +832,10 @@ static int choose_cfg(int maxM, int ngemm, int kgemm, int grouped = 0, int ktap 
   // workgroup on almost every shape; only the very large-M 3x3 convs prefer the 256x128 8-wave tile.
   const int big_minm = getenv("TDN_T192_MINM") ? atoi(getenv("TDN_T192_MINM")) : 24000;
   if (ngemm % 256 == 0 && maxM >= big_minm) return 3;   // 192x256, 8 waves: fewest L2->LDS bytes per flop
-  // too few 128x128 tiles for the chip but a K loop long enough to cut: 128x128 tiles (half the L2->LDS bytes per
-  // flop of 64x64) with the K range shared out over several workgroups per tile
-  if (can_split && ngemm % 128 == 0 && ktap % 64 == 0) {
-    const int tiles128 = ceil_div(maxM, 128) * (ngemm / 128) * ncls;
-    if (splitk_for(tiles128, kgemm / 64) > 1) return 46;
-  }
   // few tiles and a long K loop (layer4, the top FPN levels): every CU holds at most two 4-wave workgroups and the
-  // LDS-DMA stream starves (~4 B/clk per loading wave) — recruit a second wave group along K (in-workgroup split-K)
+  // LDS-DMA stream starves (~4 B/clk per loading wave) — recruit a second wave group along K (in-workgroup split-K).
+  // Cutting K over several workgroups with an exchange through memory lost to the unsplit tiles on every such layer
+  // (layer4 3x3: 28 us unsplit, 32 / 37 us XCD-local / agent scope): it multiplies the per-workgroup fixed cost.
   const int kg_tiles = getenv("TDN_KG_TILES") ? atoi(getenv("TDN_KG_TILES")) : 512;
   const int kg_kmin = getenv("TDN_KG_KMIN") ? atoi(getenv("TDN_KG_KMIN")) : 2048;
   if ((long)ceil_div(maxM, 64) * (ngemm / 64) <= kg_tiles && kgemm >= kg_kmin) return 25;
@@ -1069,10 +878,6 @@ static int launch_gemm(GemmParams& p, int maxM, hipStream_t stream) {
   p.tiles_n = p.Cout / BN;
   fast_div_init((unsigned)p.tiles_n, &p.tn_mul, &p.tn_shr);
   p.trace = nullptr;
-  {
-    const char* kr = getenv("TDN_KROT");
-    p.krot = (kr && kr[0] == '1') ? 1 : 0;   // measured: no gain (profiles/), off keeps results tile-independent
-  }
   const int ntiles = ceil_div(maxM, BM) * p.tiles_n;
   p.nwg_pad = (ntiles + 7) & ~7;
   constexpr size_t lds = (size_t)KG * NSTAGE * (BM + BN) * BK * 2;
@@ -1095,24 +900,7 @@ static int launch_gemm(GemmParams& p, int maxM, hipStream_t stream) {
               "trace config selected but tdn_debug_trace() buffer is missing or too small");
     p.trace = g_trace_buf;
   }
-  // cross-workgroup split-K where the caller gave scratch and the tile count / K length call for it
-  int splitk = 1;
-  if (KG == 1 && TAG == 0 && MODE != 3 && MODE != 4 && MODE != 7 && MODE != 8 && p.ws != nullptr && !p.grouped) {
-    const int T = p.cls[0].ntaps * (p.Ktap / BK);
-    const int tiles_lin = p.nwg_pad * p.ncls;
-    int S = splitk_for(ntiles * p.ncls, T);
-    while (S > 1 && (tiles_lin > TDN_SPLITK_TICKET_BYTES / 8 ||
-                     TDN_SPLITK_TICKET_BYTES + (int64_t)tiles_lin * S * BM * BN * 4 > p.ws_bytes))
-      --S;
-    if (S > 1) {
-      splitk = S;
-      p.ticket = (unsigned long long*)p.ws;
-      p.slab = (float*)((char*)p.ws + TDN_SPLITK_TICKET_BYTES);
-    }
-  }
-  p.splitk = splitk;
-  p.split_local = splitk_mode() == 1 ? 1 : 0;
-  dim3 grid(p.nwg_pad, p.ncls, splitk), block(WM * WN * KG * 64, 1, 1);
+  dim3 grid(p.nwg_pad, p.ncls, 1), block(WM * WN * KG * 64, 1, 1);
   TDN_LAUNCH((conv_gemm_kernel<BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, F16>), grid, block, lds, stream, p);
   TDN_LAUNCH_CHECK();
   return 0;
@@ -1121,7 +909,7 @@ static int launch_gemm(GemmParams& p, int maxM, hipStream_t stream) {
 static int dispatch_gemm(GemmParams& p, int maxM, hipStream_t stream, int dtype) {
   if (maxM <= 0) return 0;
   if (dtype == TDN_F16) {   // fp16 operands: the production tile set only
-    const int id = choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap, p.ncls, p.ws != nullptr);
+    const int id = choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap);
     switch (id) {
       case 0: return launch_gemm<64, 64, 64, 2, 2, 2, 0, 0, 1, true>(p, maxM, stream);
       case 1: return launch_gemm<64, 128, 64, 2, 2, 2, 6, 0, 1, true>(p, maxM, stream);
@@ -1133,7 +921,7 @@ static int dispatch_gemm(GemmParams& p, int maxM, hipStream_t stream, int dtype)
       default: TDN_CHECK(false, "GEMM config %d (TDN_GEMM_CFG) has no TDN_F16 build", id); return -1;
     }
   }
-  switch (choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap, p.ncls, p.ws != nullptr)) {
+  switch (choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap)) {
     case 0: return launch_gemm<64, 64, 64, 2, 2, 2, 0>(p, maxM, stream);
     case 1: return launch_gemm<64, 128, 64, 2, 2, 2, 6>(p, maxM, stream);
     case 2: return launch_gemm<128, 128, 64, 2, 2, 2, 6>(p, maxM, stream);
@@ -1211,12 +999,7 @@ static int dispatch_gemm(GemmParams& p, int maxM, hipStream_t stream, int dtype)
 static int fill_epilogue(GemmParams& p, const tdn_epilogue* ep, int Hout, int Wout) {
   p.scale = nullptr; p.shift = nullptr; p.addend = nullptr; p.mask = nullptr;
   p.addend_mode = TDN_ADD_NONE; p.addend_h = 0; p.addend_w = 0; p.relu = 0; p.out_f32 = 0;
-  p.ws = nullptr; p.ws_bytes = 0; p.splitk = 1; p.slab = nullptr; p.ticket = nullptr;
   if (!ep) return 0;
-  if (ep->splitk_ws && ep->splitk_ws_bytes > TDN_SPLITK_TICKET_BYTES && ((uintptr_t)ep->splitk_ws & 255) == 0) {
-    p.ws = ep->splitk_ws;
-    p.ws_bytes = ep->splitk_ws_bytes;
-  }
   p.out_f32 = ep->out_f32 ? 1 : 0;
   p.scale = ep->scale;
   p.shift = ep->shift;

@@ -108,9 +108,9 @@ class GraphedStep(object):
             # thread_local: other threads (the process group's watchdog, the allocator's helpers) are not policed
             # during the capture; the launches autograd's device thread makes into the capturing streams are captured
             # either way
-            # capture on the stream the warm-up ran on: per-(device, stream) state created during warm-up — the
-            # split-K scratch of ops.splitk_workspace, the side / chain stream pools of functional.py — is keyed by the
-            # raw stream and must be found again inside the capture (nothing may be allocated there)
+            # capture on the stream the warm-up ran on: per-(device, stream) state created during warm-up — the side /
+            # chain stream pools of functional.py — is keyed by the raw stream and must be found again inside the
+            # capture (nothing may be allocated there)
             from . import streams
             streams.capture_started(side.cuda_stream)
             try:
