@@ -411,6 +411,63 @@ int tdn_bbox_normalize(float* bbox, int64_t rows, const float* means4, const flo
 int tdn_bbox_denormalize(const float* bbox, float* out, int64_t rows, int cols, const float* means4,
                          const float* stds4, void* stream);
 
+/* ---- box delta encode / decode, segmented NMS, RPN proposals (the project's own spec in the
+ *      mmdetection-v0.x lineage of SURVEY Appendix B; '+1' boxes, strict IEEE fp32 in the spec's operation order) ---- */
+
+/* deltas[N][4] = (encode(proposals, gt) - means) / stds:  dx = (gx - px) / pw, dw = log(gw / pw), ... */
+int tdn_bbox2delta(const float* proposals, const float* gt, int64_t N, const float* means4, const float* stds4,
+                   float* deltas, void* stream);
+/* out[N][4C] = rois[N][4] decoded by deltas[N][4C] * stds + means; dw, dh clamped to +-|log(wh_ratio_clip)| (fp32);
+ * max_shape: HOST int32 (h, w) to clip x to [0, w-1] and y to [0, h-1], or NULL. */
+int tdn_delta2bbox(const float* rois, const float* deltas, int64_t N, int C, const float* means4,
+                   const float* stds4, const int32_t* max_shape, double wh_ratio_clip, float* out, void* stream);
+
+/* Greedy NMS of S contiguous segments in one call: segment s = rows [seg_offsets[s], seg_offsets[s+1]) (device int64),
+ * at most TDN_NMS_SEG_MAX rows; rows of different segments never suppress each other.  Order inside a segment: score
+ * desc, ties lower index first; suppress iou > thr.  keep[N] uint8 (input order, 0 outside every segment),
+ * kept_idx[N] int64: in each segment's row range its kept indices in score order, padded with -1; counts[S] int32
+ * (device): kept per segment, -1 for a segment whose offsets are out of order / range or that is too long (its rows
+ * are then left unkept).  No host synchronisation.  workspace: tdn_batched_nms_workspace(N, S) bytes, 256-aligned. */
+#define TDN_NMS_SEG_MAX 4096
+int64_t tdn_batched_nms_workspace(int N, int S);
+int tdn_batched_nms(const float* boxes, const float* scores, int N, const int64_t* seg_offsets, int S, float iou_thr,
+                    uint8_t* keep, int64_t* kept_idx, int32_t* counts, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+
+/* RPN proposals (sigmoid classification, NMS per level) of B images and `nlevels` pyramid levels in 4 launches.
+ * Level l: logits (B, A, H, W) and deltas (B, 4A, H, W) in TDN_F32 or TDN_BF16, read through their element strides
+ * (n, c, h, w) — NCHW, channels_last or anything else; anchors (H*W*A, 4) fp32 in (y, x, a) order, shared by all
+ * images.  levels: HOST array.  img_shapes: device int32 [B][2] = (h, w).
+ * Outputs (device): proposals [B][max_num][5] = x1, y1, x2, y2, sigmoid(logit), anchor_idx [B][max_num] int64 (row of
+ * the concatenated pyramid), counts [B] int32; unused rows 0 / -1.  Limits: 1..8 levels, 1 <= B <= 64, every segment
+ * entering NMS <= TDN_NMS_SEG_MAX boxes (nms_pre, or the level's anchors when nms_pre = 0), max_num <= 8192.
+ * workspace: tdn_rpn_proposals_workspace() bytes, 256-aligned. */
+enum { TDN_F32 = 2 };
+#define TDN_RPN_MAX_LEVELS 8
+#define TDN_RPN_MAX_NUM 8192
+typedef struct tdn_rpn_level {
+  const void* logits;          /* device, (B, A, H, W) */
+  const void* deltas;          /* device, (B, 4A, H, W): channel 4a+j = coordinate j of anchor a */
+  const float* anchors;        /* device, fp32 [H*W*A][4] */
+  int64_t logit_strides[4];    /* elements: n, c, h, w */
+  int64_t delta_strides[4];
+  int32_t dtype;               /* TDN_F32 or TDN_BF16, both tensors */
+  int32_t H, W, A;
+} tdn_rpn_level;
+typedef struct tdn_rpn_config {
+  int32_t nms_pre;             /* > 0: top nms_pre anchors per level by logit; 0: all */
+  int32_t nms_post;            /* > 0: survivors kept per level */
+  int32_t max_num;             /* 1..8192: proposals per image */
+  float nms_thr;
+  float min_bbox_size;         /* > 0: drop boxes with x2-x1+1 or y2-y1+1 below it */
+  float means[4], stds[4];     /* target_means / target_stds of the deltas */
+  int32_t reserved;
+} tdn_rpn_config;
+int64_t tdn_rpn_proposals_workspace(const tdn_rpn_level* levels, int nlevels, int B, const tdn_rpn_config* cfg);
+int tdn_rpn_proposals(const tdn_rpn_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                      const tdn_rpn_config* cfg, float* proposals, int64_t* anchor_idx, int32_t* counts,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

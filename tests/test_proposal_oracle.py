@@ -1,0 +1,174 @@
+"""CPU: known answers of the box-delta / RPN-proposal oracle (tests/proposal_ref.py) and the C-ABI
+layout of the new structs."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+import proposal_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+
+
+def sig(x):
+    return f32(1) / (f32(1) + f32(np.exp(-np.float64(x))))
+
+
+def test_zero_deltas_give_integer_anchors_back_and_encode_of_self_is_zero():
+    g = np.random.default_rng(0)
+    xy = g.integers(0, 1200, (500, 2))
+    a = np.concatenate([xy, xy + g.integers(0, 400, (500, 2))], 1).astype(f32)
+    out = R.delta2bbox(a, np.zeros((500, 8), f32))
+    assert np.array_equal(out.view(np.uint32), np.tile(a, 2).view(np.uint32))
+    assert np.array_equal(R.bbox2delta(a, a), np.zeros((500, 4), f32))
+    assert np.array_equal(R.bbox2delta(a, a, (0, 0, 0, 0), (0.1, 0.1, 0.2, 0.2)), np.zeros((500, 4), f32))
+
+
+def test_decode_of_encode_round_trips():
+    g = np.random.default_rng(1)
+    p = np.concatenate([g.uniform(0, 800, (1000, 2)), g.uniform(0, 800, (1000, 2)) + 900], 1).astype(f32)
+    gt = np.concatenate([g.uniform(0, 800, (1000, 2)), g.uniform(0, 800, (1000, 2)) + 900], 1).astype(f32)
+    means, stds = (0.1, 0.0, -0.1, 0.05), (0.1, 0.1, 0.2, 0.2)
+    back = R.delta2bbox(p, R.bbox2delta(p, gt, means, stds), means, stds)
+    assert np.allclose(back, gt, rtol=0, atol=2e-3)
+
+
+def test_dw_dh_clamp_at_log_of_wh_ratio_clip():
+    assert R.max_ratio() == f32(4.1351666) and R.max_ratio(16 / 1000) == f32(abs(np.log(0.016)))
+    roi = np.array([[0, 0, 15, 15]], f32)                  # pw = ph = 16, centre 7.5
+    big = R.delta2bbox(roi, np.array([[0, 0, 10, 10]], f32))
+    at = R.delta2bbox(roi, np.array([[0, 0, 4.1351666, 4.1351666]], f32))
+    assert np.array_equal(big, at)                         # clamped to exactly the limit
+    gw = f32(16) * f32(np.exp(np.float64(f32(4.1351666))))
+    assert abs(float(gw) - 1000.0) < 1e-3
+    assert np.array_equal(big[0], np.array([7.5 - gw * f32(0.5) + f32(0.5), 7.5 - gw * f32(0.5) + f32(0.5),
+                                            7.5 + gw * f32(0.5) - f32(0.5), 7.5 + gw * f32(0.5) - f32(0.5)], f32))
+    small = R.delta2bbox(roi, np.array([[0, 0, -10, -10]], f32))
+    assert np.array_equal(small, R.delta2bbox(roi, np.array([[0, 0, -4.1351666, -4.1351666]], f32)))
+    assert abs(float(small[0, 2] - small[0, 0]) - (0.256 - 1)) < 1e-5
+
+
+def test_clip_to_image():
+    roi = np.array([[0, 0, 15, 15], [40, 30, 70, 60]], f32)
+    d = np.array([[-1, -1, 0, 0], [0.5, 0.5, 0.3, 0.3]], f32)
+    out = R.delta2bbox(roi, d, max_shape=(50, 60))
+    assert out[:, 0::2].min() >= 0 and out[:, 0::2].max() <= 59 and out[:, 1::2].min() >= 0 and out[:, 1::2].max() <= 49
+    assert np.array_equal(out[0], np.array([0, 0, 0, 0], f32))   # [-16, -16, -1, -1] clipped
+    assert out[1, 2] == 59 and out[1, 3] == 49
+    free = R.delta2bbox(roi, d)
+    assert np.array_equal(out, np.minimum(np.maximum(free, 0), np.array([59, 49, 59, 49], f32)))
+
+
+def _two_levels(l0, l1, a0=((0, 0, 15, 15), (16, 0, 31, 15))):
+    cls = [np.array(l0, f32).reshape(1, 1, 1, 2), np.array(l1, f32).reshape(1, 1, 1, 1)]
+    reg = [np.zeros((1, 4, 1, 2), f32), np.zeros((1, 4, 1, 1), f32)]
+    anchors = [np.array(a0, f32), np.array([[0, 0, 31, 31]], f32)]
+    return cls, reg, anchors
+
+
+def test_hand_built_two_level_case():
+    cls, reg, anchors = _two_levels([2.0, 1.0], [1.5])
+    p, a, c = R.rpn_proposals(cls, reg, anchors, [(100, 100)], max_num=4)
+    assert c.tolist() == [3] and a.tolist() == [[0, 2, 1, -1]]
+    assert np.array_equal(p[0], np.array([[0, 0, 15, 15, sig(2.0)], [0, 0, 31, 31, sig(1.5)],
+                                          [16, 0, 31, 15, sig(1.0)], [0, 0, 0, 0, 0]], f32))
+    # nms_pre = 1: level 0 sends only its best anchor
+    p, a, c = R.rpn_proposals(cls, reg, anchors, [(100, 100)], nms_pre=1, max_num=4)
+    assert c.tolist() == [2] and a.tolist() == [[0, 2, -1, -1]]
+    # max_num = 2 keeps the two best across levels
+    p, a, c = R.rpn_proposals(cls, reg, anchors, [(100, 100)], max_num=2)
+    assert a.tolist() == [[0, 2]]
+    # NMS inside a level: IoU([0,0,15,15], [1,0,16,15]) = 240 / 272 > 0.7, the higher logit survives
+    cls, reg, anchors = _two_levels([1.0, 2.0], [1.5], a0=((0, 0, 15, 15), (1, 0, 16, 15)))
+    p, a, c = R.rpn_proposals(cls, reg, anchors, [(100, 100)], max_num=4)
+    assert c.tolist() == [2] and a.tolist() == [[1, 2, -1, -1]]
+    assert np.array_equal(p[0, :2], np.array([[1, 0, 16, 15, sig(2.0)], [0, 0, 31, 31, sig(1.5)]], f32))
+    # ... but boxes of different levels never suppress each other (the level-1 box covers both)
+    p, a, c = R.rpn_proposals(cls, reg, anchors, [(100, 100)], max_num=4, nms_thr=0.2)
+    assert a.tolist() == [[1, 2, -1, -1]]
+    # min_bbox_size drops the 16x16 boxes; clipping to a 10 x 20 image
+    cls, reg, anchors = _two_levels([2.0, 1.0], [1.5])
+    p, a, c = R.rpn_proposals(cls, reg, anchors, [(100, 100)], min_bbox_size=17, max_num=4)
+    assert a.tolist() == [[2, -1, -1, -1]]
+    p, a, c = R.rpn_proposals(cls, reg, anchors, [(10, 20)], max_num=4)
+    assert np.array_equal(p[0, :3, :4], np.array([[0, 0, 15, 9], [0, 0, 19, 9], [16, 0, 19, 9]], f32))
+
+
+def test_ties_go_to_the_lower_anchor():
+    cls, reg, anchors = _two_levels([0.5, 0.5], [0.5])
+    _, a, _ = R.rpn_proposals(cls, reg, anchors, [(100, 100)], max_num=3)
+    assert a.tolist() == [[0, 1, 2]]                        # equal logits: level, then anchor
+    _, a, _ = R.rpn_proposals(cls, reg, anchors, [(100, 100)], nms_pre=1, max_num=3)
+    assert a.tolist() == [[0, 2, -1]]                       # the nms_pre cut takes the lower anchor
+    _, a, _ = R.rpn_proposals(cls, reg, anchors, [(100, 100)], max_num=2)
+    assert a.tolist() == [[0, 1]]
+    cls, reg, anchors = _two_levels([-0.0, 0.0], [-1.0])    # -0.0 == +0.0
+    _, a, _ = R.rpn_proposals(cls, reg, anchors, [(100, 100)], nms_pre=1, max_num=3)
+    assert a.tolist() == [[0, 2, -1]]
+    assert R.key_order(np.array([0.0, -0.0, 1.0, -0.0], f32)).tolist() == [2, 0, 1, 3]
+
+
+def test_batched_nms_oracle_keeps_segments_apart():
+    boxes = np.array([[0, 0, 10, 10], [0, 0, 10, 10], [0, 0, 10, 10], [50, 50, 60, 60]], f32)
+    scores = np.array([0.5, 0.9, 0.9, 0.1], f32)
+    keep, kept, counts = R.batched_nms(boxes, scores, [0, 2, 4], 0.5)
+    assert keep.tolist() == [0, 1, 1, 1] and kept.tolist() == [1, -1, 2, 3] and counts.tolist() == [1, 2]
+    keep, kept, counts = R.batched_nms(boxes, scores, [0, 0, 4], 0.5)
+    assert counts.tolist() == [0, 2] and kept.tolist() == [1, 3, -1, -1]
+
+
+def test_rpn_struct_mirrors_match_the_header(tmp_path):
+    """sizeof / offsetof of tdn_rpn_level and tdn_rpn_config as gcc lays them out == the ctypes mirrors."""
+    from torch_detection_amd import _lib
+    mirrors = {"tdn_rpn_level": _lib.RpnLevel, "tdn_rpn_config": _lib.RpnConfig}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "tdn.h"', 'int main(void) {']
+    for cname, cls in mirrors.items():
+        lines.append('printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname))
+        for fname, _ in cls._fields_:
+            lines.append('printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, fname, cname, fname))
+    lines += ['printf("const F32 %d\\n", TDN_F32);', 'printf("const SEG %d\\n", TDN_NMS_SEG_MAX);',
+              'printf("const LVL %d\\n", TDN_RPN_MAX_LEVELS);', 'printf("const NUM %d\\n", TDN_RPN_MAX_NUM);',
+              'return 0; }']
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    consts = {"F32": _lib.TDN_F32, "SEG": _lib.NMS_SEG_MAX, "LVL": _lib.RPN_MAX_LEVELS, "NUM": _lib.RPN_MAX_NUM}
+    seen = 0
+    for ln in subprocess.check_output([str(exe)]).decode().split("\n"):
+        if not ln:
+            continue
+        cname, fname, val = ln.split()
+        if cname == "const":
+            assert consts[fname] == int(val), (fname, val)
+            continue
+        cls = mirrors[cname]
+        got = ctypes.sizeof(cls) if fname == "sizeof" else getattr(cls, fname).offset
+        assert got == int(val), (cname, fname, got, val)
+        seen += 1
+    assert seen == sum(len(c._fields_) + 1 for c in mirrors.values())
+
+
+def test_rpn_host_validation_without_a_gpu():
+    """tdn_rpn_proposals_workspace validates on the host: limits are reported through tdn_last_error."""
+    from torch_detection_amd import _lib
+    lib = _lib.load()
+    lv = (_lib.RpnLevel * 2)()
+    for v, (h, w) in zip(lv, [(50, 84), (13, 21)]):
+        v.dtype, v.H, v.W, v.A = _lib.TDN_BF16, h, w, 3
+        v.logits = v.deltas = v.anchors = 256                # never dereferenced on the host
+    cfg = _lib.RpnConfig(nms_pre=2000, nms_post=2000, max_num=2000, nms_thr=0.7)
+    assert lib.tdn_rpn_proposals_workspace(lv, 2, 2, ctypes.byref(cfg)) > 0
+    cfg.nms_pre = 0                                          # 12600 anchors would enter NMS
+    assert lib.tdn_rpn_proposals_workspace(lv, 2, 2, ctypes.byref(cfg)) < 0
+    assert b"NMS" in lib.tdn_last_error()
+    cfg.nms_pre, cfg.max_num = 2000, 8193
+    assert lib.tdn_rpn_proposals_workspace(lv, 2, 2, ctypes.byref(cfg)) < 0
+    cfg.max_num = 2000
+    assert lib.tdn_rpn_proposals_workspace(lv, 2, 65, ctypes.byref(cfg)) < 0
+    assert lib.tdn_rpn_proposals_workspace(lv, 0, 2, ctypes.byref(cfg)) < 0
+    lv[1].dtype = 1                                          # TDN_F16 is not an input type here
+    assert lib.tdn_rpn_proposals_workspace(lv, 2, 2, ctypes.byref(cfg)) < 0
+    assert lib.tdn_batched_nms_workspace(10000, 3) > 0 and lib.tdn_batched_nms_workspace(-1, 3) < 0

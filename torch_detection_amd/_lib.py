@@ -16,6 +16,10 @@ LIB_PATH = os.path.join(_HERE, os.path.basename(os.environ.get("TDN_LIB", "") or
 
 TDN_BF16 = 0
 TDN_F16 = 1
+TDN_F32 = 2
+NMS_SEG_MAX = 4096
+RPN_MAX_LEVELS = 8
+RPN_MAX_NUM = 8192
 ADD_NONE, ADD_SAME, ADD_UP2X, ADD_SUMPOOL2 = 0, 1, 2, 3
 
 c_void_p = ctypes.c_void_p
@@ -82,6 +86,24 @@ class AnchorLevel(ctypes.Structure):
 
 
 _AL = ctypes.POINTER(AnchorLevel)
+
+
+class RpnLevel(ctypes.Structure):
+    """Mirror of ``tdn_rpn_level`` (include/tdn.h)."""
+    _fields_ = [("logits", c_void_p), ("deltas", c_void_p), ("anchors", c_void_p),
+                ("logit_strides", c_i64 * 4), ("delta_strides", c_i64 * 4),
+                ("dtype", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("A", ctypes.c_int32)]
+
+
+class RpnConfig(ctypes.Structure):
+    """Mirror of ``tdn_rpn_config`` (include/tdn.h)."""
+    _fields_ = [("nms_pre", ctypes.c_int32), ("nms_post", ctypes.c_int32), ("max_num", ctypes.c_int32),
+                ("nms_thr", c_float), ("min_bbox_size", c_float), ("means", c_float * 4), ("stds", c_float * 4),
+                ("reserved", ctypes.c_int32)]
+
+
+_RL = ctypes.POINTER(RpnLevel)
+_RC = ctypes.POINTER(RpnConfig)
 
 
 class BottleneckArgs(ctypes.Structure):
@@ -154,6 +176,16 @@ SIGNATURES = {
     "tdn_bbox_normalize": (c_int, [c_void_p, c_i64, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p]),
     "tdn_bbox_denormalize": (c_int, [c_void_p, c_void_p, c_i64, c_int, ctypes.POINTER(c_float),
                                      ctypes.POINTER(c_float), c_void_p]),
+    "tdn_bbox2delta": (c_int, [c_void_p, c_void_p, c_i64, ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p,
+                               c_void_p]),
+    "tdn_delta2bbox": (c_int, [c_void_p, c_void_p, c_i64, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
+                               ctypes.POINTER(ctypes.c_int32), ctypes.c_double, c_void_p, c_void_p]),
+    "tdn_batched_nms_workspace": (c_i64, [c_int, c_int]),
+    "tdn_batched_nms": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_i64, c_void_p]),
+    "tdn_rpn_proposals_workspace": (c_i64, [_RL, c_int, c_int, _RC]),
+    "tdn_rpn_proposals": (c_int, [_RL, c_int, c_int, c_void_p, _RC, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                  c_void_p]),
     "tdn_pack_gconv_weight": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p, c_void_p, c_int, c_void_p]),
     "tdn_bottleneck_supported": (c_int, [c_int] * 5),

@@ -118,3 +118,48 @@ def nms_mask(boxes, scores, iou_thr):
     """(keep uint8 (N,) in input order, kept indices int64 (N,) in score order padded with -1, count int32 (1,))
     without any host synchronisation."""
     return ops.nms(boxes.contiguous(), scores.contiguous(), iou_thr)
+
+
+def bbox2delta(proposals, gt, means=(0, 0, 0, 0), stds=(1, 1, 1, 1)):
+    """(N, 4) regression targets of ``gt`` relative to ``proposals`` (both (N, 4) float32 CUDA):
+    ``dx = (gx - px) / pw``, ``dw = log(gw / pw)`` ('+1' widths, centres ``(x1 + x2) * 0.5``), then
+    ``(d - means) / stds`` — the reference's ``bbox_normalize``.  DESIGN.md §4b has the exact operation order."""
+    return ops.bbox2delta(proposals.contiguous(), gt.contiguous(), means, stds)
+
+
+def delta2bbox(rois, deltas, means=(0, 0, 0, 0), stds=(1, 1, 1, 1), max_shape=None, wh_ratio_clip=16 / 1000):
+    """Boxes (N, 4C) from ``rois`` (N, 4) and class-specific ``deltas`` (N, 4C): ``deltas * stds + means`` (the
+    reference's ``bbox_denormalize``), ``dw, dh`` clamped to ``±|log(wh_ratio_clip)|``, ``gw = pw * exp(dw)``,
+    ``gx = px + pw * dx``, ``x1 = gx - gw * 0.5 + 0.5``, ``x2 = gx + gw * 0.5 - 0.5``; with ``max_shape = (h, w)``
+    x is clipped to ``[0, w-1]`` and y to ``[0, h-1]``."""
+    return ops.delta2bbox(rois.contiguous(), deltas.contiguous(), means, stds, max_shape, wh_ratio_clip)
+
+
+def batched_nms(boxes, scores, seg_offsets, iou_thr):
+    """Greedy NMS (Appendix B) of every segment ``[seg_offsets[s], seg_offsets[s+1])`` of ``boxes`` (N, 4) /
+    ``scores`` (N,) in one call; boxes of different segments never suppress each other, a segment holds at most 4096
+    boxes.  Returns ``keep`` (N,) uint8, kept indices (N,) int64 — in each segment's range its kept indices in score
+    order, padded with -1 — and ``counts`` (S,) int32 (-1 for a malformed segment of a CUDA ``seg_offsets``).  No
+    host synchronisation."""
+    return ops.batched_nms(boxes.contiguous(), scores.contiguous(), seg_offsets, iou_thr)
+
+
+def rpn_proposals(cls_scores, bbox_preds, anchors, img_shapes, nms_pre=2000, nms_post=2000, max_num=2000,
+                  nms_thr=0.7, min_bbox_size=0, target_means=(0, 0, 0, 0), target_stds=(1, 1, 1, 1),
+                  use_sigmoid_cls=True, nms_across_levels=False):
+    """RPN proposals of a batch from per-level head outputs, in four kernel launches.
+
+    ``cls_scores[l]``: (B, A, H_l, W_l) sigmoid logits, ``bbox_preds[l]``: (B, 4A, H_l, W_l) deltas (channel 4a+j =
+    coordinate j of anchor a), float32 or bfloat16, any strides (NCHW, channels_last); ``anchors[l]``: the level's
+    (H_l*W_l*A, 4) anchors from :func:`anchor_pyramid`; ``img_shapes``: CUDA int32 (B, 2) of (h, w) (a sequence of
+    pairs is accepted outside graph capture).  Per (image, level): the ``nms_pre`` highest logits, decode, clip,
+    min-size filter, NMS at ``nms_thr``, the first ``nms_post`` survivors; per image the best ``max_num`` of those by
+    (logit desc, level, anchor).  Returns ``proposals`` (B, max_num, 5) = [x1, y1, x2, y2, sigmoid score],
+    ``anchor_idx`` (B, max_num) int64 (row of the concatenated pyramid) and ``counts`` (B,) int32; unused rows are 0
+    with index -1.  No host synchronisation: graph-capturable."""
+    if not use_sigmoid_cls:
+        raise NotImplementedError("rpn_proposals supports sigmoid classification only")
+    if nms_across_levels:
+        raise NotImplementedError("rpn_proposals supports nms_across_levels=False only")
+    return ops.rpn_proposals(list(cls_scores), list(bbox_preds), list(anchors), img_shapes, nms_pre, nms_post,
+                             max_num, nms_thr, min_bbox_size, target_means, target_stds)

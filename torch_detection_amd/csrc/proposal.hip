@@ -1,0 +1,691 @@
+// Box delta encode / decode, segmented greedy NMS and the fused RPN proposal pipeline.
+//
+// Semantics are the project's own spec in the mmdetection-v0.x lineage of SURVEY Appendix B ('+1' boxes, strict IEEE
+// fp32 in the spec's operation order: this file is compiled with -ffp-contract=off, products and sums are __f*_rn);
+// the CPU restatement is tests/proposal_ref.py.
+//
+// rpn_proposals is four launches for any B and L:
+//   1 rpn_topk_decode_kernel  one workgroup per (image, level) segment: radix select of the nms_pre highest logits
+//                             (11/11/10-bit digits over an order-preserving 32-bit key, LDS histograms), an ordered
+//                             compaction (ties at the threshold key lowest anchor first), an LDS bitonic sort of the
+//                             composite keys (key << 32 | ~anchor), then per selected row: anchor + delta gather,
+//                             decode, clip, min-size filter, ordered compaction into the segment's rows.
+//   2 nms_mask_seg_kernel     suppression words of every segment: grid (column block, row block, segment).
+//   3 nms_scan_seg_kernel     the 1024-thread keep scan of box.hip, one workgroup per segment.  The rows of a segment
+//                             already are in key order, so no ranking step.
+//   4 rpn_merge_kernel        one workgroup per image: select + sort the best max_num of the levels' first nms_post
+//                             survivors by (logit desc, concatenated anchor index asc), write the padded outputs.
+// batched_nms is a sort kernel (one workgroup per segment: bitonic sort of (score key, ~row)) + launches 2 and 3.
+// Nothing here uses a float atomic or waits on another workgroup; the integer LDS atomics only count, so every
+// output is a pure function of the inputs.
+#include "nms_core.h"
+#include <math.h>
+#include <string.h>
+
+typedef unsigned long long u64;
+
+// ---- keys ----------------------------------------------------------------------------------------------------
+// order-preserving: a > b (as floats, -0 == +0)  <=>  order_key(a) > order_key(b)
+__device__ __forceinline__ uint32_t order_key(float f) {
+  uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ u64 compose(uint32_t key, uint32_t i) { return ((u64)key << 32) | (uint32_t)~i; }
+
+__device__ __forceinline__ float load_elem(const void* p, int dtype, int64_t off) {
+  if (dtype == TDN_F32) return ((const float*)p)[off];
+  return __uint_as_float((uint32_t)((const uint16_t*)p)[off] << 16);   // bf16 -> fp32 is exact
+}
+
+// ---- encode / decode (spec order, one rounding per operation) ---------------------------------------------------
+__device__ __forceinline__ f32x4_t encode_box(const f32x4_t p, const f32x4_t g, const f32x4_t means,
+                                              const f32x4_t stds) {
+  const float px = __fmul_rn(__fadd_rn(p[0], p[2]), 0.5f), py = __fmul_rn(__fadd_rn(p[1], p[3]), 0.5f);
+  const float pw = __fadd_rn(__fsub_rn(p[2], p[0]), 1.0f), ph = __fadd_rn(__fsub_rn(p[3], p[1]), 1.0f);
+  const float gx = __fmul_rn(__fadd_rn(g[0], g[2]), 0.5f), gy = __fmul_rn(__fadd_rn(g[1], g[3]), 0.5f);
+  const float gw = __fadd_rn(__fsub_rn(g[2], g[0]), 1.0f), gh = __fadd_rn(__fsub_rn(g[3], g[1]), 1.0f);
+  f32x4_t d;
+  d[0] = __fdiv_rn(__fsub_rn(gx, px), pw);
+  d[1] = __fdiv_rn(__fsub_rn(gy, py), ph);
+  d[2] = logf(__fdiv_rn(gw, pw));
+  d[3] = logf(__fdiv_rn(gh, ph));
+#pragma unroll
+  for (int e = 0; e < 4; ++e) d[e] = __fdiv_rn(__fsub_rn(d[e], means[e]), stds[e]);
+  return d;
+}
+
+// clip_w < 0: no clipping
+__device__ __forceinline__ f32x4_t decode_box(const f32x4_t r, const f32x4_t delta, const f32x4_t means,
+                                              const f32x4_t stds, float max_ratio, int clip_h, int clip_w) {
+  f32x4_t d;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) d[e] = __fadd_rn(__fmul_rn(delta[e], stds[e]), means[e]);
+  const float dw = fminf(fmaxf(d[2], -max_ratio), max_ratio), dh = fminf(fmaxf(d[3], -max_ratio), max_ratio);
+  const float px = __fmul_rn(__fadd_rn(r[0], r[2]), 0.5f), py = __fmul_rn(__fadd_rn(r[1], r[3]), 0.5f);
+  const float pw = __fadd_rn(__fsub_rn(r[2], r[0]), 1.0f), ph = __fadd_rn(__fsub_rn(r[3], r[1]), 1.0f);
+  const float gw = __fmul_rn(pw, expf(dw)), gh = __fmul_rn(ph, expf(dh));
+  const float gx = __fadd_rn(px, __fmul_rn(pw, d[0])), gy = __fadd_rn(py, __fmul_rn(ph, d[1]));
+  const float hw = __fmul_rn(gw, 0.5f), hh = __fmul_rn(gh, 0.5f);
+  f32x4_t o;
+  o[0] = __fadd_rn(__fsub_rn(gx, hw), 0.5f);
+  o[1] = __fadd_rn(__fsub_rn(gy, hh), 0.5f);
+  o[2] = __fsub_rn(__fadd_rn(gx, hw), 0.5f);
+  o[3] = __fsub_rn(__fadd_rn(gy, hh), 0.5f);
+  if (clip_w >= 0) {
+    const float xm = (float)(clip_w - 1), ym = (float)(clip_h - 1);
+    o[0] = fminf(fmaxf(o[0], 0.f), xm);
+    o[1] = fminf(fmaxf(o[1], 0.f), ym);
+    o[2] = fminf(fmaxf(o[2], 0.f), xm);
+    o[3] = fminf(fmaxf(o[3], 0.f), ym);
+  }
+  return o;
+}
+
+__global__ void bbox2delta_kernel(const float* __restrict__ prop, const float* __restrict__ gt, int64_t N,
+                                  f32x4_t means, f32x4_t stds, float* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x)
+    *(f32x4_t*)(out + i * 4) = encode_box(*(const f32x4_t*)(prop + i * 4), *(const f32x4_t*)(gt + i * 4), means, stds);
+}
+
+__global__ void delta2bbox_kernel(const float* __restrict__ rois, const float* __restrict__ deltas, int64_t N, int C,
+                                  f32x4_t means, f32x4_t stds, float max_ratio, int clip_h, int clip_w,
+                                  float* __restrict__ out) {
+  const int64_t total = N * C;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = q / C;
+    *(f32x4_t*)(out + q * 4) = decode_box(*(const f32x4_t*)(rois + row * 4), *(const f32x4_t*)(deltas + q * 4), means,
+                                          stds, max_ratio, clip_h, clip_w);
+  }
+}
+
+static f32x4_t host_f4(const float* v) { return (f32x4_t){v[0], v[1], v[2], v[3]}; }
+
+extern "C" int tdn_bbox2delta(const float* proposals, const float* gt, int64_t N, const float* means4,
+                              const float* stds4, float* deltas, void* stream) {
+  TDN_CHECK(N >= 0 && means4 && stds4, "tdn_bbox2delta: bad arguments");
+  if (N == 0) return 0;
+  TDN_CHECK(proposals && gt && deltas, "tdn_bbox2delta: NULL pointer");
+  int64_t grid = (N + 255) / 256;
+  if (grid > 4096) grid = 4096;
+  TDN_LAUNCH(bbox2delta_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, proposals, gt, N,
+             host_f4(means4), host_f4(stds4), deltas);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+// |log(wh_ratio_clip)| evaluated in double, rounded to fp32 (16/1000 -> 4.1351666f)
+static float max_ratio_of(double wh_ratio_clip) { return (float)fabs(log(wh_ratio_clip)); }
+
+extern "C" int tdn_delta2bbox(const float* rois, const float* deltas, int64_t N, int C, const float* means4,
+                              const float* stds4, const int32_t* max_shape, double wh_ratio_clip, float* out,
+                              void* stream) {
+  TDN_CHECK(N >= 0 && C > 0 && means4 && stds4, "tdn_delta2bbox: bad arguments");
+  TDN_CHECK(wh_ratio_clip > 0.0 && wh_ratio_clip < 1.0, "tdn_delta2bbox: wh_ratio_clip must be in (0, 1)");
+  TDN_CHECK(!max_shape || (max_shape[0] > 0 && max_shape[1] > 0), "tdn_delta2bbox: bad max_shape");
+  if (N == 0) return 0;
+  TDN_CHECK(rois && deltas && out, "tdn_delta2bbox: NULL pointer");
+  int64_t grid = (N * C + 255) / 256;
+  if (grid > 4096) grid = 4096;
+  TDN_LAUNCH(delta2bbox_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, rois, deltas, N, C,
+             host_f4(means4), host_f4(stds4), max_ratio_of(wh_ratio_clip), max_shape ? max_shape[0] : -1,
+             max_shape ? max_shape[1] : -1, out);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- block-wide helpers (1024 threads) -------------------------------------------------------------------------
+constexpr int BLK = 1024;
+constexpr int TK_PER = 8;                     // keys per thread per step, consecutive: one scan orders a whole step
+constexpr int TK_STEP = BLK * TK_PER;
+constexpr int TK_BINS = 2048;                 // 11-bit digits: 21..31, 10..20, 0..9
+constexpr int TK_MISC = 64;                   // ints of scratch: [0,16) scan, [16,18) bin choice, [32,64) caller
+
+// exclusive prefix sum over the workgroup in thread order; *total = the sum of all
+__device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) sh[wave] = incl;
+  __syncthreads();
+  int before = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < BLK / 64; ++w) {
+    const int c = sh[w];
+    before += (w < wave) ? c : 0;
+    tot += c;
+  }
+  __syncthreads();
+  *total = tot;
+  return before + incl - v;
+}
+
+// descending bitonic sort of s[0, P), P a power of two
+__device__ __forceinline__ void block_sort_desc(u64* s, int P) {
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < (P >> 1); t += BLK) {
+        const int i = 2 * t - (t & (stride - 1));
+        const int j = i + stride;
+        const u64 a = s[i], c = s[j];
+        if ((a < c) == ((i & size) == 0)) {
+          s[i] = c;
+          s[j] = a;
+        }
+      }
+      __syncthreads();
+    }
+}
+
+__host__ __device__ __forceinline__ int pow2_ceil(int m) {
+  int p = 1;
+  while (p < m) p <<= 1;
+  return p;
+}
+
+// The k highest of n keys (ties: lower index first) as composite keys (key << 32 | ~index), sorted descending into
+// skeys[0, pow2_ceil(k)) (zero padding).  F(i0, cnt, keys) fetches keys i0 .. i0+cnt-1 (cnt <= TK_PER).  Returns
+// min(n, k).  hist: TK_BINS ints of LDS, misc: TK_MISC ints.
+template <class Fetch>
+__device__ int block_topk(const Fetch& F, int n, int k, u64* skeys, int* hist, int* misc) {
+  const int tid = threadIdx.x;
+  int m;
+  if (n <= k) {
+    for (int i0 = tid * TK_PER; i0 < n; i0 += TK_STEP) {
+      const int cnt = min(TK_PER, n - i0);
+      uint32_t kk[TK_PER];
+      F(i0, cnt, kk);
+#pragma unroll
+      for (int e = 0; e < TK_PER; ++e)
+        if (e < cnt) skeys[i0 + e] = compose(kk[e], i0 + e);
+    }
+    m = n;
+  } else {
+    // radix select of the threshold key T: k - need keys are > T, and the first `need` keys == T are taken
+    uint32_t prefix = 0u, pmask = 0u;
+    int need = k;
+    for (int pass = 0; pass < 3; ++pass) {
+      const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
+      const uint32_t dmask = pass == 2 ? 0x3FFu : 0x7FFu;
+      for (int b = tid; b < TK_BINS; b += BLK) hist[b] = 0;
+      __syncthreads();
+      for (int i0 = tid * TK_PER; i0 < n; i0 += TK_STEP) {
+        const int cnt = min(TK_PER, n - i0);
+        uint32_t kk[TK_PER];
+        F(i0, cnt, kk);
+#pragma unroll
+        for (int e = 0; e < TK_PER; ++e)
+          if (e < cnt && (kk[e] & pmask) == prefix) atomicAdd(&hist[(kk[e] >> shift) & dmask], 1);
+      }
+      __syncthreads();
+      // thread t owns bins 2047-2t and 2046-2t: an exclusive scan in thread order counts the keys in higher bins
+      const int hi = TK_BINS - 1 - 2 * tid;
+      const int ch = hist[hi], cl = hist[hi - 1];
+      int tot;
+      const int above = block_excl_scan(ch + cl, misc, &tot);
+      if (above < need && need <= above + ch) {
+        misc[16] = hi;
+        misc[17] = above;
+      } else if (above + ch < need && need <= above + ch + cl) {
+        misc[16] = hi - 1;
+        misc[17] = above + ch;
+      }
+      __syncthreads();
+      need -= misc[17];
+      prefix |= (uint32_t)misc[16] << shift;
+      pmask |= dmask << shift;
+      __syncthreads();
+    }
+    // ordered compaction: keys > T go to [0, k - need) in any order (the sort below orders them), the first `need`
+    // keys == T in index order to [k - need, k)
+    const uint32_t T = prefix;
+    const int ngt = k - need;
+    int gt_done = 0, ties_done = 0;
+    for (int base = 0; base < n; base += TK_STEP) {
+      const int i0 = base + tid * TK_PER;
+      const int cnt = max(0, min(TK_PER, n - i0));
+      uint32_t kk[TK_PER];
+      if (cnt > 0) F(i0, cnt, kk);
+      int ng = 0, nt = 0;
+#pragma unroll
+      for (int e = 0; e < TK_PER; ++e)
+        if (e < cnt) {
+          ng += kk[e] > T ? 1 : 0;
+          nt += kk[e] == T ? 1 : 0;
+        }
+      int tot;   // both counts packed: a step holds at most 8192 of either
+      const int ex = block_excl_scan(ng | (nt << 16), misc, &tot);
+      int gpos = gt_done + (ex & 0xFFFF), tpos = ties_done + (ex >> 16);
+#pragma unroll
+      for (int e = 0; e < TK_PER; ++e)
+        if (e < cnt) {
+          if (kk[e] > T) {
+            skeys[gpos++] = compose(kk[e], i0 + e);
+          } else if (kk[e] == T) {
+            if (tpos < need) skeys[ngt + tpos] = compose(kk[e], i0 + e);
+            ++tpos;
+          }
+        }
+      gt_done += tot & 0xFFFF;
+      ties_done += tot >> 16;
+    }
+    m = k;
+  }
+  const int P = pow2_ceil(m);
+  for (int i = m + tid; i < P; i += BLK) skeys[i] = 0ull;   // below every real key
+  block_sort_desc(skeys, P);
+  return m;
+}
+
+// ---- RPN proposals ----------------------------------------------------------------------------------------------
+struct RpnArgs {
+  int L, per_img, nms_post, max_num, pitch;
+  float min_size, max_ratio;
+  f32x4_t means, stds;
+  const void* logits[TDN_RPN_MAX_LEVELS];
+  const void* deltas[TDN_RPN_MAX_LEVELS];
+  const float* anchors[TDN_RPN_MAX_LEVELS];
+  int64_t ls[TDN_RPN_MAX_LEVELS][4], ds[TDN_RPN_MAX_LEVELS][4];
+  int dtype[TDN_RPN_MAX_LEVELS], W[TDN_RPN_MAX_LEVELS], A[TDN_RPN_MAX_LEVELS];
+  int n[TDN_RPN_MAX_LEVELS], cap[TDN_RPN_MAX_LEVELS], cap_off[TDN_RPN_MAX_LEVELS], aoff[TDN_RPN_MAX_LEVELS];
+};
+
+// logit keys of one (image, level): anchor i = (y*W + x)*A + a -> element (b, a, y, x) through the strides
+struct LogitFetch {
+  const void* p;
+  int64_t base, sc, sh, sw;
+  int dtype, A, W;
+  __device__ __forceinline__ void operator()(int i0, int cnt, uint32_t* kk) const {
+    int a = i0 % A;
+    const int cell = i0 / A;
+    int y = cell / W, x = cell - (cell / W) * W;
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e) {
+      if (e < cnt) kk[e] = order_key(load_elem(p, dtype, base + a * sc + y * sh + x * sw));
+      if (++a == A) {
+        a = 0;
+        if (++x == W) {
+          x = 0;
+          ++y;
+        }
+      }
+    }
+  }
+};
+
+constexpr int RPN_SEG_MAX = TDN_NMS_SEG_MAX;
+constexpr size_t TOPK_LDS = (size_t)RPN_SEG_MAX * 8 + TK_BINS * 4 + TK_MISC * 4;               // 41.2 KB
+constexpr size_t MERGE_LDS = (size_t)TDN_RPN_MAX_NUM * 8 + TK_BINS * 4 + TK_MISC * 4;          // 72.3 KB
+
+__global__ __launch_bounds__(1024) void rpn_topk_decode_kernel(const RpnArgs P, const int32_t* __restrict__ img_shapes,
+                                                               f32x4_t* seg_box, uint32_t* seg_key, int* seg_aidx,
+                                                               int* seg_start, int* seg_count) {
+  extern __shared__ __attribute__((aligned(16))) u64 smem[];
+  u64* skeys = smem;                                  // [RPN_SEG_MAX]
+  int* hist = (int*)(smem + RPN_SEG_MAX);             // [TK_BINS]
+  int* misc = hist + TK_BINS;                         // [TK_MISC]
+  const int tid = threadIdx.x;
+  const int s = blockIdx.x, b = s / P.L, l = s - (s / P.L) * P.L;
+  const int n = P.n[l], A = P.A[l], W = P.W[l];
+  const int start = b * P.per_img + P.cap_off[l];
+  const LogitFetch F{P.logits[l], b * P.ls[l][0], P.ls[l][1], P.ls[l][2], P.ls[l][3], P.dtype[l], A, W};
+  const int m = block_topk(F, n, P.cap[l], skeys, hist, misc);
+  // decode the selected rows in key order; a thread takes `per` consecutive rows, so one scan keeps the order
+  const int ih = img_shapes[2 * b], iw = img_shapes[2 * b + 1];
+  const int per = (m + BLK - 1) / BLK;                // <= 4
+  const int64_t* ds = P.ds[l];
+  f32x4_t box[RPN_SEG_MAX / BLK];
+  uint32_t key[RPN_SEG_MAX / BLK];
+  int idx[RPN_SEG_MAX / BLK];
+  int ok = 0;
+#pragma unroll
+  for (int e = 0; e < RPN_SEG_MAX / BLK; ++e) {
+    const int p = tid * per + e;
+    key[e] = 0u;
+    idx[e] = -1;
+    if (e < per && p < m) {
+      const u64 c = skeys[p];
+      key[e] = (uint32_t)(c >> 32);
+      const int i = (int)~(uint32_t)c;
+      const int a = i % A, cell = i / A, y = cell / W, x = cell - (cell / W) * W;
+      const int64_t o = b * ds[0] + y * ds[2] + x * ds[3] + (int64_t)(4 * a) * ds[1];
+      f32x4_t d;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) d[j] = load_elem(P.deltas[l], P.dtype[l], o + j * ds[1]);
+      box[e] = decode_box(*(const f32x4_t*)(P.anchors[l] + (int64_t)i * 4), d, P.means, P.stds, P.max_ratio, ih, iw);
+      bool keep = true;
+      if (P.min_size > 0.f)
+        keep = !(__fadd_rn(__fsub_rn(box[e][2], box[e][0]), 1.0f) < P.min_size ||
+                 __fadd_rn(__fsub_rn(box[e][3], box[e][1]), 1.0f) < P.min_size);
+      if (keep) {
+        idx[e] = i;
+        ++ok;
+      }
+    }
+  }
+  int total;
+  int q = start + block_excl_scan(ok, misc, &total);
+#pragma unroll
+  for (int e = 0; e < RPN_SEG_MAX / BLK; ++e)
+    if (idx[e] >= 0) {
+      seg_box[q] = box[e];
+      seg_key[q] = key[e];
+      seg_aidx[q] = P.aoff[l] + idx[e];
+      ++q;
+    }
+  if (tid == 0) {
+    seg_start[s] = start;
+    seg_count[s] = total;
+  }
+}
+
+// one workgroup per segment: rows [seg_start, +seg_count) of sboxes, mask rows of `pitch` words
+__global__ __launch_bounds__(64) void nms_mask_seg_kernel(const float* __restrict__ sboxes, const int* seg_start,
+                                                          const int* seg_count, float thr, int pitch,
+                                                          unsigned long long* __restrict__ mask) {
+  const int s = blockIdx.z, rb = blockIdx.y, cb = blockIdx.x;
+  if (cb < rb) return;
+  const int n = seg_count[s];
+  if (cb * 64 >= n) return;                           // also n <= 0; rb <= cb
+  const int64_t start = seg_start[s];
+  nms_mask_block(sboxes + start * 4, n, thr, pitch, rb, cb, mask + start * pitch);
+}
+
+// kept_idx[start + r]: kept rows (order == nullptr: segment-local row, else order[start + row]); num_kept[s] = count,
+// -1 for a segment marked invalid (seg_count < 0)
+__global__ __launch_bounds__(1024) void nms_scan_seg_kernel(const unsigned long long* __restrict__ mask,
+                                                            const int* __restrict__ order, const int* seg_start,
+                                                            const int* seg_count, int pitch, uint8_t* keep,
+                                                            int64_t* kept_idx, int* num_kept) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long sm[];
+  const int s = blockIdx.x;
+  const int n = seg_count[s];
+  if (n <= 0) {
+    if (threadIdx.x == 0) num_kept[s] = n < 0 ? -1 : 0;
+    return;
+  }
+  const int64_t start = seg_start[s];
+  nms_scan_block(mask + start * pitch, order ? order + start : nullptr, n, (n + 63) / 64, pitch, keep,
+                 kept_idx + start, num_kept + s, sm);
+}
+
+// candidates of one image: the first min(num_kept, nms_post) survivors of each level, level after level
+struct MergeFetch {
+  const int* cum;           // [L + 1] LDS
+  const int* st;            // [L] LDS: segment starts
+  int L;
+  const int64_t* kept;
+  const uint32_t* seg_key;
+  __device__ __forceinline__ int row(int j) const {
+    int l = 0;
+    while (l + 1 < L && j >= cum[l + 1]) ++l;
+    return st[l] + (int)kept[st[l] + j - cum[l]];
+  }
+  __device__ __forceinline__ void operator()(int i0, int cnt, uint32_t* kk) const {
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e)
+      if (e < cnt) kk[e] = seg_key[row(i0 + e)];
+  }
+};
+
+__global__ __launch_bounds__(1024) void rpn_merge_kernel(const RpnArgs P, const f32x4_t* __restrict__ seg_box,
+                                                         const uint32_t* __restrict__ seg_key,
+                                                         const int* __restrict__ seg_aidx, const int* seg_start,
+                                                         const int64_t* __restrict__ kept, const int* num_kept,
+                                                         float* proposals, int64_t* anchor_idx, int32_t* counts) {
+  extern __shared__ __attribute__((aligned(16))) u64 smem[];
+  u64* skeys = smem;                                  // [TDN_RPN_MAX_NUM]
+  int* hist = (int*)(smem + TDN_RPN_MAX_NUM);         // [TK_BINS]
+  int* misc = hist + TK_BINS;                         // [TK_MISC]
+  int* cum = misc + 32;                               // [L + 1]
+  int* st = cum + TDN_RPN_MAX_LEVELS + 1;             // [L]
+  const int tid = threadIdx.x, b = blockIdx.x;
+  if (tid == 0) {
+    int c = 0;
+    for (int l = 0; l < P.L; ++l) {
+      const int s = b * P.L + l;
+      cum[l] = c;
+      st[l] = seg_start[s];
+      c += min(num_kept[s], P.nms_post);
+    }
+    cum[P.L] = c;
+  }
+  __syncthreads();
+  const MergeFetch F{cum, st, P.L, kept, seg_key};
+  const int T = cum[P.L];
+  const int m = block_topk(F, T, min(P.max_num, T), skeys, hist, misc);
+  for (int p = tid; p < P.max_num; p += BLK) {
+    float* o = proposals + ((int64_t)b * P.max_num + p) * 5;
+    int64_t* ai = anchor_idx + (int64_t)b * P.max_num + p;
+    if (p < m) {
+      const u64 c = skeys[p];
+      const int r = F.row((int)~(uint32_t)c);
+      const f32x4_t bx = seg_box[r];
+      const float logit = key_value((uint32_t)(c >> 32));
+      o[0] = bx[0];
+      o[1] = bx[1];
+      o[2] = bx[2];
+      o[3] = bx[3];
+      o[4] = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-logit)));
+      *ai = seg_aidx[r];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 5; ++e) o[e] = 0.f;
+      *ai = -1;
+    }
+  }
+  if (tid == 0) counts[b] = m;
+}
+
+static inline int64_t align256(int64_t x) { return (x + 255) & ~255ll; }
+
+// LDS beyond 64 KB: attribute once per kernel and device
+#define TDN_BIG_LDS(kernel)                                                                                       \
+  do {                                                                                                            \
+    static tdn_attr_once attr_once;                                                                               \
+    if (attr_once.need()) {                                                                                       \
+      hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,          \
+                                         160 * 1024);                                                             \
+      TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(" #kernel ") failed: %s", hipGetErrorString(e));            \
+      attr_once.mark();                                                                                           \
+    }                                                                                                             \
+  } while (0)
+
+struct RpnPlan {
+  RpnArgs P;
+  int B, S, maxcap;
+  int64_t rows;
+};
+
+static int rpn_plan(const tdn_rpn_level* levels, int nlevels, int B, const tdn_rpn_config* cfg, RpnPlan* out) {
+  TDN_CHECK(levels && cfg, "tdn_rpn_proposals: NULL levels / config");
+  TDN_CHECK(nlevels >= 1 && nlevels <= TDN_RPN_MAX_LEVELS, "tdn_rpn_proposals: 1..%d levels", TDN_RPN_MAX_LEVELS);
+  TDN_CHECK(B >= 1 && B <= 64, "tdn_rpn_proposals: B=%d out of 1..64", B);
+  TDN_CHECK(cfg->nms_pre >= 0 && cfg->nms_post >= 1 && cfg->max_num >= 1 && cfg->max_num <= TDN_RPN_MAX_NUM,
+            "tdn_rpn_proposals: bad nms_pre / nms_post / max_num");
+  TDN_CHECK(cfg->min_bbox_size >= 0.f && cfg->nms_thr == cfg->nms_thr, "tdn_rpn_proposals: bad min_bbox_size / nms_thr");
+  RpnArgs& P = out->P;
+  memset(&P, 0, sizeof(P));
+  P.L = nlevels;
+  P.nms_post = cfg->nms_post;
+  P.max_num = cfg->max_num;
+  P.min_size = cfg->min_bbox_size;
+  P.max_ratio = max_ratio_of(16.0 / 1000.0);
+  P.means = host_f4(cfg->means);
+  P.stds = host_f4(cfg->stds);
+  int64_t per_img = 0, aoff = 0;
+  int maxcap = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    const tdn_rpn_level& v = levels[l];
+    TDN_CHECK(v.dtype == TDN_F32 || v.dtype == TDN_BF16, "tdn_rpn_proposals: level %d: dtype must be TDN_F32 or TDN_BF16", l);
+    TDN_CHECK(v.H >= 0 && v.W >= 0 && v.A >= 1, "tdn_rpn_proposals: level %d: bad H / W / A", l);
+    const int64_t n = (int64_t)v.H * v.W * v.A;
+    TDN_CHECK(n == 0 || (v.logits && v.deltas && v.anchors), "tdn_rpn_proposals: level %d: NULL pointer", l);
+    const int64_t cap = cfg->nms_pre > 0 ? (n < cfg->nms_pre ? n : cfg->nms_pre) : n;
+    TDN_CHECK(cap <= RPN_SEG_MAX, "tdn_rpn_proposals: level %d sends %lld boxes to NMS (max %d)", l, (long long)cap,
+              RPN_SEG_MAX);
+    for (int e = 0; e < 4; ++e)
+      TDN_CHECK(v.logit_strides[e] >= 0 && v.delta_strides[e] >= 0, "tdn_rpn_proposals: level %d: negative stride", l);
+    P.logits[l] = v.logits;
+    P.deltas[l] = v.deltas;
+    P.anchors[l] = v.anchors;
+    memcpy(P.ls[l], v.logit_strides, sizeof(P.ls[l]));
+    memcpy(P.ds[l], v.delta_strides, sizeof(P.ds[l]));
+    P.dtype[l] = v.dtype;
+    P.W[l] = v.W > 0 ? v.W : 1;
+    P.A[l] = v.A;
+    P.n[l] = (int)n;
+    P.cap[l] = (int)cap;
+    P.cap_off[l] = (int)per_img;
+    P.aoff[l] = (int)aoff;
+    per_img += cap;
+    aoff += n;
+    TDN_CHECK(aoff < (1ll << 30), "tdn_rpn_proposals: too many anchors");
+    if (cap > maxcap) maxcap = (int)cap;
+  }
+  P.per_img = (int)per_img;
+  P.pitch = maxcap > 0 ? (maxcap + 63) / 64 : 1;
+  out->B = B;
+  out->S = B * nlevels;
+  out->maxcap = maxcap;
+  out->rows = per_img * B;
+  return 0;
+}
+
+static int64_t rpn_ws_bytes(const RpnPlan& p) {
+  const int64_t R = p.rows > 0 ? p.rows : 1;
+  return align256(R * 16) + align256(R * 4) * 2 + align256(R * 8) + align256((int64_t)p.S * 4) * 3 +
+         align256(R * p.P.pitch * 8);
+}
+
+extern "C" int64_t tdn_rpn_proposals_workspace(const tdn_rpn_level* levels, int nlevels, int B,
+                                               const tdn_rpn_config* cfg) {
+  RpnPlan p;
+  if (rpn_plan(levels, nlevels, B, cfg, &p) != 0) return -1;
+  return rpn_ws_bytes(p);
+}
+
+extern "C" int tdn_rpn_proposals(const tdn_rpn_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                                 const tdn_rpn_config* cfg, float* proposals, int64_t* anchor_idx, int32_t* counts,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+  RpnPlan p;
+  if (rpn_plan(levels, nlevels, B, cfg, &p) != 0) return -1;
+  TDN_CHECK(img_shapes && proposals && anchor_idx && counts && workspace, "tdn_rpn_proposals: NULL pointer");
+  TDN_CHECK(workspace_bytes >= rpn_ws_bytes(p), "tdn_rpn_proposals: workspace too small");
+  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "tdn_rpn_proposals: workspace must be 256-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t R = p.rows > 0 ? p.rows : 1;
+  const int pitch = p.P.pitch;
+  char* ws = (char*)workspace;
+  f32x4_t* seg_box = (f32x4_t*)ws; ws += align256(R * 16);
+  uint32_t* seg_key = (uint32_t*)ws; ws += align256(R * 4);
+  int* seg_aidx = (int*)ws; ws += align256(R * 4);
+  int64_t* kept = (int64_t*)ws; ws += align256(R * 8);
+  int* seg_start = (int*)ws; ws += align256((int64_t)p.S * 4);
+  int* seg_count = (int*)ws; ws += align256((int64_t)p.S * 4);
+  int* num_kept = (int*)ws; ws += align256((int64_t)p.S * 4);
+  unsigned long long* mask = (unsigned long long*)ws;
+  TDN_LAUNCH(rpn_topk_decode_kernel, dim3(p.S), dim3(BLK), TOPK_LDS, st, p.P, img_shapes, seg_box, seg_key, seg_aidx,
+             seg_start, seg_count);
+  TDN_LAUNCH_CHECK();
+  TDN_LAUNCH(nms_mask_seg_kernel, dim3(pitch, pitch, p.S), dim3(64), 0, st, (const float*)seg_box,
+             (const int*)seg_start, (const int*)seg_count, cfg->nms_thr, pitch, mask);
+  TDN_LAUNCH_CHECK();
+  TDN_BIG_LDS(nms_scan_seg_kernel);
+  TDN_LAUNCH(nms_scan_seg_kernel, dim3(p.S), dim3(BLK), nms_scan_block_lds(pitch), st,
+             (const unsigned long long*)mask, (const int*)nullptr, (const int*)seg_start, (const int*)seg_count, pitch,
+             (uint8_t*)nullptr, kept, num_kept);
+  TDN_LAUNCH_CHECK();
+  TDN_BIG_LDS(rpn_merge_kernel);
+  TDN_LAUNCH(rpn_merge_kernel, dim3(p.B), dim3(BLK), MERGE_LDS, st, p.P, (const f32x4_t*)seg_box,
+             (const uint32_t*)seg_key, (const int*)seg_aidx, (const int*)seg_start, (const int64_t*)kept,
+             (const int*)num_kept, proposals, anchor_idx, counts);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- batched NMS ------------------------------------------------------------------------------------------------
+// one workgroup per segment: (score key, ~row) sorted descending -> order (input index) and the boxes in that order
+__global__ __launch_bounds__(1024) void nms_seg_sort_kernel(const float* __restrict__ boxes,
+                                                            const float* __restrict__ scores, int N,
+                                                            const int64_t* __restrict__ seg_offsets, int* order,
+                                                            float* sboxes, int* seg_start, int* seg_count) {
+  extern __shared__ __attribute__((aligned(16))) u64 skeys[];   // [TDN_NMS_SEG_MAX]
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const int64_t a = seg_offsets[s], e = seg_offsets[s + 1];
+  if (!(a >= 0 && a <= e && e <= N && e - a <= TDN_NMS_SEG_MAX)) {
+    if (tid == 0) {
+      seg_start[s] = 0;
+      seg_count[s] = -1;
+    }
+    return;
+  }
+  const int n = (int)(e - a);
+  const int P = pow2_ceil(n);
+  for (int i = tid; i < P; i += BLK) skeys[i] = i < n ? compose(order_key(scores[a + i]), i) : 0ull;
+  block_sort_desc(skeys, P);
+  for (int p = tid; p < n; p += BLK) {
+    const int i = (int)~(uint32_t)skeys[p];
+    order[a + p] = (int)a + i;
+    *(f32x4_t*)(sboxes + (a + p) * 4) = *(const f32x4_t*)(boxes + (a + i) * 4);
+  }
+  if (tid == 0) {
+    seg_start[s] = (int)a;
+    seg_count[s] = n;
+  }
+}
+
+static int nms_seg_pitch(int N) {
+  const int m = N < TDN_NMS_SEG_MAX ? N : TDN_NMS_SEG_MAX;
+  return m > 0 ? (m + 63) / 64 : 1;
+}
+
+extern "C" int64_t tdn_batched_nms_workspace(int N, int S) {
+  if (N < 0 || S < 0) return -1;
+  const int64_t n = N > 0 ? N : 1;
+  return align256(n * 4) + align256(n * 16) + align256((int64_t)(S > 0 ? S : 1) * 4) * 2 +
+         align256(n * nms_seg_pitch(N) * 8);
+}
+
+extern "C" int tdn_batched_nms(const float* boxes, const float* scores, int N, const int64_t* seg_offsets, int S,
+                               float iou_thr, uint8_t* keep, int64_t* kept_idx, int32_t* counts, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  TDN_CHECK(N >= 0 && N < (1 << 30) && S >= 0 && S < (1 << 24), "tdn_batched_nms: bad N / S");
+  if (N > 0) {
+    TDN_CHECK(keep && kept_idx, "tdn_batched_nms: NULL keep / kept_idx");
+    TDN_MEMSET_ASYNC(keep, 0, (size_t)N, st);
+    TDN_MEMSET_ASYNC(kept_idx, 0xFF, (size_t)N * 8, st);             // -1
+  }
+  if (S == 0) return 0;
+  TDN_CHECK(seg_offsets && counts && workspace && (N == 0 || (boxes && scores)), "tdn_batched_nms: NULL pointer");
+  TDN_CHECK(workspace_bytes >= tdn_batched_nms_workspace(N, S), "tdn_batched_nms: workspace too small");
+  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "tdn_batched_nms: workspace must be 256-byte aligned");
+  const int64_t n = N > 0 ? N : 1;
+  const int pitch = nms_seg_pitch(N);
+  char* ws = (char*)workspace;
+  int* order = (int*)ws; ws += align256(n * 4);
+  float* sboxes = (float*)ws; ws += align256(n * 16);
+  int* seg_start = (int*)ws; ws += align256((int64_t)S * 4);
+  int* seg_count = (int*)ws; ws += align256((int64_t)S * 4);
+  unsigned long long* mask = (unsigned long long*)ws;
+  TDN_LAUNCH(nms_seg_sort_kernel, dim3(S), dim3(BLK), (size_t)TDN_NMS_SEG_MAX * 8, st, boxes, scores, N, seg_offsets,
+             order, sboxes, seg_start, seg_count);
+  TDN_LAUNCH_CHECK();
+  TDN_LAUNCH(nms_mask_seg_kernel, dim3(pitch, pitch, S), dim3(64), 0, st, (const float*)sboxes,
+             (const int*)seg_start, (const int*)seg_count, iou_thr, pitch, mask);
+  TDN_LAUNCH_CHECK();
+  TDN_BIG_LDS(nms_scan_seg_kernel);
+  TDN_LAUNCH(nms_scan_seg_kernel, dim3(S), dim3(BLK), nms_scan_block_lds(pitch), st, (const unsigned long long*)mask,
+             (const int*)order, (const int*)seg_start, (const int*)seg_count, pitch, keep, kept_idx, counts);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}

@@ -846,6 +846,161 @@ def nms(boxes, scores, iou_thr):
     return keep, kept_idx, num
 
 
+def _aligned_ws(nbytes, dev):
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    return ws, ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256)
+
+
+def bbox2delta(proposals, gt, means, stds):
+    """(N,4) deltas = (encode(proposals, gt) - means) / stds."""
+    _chk_boxes(proposals, "proposals")
+    _chk_boxes(gt, "gt")
+    if proposals.shape != gt.shape:
+        raise ValueError("proposals %s and gt %s differ in shape" % (tuple(proposals.shape), tuple(gt.shape)))
+    _chk_dev(gt, "gt")
+    out = torch.empty_like(proposals)
+    _lib.check(_lib.load().tdn_bbox2delta(_ptr(proposals), _ptr(gt), proposals.shape[0], _f4(means), _f4(stds),
+                                          _ptr(out), _lib.stream_ptr()), "tdn_bbox2delta")
+    return out
+
+
+def delta2bbox(rois, deltas, means, stds, max_shape, wh_ratio_clip):
+    """(N,4C) boxes: rois (N,4) decoded by deltas (N,4C) * stds + means, clipped to max_shape = (h, w) if given."""
+    _chk_boxes(rois, "rois")
+    if deltas.dtype != torch.float32 or not deltas.is_cuda or deltas.dim() != 2 or not deltas.is_contiguous() or \
+            deltas.shape[0] != rois.shape[0] or deltas.shape[1] == 0 or deltas.shape[1] % 4:
+        raise ValueError("deltas must be a contiguous CUDA float32 (N, 4C) tensor with N = rois.shape[0]")
+    _chk_dev(deltas, "deltas")
+    if not 0.0 < float(wh_ratio_clip) < 1.0:
+        raise ValueError("wh_ratio_clip must be in (0, 1)")
+    ms = None
+    if max_shape is not None:
+        h, w = int(max_shape[0]), int(max_shape[1])
+        if h <= 0 or w <= 0:
+            raise ValueError("max_shape must be a positive (h, w)")
+        ms = (ctypes.c_int32 * 2)(h, w)
+    out = torch.empty_like(deltas)
+    _lib.check(_lib.load().tdn_delta2bbox(_ptr(rois), _ptr(deltas), rois.shape[0], deltas.shape[1] // 4, _f4(means),
+                                          _f4(stds), ms, float(wh_ratio_clip), _ptr(out), _lib.stream_ptr()),
+               "tdn_delta2bbox")
+    return out
+
+
+def batched_nms(boxes, scores, seg_offsets, iou_thr):
+    """Greedy NMS of the contiguous segments of a CSR int64 ``seg_offsets`` (S+1,) in one call (tdn_batched_nms).
+    A CPU ``seg_offsets`` is validated here and copied; a CUDA one is checked on the device (a bad segment gets
+    count -1).  Returns (keep (N,) uint8, kept indices (N,) int64, counts (S,) int32); never synchronises."""
+    _chk_boxes(boxes, "boxes")
+    N = boxes.shape[0]
+    if scores.dtype != torch.float32 or not scores.is_cuda or scores.dim() != 1 or scores.numel() != N or \
+            not scores.is_contiguous():
+        raise ValueError("scores must be a contiguous CUDA float32 (N,) tensor")
+    _chk_dev(scores, "scores")
+    if not torch.is_tensor(seg_offsets) or seg_offsets.dtype != torch.int64 or seg_offsets.dim() != 1 or \
+            seg_offsets.numel() < 1:
+        raise ValueError("seg_offsets must be an int64 (S+1,) tensor")
+    dev = boxes.device
+    if not seg_offsets.is_cuda:
+        off = seg_offsets.tolist()
+        if off[0] < 0 or off[-1] > N or any(b < a for a, b in zip(off, off[1:])):
+            raise ValueError("seg_offsets must be non-decreasing within [0, %d]" % N)
+        if any(b - a > _lib.NMS_SEG_MAX for a, b in zip(off, off[1:])):
+            raise ValueError("a segment holds more than %d boxes" % _lib.NMS_SEG_MAX)
+        seg_offsets = seg_offsets.to(dev)
+    else:
+        _chk_dev(seg_offsets, "seg_offsets")
+    seg_offsets = seg_offsets.contiguous()
+    S = seg_offsets.numel() - 1
+    keep = torch.empty(N, dtype=torch.uint8, device=dev)
+    kept_idx = torch.empty(N, dtype=torch.int64, device=dev)
+    counts = torch.empty(S, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.tdn_batched_nms_workspace(N, S)
+    ws, wp = _aligned_ws(nbytes, dev)
+    _lib.check(lib.tdn_batched_nms(_ptr(boxes), _ptr(scores), N, _ptr(seg_offsets), S, float(iou_thr), _ptr(keep),
+                                   _ptr(kept_idx), _ptr(counts), wp, nbytes, _lib.stream_ptr()), "tdn_batched_nms")
+    return keep, kept_idx, counts
+
+
+_RPN_DTYPES = {torch.float32: _lib.TDN_F32, torch.bfloat16: TDN_BF16}
+
+
+def rpn_proposals(cls_scores, bbox_preds, anchors, img_shapes, nms_pre, nms_post, max_num, nms_thr, min_bbox_size,
+                  means, stds):
+    """The fused RPN proposal pipeline (tdn_rpn_proposals).  Every shape, dtype and limit is checked
+    here, before any launch (ValueError).  Returns (proposals (B, max_num, 5) float32, anchor_idx (B, max_num) int64,
+    counts (B,) int32); never synchronises, so it can be captured in a graph when img_shapes is a CUDA tensor."""
+    L = len(cls_scores)
+    if not (1 <= L <= _lib.RPN_MAX_LEVELS) or len(bbox_preds) != L or len(anchors) != L:
+        raise ValueError("rpn_proposals takes 1..%d levels with one cls_score / bbox_pred / anchors each"
+                         % _lib.RPN_MAX_LEVELS)
+    B = cls_scores[0].shape[0] if cls_scores[0].dim() == 4 else -1
+    if not 1 <= B <= 64:
+        raise ValueError("rpn_proposals: batch size must be 1..64")
+    nms_pre, nms_post, max_num = int(nms_pre), int(nms_post), int(max_num)
+    if not 0 <= nms_pre <= _lib.NMS_SEG_MAX:
+        raise ValueError("nms_pre must be in 0..%d" % _lib.NMS_SEG_MAX)
+    if nms_post < 1:
+        raise ValueError("nms_post must be positive")
+    if not 1 <= max_num <= _lib.RPN_MAX_NUM:
+        raise ValueError("max_num must be in 1..%d" % _lib.RPN_MAX_NUM)
+    if float(min_bbox_size) < 0:
+        raise ValueError("min_bbox_size must be >= 0")
+    if len(means) != 4 or len(stds) != 4:
+        raise ValueError("target_means / target_stds must have 4 entries")
+    dev = cls_scores[0].device
+    arr = (_lib.RpnLevel * L)()
+    for l in range(L):
+        c, d, a = cls_scores[l], bbox_preds[l], anchors[l]
+        if c.dim() != 4 or d.dim() != 4 or c.dtype not in _RPN_DTYPES or d.dtype != c.dtype or not c.is_cuda or \
+                not d.is_cuda:
+            raise ValueError("level %d: cls_score / bbox_pred must be 4-D CUDA float32 or bfloat16 tensors of one "
+                             "dtype" % l)
+        Bl, A, H, W = c.shape
+        if Bl != B or tuple(d.shape) != (B, 4 * A, H, W) or A < 1:
+            raise ValueError("level %d: cls_score %s and bbox_pred %s do not match (B, A, H, W) / (B, 4A, H, W)"
+                             % (l, tuple(c.shape), tuple(d.shape)))
+        if a.dtype != torch.float32 or not a.is_cuda or not a.is_contiguous() or tuple(a.shape) != (H * W * A, 4):
+            raise ValueError("level %d: anchors must be a contiguous CUDA float32 (%d, 4) tensor" % (l, H * W * A))
+        if nms_pre == 0 and H * W * A > _lib.NMS_SEG_MAX:
+            raise ValueError("level %d: %d anchors enter NMS with nms_pre=0 (max %d)"
+                             % (l, H * W * A, _lib.NMS_SEG_MAX))
+        for t, nm in ((c, "cls_score"), (d, "bbox_pred"), (a, "anchors")):
+            _chk_dev(t, "%s[%d]" % (nm, l))
+        v = arr[l]
+        v.logits, v.deltas, v.anchors = c.data_ptr(), d.data_ptr(), a.data_ptr()
+        v.logit_strides[:] = list(c.stride())
+        v.delta_strides[:] = list(d.stride())
+        v.dtype, v.H, v.W, v.A = _RPN_DTYPES[c.dtype], H, W, A
+    if torch.is_tensor(img_shapes):
+        if img_shapes.dtype != torch.int32 or not img_shapes.is_cuda or tuple(img_shapes.shape) != (B, 2) or \
+                not img_shapes.is_contiguous():
+            raise ValueError("img_shapes must be a contiguous CUDA int32 (B, 2) tensor of (h, w)")
+        _chk_dev(img_shapes, "img_shapes")
+    else:
+        shapes = [(int(h), int(w)) for h, w in img_shapes]
+        if len(shapes) != B or any(h < 1 or w < 1 for h, w in shapes):
+            raise ValueError("img_shapes must hold B positive (h, w) pairs")
+        img_shapes = torch.tensor(shapes, dtype=torch.int32).to(dev)
+    cfg = _lib.RpnConfig()
+    cfg.nms_pre, cfg.nms_post, cfg.max_num = nms_pre, nms_post, max_num
+    cfg.nms_thr, cfg.min_bbox_size = float(nms_thr), float(min_bbox_size)
+    cfg.means[:] = [float(x) for x in means]
+    cfg.stds[:] = [float(x) for x in stds]
+    lib = _lib.load()
+    nbytes = lib.tdn_rpn_proposals_workspace(arr, L, B, ctypes.byref(cfg))
+    if nbytes < 0:
+        raise ValueError("rpn_proposals: %s" % lib.tdn_last_error().decode())
+    proposals = torch.empty(B, max_num, 5, dtype=torch.float32, device=dev)
+    anchor_idx = torch.empty(B, max_num, dtype=torch.int64, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    ws, wp = _aligned_ws(nbytes, dev)
+    _lib.check(lib.tdn_rpn_proposals(arr, L, B, _ptr(img_shapes), ctypes.byref(cfg), _ptr(proposals),
+                                     _ptr(anchor_idx), _ptr(counts), wp, nbytes, _lib.stream_ptr()),
+               "tdn_rpn_proposals")
+    return proposals, anchor_idx, counts
+
+
 # ---- image batch staging ---------------------------------------------------------------------------
 COLLATE_MAX = 16
 
