@@ -468,6 +468,50 @@ int tdn_rpn_proposals(const tdn_rpn_level* levels, int nlevels, int B, const int
                       const tdn_rpn_config* cfg, float* proposals, int64_t* anchor_idx, int32_t* counts,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- multi-level RoIAlign, the FPN RoI extractor (the project's own spec in the mmdetection-v1
+ *      lineage, SingleRoIExtractor + RoIAlign with aligned=False and the '+1' end; strict IEEE fp32 in the spec's
+ *      operation order) ----
+ * rois: device fp32 [R][5] = (batch_idx, x1, y1, x2, y2) in input-image pixels.  A row whose (int)batch_idx is not
+ * in [0, B) is invalid: zero output, no gradient (padded rows of tdn_rpn_proposals with index -1 pass straight in).
+ * Level of a row: floor(log2(sqrt((x2-x1+1)*(y2-y1+1)) / finest_scale + 1e-6)) from the exponent of the fp32 value,
+ * clamped to [0, nlevels-1].  Level l of B images, C channels: (B, C, H, W) 16-bit in memory addressed by the element
+ * strides (n, c, h, w); the channel stride must be 1 (NHWC memory), the others multiples of 8, data 16-byte aligned.
+ * Limits: 1..8 levels of one dtype, C % 8 == 0, 1 <= out_size <= 16, 0 <= sampling_ratio <= 512 (0: ceil(bin size)
+ * samples per bin side, capped at 512).  No host synchronisation, no allocation, no float atomics. */
+#define TDN_ROI_MAX_LEVELS 8
+#define TDN_ROI_MAX_OUT 16
+#define TDN_ROI_MAX_SAMPLES 512
+typedef struct tdn_roi_level {
+  void* data;                  /* device: features (fwd, read) or their gradient (bwd, written in full) */
+  int64_t strides[4];          /* elements: n, c, h, w (c must be 1) */
+  int32_t H, W;
+  int32_t dtype;               /* TDN_BF16 or TDN_F16, the same on every level */
+  int32_t reserved;
+} tdn_roi_level;
+typedef struct tdn_roi_config {
+  int32_t out_size;            /* S: output bins per side */
+  int32_t sampling_ratio;      /* > 0: samples per bin side; 0: adaptive */
+  float finest_scale;          /* > 0 (mmdetection: 56) */
+  int32_t reserved;
+  float scales[TDN_ROI_MAX_LEVELS];   /* spatial_scale of level l = 1 / featmap_stride_l (fp32), > 0 */
+} tdn_roi_config;
+/* levels[R] int64 = the level of every row (batch index ignored), as above. */
+int tdn_roi_map_levels(const float* rois, int64_t R, int nlevels, float finest_scale, int64_t* levels, void* stream);
+/* out: device 16-bit (R, S, S, C) contiguous (channels_last (R, C, S, S)); one launch. */
+int tdn_roi_align_fwd(const tdn_roi_level* feats, int nlevels, int B, int C, const float* rois, int64_t R,
+                      const tdn_roi_config* cfg, void* out, void* stream);
+/* dout: device 16-bit (R, S, S, C) contiguous.  grads[l].data: every element of every level is written (pixels no
+ * valid row touches get 0), fp32 sums rounded once; bitwise reproducible.  Two launches (per-row geometry, then one
+ * workgroup per 4x16-pixel tile x 256 channels summing its rows in row order).  workspace:
+ * tdn_roi_align_bwd_workspace(R) bytes, 256-aligned. */
+int64_t tdn_roi_align_bwd_workspace(int64_t R);
+int tdn_roi_align_bwd(const tdn_roi_level* grads, int nlevels, int B, int C, const float* rois, int64_t R,
+                      const tdn_roi_config* cfg, const void* dout, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+/* rois[B*M][5] from tdn_rpn_proposals' proposals[B][M][5]: row b*M+m = (b, x1, y1, x2, y2) when m < counts[b], else
+ * (-1, x1, y1, x2, y2) — an invalid row for tdn_roi_align_*.  No host synchronisation. */
+int tdn_rois_from_proposals(const float* proposals, const int32_t* counts, int B, int M, float* rois, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

@@ -20,6 +20,9 @@ TDN_F32 = 2
 NMS_SEG_MAX = 4096
 RPN_MAX_LEVELS = 8
 RPN_MAX_NUM = 8192
+ROI_MAX_LEVELS = 8
+ROI_MAX_OUT = 16
+ROI_MAX_SAMPLES = 512
 ADD_NONE, ADD_SAME, ADD_UP2X, ADD_SUMPOOL2 = 0, 1, 2, 3
 
 c_void_p = ctypes.c_void_p
@@ -106,6 +109,22 @@ _RL = ctypes.POINTER(RpnLevel)
 _RC = ctypes.POINTER(RpnConfig)
 
 
+class RoiLevel(ctypes.Structure):
+    """Mirror of ``tdn_roi_level`` (include/tdn.h)."""
+    _fields_ = [("data", c_void_p), ("strides", c_i64 * 4), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class RoiConfig(ctypes.Structure):
+    """Mirror of ``tdn_roi_config`` (include/tdn.h)."""
+    _fields_ = [("out_size", ctypes.c_int32), ("sampling_ratio", ctypes.c_int32), ("finest_scale", c_float),
+                ("reserved", ctypes.c_int32), ("scales", c_float * 8)]
+
+
+_RoL = ctypes.POINTER(RoiLevel)
+_RoC = ctypes.POINTER(RoiConfig)
+
+
 class BottleneckArgs(ctypes.Structure):
     """Mirror of ``tdn_bottleneck_args`` (include/tdn.h)."""
     _fields_ = [("in_", c_void_p), ("w1", c_void_p), ("w2", c_void_p), ("w3", c_void_p),
@@ -186,6 +205,12 @@ SIGNATURES = {
     "tdn_rpn_proposals_workspace": (c_i64, [_RL, c_int, c_int, _RC]),
     "tdn_rpn_proposals": (c_int, [_RL, c_int, c_int, c_void_p, _RC, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
                                   c_void_p]),
+    "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
+    "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
+    "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),
+    "tdn_roi_align_bwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p, c_i64,
+                                  c_void_p]),
+    "tdn_rois_from_proposals": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tdn_pack_gconv_weight": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p, c_void_p, c_int, c_void_p]),
     "tdn_bottleneck_supported": (c_int, [c_int] * 5),

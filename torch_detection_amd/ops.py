@@ -1001,6 +1001,137 @@ def rpn_proposals(cls_scores, bbox_preds, anchors, img_shapes, nms_pre, nms_post
     return proposals, anchor_idx, counts
 
 
+# ---- multi-level RoIAlign ------------------------------------------------------------------------
+def _chk_rois(rois):
+    if not torch.is_tensor(rois) or rois.dtype != torch.float32 or not rois.is_cuda or rois.dim() != 2 or \
+            rois.shape[1] != 5 or not rois.is_contiguous():
+        raise ValueError("rois must be a contiguous CUDA float32 (R, 5) tensor of (batch_idx, x1, y1, x2, y2)")
+    _chk_dev(rois, "rois")
+
+
+def _roi_config(out_size, scales, sampling_ratio, finest_scale):
+    S, sr, fs = int(out_size), int(sampling_ratio), float(finest_scale)
+    if not 1 <= S <= _lib.ROI_MAX_OUT:
+        raise ValueError("out_size must be in 1..%d" % _lib.ROI_MAX_OUT)
+    if not 0 <= sr <= _lib.ROI_MAX_SAMPLES:
+        raise ValueError("sampling_ratio must be in 0..%d" % _lib.ROI_MAX_SAMPLES)
+    if not 0.0 < fs < float("inf"):
+        raise ValueError("finest_scale must be positive")
+    if not 1 <= len(scales) <= _lib.ROI_MAX_LEVELS:
+        raise ValueError("RoIAlign takes 1..%d levels" % _lib.ROI_MAX_LEVELS)
+    cfg = _lib.RoiConfig()
+    cfg.out_size, cfg.sampling_ratio, cfg.finest_scale = S, sr, fs
+    for l, sc in enumerate(scales):
+        sc = float(ctypes.c_float(sc).value)
+        if not 0.0 < sc < float("inf"):
+            raise ValueError("level %d: spatial scale must be positive" % l)
+        cfg.scales[l] = sc
+    return cfg
+
+
+def roi_level_shapes(feats):
+    """Validate RoIAlign's feature levels (logical (B, C, H_l, W_l), 16-bit, one CUDA device, B / C / dtype shared,
+    C % 8 == 0) on the host and return (B, C, dtype, [(H_l, W_l)])."""
+    if not 1 <= len(feats) <= _lib.ROI_MAX_LEVELS:
+        raise ValueError("RoIAlign takes 1..%d feature levels, got %d" % (_lib.ROI_MAX_LEVELS, len(feats)))
+    f0 = feats[0]
+    for l, f in enumerate(feats):
+        if not torch.is_tensor(f) or f.dim() != 4 or f.dtype not in _CODES or not f.is_cuda:
+            raise ValueError("level %d: features must be a 4-D CUDA bfloat16/float16 tensor, got %s" %
+                             (l, (f.dtype, str(f.device), tuple(f.shape)) if torch.is_tensor(f) else type(f)))
+        _chk_dev(f, "feats[%d]" % l)
+        if f.dtype != f0.dtype or f.shape[0] != f0.shape[0] or f.shape[1] != f0.shape[1]:
+            raise ValueError("level %d: %s %s does not match level 0's batch, channels and dtype %s %s" %
+                             (l, f.dtype, tuple(f.shape), f0.dtype, tuple(f0.shape)))
+        if f.shape[2] < 1 or f.shape[3] < 1:
+            raise ValueError("level %d: empty feature map %s" % (l, tuple(f.shape)))
+    B, C = f0.shape[0], f0.shape[1]
+    if B < 1 or C < 8 or C % 8:
+        raise ValueError("RoIAlign needs B >= 1 and C a positive multiple of 8, got B=%d C=%d" % (B, C))
+    return B, C, f0.dtype, [(f.shape[2], f.shape[3]) for f in feats]
+
+
+def _roi_levels(ts, dtype):
+    arr = (_lib.RoiLevel * len(ts))()
+    for v, t in zip(arr, ts):            # t: NHWC (B, H, W, C) contiguous
+        v.data = t.data_ptr()
+        v.strides[:] = [t.stride(0), t.stride(3), t.stride(1), t.stride(2)]
+        v.H, v.W, v.dtype = t.shape[1], t.shape[2], dtype_code(dtype)
+    return arr
+
+
+def roi_map_levels(rois, num_levels, finest_scale=56.0):
+    """(R,) int64 FPN level of every row of ``rois`` (tdn_roi_map_levels; the batch index is not looked at)."""
+    if rois.dim() == 2 and rois.shape[1] == 4:
+        raise ValueError("rois must be (R, 5) = (batch_idx, x1, y1, x2, y2)")
+    _chk_rois(rois)
+    L = int(num_levels)
+    if not 1 <= L <= _lib.ROI_MAX_LEVELS:
+        raise ValueError("num_levels must be in 1..%d" % _lib.ROI_MAX_LEVELS)
+    if not 0.0 < float(finest_scale) < float("inf"):
+        raise ValueError("finest_scale must be positive")
+    out = torch.empty(rois.shape[0], dtype=torch.int64, device=rois.device)
+    _lib.check(_lib.load().tdn_roi_map_levels(_ptr(rois), rois.shape[0], L, float(finest_scale), _ptr(out),
+                                              _lib.stream_ptr()), "tdn_roi_map_levels")
+    return out
+
+
+def roi_align_fwd(feats, rois, out_size, scales, sampling_ratio, finest_scale):
+    """Multi-level RoIAlign forward (tdn_roi_align_fwd, one launch).  ``feats``: logical (B, C, H_l, W_l) 16-bit
+    tensors; NHWC memory is read in place, any other layout goes once through tdn_nchw16_to_nhwc.  Everything is
+    checked here before the first launch.  Returns (R, C, S, S) in ``feats``' dtype, channels_last memory."""
+    B, C, dtype, _ = roi_level_shapes(feats)
+    _chk_rois(rois)
+    if rois.device != feats[0].device:
+        raise ValueError("rois are on %s, features on %s" % (rois.device, feats[0].device))
+    if len(scales) != len(feats):
+        raise ValueError("%d feature levels but %d featmap strides" % (len(feats), len(scales)))
+    cfg = _roi_config(out_size, scales, sampling_ratio, finest_scale)
+    S, R = cfg.out_size, rois.shape[0]
+    xs = [to_nhwc_bf16(f, dtype) for f in feats]
+    out = torch.empty(R, S, S, C, dtype=dtype, device=rois.device)
+    _lib.check(_lib.load().tdn_roi_align_fwd(_roi_levels(xs, dtype), len(xs), B, C, _ptr(rois), R, ctypes.byref(cfg),
+                                             _ptr(out), _lib.stream_ptr()), "tdn_roi_align_fwd")
+    return out.permute(0, 3, 1, 2)
+
+
+def roi_align_bwd(dout, rois, level_shapes, B, C, dtype, out_size, scales, sampling_ratio, finest_scale):
+    """Gradients of every level, NHWC (B, H_l, W_l, C) in ``dtype``, from the cotangent ``dout`` (R, C, S, S) of
+    roi_align_fwd (tdn_roi_align_bwd, two launches; fixed summation order, no atomics).  Pixels no valid row touches
+    are 0."""
+    cfg = _roi_config(out_size, scales, sampling_ratio, finest_scale)
+    S, R = cfg.out_size, rois.shape[0]
+    if tuple(dout.shape) != (R, C, S, S) or not dout.is_cuda:
+        raise ValueError("dout must be a CUDA (%d, %d, %d, %d) tensor, got %s" % (R, C, S, S, tuple(dout.shape)))
+    d = to_nhwc_bf16(dout, dtype) if R > 0 else None
+    dev = rois.device
+    grads = [torch.empty(B, h, w, C, dtype=dtype, device=dev) for h, w in level_shapes]
+    lib = _lib.load()
+    nbytes = lib.tdn_roi_align_bwd_workspace(R)
+    ws, wp = _aligned_ws(nbytes, dev)
+    _lib.check(lib.tdn_roi_align_bwd(_roi_levels(grads, dtype), len(grads), B, C, _ptr(rois), R, ctypes.byref(cfg),
+                                     _ptr(d), wp, nbytes, _lib.stream_ptr()), "tdn_roi_align_bwd")
+    return grads
+
+
+def rois_from_proposals(proposals, counts):
+    """(B*M, 5) rois (batch_idx, x1, y1, x2, y2) from rpn_proposals' (B, M, 5) output; rows at or past counts[b] get
+    batch index -1 (tdn_rois_from_proposals; no host synchronisation)."""
+    if not torch.is_tensor(proposals) or proposals.dtype != torch.float32 or not proposals.is_cuda or \
+            proposals.dim() != 3 or proposals.shape[2] != 5 or not proposals.is_contiguous():
+        raise ValueError("proposals must be a contiguous CUDA float32 (B, M, 5) tensor")
+    B, M = proposals.shape[0], proposals.shape[1]
+    if not torch.is_tensor(counts) or counts.dtype != torch.int32 or not counts.is_cuda or \
+            tuple(counts.shape) != (B,) or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous CUDA int32 (B,) tensor")
+    _chk_dev(proposals, "proposals")
+    _chk_dev(counts, "counts")
+    rois = torch.empty(B * M, 5, dtype=torch.float32, device=proposals.device)
+    _lib.check(_lib.load().tdn_rois_from_proposals(_ptr(proposals), _ptr(counts), B, M, _ptr(rois),
+                                                   _lib.stream_ptr()), "tdn_rois_from_proposals")
+    return rois
+
+
 # ---- image batch staging ---------------------------------------------------------------------------
 COLLATE_MAX = 16
 
