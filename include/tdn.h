@@ -153,8 +153,9 @@ typedef struct tdn_wgrad_item {
 int64_t tdn_wgrad_group_workspace(const tdn_wgrad_item* items, int n, int dtype);
 int tdn_wgrad_group(const tdn_wgrad_item* items, int n, void* workspace, int64_t workspace_bytes, int dtype,
                     void* stream);
-/* Host-only: the decomposition tdn_wgrad_group would use.  per_item[n][8] = {kernel (0 tap-per-tile, 1 nine-tap),
- * tile_co, tile_ci, splits, pixels per split, direct (1: no slabs), workgroups, fp32 slab bytes / 1024};
+/* Host-only: the decomposition tdn_wgrad_group would use.  per_item[n][8] = {kernel (0 tap-per-tile, 1 / 2 nine-tap
+ * with 128- / 64-wide tiles), tile_co, tile_ci, splits, pixels per split, direct (1: no slabs), workgroups, fp32 slab
+ * bytes / 1024};
  * totals[4] = {gradient-kernel launches, finalize launches, workgroups, slab KiB}. */
 int tdn_wgrad_group_plan(const tdn_wgrad_item* items, int n, int dtype, int32_t* per_item, int32_t* totals);
 

@@ -82,8 +82,7 @@ SHAPES = [(1, 8, 16), (1, 16, 32), (2, 24, 48), (1, 13, 21), (3, 5, 7), (1, 17, 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("N,H,W", SHAPES)
 def test_block_forward(ops, generic_tiles, N, H, W, dtype, C):
-    if not ops.bottleneck_supported(H, W, C):
-        pytest.skip("no one-launch kernel for C=%d in this build" % C)
+    assert ops.bottleneck_supported(H, W, C), "no one-launch kernel for C=%d in this build" % C
     x, w1, w2, w3, aff = _case(N, H, W, C, dtype, 100 * H + W)
     dev = torch.device("cuda")
     xg, w1g, w2g, w3g = (t.contiguous().to(dev) for t in (x, w1, w2, w3))
@@ -112,8 +111,7 @@ def test_block_forward(ops, generic_tiles, N, H, W, dtype, C):
 @pytest.mark.parametrize("N,H,W", SHAPES)
 @pytest.mark.parametrize("with_mask3", [True, False])
 def test_block_dgrad(ops, generic_tiles, N, H, W, dtype, with_mask3, C):
-    if not ops.bottleneck_supported(H, W, C):
-        pytest.skip("no one-launch kernel for C=%d in this build" % C)
+    assert ops.bottleneck_supported(H, W, C), "no one-launch kernel for C=%d in this build" % C
     C4 = 4 * C
     seed = 100 * H + W + 7
     x, w1, w2, w3, aff = _case(N, H, W, C, dtype, seed)
@@ -252,8 +250,7 @@ def test_head_block_forward_and_dgrad(ops, generic_tiles, N, H, W, dtype, with_b
     """Bit for bit against the per-conv launches of layer1.0: downsample conv, conv1, conv2, conv3 + residual, and their
     input gradients (dx = conv1^T(g1) + downsample^T(g), unmasked)."""
     C, C4 = 64, 256
-    if not ops.bottleneck_head_supported(H, W, C, C):
-        pytest.skip("no head kernel in this build")
+    assert ops.bottleneck_head_supported(H, W, C, C), "no head kernel in this build"
     x, w1, w2, w3, wd, aff = _head_case(N, H, W, dtype, 100 * H + W + 3)
     dev = torch.device("cuda")
     xg, w1g, w2g, w3g, wdg = (t.contiguous().to(dev) for t in (x, w1, w2, w3, wd))

@@ -81,8 +81,15 @@ struct BlockParams {
 // Store target of output pixels that lie outside the image (ragged right / bottom tiles): the epilogue's loads and
 // stores are then unconditional — address selects, no branches — so the compiler can count what is in flight behind a
 // load instead of waiting vmcnt(0), which would drain the stores issued before it.
-static __device__ __attribute__((aligned(256))) unsigned char g_blk_sink[512];
-static __device__ __attribute__((aligned(256))) unsigned char g_blk_zero[512];   // load source of such pixels (a lane reads up to 288 B behind its base)
+// An invalid pixel's base is the page itself, and phase 3 of the C = 64 / C = 128 kernels still adds its pass and half
+// offsets to it: nc * kPass + h * 8 elements with nc, h in {0, 1} and kPass = 2C the channels of one pass, then one
+// 16-byte vector — 288 B behind the base for C = 64, 544 B for C = 128 (blk_page_reach; each kernel names kPass once,
+// uses it in those accesses and asserts its reach against kBlkPageBytes).
+constexpr int kBlkPageBytes = 1024;
+constexpr int blk_page_reach(int pass) { return (pass + 8) * 2 + 16; }
+static_assert(blk_page_reach(128) == 288 && blk_page_reach(256) == 544, "see the comment above");
+static __device__ __attribute__((aligned(256))) unsigned char g_blk_sink[kBlkPageBytes];
+static __device__ __attribute__((aligned(256))) unsigned char g_blk_zero[kBlkPageBytes];   // load source of such pixels
 
 // bit e of the result: element e of v is > 0 (what the ReLU masks of the backward pass test).  Both 16-bit float formats
 // are sign-magnitude, so "> 0" is the signed 16-bit integer test: max(min(h, 1), 0) is 1 for a positive half-word and 0
@@ -489,6 +496,9 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
     const int y = y0 + wm * 4 + j, x = x0 + fr;
     pixj[j] = ((y < H) && (x < W)) ? (int)(img_pix0 + (int64_t)y * W + x) : -1;
   }
+  // adp / mkp / o3p are used at + nc * kPass + h * 8 elements (nc, h < 2), b3r at + nc * (C / 16) words
+  constexpr int kPass = 2 * C;      // output channels per phase-3 pass
+  static_assert(blk_page_reach(kPass) <= kBlkPageBytes, "zero / sink page too small for an invalid pixel's accesses");
   auto adp = [&](int j) { return pixj[j] >= 0 ? (HEAD ? p.ad : p.a) + (int64_t)pixj[j] * C4 + chw : (const bf16_t*)g_blk_zero; };
   auto mkp = [&](int j) { return (pixj[j] >= 0 && p.m3 && !MB) ? p.m3 + (int64_t)pixj[j] * C4 + chw : (const bf16_t*)g_blk_zero; };
   auto o3p = [&](int j) { return pixj[j] >= 0 ? p.o3 + (int64_t)pixj[j] * C4 + chw : (bf16_t*)g_blk_sink; };
@@ -500,14 +510,14 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) dst[j][h] = *(const bf16x8_t*)(adp(j) + nc * 128 + h * 8);
+      for (int h = 0; h < 2; ++h) dst[j][h] = *(const bf16x8_t*)(adp(j) + nc * kPass + h * 8);
   };
   auto load_mask3 = [&](int nc) {
     if constexpr (!MB) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) mk3[j][h] = *(const bf16x8_t*)(mkp(j) + nc * 128 + h * 8);
+        for (int h = 0; h < 2; ++h) mk3[j][h] = *(const bf16x8_t*)(mkp(j) + nc * kPass + h * 8);
     }
   };
   bf16x8_t adh[(BWD && HEAD) ? 4 : 1];   // head, backward: this lane's 8 channels of the downsample branch's input gradient
@@ -879,7 +889,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) *(bf16x8_t*)(o3p(j) + nc * 128 + h * 8) = ov[j][h];
+        for (int h = 0; h < 2; ++h) *(bf16x8_t*)(o3p(j) + nc * kPass + h * 8) = ov[j][h];
       if constexpr (!BWD && !HEAD) {
         if (p.b3) {   // x > 0: the pixel's 64-channel word pair from the four lanes' 16 bits each; lane fq stores row fq's
           const bf16x8_t (&ad)[4][2] = nc == 0 ? ad0 : ad1;
@@ -1181,6 +1191,9 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
     const int y = y0 + wm * 4 + j, x = x0 + pi;
     pixj[j] = ((y < H) && (x < W)) ? (int)(img_pix0 + (int64_t)y * W + x) : -1;
   }
+  // adp / mkp / o3p are used at + nc * kPass + h * 8 elements (nc, h < 2), b3r at + nc * (C / 16) words
+  constexpr int kPass = 2 * C;      // output channels per phase-3 pass
+  static_assert(blk_page_reach(kPass) <= kBlkPageBytes, "zero / sink page too small for an invalid pixel's accesses");
   auto adp = [&](int j) { return pixj[j] >= 0 ? p.a + (int64_t)pixj[j] * C4 + chw : (const bf16_t*)g_blk_zero; };
   auto mkp = [&](int j) { return (pixj[j] >= 0 && p.m3 && !MB) ? p.m3 + (int64_t)pixj[j] * C4 + chw : (const bf16_t*)g_blk_zero; };
   auto o3p = [&](int j) { return pixj[j] >= 0 ? p.o3 + (int64_t)pixj[j] * C4 + chw : (bf16_t*)g_blk_sink; };
@@ -1198,7 +1211,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) mk3[j][h] = *(const bf16x8_t*)(mkp(j) + nc * 256 + h * 8);
+        for (int h = 0; h < 2; ++h) mk3[j][h] = *(const bf16x8_t*)(mkp(j) + nc * kPass + h * 8);
     }
   };
 #pragma unroll
@@ -1253,7 +1266,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) ad1[j][h] = *(const bf16x8_t*)(adp(j) + 256 + h * 8);
+      for (int h = 0; h < 2; ++h) ad1[j][h] = *(const bf16x8_t*)(adp(j) + kPass + h * 8);
   };
   if constexpr (!BWD) load_ad1();
   f32x4_t sc3v[4], sh3v[4];
@@ -1394,7 +1407,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) *(bf16x8_t*)(o3p(j) + nc * 256 + h * 8) = ov[j][h];
+      for (int h = 0; h < 2; ++h) *(bf16x8_t*)(o3p(j) + nc * kPass + h * 8) = ov[j][h];
     if constexpr (!BWD) {
       if (p.b3) {   // x > 0: the pixel's 64-channel word pair from the four lanes' 16 bits each; lane fq stores row fq's
         const bf16x8_t (&ad)[4][2] = nc == 0 ? ad0 : ad1;
