@@ -51,8 +51,20 @@ class Unit(object):
         self.wd = rnd(self.wb * sc, quant)       # dgrad operand: bf16(scale * bf16(w))
         self.quant = quant
 
-    def fwd(self, x, addend=None, mode=None, relu=False):
-        v = F.conv2d(x, self.wb, None, self.stride, self.pad)
+    def conv(self, x):
+        """The bare fp32 convolution of fwd(): callers that also need the unrounded value compute it once and hand it
+        back through ``conv=``."""
+        return F.conv2d(x, self.wb, None, self.stride, self.pad)
+
+    def conv_t(self, g, in_hw):
+        """The bare fp32 transposed convolution of dgrad() (see conv())."""
+        H, W = in_hw
+        oph = H - ((g.shape[2] - 1) * self.stride - 2 * self.pad + self.k)
+        opw = W - ((g.shape[3] - 1) * self.stride - 2 * self.pad + self.k)
+        return F.conv_transpose2d(g, self.wd, None, self.stride, self.pad, (oph, opw))
+
+    def fwd(self, x, addend=None, mode=None, relu=False, conv=None):
+        v = self.conv(x) if conv is None else conv
         if self.scale is not None:
             v = v * self.scale.view(1, -1, 1, 1)
         if self.shift is not None:
@@ -63,20 +75,19 @@ class Unit(object):
             v = F.relu(v)
         return rnd(v, self.quant)
 
-    def dgrad(self, g, in_hw, addend=None, mode=None, mask_src=None):
-        H, W = in_hw
-        oph = H - ((g.shape[2] - 1) * self.stride - 2 * self.pad + self.k)
-        opw = W - ((g.shape[3] - 1) * self.stride - 2 * self.pad + self.k)
-        dx = F.conv_transpose2d(g, self.wd, None, self.stride, self.pad, (oph, opw))
+    def dgrad(self, g, in_hw, addend=None, mode=None, mask_src=None, conv=None):
+        dx = self.conv_t(g, in_hw) if conv is None else conv
         if addend is not None:
             dx = dx + (addend if mode == 'same' else F.avg_pool2d(addend, 2) * 4.0)
         if mask_src is not None:
             dx = dx * (mask_src > 0).to(dx.dtype)
         return rnd(dx, self.quant)
 
-    def wgrad(self, x, g):
-        """Returns grads aligned with the parameters: BN -> (dw, dgamma, dbeta); bias -> (dw, dbias); else (dw,)."""
-        G = torch.nn.grad.conv2d_weight(x, self.w.shape, g, self.stride, self.pad)
+    def wgrad(self, x, g, G=None):
+        """Returns grads aligned with the parameters: BN -> (dw, dgamma, dbeta); bias -> (dw, dbias); else (dw,).
+        ``G``: the bare fp32 conv2d_weight(x, g), where the caller has it already."""
+        if G is None:
+            G = torch.nn.grad.conv2d_weight(x, self.w.shape, g, self.stride, self.pad)
         colsum = g.sum((0, 2, 3))
         if self.invstd is not None:
             dw = G * self.scale.view(-1, 1, 1, 1)

@@ -15,6 +15,7 @@ import os
 import torch
 import torch.nn.functional as F
 
+import bound_util as B
 from golden_util import det_tensor, fill_state_dict, rel_l2
 
 
@@ -22,10 +23,83 @@ def nchw(t):
     return t.detach().float().cpu().permute(0, 3, 1, 2).contiguous()
 
 
+class Elementwise(object):
+    """Worst elementwise ratio |got - v| / allowance (tests/bound_util.py) per launch kind, with the element it
+    occurred at.  ``cheap``: the full-size form — v from the oracle's own fp32 convolution (its error term added to the
+    allowance) and the Cauchy-Schwarz bound for S; otherwise fp64 v and the exact S."""
+
+    def __init__(self, cheap, dtype):
+        self.cheap, self.dtype = cheap, dtype
+        self.rec = {}
+
+    def put(self, kind, r):
+        if kind not in self.rec or r["ratio"] > self.rec[kind]["ratio"]:
+            self.rec[kind] = r
+
+    def fwd(self, kind, name, ref_u, gu, x, got, addend=None, mode=None, relu=False, extra=None):
+        """One forward launch: the oracle unit's 16-bit weights, the GPU unit's own fp32 scale / shift vectors (the
+        operands of the launch).  Returns (bound, the oracle's fp32 conv for its own fwd(conv=) or None)."""
+        pin_fold(name, ref_u, gu)
+        conv = ref_u.conv(x) if self.cheap else None
+        b = B.fwd_bound(x, ref_u.wb, ref_u.stride, ref_u.pad, gu.scale, gu.shift, addend, mode, relu,
+                        cheap=self.cheap, conv32=conv)
+        if got is not None:
+            self.put(kind, B.check(got, b, self.dtype, extra, name))
+        return b, conv
+
+    def result(self):
+        out = dict(self.rec)
+        out["mode"] = ("fp32 reference + its K*2^-24*S term, Cauchy-Schwarz S" if self.cheap else "fp64 reference, exact S")
+        return out
+
+
+FOLD_RTOL = 2.0 ** -19     # scale = gamma / sqrt(var + eps): four rounded fp32 operations on either side (2^-24 each)
+                           # and a reciprocal square root good to two ulps on the GPU: under 2^-20; one bit of margin
+
+
+def pin_fold(name, ref_u, gu):
+    """The launch's own fp32 scale / shift vectors (the elementwise checks take them as operands) against the oracle's
+    fold: a bias is the parameter itself, bit for bit; a BN fold agrees to FOLD_RTOL, the shift = beta - mean * scale
+    relative to |beta| + |mean * scale|."""
+    if ref_u.scale is None:
+        assert gu.scale is None, name
+        assert (gu.shift is None) == (ref_u.shift is None), name
+        if ref_u.shift is not None:
+            assert torch.equal(gu.shift.detach().float().cpu(), ref_u.shift), name + ": bias"
+        return
+    sc, sh = gu.scale.detach().double().cpu(), gu.shift.detach().double().cpu()
+    rs, rh = ref_u.scale.double(), ref_u.shift.double()
+    assert bool(((sc - rs).abs() <= FOLD_RTOL * rs.abs()).all()), name + ": folded scale"
+    ms = (ref_u.mean.double() * rs).abs()
+    assert bool(((sh - rh).abs() <= FOLD_RTOL * ((rh.abs() + ms) + ms)).all()), name + ": folded shift"
+
+
+def pin_dgrad_weights(name, w_eff, ref_u, dtype):
+    """The launch's packed dgrad operand against the oracle's 16-bit(scale * 16-bit(w)): the scale may differ by
+    FOLD_RTOL and the product is rounded once more, so the two lie within one ulp16 of each other."""
+    d = (w_eff.double() - ref_u.wd.double()).abs()
+    assert bool((d <= 2.0 * B.half_ulp16(ref_u.wd, dtype)).all()), name + ": packed dgrad weights"
+
+
+ELEMENTWISE_GATED = ("stem", "block_conv1", "block_conv2", "block_conv3", "block_residual_downsample", "block_last_basic",
+                     "fpn_lateral", "fpn_lateral_up2x", "fpn_out", "dgrad")
+
+
+def gpu_units(rb, rf, launches):
+    """conv name -> the HIP path's ConvUnit, from the recorded backward launches (every conv has a weight gradient)."""
+    names = {}
+    for prefix, mod in (("backbone.", rb), ("neck.", rf)):
+        for name, m in mod.named_modules():
+            if isinstance(m, torch.nn.Conv2d):
+                names[id(m)] = prefix + name
+    return {names[id(rec[1].conv)]: rec[1] for rec in launches}
+
+
 def run_teacher_forced(T, depth, shape, dev="cuda", threads=None, dtype=torch.bfloat16, cot_scale=1.0,
-                       res_gain=1.0, end_to_end=True):
+                       res_gain=1.0, end_to_end=True, cheap_bound=False):
     """Returns a dict of measured relative-L2 errors (forward in situ, backward teacher-forced, and the plain
-    end-to-end distances to the fp32 autograd oracle for the record)."""
+    end-to-end distances to the fp32 autograd oracle for the record) and, under "elementwise", the worst ratio of every
+    launch kind against the a-priori rounding bound of tests/bound_util.py (``cheap_bound``: its full-size form)."""
     from oracle import sched_ref as S
     from oracle import torch_ref as O
     from torch_detection_amd import functional as HF
@@ -76,29 +150,63 @@ def run_teacher_forced(T, depth, shape, dev="cuda", threads=None, dtype=torch.bf
     sch = S.Sched(sdb, sdf, depth, 5, quant=dtype)
     fwd = {}
     # ---- forward, launch by launch, from the GPU's own inputs ----
-    fwd["stem"] = rel_l2(g_s, sch.stem.fwd(S.rnd(x, dtype), relu=True))
+    gu = gpu_units(rb, rf, bwd_launches)
+    el = Elementwise(cheap_bound, dtype)
+    xq = S.rnd(x, dtype)
+    _, cv = el.fwd("stem", "backbone.conv1", sch.stem, gu["backbone.conv1"], xq, g_s, relu=True)
+    fwd["stem"] = rel_l2(g_s, sch.stem.fwd(xq, relu=True, conv=cv))
+    # exact operations (selections of already-rounded values): the max pool of the GPU's own stem output, and P6
     fwd["maxpool"] = rel_l2(g_saved[0][0], F.max_pool2d(g_s, 3, 2, 1))
+    exact = {"maxpool": bool(torch.equal(g_saved[0][0], F.max_pool2d(g_s, 3, 2, 1))),
+             "p6": bool(torch.equal(g_outs[4], g_outs[3][:, :, ::2, ::2]))}
     worst_blk = 0.0
     for blk, (bx, h1, h2, out) in zip(sch.blocks, g_saved):
-        worst_blk = max(worst_blk, rel_l2(h1, blk.u1.fwd(bx, relu=True)))
-        res = bx if blk.ud is None else blk.ud.fwd(bx)   # not saved by the HIP path: one launch deep on CPU
+        pre = "backbone.%s." % blk.p
+        _, cv = el.fwd("block_conv1", pre + "conv1", blk.u1, gu[pre + "conv1"], bx, h1, relu=True)
+        worst_blk = max(worst_blk, rel_l2(h1, blk.u1.fwd(bx, relu=True, conv=cv)))
+        res, res_e, extra = bx, bx, None
+        if blk.ud is not None:   # not saved by the HIP path: one launch deep on CPU
+            # the elementwise check takes the residual from the same bound it derives the operand slack from (the
+            # GPU's own scale / shift): the GPU's 16-bit residual is within E (+ R) + one ulp16 of it
+            bd, cv = el.fwd(None, pre + "downsample.0", blk.ud, gu[pre + "downsample.0"], bx, None)
+            res = blk.ud.fwd(bx, conv=cv)
+            res_e = S.rnd(bd.v.float(), dtype)
+            extra = B.operand_slack(bd, dtype)
+            del bd
+        last = "conv3" if blk.kind == "bottleneck" else "conv2"
         if blk.kind == "bottleneck":
-            worst_blk = max(worst_blk, rel_l2(h2, blk.u2.fwd(h1, relu=True)))
-            worst_blk = max(worst_blk, rel_l2(out, blk.u3.fwd(h2, res, "same", True)))
+            _, cv = el.fwd("block_conv2", pre + "conv2", blk.u2, gu[pre + "conv2"], h1, h2, relu=True)
+            worst_blk = max(worst_blk, rel_l2(h2, blk.u2.fwd(h1, relu=True, conv=cv)))
+            kind = "block_conv3" if blk.ud is None else "block_residual_downsample"
+            _, cv = el.fwd(kind, pre + last, blk.u3, gu[pre + last], h2, out, res_e, "same", True, extra)
+            worst_blk = max(worst_blk, rel_l2(out, blk.u3.fwd(h2, res, "same", True, conv=cv)))
         else:
-            worst_blk = max(worst_blk, rel_l2(out, blk.u2.fwd(h1, res, "same", True)))
+            kind = "block_last_basic" if blk.ud is None else "block_residual_downsample"
+            _, cv = el.fwd(kind, pre + last, blk.u2, gu[pre + last], h1, out, res_e, "same", True, extra)
+            worst_blk = max(worst_blk, rel_l2(out, blk.u2.fwd(h1, res, "same", True, conv=cv)))
     fwd["blocks_worst"] = worst_blk
     feats = [g_saved[i][3] for i in sch.stage_last]
     worst = 0.0
     for i in reversed(range(4)):
-        ref = sch.lat_u[i].fwd(feats[i]) if i == 3 else sch.lat_u[i].fwd(feats[i], g_lat[i + 1], "up2x")
+        name = "neck.lateral_convs.%d.conv" % i
+        if i == 3:
+            _, cv = el.fwd("fpn_lateral", name, sch.lat_u[i], gu[name], feats[i], g_lat[i])
+            ref = sch.lat_u[i].fwd(feats[i], conv=cv)
+        else:
+            _, cv = el.fwd("fpn_lateral_up2x", name, sch.lat_u[i], gu[name], feats[i], g_lat[i], g_lat[i + 1], "up2x")
+            ref = sch.lat_u[i].fwd(feats[i], g_lat[i + 1], "up2x", conv=cv)
         worst = max(worst, rel_l2(g_lat[i], ref))
     for i in range(4):
-        worst = max(worst, rel_l2(g_outs[i], sch.fpn_u[i].fwd(g_lat[i])))
+        name = "neck.fpn_convs.%d.conv" % i
+        _, cv = el.fwd("fpn_out", name, sch.fpn_u[i], gu[name], g_lat[i], g_outs[i])
+        worst = max(worst, rel_l2(g_outs[i], sch.fpn_u[i].fwd(g_lat[i], conv=cv)))
     worst = max(worst, rel_l2(g_outs[4], g_outs[3][:, :, ::2, ::2]))
     fwd["fpn_worst"] = worst
+    del cv
     # ---- backward, launch by launch, from the GPU's own operands of that launch ----
-    bwd = backward_in_situ(sch, rb, rf, bwd_launches, S.rnd(x, dtype))
+    bwd = backward_in_situ(sch, rb, rf, bwd_launches, xq, cheap=cheap_bound)
+    elem = el.result()
+    elem.update({k: v for k, v in bwd.pop("elementwise").items() if k != "mode"})
     # ---- backward with the GPU's saved activations ----
     sch.x = S.rnd(x, dtype)
     sch.out_shapes = [tuple(o.shape) for o in g_outs]
@@ -116,19 +224,24 @@ def run_teacher_forced(T, depth, shape, dev="cuda", threads=None, dtype=torch.bf
     else:   # full-size runs skip the fp32 autograd pass of the whole net (the in-situ checks are the point there)
         eo32, eg32 = [0.0], [0.0]
     return {"forward_in_situ": fwd,
+            "forward_exact": exact,
+            "elementwise": elem,
             "backward_in_situ": bwd,
             "backward_teacher_forced": {"grad_worst": list(worst_g), "grad_median": srt[len(srt) // 2]},
             "end_to_end_vs_fp32_autograd": {"out": eo32, "grad_median": eg32[len(eg32) // 2],
                                             "grad_worst": eg32[-1]}}
 
 
-def backward_in_situ(sch, rb, rf, launches, x_img):
+def backward_in_situ(sch, rb, rf, launches, x_img, cheap=False):
     """Every dgrad launch and every weight-gradient member of the GPU's backward pass, recomputed on the CPU by the
     schedule oracle's unit of the same layer from the GPU's OWN operands of that launch (the activation gradient g it
     read, the addend / ReLU-mask tensors of its epilogue, the saved forward input).  Identical inputs on both sides:
     what is left is one layer's arithmetic — fp32 accumulation order and one rounding to the 16-bit storage type —
     so the per-launch bound is the north star's 1e-3, for every layer, at any depth.
-    Returns the worst relative-L2 error per kind and where it occurred."""
+    Returns the worst relative-L2 error per kind and where it occurred; under "elementwise" the worst ratio against
+    the a-priori rounding bound (tests/bound_util.py) of the dgrad launches — computed on the launch's own packed
+    dgrad weights — and of dw (recorded; a gate only where the caller makes it one: at full size K = N * Ho * Wo makes
+    the worst-case bound looser than a typical element)."""
     from torch_detection_amd import ops
     units = {}
     conv_name = {}
@@ -149,6 +262,8 @@ def backward_in_situ(sch, rb, rf, launches, x_img):
         units["neck.fpn_convs.%d.conv" % i] = sch.fpn_u[i]
     worst = {"dgrad": [0.0, None], "dw": [0.0, None], "dgamma": [0.0, None], "dbeta_or_dbias": [0.0, None]}
     count = {"dgrad": 0, "wgrad": 0}
+    dtype = torch.bfloat16 if sch.q is True else sch.q
+    el = Elementwise(cheap, dtype)
 
     def upd(kind, err, name):
         if err > worst[kind][0]:
@@ -160,14 +275,30 @@ def backward_in_situ(sch, rb, rf, launches, x_img):
         if rec[0] == 'dgrad':
             _, u, g, in_hw, addend, mode, mask_src, dx = rec
             a = nchw(addend) if addend is not None and mode != ops.ADD_NONE else None
-            ref = ref_u.dgrad(nchw(g), in_hw, a, 'same' if mode == ops.ADD_SAME else 'sumpool',
-                              nchw(mask_src) if mask_src is not None else None)
+            gc, mode_s = nchw(g), 'same' if mode == ops.ADD_SAME else 'sumpool'
+            msk = nchw(mask_src) if mask_src is not None else None
+            # the launch's own dgrad operand [Cin][kh][kw][Cout] (16-bit(scale * 16-bit(w)), packed on the GPU)
+            w_eff = u.w_dgrad.detach().float().cpu().permute(3, 0, 1, 2).contiguous()
+            pin_dgrad_weights(name, w_eff, ref_u, dtype)
+            same_w = torch.equal(w_eff, ref_u.wd)
+            cv = ref_u.conv_t(gc, in_hw) if cheap else None
+            cv_e = cv if same_w or not cheap else True
+            b = B.dgrad_bound(gc, w_eff, in_hw, ref_u.stride, ref_u.pad, a, mode_s if a is not None else None, msk,
+                              cheap=cheap, conv32=cv_e)
+            el.put("dgrad", B.check(nchw(dx), b, dtype, None, name))
+            del b
+            ref = ref_u.dgrad(gc, in_hw, a, mode_s, msk, conv=cv)
             upd("dgrad", rel_l2(nchw(dx), ref), name)
             count["dgrad"] += 1
         else:
             _, u, x_in, g, img_hw, (dw, dg, db) = rec
             xin = x_img if u.is_stem else nchw(x_in)
-            ref = ref_u.wgrad(xin, nchw(g))
+            gc = nchw(g)
+            G = torch.nn.grad.conv2d_weight(xin, ref_u.w.shape, gc, ref_u.stride, ref_u.pad)
+            b = B.wgrad_bound(xin, gc, ref_u.w.shape, ref_u.stride, ref_u.pad, u.scale, cheap=cheap, G32=G)
+            el.put("dw", B.check(dw.detach().float().cpu(), b, torch.float32, None, name))
+            del b
+            ref = ref_u.wgrad(xin, gc, G=G)
             upd("dw", rel_l2(dw.detach().float().cpu(), ref[0]), name)
             if len(ref) == 3:
                 upd("dgamma", rel_l2(dg.float().cpu(), ref[1]), name)
@@ -177,6 +308,7 @@ def backward_in_situ(sch, rb, rf, launches, x_img):
             count["wgrad"] += 1
     out = {k: v for k, v in worst.items()}
     out["launches"] = count
+    out["elementwise"] = el.result()
     return out
 
 
@@ -196,9 +328,22 @@ BWD_IN_SITU_TOL = 1e-3      # every dgrad launch / weight-gradient member on its
                             # weight gradients: accumulation order only; dgrad: one 16-bit rounding, like the forward)
 
 
+def check_elementwise(res, weights=False):
+    """Every forward and dgrad launch kind: worst |got - v| / allowance <= 1, the failure naming the element; the two
+    exact operations bit for bit.  ``weights``: dw too (sizes where K = N * Ho * Wo is a few thousand)."""
+    e = res["elementwise"]
+    kinds = [k for k in ELEMENTWISE_GATED if k in e]
+    assert "stem" in kinds and "dgrad" in kinds and "fpn_out" in kinds and len(kinds) >= 7, kinds
+    for k in kinds + (["dw"] if weights else []):
+        assert e[k]["ratio"] <= 1.0, k + " / " + B.message(e[k])
+    assert "dw" in e
+    assert res["forward_exact"] == {"maxpool": True, "p6": True}, res["forward_exact"]
+
+
 def check(res, depth=50):
     f = res["forward_in_situ"]
     assert max(f.values()) <= FWD_IN_SITU_TOL, f
+    check_elementwise(res, weights=True)
     b = res["backward_in_situ"]
     assert b["launches"]["dgrad"] > 0 and b["launches"]["wgrad"] > 0, b
     for kind in ("dgrad", "dw", "dgamma", "dbeta_or_dbias"):

@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bound_util as B
 from golden_util import det_tensor, max_rel
 
 pytestmark = pytest.mark.gpu
@@ -75,6 +76,32 @@ def _fwd_ref(x, w1, w2, w3, aff, dtype):
     return [t.permute(0, 2, 3, 1).contiguous() for t in (h1, h2, out)]
 
 
+def _nchw(t):
+    return t.float().cpu().permute(0, 3, 1, 2).contiguous()
+
+
+def _elementwise_fwd(dtype, x, w1, w2, w3, aff, h1, h2, out, res=None):
+    """Every element of the three stored tensors against the a-priori rounding bound (tests/bound_util.py), each conv
+    on the GPU's own input of that stage (h2 from the stored h1, out from the stored h2)."""
+    xc = _nchw(x)
+    B.assert_within(_nchw(h1), B.fwd_bound(xc, _oihw(w1), 1, 0, aff[0], aff[1], relu=True), dtype, "block h1")
+    B.assert_within(_nchw(h2), B.fwd_bound(_nchw(h1), _oihw(w2), 1, 1, aff[2], aff[3], relu=True), dtype, "block h2")
+    B.assert_within(_nchw(out), B.fwd_bound(_nchw(h2), _oihw(w3), 1, 0, aff[4], aff[5],
+                                            xc if res is None else _nchw(res), "same", True), dtype, "block out")
+
+
+def _elementwise_dgrad(dtype, g, w3d, w2d, w1d, h2, h1, m3, add, g2, g1, dx):
+    """The same for the input-gradient chain; the packed dgrad weights are [Cin][kh][kw][Cout]."""
+    hw = (g.shape[1], g.shape[2])
+
+    def oi(wd):
+        return wd.float().cpu().permute(3, 0, 1, 2).contiguous()
+    B.assert_within(_nchw(g2), B.dgrad_bound(_nchw(g), oi(w3d), hw, 1, 0, mask_src=_nchw(h2)), dtype, "block g2")
+    B.assert_within(_nchw(g1), B.dgrad_bound(_nchw(g2), oi(w2d), hw, 1, 1, mask_src=_nchw(h1)), dtype, "block g1")
+    B.assert_within(_nchw(dx), B.dgrad_bound(_nchw(g1), oi(w1d), hw, 1, 0, _nchw(add), "same",
+                                             _nchw(m3) if m3 is not None else None), dtype, "block dx")
+
+
 SHAPES = [(1, 8, 16), (1, 16, 32), (2, 24, 48), (1, 13, 21), (3, 5, 7), (1, 17, 40), (2, 9, 33)]
 
 
@@ -104,6 +131,7 @@ def test_block_forward(ops, generic_tiles, N, H, W, dtype, C):
         # 16-bit outputs: within one rounding step of the fp32 reference (plus the fp32 accumulation tolerance)
         err = (a.float().cpu() - b).abs().max().item()
         assert err <= (TOL + ulp) * b.abs().max().item() + 1e-6, (name, err, b.abs().max().item())
+    _elementwise_fwd(dtype, x, w1, w2, w3, aff, h1, h2, out)
 
 
 @pytest.mark.parametrize("C", [64, 128])
@@ -150,6 +178,7 @@ def test_block_dgrad(ops, generic_tiles, N, H, W, dtype, with_mask3, C):
     if with_mask3:
         cx = torch.where(x > 0, cx, torch.zeros(()))
     assert max_rel(dx.float().cpu(), cx) <= TOL + ulp
+    _elementwise_dgrad(dtype, g, w3d, w2d, w1d, h2, h1, m3, g, g2, g1, dx)
 
 
 @pytest.mark.parametrize("rep", range(3))
@@ -290,6 +319,8 @@ def test_head_block_forward_and_dgrad(ops, generic_tiles, N, H, W, dtype, with_b
     fo = torch.relu(bn(F.conv2d(f2, _oihw(w3)), aff[4], aff[5]) + fr).permute(0, 2, 3, 1)
     ulp = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
     assert max_rel(out.float().cpu(), fo) <= TOL + 2 * ulp
+    B.assert_within(_nchw(res), B.fwd_bound(_nchw(x), _oihw(wd), 1, 0, aff[6], aff[7]), dtype, "head downsample")
+    _elementwise_fwd(dtype, x, w1, w2, w3, aff, h1, h2, out, res)
     # backward
     w1d, w2d, w3d, wdd = (w.permute(3, 1, 2, 0).contiguous() for w in (w1g, w2g, w3g, wdg))
     g = torch.where(out > 0, (det_tensor((N, H, W, C4), 555) * 0.1).to(dtype).to(dev), torch.zeros((), device=dev, dtype=dtype))
@@ -307,6 +338,9 @@ def test_head_block_forward_and_dgrad(ops, generic_tiles, N, H, W, dtype, with_b
         ne = a.view(torch.int16) != b.view(torch.int16)
         assert not bool(ne.any()), "%s: %d of %d elements differ, first %s" % (name, int(ne.sum()), a.numel(), ne.nonzero()[:4].tolist())
     assert dx.shape == (N, H, W, C)
+    B.assert_within(_nchw(t), B.dgrad_bound(_nchw(g), wdd.float().cpu().permute(3, 0, 1, 2).contiguous(), (H, W), 1, 0),
+                    dtype, "head downsample dgrad")
+    _elementwise_dgrad(dtype, g, w3d, w2d, w1d, h2, h1, None, t, g2, g1, dx)
     # the same with the downsample conv's input gradient computed inside the launch
     if with_bits:
         k2, k1, kx = ops.bottleneck_head_dgrad(g, w3d, w2d, w1d, None, None, bits=bits, down=wdd)
@@ -350,6 +384,7 @@ def test_block128_tall_tiles(ops, generic_tiles, monkeypatch, N, H, W, dtype, mo
     if bits is not None:
         for name, b, ref, ch in (("h1", bits[0], h1, C), ("h2", bits[1], h2, C), ("x", bits[2], xg, C4)):
             assert torch.equal(_unpack_bits(b, ch), (ref.float().cpu() > 0)), name
+    _elementwise_fwd(dtype, x, w1, w2, w3, aff, h1, h2, out)
     w1d, w2d, w3d = (w.permute(3, 1, 2, 0).contiguous() for w in (w1g, w2g, w3g))
     g = torch.where(out > 0, (det_tensor((N, H, W, C4), 313) * 0.1).to(dtype).to(dev), torch.zeros((), device=dev, dtype=dtype))
     g = g.contiguous()
@@ -365,3 +400,4 @@ def test_block128_tall_tiles(ops, generic_tiles, monkeypatch, N, H, W, dtype, mo
     for name, a, b in (("g2", g2, q2), ("g1", g1, q1), ("dx", dx, qx)):
         ne = a.view(torch.int16) != b.view(torch.int16)
         assert not bool(ne.any()), "%s: %d of %d elements differ, first %s" % (name, int(ne.sum()), a.numel(), ne.nonzero()[:4].tolist())
+    _elementwise_dgrad(dtype, g, w3d, w2d, w1d, h2, h1, m3, g, g2, g1, dx)

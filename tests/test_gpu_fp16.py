@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bound_util as B
 from golden_util import det_tensor, max_rel, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -73,10 +74,13 @@ def test_conv_fwd_dgrad_f16(ops, case):
     y32 = ops.conv2d_fwd(nhwc(x), wf, k, s, k // 2, scale.cuda(), shift.cuda(), nhwc(res), ops.ADD_SAME, True,
                          out_f32=True)
     assert max_rel(nchw(y32), ref_r) <= TOL
+    bound = B.fwd_bound(x, w, s, k // 2, scale, shift, res, "same", True)
+    B.assert_within(nchw(y32), bound, torch.float32, "conv2d_fwd f16 operands, f32 out %s" % (case,))
     y16 = ops.conv2d_fwd(nhwc(x), wf, k, s, k // 2, scale.cuda(), shift.cuda(), nhwc(res), ops.ADD_SAME, True)
     assert y16.dtype == H16
     # one fp16 ulp of the reference + the fp32 accumulation noise (relative to the largest output, K up to 4608)
     assert bool(((nchw(y16) - ref_r).abs() <= ref_r.abs() * 2 ** -10 + 1e-5 * float(ref_r.abs().max())).all())
+    B.assert_within(nchw(y16), bound, H16, "conv2d_fwd f16 %s" % (case,))
     # dgrad with the folded fp16(scale * fp16(w)) operand, + addend, ReLU mask
     Ho, Wo = ref.shape[2], ref.shape[3]
     g = q(det_tensor((N, Cout, Ho, Wo), 11, -1, 1, bf16=False))
@@ -93,6 +97,8 @@ def test_conv_fwd_dgrad_f16(ops, case):
     ref2 = (xz.grad + add) * (msk > 0).float()
     dx = ops.conv2d_dgrad(nhwc(g), wd, (H, W), k, s, k // 2, nhwc(add), ops.ADD_SAME, nhwc(msk), out_f32=True)
     assert max_rel(nchw(dx), ref2) <= TOL
+    B.assert_within(nchw(dx), B.dgrad_bound(g, w_eff, (H, W), s, k // 2, add, "same", msk), torch.float32,
+                    "conv2d_dgrad f16 operands %s" % (case,))
     # mixing element types is refused on the host
     with pytest.raises(ValueError):
         ops.conv2d_fwd(nhwc(x).bfloat16(), wf, k, s, k // 2)
@@ -117,6 +123,8 @@ def test_conv_wgrad_f16(ops, case):
     assert rel_l2(dw.cpu().permute(0, 3, 1, 2), w.grad) <= TOL
     assert rel_l2(dg.cpu(), gamma.grad) <= TOL
     assert rel_l2(db.cpu(), beta.grad) <= TOL      # the ones-fragment column sum
+    B.assert_within(dw.cpu().permute(0, 3, 1, 2), B.wgrad_bound(x, g, w.shape, s, k // 2, scale), torch.float32,
+                    "conv2d_wgrad f16 dw %s" % (case,))
 
 
 def test_stem_pool_elementwise_f16(ops):
@@ -134,6 +142,7 @@ def test_stem_pool_elementwise_f16(ops):
     scale, shift, invstd = ops.bn_fold(gamma.detach().cuda(), beta.detach().cuda(), mean.cuda(), var.cuda(), 1e-5)
     y = ops.stem_conv_fwd(xp, ws, (H, W), scale, shift, True, out_f32=True)
     assert max_rel(nchw(y), F.relu(pre)) <= TOL
+    B.assert_within(nchw(y), B.fwd_bound(img, w.detach(), 2, 3, scale, shift, relu=True), torch.float32, "stem f16")
     g = q(det_tensor(tuple(pre.shape), 47, -1, 1, bf16=False))
     pre.backward(g)
     dw, dg, db = ops.stem_conv_wgrad(xp, nhwc(g), ws, (H, W), scale, mean.cuda(), invstd)

@@ -8,7 +8,9 @@
     full size — one of the 27 conv shapes no kernel test runs at this size, a missing stream dependency that needs
     long kernels to bite, a graph replay reading a recycled buffer — breaks one of these.
   * in-situ parity — every fused launch of the full-size forward AND backward recomputed on the CPU from the GPU's
-    own operands (tests/parity_util.py), <= 1e-3 per launch.
+    own operands (tests/parity_util.py), <= 1e-3 per launch in relative L2 and, element by element, inside the
+    a-priori rounding bound of tests/bound_util.py (the M-tail tile, the pixel between two images, one lane of an
+    epilogue: a handful of wrong elements that a norm over 3.4e7 of them does not see).
 """
 import os
 
@@ -115,7 +117,7 @@ def test_full_size_in_situ(T, depth, batch, dtype):
     import json
     import parity_util
     deep = dtype == torch.float16
-    res = parity_util.run_teacher_forced(T, depth, (batch, 3, H, W), dtype=dtype, end_to_end=False,
+    res = parity_util.run_teacher_forced(T, depth, (batch, 3, H, W), dtype=dtype, end_to_end=False, cheap_bound=True,
                                          cot_scale=2.0 ** -6 if deep else 1.0, res_gain=0.25 if deep else 1.0)
     if os.path.isdir("gpurun_out"):
         with open("gpurun_out/parity_fullsize_r%d_b%d.json" % (depth, batch), "w") as f:
@@ -125,6 +127,9 @@ def test_full_size_in_situ(T, depth, batch, dtype):
     for kind in ("dgrad", "dw", "dgamma", "dbeta_or_dbias"):
         assert b[kind][0] <= parity_util.BWD_IN_SITU_TOL, (kind, b[kind])
     assert b["launches"]["dgrad"] >= (52 if depth == 50 else 103) and b["launches"]["wgrad"] >= 61
+    # every element of every forward and dgrad launch inside its a-priori rounding bound (tests/bound_util.py; the
+    # JSON above holds the worst ratio, its element and border classification per launch kind); dw is recorded only
+    parity_util.check_elementwise(res)
 
 
 def test_full_size_schedule(T, monkeypatch):

@@ -15,6 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bound_util as B
 from golden_util import det_tensor, max_rel
 
 pytestmark = pytest.mark.gpu
@@ -93,10 +94,13 @@ def test_halo_conv3x3_fwd_dgrad(ops, case, cfg):
         ran = True
         y = ops.conv2d_fwd(*args, out_f32=True)
         assert max_rel(nchw(y), ref) <= TOL
+        bound = B.fwd_bound(x, w, 1, 1, scale, shift, res, "same", True)
+        B.assert_within(nchw(y), bound, torch.float32, "halo fwd f32 %s cfg %d" % (case, cfg))
         assert torch.equal(y, y_gen), "halo and generic kernels share the K order: bit-identical"
         y16 = ops.conv2d_fwd(*args)
         err = (nchw(y16) - ref).abs()
         assert bool((err <= ref.abs() * 2 ** -7 + 1e-6).all())
+        B.assert_within(nchw(y16), bound, torch.bfloat16, "halo fwd bf16 %s cfg %d" % (case, cfg))
     # input gradient (GEMM N = Cin): + addend, ReLU mask of the producer
     if Cin % CFG3[cfg] != 0 or not uses_halo(ops, 1, N, H, W, Cin, Cout, 3, 1, 1):
         if not ran:
@@ -111,6 +115,8 @@ def test_halo_conv3x3_fwd_dgrad(ops, case, cfg):
     ref2 = (xz.grad + add) * (msk > 0).float()
     dx = ops.conv2d_dgrad(nhwc(g), wd, (H, W), 3, 1, 1, nhwc(add), ops.ADD_SAME, nhwc(msk), out_f32=True)
     assert max_rel(nchw(dx), ref2) <= TOL
+    B.assert_within(nchw(dx), B.dgrad_bound(g, w, (H, W), 1, 1, add, "same", msk), torch.float32,
+                    "halo dgrad %s cfg %d" % (case, cfg))
     os.environ.pop("TDN_HALO_CFG3")
     os.environ["TDN_GEMM_CFG"] = "0"
     dx_gen = ops.conv2d_dgrad(nhwc(g), wd, (H, W), 3, 1, 1, nhwc(add), ops.ADD_SAME, nhwc(msk), out_f32=True)
@@ -152,6 +158,7 @@ def test_halo_patch_shapes(ops, patch):
     assert uses_halo(ops, 0, N, H, W, Cin, Cout, 3, 1, 1)
     y = ops.conv2d_fwd(nhwc(x), pack_w(w), 3, 1, 1, out_f32=True)
     assert max_rel(nchw(y), ref) <= TOL
+    B.assert_within(nchw(y), B.fwd_bound(x, w, 1, 1), torch.float32, "halo patch %s" % (patch,))
 
 
 def test_halo_dilated_and_epilogue_modes(ops):
@@ -164,11 +171,13 @@ def test_halo_dilated_and_epilogue_modes(ops):
     assert uses_halo(ops, 0, N, H, W, C, C, 3, 1, 2)
     y = ops.conv2d_fwd(nhwc(x), pack_w(w), 3, 1, 2, out_f32=True)
     assert max_rel(nchw(y), F.conv2d(x, w, None, 1, 2, 2)) <= TOL
+    B.assert_within(nchw(y), B.fwd_bound(x, w, 1, 2, dilation=2), torch.float32, "halo dilation 2")
     coarse = det_tensor((N, C, H // 2, W // 2), 53, -1, 1)
     bias = det_tensor((C,), 54, -0.5, 0.5, bf16=False)
     ref = F.conv2d(x, w, bias, 1, 1) + F.interpolate(coarse, scale_factor=2, mode="nearest")
     y = ops.conv2d_fwd(nhwc(x), pack_w(w), 3, 1, 1, None, bias.cuda(), nhwc(coarse), ops.ADD_UP2X, True, out_f32=True)
     assert max_rel(nchw(y), ref.clamp(min=0)) <= TOL
+    B.assert_within(nchw(y), B.fwd_bound(x, w, 1, 1, None, bias, coarse, "up2x", True), torch.float32, "halo up2x + ReLU")
     # ReLU6: values stored under 6 stay under 6 (relu6_top, common.h), so compare below the knee and at the clamp
     y6 = nchw(ops.conv2d_fwd(nhwc(x), pack_w(w), 3, 1, 1, None, bias.cuda(), nhwc(coarse), ops.ADD_UP2X, 2,
                              out_f32=True))
@@ -182,10 +191,12 @@ def test_halo_dilated_and_epilogue_modes(ops):
     ref2 = xz.grad + F.avg_pool2d(fine, 2) * 4
     dx = ops.conv2d_dgrad(nhwc(g), pack_wd(w), (H, W), 3, 1, 1, nhwc(fine), ops.ADD_SUMPOOL2, None, out_f32=True)
     assert max_rel(nchw(dx), ref2) <= TOL
+    B.assert_within(nchw(dx), B.dgrad_bound(g, w, (H, W), 1, 1, fine, "sumpool"), torch.float32, "halo dgrad + sumpool")
     # float16 operands
     xh, wh = x.half().float(), w.half().float()
     yh = ops.conv2d_fwd(nhwc(xh, torch.float16), pack_w(wh, torch.float16), 3, 1, 1, out_f32=True)
     assert max_rel(nchw(yh), F.conv2d(xh, wh, None, 1, 1)) <= TOL
+    B.assert_within(nchw(yh), B.fwd_bound(xh, wh, 1, 1), torch.float32, "halo float16 operands")
 
 
 CASES1 = [(1, 20, 24, 64, 256, 1), (2, 10, 12, 256, 128, 1), (1, 12, 16, 256, 512, 2), (1, 25, 43, 64, 128, 2),
@@ -207,7 +218,9 @@ def test_halo_conv1x1(ops, case, cfg):
     os.environ.update({"TDN_HALO": "3", "TDN_HALO_CFG1": str(cfg)})
     if not uses_halo(ops, 0, N, H, W, Cin, Cout, 1, s, 0):
         pytest.skip("plan does not fit LDS for this shape")
+    bound = B.fwd_bound(x, w, s, 0, None, shift, relu=True)
     for nt in ("1", "2"):
         os.environ["TDN_HALO_NT"] = nt
         y = ops.conv2d_fwd(nhwc(x), pack_w(w), 1, s, 0, None, shift.cuda(), None, ops.ADD_NONE, True, out_f32=True)
         assert max_rel(nchw(y), ref) <= TOL
+        B.assert_within(nchw(y), bound, torch.float32, "halo 1x1 %s cfg %d nt %s" % (case, cfg, nt))

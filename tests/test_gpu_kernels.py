@@ -4,6 +4,8 @@ Operands are bf16-representable, accumulation is fp32.  Tolerances (written here
   * forward / dgrad with fp32 output (pre-rounding value): max|err| / max|ref| <= 1e-3   (north-star figure)
   * the same kernels with bf16 output: <= 1 bf16 ulp of the bf16-rounded reference (2^-7 relative, loose bound)
   * wgrad (fp32 output, K up to N*H*W): rel-L2 <= 1e-3
+  * next to each of these, every element of every conv / dgrad / dw output against the a-priori rounding bound of
+    tests/bound_util.py (fp64 reference, exact S): worst |got - v| / allowance <= 1, the failure naming the element
 """
 import os
 
@@ -11,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bound_util as B
 from golden_util import det_tensor, max_rel, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -84,12 +87,16 @@ def test_conv_fwd(ops, case, tile):
         y32 = ops.conv2d_fwd(xg, wg, k, s, k // 2, scale.cuda(), shift.cuda(), nhwc(res), ops.ADD_SAME, True,
                              out_f32=True)
         assert max_rel(nchw(y32), ref_r) <= TOL
+        bound = B.fwd_bound(x, w, s, k // 2, scale, shift, res, "same", True)
+        B.assert_within(nchw(y32), bound, torch.float32, "conv2d_fwd f32 %s tile %s" % (case, tile))
         y16 = ops.conv2d_fwd(xg, wg, k, s, k // 2, scale.cuda(), shift.cuda(), nhwc(res), ops.ADD_SAME, True)
         err = (nchw(y16) - ref_r).abs()
         assert bool((err <= ref_r.abs() * 2 ** -7 + 1e-6).all())
+        B.assert_within(nchw(y16), bound, torch.bfloat16, "conv2d_fwd bf16 %s tile %s" % (case, tile))
         # no epilogue at all
         y0 = ops.conv2d_fwd(xg, wg, k, s, k // 2, out_f32=True)
         assert max_rel(nchw(y0), F.conv2d(x, w, None, s, k // 2)) <= TOL
+        B.assert_within(nchw(y0), B.fwd_bound(x, w, s, k // 2), torch.float32, "conv2d_fwd plain %s tile %s" % (case, tile))
     finally:
         os.environ.pop("TDN_GEMM_CFG", None)
 
@@ -113,15 +120,19 @@ def test_conv_dgrad(ops, case, tile, monkeypatch):
     ref = xz.grad
     dx = ops.conv2d_dgrad(nhwc(g), wd, (H, W), k, s, k // 2, out_f32=True)
     assert max_rel(nchw(dx), ref) <= TOL
+    B.assert_within(nchw(dx), B.dgrad_bound(g, w_eff, (H, W), s, k // 2), torch.float32, "conv2d_dgrad %s tile %s" % (case, tile))
     # fused epilogue: + addend, ReLU mask
     add = det_tensor((N, Cin, H, W), 14, -1, 1)
     msk = det_tensor((N, Cin, H, W), 15, -1, 1)
     ref2 = (ref + add) * (msk > 0).float()
     dx2 = ops.conv2d_dgrad(nhwc(g), wd, (H, W), k, s, k // 2, nhwc(add), ops.ADD_SAME, nhwc(msk), out_f32=True)
     assert max_rel(nchw(dx2), ref2) <= TOL
+    bound = B.dgrad_bound(g, w_eff, (H, W), s, k // 2, add, "same", msk)
+    B.assert_within(nchw(dx2), bound, torch.float32, "conv2d_dgrad + addend, mask %s tile %s" % (case, tile))
     dx3 = ops.conv2d_dgrad(nhwc(g), wd, (H, W), k, s, k // 2, nhwc(add), ops.ADD_SAME, nhwc(msk))
     err = (nchw(dx3) - ref2).abs()
     assert bool((err <= ref2.abs() * 2 ** -7 + 1e-6).all())
+    B.assert_within(nchw(dx3), bound, torch.bfloat16, "conv2d_dgrad bf16 %s tile %s" % (case, tile))
 
 
 def test_conv_epilogue_up2x_and_sumpool(ops):
@@ -133,6 +144,7 @@ def test_conv_epilogue_up2x_and_sumpool(ops):
     ref = F.conv2d(x, w, bias) + F.interpolate(coarse, scale_factor=2, mode="nearest")
     y = ops.conv2d_fwd(nhwc(x), pack_w(w), 1, 1, 0, None, bias.cuda(), nhwc(coarse), ops.ADD_UP2X, False, out_f32=True)
     assert max_rel(nchw(y), ref) <= TOL
+    B.assert_within(nchw(y), B.fwd_bound(x, w, 1, 0, None, bias, coarse, "up2x"), torch.float32, "1x1 + bias + up2x")
     # adjoint: dgrad of a 3x3 conv + 2x2 sum-pool of the finer gradient
     g = det_tensor((N, C, H, W), 25, -1, 1)
     w3 = det_tensor((C, C, 3, 3), 26, -0.2, 0.2)
@@ -142,6 +154,7 @@ def test_conv_epilogue_up2x_and_sumpool(ops):
     ref2 = xz.grad + F.avg_pool2d(fine, 2) * 4
     dx = ops.conv2d_dgrad(nhwc(g), pack_wd(w3), (H, W), 3, 1, 1, nhwc(fine), ops.ADD_SUMPOOL2, None, out_f32=True)
     assert max_rel(nchw(dx), ref2) <= TOL
+    B.assert_within(nchw(dx), B.dgrad_bound(g, w3, (H, W), 1, 1, fine, "sumpool"), torch.float32, "3x3 dgrad + sumpool")
     with pytest.raises(RuntimeError):
         ops.conv2d_fwd(nhwc(x), pack_w(w), 1, 1, 0, None, None, nhwc(det_tensor((N, C, 3, 6), 1)), ops.ADD_UP2X)
 
@@ -183,6 +196,9 @@ def test_conv_wgrad(ops, case, bn, monkeypatch):
         dw, dg, db = ops.conv2d_wgrad(nhwc(x), nhwc(g), wf, k, s, k // 2)
     assert rel_l2(dw.cpu().permute(0, 3, 1, 2), w.grad) <= TOL
     assert rel_l2(db.cpu(), beta.grad) <= TOL
+    # every element of dw: K = N * Ho * Wo rounded additions (a few thousand here), one more for the folded scale
+    B.assert_within(dw.cpu().permute(0, 3, 1, 2), B.wgrad_bound(x, g, w.shape, s, k // 2, scale if bn else None),
+                    torch.float32, "conv2d_wgrad dw %s bn=%s" % (case, bn))
     # accumulate mode (beta=1): second call doubles
     dw2, _, db2 = ops.conv2d_wgrad(nhwc(x), nhwc(g), wf, k, s, k // 2,
                                    *( (scale.cuda(), mean.cuda(), invstd.cuda()) if bn else (None, None, None)),
@@ -232,6 +248,7 @@ def test_stem(ops, shape):
     scale, shift, invstd = ops.bn_fold(gamma.detach().cuda(), beta.detach().cuda(), mean.cuda(), var.cuda(), 1e-5)
     y = ops.stem_conv_fwd(xp, ws, (H, W), scale, shift, True, out_f32=True)
     assert max_rel(nchw(y), ref) <= TOL
+    B.assert_within(nchw(y), B.fwd_bound(img, w.detach(), 2, 3, scale, shift, relu=True), torch.float32, "stem 7x7/s2")
     # wgrad
     g = det_tensor(tuple(ref.shape), 47, -1, 1)
     pre.backward(g)
@@ -239,6 +256,7 @@ def test_stem(ops, shape):
     assert rel_l2(dw.cpu(), w.grad) <= TOL
     assert rel_l2(dg.cpu(), gamma.grad) <= TOL
     assert rel_l2(db.cpu(), beta.grad) <= TOL
+    B.assert_within(dw.cpu(), B.wgrad_bound(img, g, w.shape, 2, 3, scale), torch.float32, "stem dw")
 
 
 @pytest.mark.parametrize("shape", [(2, 16, 24, 64), (1, 15, 21, 64), (1, 8, 8, 128)])
@@ -404,6 +422,8 @@ def test_grouped_conv(ops, case):
     wf, wd = ops.pack_gconv_weight(w.detach().cuda(), G, scale.cuda())
     y = ops.gconv2d_fwd(nhwc(x.detach()), wf, G, k, s, k // 2, scale.cuda(), shift.cuda(), relu=True, out_f32=True)
     assert max_rel(nchw(y), ref.detach()) <= TOL
+    B.assert_within(nchw(y), B.fwd_bound(x.detach(), w.detach(), s, k // 2, scale, shift, relu=True, groups=G),
+                    torch.float32, "gconv2d_fwd %s" % (case,))
     g = det_tensor(tuple(pre.shape), 97, -1, 1)
     pre.backward(g)
     # dgrad: the packed operand folds scale (rounded to bf16): compare against conv_transpose with those weights
@@ -412,12 +432,15 @@ def test_grouped_conv(ops, case):
     F.conv2d(xz, w_eff, None, s, k // 2, 1, G).backward(g)
     dx = ops.gconv2d_dgrad(nhwc(g), wd, G, (H, W), k, s, k // 2, out_f32=True)
     assert max_rel(nchw(dx), xz.grad) <= TOL
+    B.assert_within(nchw(dx), B.dgrad_bound(g, w_eff, (H, W), s, k // 2, groups=G), torch.float32, "gconv2d_dgrad %s" % (case,))
     dw, dg, db = ops.gconv2d_wgrad(nhwc(x.detach()), nhwc(g), wf, G, k, s, k // 2, scale.cuda(), mean.cuda(),
                                    invstd.cuda())
     assert tuple(dw.shape) == (C, k, k, cpg)
     assert rel_l2(dw.cpu().permute(0, 3, 1, 2), w.grad) <= TOL
     assert rel_l2(dg.cpu(), gamma.grad) <= TOL
     assert rel_l2(db.cpu(), beta.grad) <= TOL
+    B.assert_within(dw.cpu().permute(0, 3, 1, 2), B.wgrad_bound(x.detach(), g, w.shape, s, k // 2, scale, groups=G),
+                    torch.float32, "gconv2d_wgrad dw %s" % (case,))
     with pytest.raises(RuntimeError):
         ops.pack_gconv_weight(torch.zeros(96, 3, 3, 3, device="cuda"), 32)   # 96 channels: not a multiple of 64
 
@@ -533,8 +556,107 @@ def test_dilated_conv(ops, case):
     y = ops.conv2d_fwd(nhwc(x.detach()), pack_w(w.detach()), 3, s, d, out_f32=True)
     assert tuple(y.shape) == (N, ref.shape[2], ref.shape[3], Cout)
     assert max_rel(nchw(y), ref.detach()) <= TOL
+    B.assert_within(nchw(y), B.fwd_bound(x.detach(), w.detach(), s, d, dilation=d), torch.float32, "dilated fwd %s" % (case,))
     dx = ops.conv2d_dgrad(nhwc(g), pack_wd(w.detach()), (H, W), 3, s, d, out_f32=True)
     assert max_rel(nchw(dx), x.grad) <= TOL
+    B.assert_within(nchw(dx), B.dgrad_bound(g, w.detach(), (H, W), s, d, dilation=d), torch.float32, "dilated dgrad %s" % (case,))
     dw, _, db = ops.conv2d_wgrad(nhwc(x.detach()), nhwc(g), pack_w(w.detach()), 3, s, d)
     assert rel_l2(dw.cpu().permute(0, 3, 1, 2), w.grad) <= TOL
+    B.assert_within(dw.cpu().permute(0, 3, 1, 2), B.wgrad_bound(x.detach(), g, w.shape, s, d, dilation=d), torch.float32,
+                    "dilated dw %s" % (case,))
     assert rel_l2(db.cpu(), g.sum((0, 2, 3))) <= TOL
+
+
+# ---- single-image tails: pixel counts just past / just short of a tile's M extent, an image boundary inside a tile ----
+def _plan(ops, kind, N, H, W, Cin, Cout, k, s, pad):
+    import ctypes
+    o = (ctypes.c_int32 * 16)()
+    assert ops._lib.load().tdn_conv2d_plan(kind, N, H, W, Cin, Cout, k, s, pad, o) == 0
+    return list(o)
+
+
+TAIL_N = 5
+
+
+def _tail_shape(ops, kind, r, k, s):
+    """The first (H, W) in a fixed scan order whose GEMM of ``kind`` (0 forward, 1 dgrad) has M = r modulo the tile's M
+    extent BM, as tdn_conv2d_plan reports them under the current TDN_* environment (a 64-row tile folds 65 and 127 onto
+    1 and 63).  M is the pixel count the kernel tiles: out[0] for one GEMM; for a strided dgrad, whose output-parity
+    classes are tiled one by one, out[15] — the largest class, the (even, even) one.  Five images (coprime to every BM,
+    192 included) of an odd pixel count: no image ends on a tile boundary."""
+    for H in range(9, 96):
+        for W in range(11, 128):
+            o = _plan(ops, kind, TAIL_N, H, W, 256, 256, k, s, k // 2)
+            M, BM = (o[15] if o[9] > 1 else o[0]), o[3]
+            if o[8] < 100 and M % TAIL_N == 0 and M % BM == r % BM and (M // TAIL_N) % BM != 0:
+                return H, W, M, BM
+    raise AssertionError("no shape with M = %d mod BM" % r)
+
+
+def _halo_tail_shape(ops, kind, r):
+    """The LDS-patch kernel tiles each image in TH x TW patches (out[11]), not M: the first (H, W) it takes whose last
+    patch row AND last patch column are partial, with N * H * W = r modulo 64 to vary the shape with ``r``."""
+    for H in range(9, 96):
+        for W in range(11, 128):
+            o = _plan(ops, kind, TAIL_N, H, W, 256, 256, 3, 1, 1)
+            th, tw = o[11] // 1000, o[11] % 1000
+            if o[8] >= 100 and H % th != 0 and W % tw != 0 and (TAIL_N * H * W) % 64 == r % 64:
+                return H, W, TAIL_N * H * W, th * tw
+    raise AssertionError("no halo shape for r = %d" % r)
+
+
+TAIL_GEOMS = {"3x3s1_gemm": (3, 1, False), "3x3s1_halo": (3, 1, True), "3x3s2": (3, 2, False), "1x1s2": (1, 2, False)}
+
+
+# a forced GEMM tile keeps the generic kernel, so the halo variant runs on the library's own choice only
+TAIL_CASES = [(geom, tile) for geom in TAIL_GEOMS for tile in GEMM_CFGS if tile is None or not TAIL_GEOMS[geom][2]]
+
+
+@pytest.mark.parametrize("r", [1, 63, 65, 127])
+@pytest.mark.parametrize("geom,tile", TAIL_CASES, ids=["%s-tile%s" % c for c in TAIL_CASES])
+def test_conv_single_image_tail(ops, geom, r, tile, monkeypatch):
+    """Forward and dgrad, 256 -> 256 channels (every production tile divides them), N = 5, N * Ho * Wo = 1, 63, 65, 127
+    modulo the tile's M extent — on the library's own tile choice and on each forced production tile — judged element
+    by element (tests/bound_util.py): the M-tail tile, the pixel that straddles two images, the last row and column
+    are single elements to a norm.  The halo variant runs the LDS-patch kernel (its own configuration 5; a forced GEMM
+    tile would keep the generic kernel), which has no linear M tiling: there the shape has a partial last patch row and
+    column (_halo_tail_shape)."""
+    k, s, halo = TAIL_GEOMS[geom]
+    N, C = TAIL_N, 256
+    for name in ("TDN_HALO", "TDN_HALO_CFG3", "TDN_GEMM_CFG"):
+        monkeypatch.delenv(name, raising=False)
+    if halo:
+        monkeypatch.setenv("TDN_HALO_CFG3", "5")
+        shapes = [_halo_tail_shape(ops, kind, r) for kind in (0, 1)]
+    else:
+        monkeypatch.setenv("TDN_HALO", "0")
+        if tile is not None:
+            monkeypatch.setenv("TDN_GEMM_CFG", str(tile))
+        shapes = [_tail_shape(ops, kind, r, k, s) for kind in (0, 1)]
+    w = det_tensor((C, C, k, k), 122, -0.1, 0.1)
+    scale = det_tensor((C,), 123, 0.5, 1.5, bf16=False)
+    shift = det_tensor((C,), 124, -0.5, 0.5, bf16=False)
+    # forward: + scale, shift, residual, ReLU, stored in bf16
+    H, W, M, BM = shapes[0]
+    if halo:
+        assert _plan(ops, 0, N, H, W, C, C, k, s, k // 2)[8] >= 100, "the halo kernel was meant to take this shape"
+    x = det_tensor((N, C, H, W), 121, -1, 1)
+    Ho, Wo = ops.conv_out_size(H, k, s, k // 2), ops.conv_out_size(W, k, s, k // 2)
+    assert N * Ho * Wo == M
+    res = det_tensor((N, C, Ho, Wo), 125, -1, 1)
+    y = ops.conv2d_fwd(nhwc(x), pack_w(w), k, s, k // 2, scale.cuda(), shift.cuda(), nhwc(res), ops.ADD_SAME, True)
+    B.assert_within(nchw(y), B.fwd_bound(x, w, s, k // 2, scale, shift, res, "same", True), torch.bfloat16,
+                    "forward %s, M = %d = %d mod %d, tile %s" % (geom, M, M % BM, BM, tile))
+    # dgrad: + addend, ReLU mask, stored in bf16
+    H, W, M, BM = shapes[1]
+    if halo:
+        assert _plan(ops, 1, N, H, W, C, C, k, s, k // 2)[8] >= 100, "the halo kernel was meant to take this shape"
+    Ho, Wo = ops.conv_out_size(H, k, s, k // 2), ops.conv_out_size(W, k, s, k // 2)
+    g = det_tensor((N, C, Ho, Wo), 126, -1, 1)
+    wd = pack_wd(w, scale)
+    w_eff = wd.float().cpu().permute(3, 0, 1, 2).contiguous()
+    add = det_tensor((N, C, H, W), 127, -1, 1)
+    msk = det_tensor((N, C, H, W), 128, -1, 1)
+    dx = ops.conv2d_dgrad(nhwc(g), wd, (H, W), k, s, k // 2, nhwc(add), ops.ADD_SAME, nhwc(msk))
+    B.assert_within(nchw(dx), B.dgrad_bound(g, w_eff, (H, W), s, k // 2, add, "same", msk), torch.bfloat16,
+                    "dgrad %s, M = %d = %d mod %d, tile %s" % (geom, M, M % BM, BM, tile))
