@@ -513,6 +513,69 @@ int tdn_roi_align_bwd(const tdn_roi_level* grads, int nlevels, int B, int C, con
  * (-1, x1, y1, x2, y2) — an invalid row for tdn_roi_align_*.  No host synchronisation. */
 int tdn_rois_from_proposals(const float* proposals, const int32_t* counts, int B, int M, float* rois, void* stream);
 
+/* ---- training targets: max-IoU assignment, random sampling, RPN and RoI-head targets (the project's
+ *      own spec in the mmdetection-v0.x/v1 lineage of MaxIoUAssigner / RandomSampler / anchor_target / bbox_target;
+ *      IoU is tdn_bbox_iou_pairwise's value bit for bit, encode is tdn_bbox2delta's arithmetic) ----
+ * Common to all four: B images (1..64), boxes fp32 xyxy '+1'; box_stride = floats between the boxes of consecutive
+ * images (0: one set of N boxes shared by all images, else >= 4N); gt: device fp32 [B][G][4], rows at or beyond
+ * gt_counts[b] (device int32 [B], clamped to 0..G) are padding and never read; G <= TDN_TARGET_MAX_GT,
+ * N <= TDN_TARGET_MAX_BOXES, num <= TDN_TARGET_MAX_NUM.  The (N, G) IoU matrix is never stored: pass 1 keeps the row
+ * maximum / argmax per box and merges the per-ground-truth column maxima with integer atomicMax on the IoU's bit
+ * pattern, pass 2 recomputes the IoUs against them.  No float atomics, no host synchronisation, no allocation; the
+ * first launch of a call clears what the call's workspace needs cleared.  Workspaces: the *_workspace_bytes() query of
+ * the entry point, 256-aligned. */
+#define TDN_TARGET_MAX_GT 256
+#define TDN_TARGET_MAX_BOXES (1 << 20)
+#define TDN_TARGET_MAX_NUM 8192
+typedef struct tdn_target_config {
+  float pos_iou_thr, neg_iou_thr, min_pos_iou;   /* compared in fp32 */
+  int32_t gt_max_assign_all;   /* step 6: 1 = every box attaining a ground truth's maximum, 0 = the lowest such box */
+  int32_t num;                 /* samples per image, 0..TDN_TARGET_MAX_NUM */
+  int32_t num_pos_expected;    /* int(num * pos_fraction), evaluated by the caller in double; 0..num */
+  int32_t allowed_border;      /* tdn_anchor_target: >= 0 drops anchors leaving the image by more than this; < 0: off */
+  int32_t add_gt_as_proposals; /* tdn_sample_rois */
+  double neg_pos_ub;           /* >= 0: negatives <= int(neg_pos_ub * max(1, positives)); < 0: no bound */
+  float means[4], stds[4];     /* target_means / target_stds of the deltas */
+  uint32_t seed;               /* of the generated keys (keys == NULL) */
+  int32_t reserved;
+} tdn_target_config;
+/* assigned[B][N] int32: -1 ignored / not taking part, 0 negative, j+1 ground truth j; max_overlaps[B][N] fp32 (0 for a
+ * box that does not take part, may be NULL).  valid: uint8 [N] shared by all images (valid_stride 0) or [B][N]
+ * (valid_stride N) whatever box_stride is, or NULL.  Three launches (four with gt_max_assign_all = 0). */
+int64_t tdn_assign_max_iou_workspace_bytes(int B, int G);
+int tdn_assign_max_iou(const float* boxes, int64_t box_stride, const uint8_t* valid, int64_t valid_stride, const float* gt,
+                       const int32_t* gt_counts, int B, int N, int G, const tdn_target_config* cfg, int32_t* assigned,
+                       float* max_overlaps, void* workspace, int64_t workspace_bytes, void* stream);
+/* The pos / neg smallest (key, index) among assigned > 0 / == 0 of every image: pos = min(#positives,
+ * num_pos_expected), neg = min(#negatives, num - pos [, neg_pos_ub bound]).  keys: device int32 [B][N], non-negative, or
+ * NULL for key = tdn_target_key(seed, b, i).  pos_mask / neg_mask uint8 [B][N], num_pos / num_neg int32
+ * [B].  One launch, two workgroups per image; no workspace. */
+int tdn_sample_assigned(const int32_t* assigned, int B, int N, const tdn_target_config* cfg, const int32_t* keys,
+                        uint8_t* pos_mask, uint8_t* neg_mask, int32_t* num_pos, int32_t* num_neg, void* stream);
+/* RPN targets: assignment (valid flags [N] or [B][N] or NULL, and allowed_border against img_shapes int32 [B][2] =
+ * (h, w)), sampling, encode.  labels int64 [B][N] (1 on sampled positives), label_weights fp32 [B][N] (1 on sampled
+ * positives and negatives), bbox_targets / bbox_weights fp32 [B][N][4], num_pos / num_neg int32 [B], assigned int32
+ * [B][N].  Five launches (six with gt_max_assign_all = 0). */
+int64_t tdn_anchor_target_workspace_bytes(int B, int N, int G);
+int tdn_anchor_target(const float* anchors, int64_t box_stride, const uint8_t* valid, int64_t valid_stride, const float* gt,
+                      const int32_t* gt_counts, const int32_t* img_shapes, int B, int N, int G,
+                      const tdn_target_config* cfg, const int32_t* keys, int64_t* labels, float* label_weights,
+                      float* bbox_targets, float* bbox_weights, int32_t* num_pos, int32_t* num_neg, int32_t* assigned,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+/* RoI-head targets from tdn_rpn_proposals' padded output: proposals [B][P][5], counts [B].  Candidates of image b: its
+ * gt_counts[b] ground truths first (add_gt_as_proposals), then its counts[b] proposals; keys int32 [B][G + P] (or
+ * [B][P] without the ground truths) or NULL.  Image b owns rows [b*num, (b+1)*num): sampled positives in ascending
+ * candidate index, then sampled negatives likewise, then padding (batch index -1, zeros, weight 0, gt index -1).
+ * rois fp32 [B*num][5] = (b, x1, y1, x2, y2), labels int64 (gt_labels[b][assigned-1] on positives, gt_labels int64
+ * [B][G]), label_weights fp32, bbox_targets / bbox_weights fp32 [B*num][4], pos_gt_inds int32 [B*num].  Five launches
+ * (six with gt_max_assign_all = 0). */
+int64_t tdn_sample_rois_workspace_bytes(int B, int P, int G, int add_gt_as_proposals);
+int tdn_sample_rois(const float* proposals, const int32_t* counts, const float* gt, const int64_t* gt_labels,
+                    const int32_t* gt_counts, int B, int P, int G, const tdn_target_config* cfg, const int32_t* keys,
+                    float* rois, int64_t* labels, float* label_weights, float* bbox_targets, float* bbox_weights,
+                    int32_t* pos_gt_inds, int32_t* num_pos, int32_t* num_neg, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

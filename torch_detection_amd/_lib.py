@@ -23,6 +23,9 @@ RPN_MAX_NUM = 8192
 ROI_MAX_LEVELS = 8
 ROI_MAX_OUT = 16
 ROI_MAX_SAMPLES = 512
+TARGET_MAX_GT = 256
+TARGET_MAX_BOXES = 1 << 20
+TARGET_MAX_NUM = 8192
 ADD_NONE, ADD_SAME, ADD_UP2X, ADD_SUMPOOL2 = 0, 1, 2, 3
 
 c_void_p = ctypes.c_void_p
@@ -107,6 +110,18 @@ class RpnConfig(ctypes.Structure):
 
 _RL = ctypes.POINTER(RpnLevel)
 _RC = ctypes.POINTER(RpnConfig)
+
+
+class TargetConfig(ctypes.Structure):
+    """Mirror of ``tdn_target_config`` (include/tdn.h)."""
+    _fields_ = [("pos_iou_thr", c_float), ("neg_iou_thr", c_float), ("min_pos_iou", c_float),
+                ("gt_max_assign_all", ctypes.c_int32), ("num", ctypes.c_int32), ("num_pos_expected", ctypes.c_int32),
+                ("allowed_border", ctypes.c_int32), ("add_gt_as_proposals", ctypes.c_int32),
+                ("neg_pos_ub", ctypes.c_double), ("means", c_float * 4), ("stds", c_float * 4),
+                ("seed", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
+
+
+_TC = ctypes.POINTER(TargetConfig)
 
 
 class RoiLevel(ctypes.Structure):
@@ -205,6 +220,15 @@ SIGNATURES = {
     "tdn_rpn_proposals_workspace": (c_i64, [_RL, c_int, c_int, _RC]),
     "tdn_rpn_proposals": (c_int, [_RL, c_int, c_int, c_void_p, _RC, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
                                   c_void_p]),
+    "tdn_assign_max_iou_workspace_bytes": (c_i64, [c_int, c_int]),
+    "tdn_assign_max_iou": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, _TC, c_void_p,
+                                   c_void_p, c_void_p, c_i64, c_void_p]),
+    "tdn_sample_assigned": (c_int, [c_void_p, c_int, c_int, _TC] + [c_void_p] * 6),
+    "tdn_anchor_target_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "tdn_anchor_target": (c_int, [c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 3 + [c_int, c_int, c_int, _TC] + [c_void_p] * 9 +
+                          [c_i64, c_void_p]),
+    "tdn_sample_rois_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "tdn_sample_rois": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, _TC] + [c_void_p] * 10 + [c_i64, c_void_p]),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),

@@ -19,6 +19,8 @@
 // Nothing here uses a float atomic or waits on another workgroup; the integer LDS atomics only count, so every
 // output is a pure function of the inputs.
 #include "nms_core.h"
+#include "select_core.h"
+#include "delta_core.h"
 #include <math.h>
 #include <string.h>
 
@@ -41,23 +43,7 @@ __device__ __forceinline__ float load_elem(const void* p, int dtype, int64_t off
   return __uint_as_float((uint32_t)((const uint16_t*)p)[off] << 16);   // bf16 -> fp32 is exact
 }
 
-// ---- encode / decode (spec order, one rounding per operation) ---------------------------------------------------
-__device__ __forceinline__ f32x4_t encode_box(const f32x4_t p, const f32x4_t g, const f32x4_t means,
-                                              const f32x4_t stds) {
-  const float px = __fmul_rn(__fadd_rn(p[0], p[2]), 0.5f), py = __fmul_rn(__fadd_rn(p[1], p[3]), 0.5f);
-  const float pw = __fadd_rn(__fsub_rn(p[2], p[0]), 1.0f), ph = __fadd_rn(__fsub_rn(p[3], p[1]), 1.0f);
-  const float gx = __fmul_rn(__fadd_rn(g[0], g[2]), 0.5f), gy = __fmul_rn(__fadd_rn(g[1], g[3]), 0.5f);
-  const float gw = __fadd_rn(__fsub_rn(g[2], g[0]), 1.0f), gh = __fadd_rn(__fsub_rn(g[3], g[1]), 1.0f);
-  f32x4_t d;
-  d[0] = __fdiv_rn(__fsub_rn(gx, px), pw);
-  d[1] = __fdiv_rn(__fsub_rn(gy, py), ph);
-  d[2] = logf(__fdiv_rn(gw, pw));
-  d[3] = logf(__fdiv_rn(gh, ph));
-#pragma unroll
-  for (int e = 0; e < 4; ++e) d[e] = __fdiv_rn(__fsub_rn(d[e], means[e]), stds[e]);
-  return d;
-}
-
+// ---- decode (spec order, one rounding per operation; the encode is in delta_core.h) ---------------------------------
 // clip_w < 0: no clipping
 __device__ __forceinline__ f32x4_t decode_box(const f32x4_t r, const f32x4_t delta, const f32x4_t means,
                                               const f32x4_t stds, float max_ratio, int clip_h, int clip_w) {
@@ -137,36 +123,7 @@ extern "C" int tdn_delta2bbox(const float* rois, const float* deltas, int64_t N,
   return 0;
 }
 
-// ---- block-wide helpers (1024 threads) -------------------------------------------------------------------------
-constexpr int BLK = 1024;
-constexpr int TK_PER = 8;                     // keys per thread per step, consecutive: one scan orders a whole step
-constexpr int TK_STEP = BLK * TK_PER;
-constexpr int TK_BINS = 2048;                 // 11-bit digits: 21..31, 10..20, 0..9
-constexpr int TK_MISC = 64;                   // ints of scratch: [0,16) scan, [16,18) bin choice, [32,64) caller
-
-// exclusive prefix sum over the workgroup in thread order; *total = the sum of all
-__device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) sh[wave] = incl;
-  __syncthreads();
-  int before = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < BLK / 64; ++w) {
-    const int c = sh[w];
-    before += (w < wave) ? c : 0;
-    tot += c;
-  }
-  __syncthreads();
-  *total = tot;
-  return before + incl - v;
-}
-
+// ---- block-wide helpers (1024 threads; the scan and the radix select are in select_core.h) ----------------------
 // descending bitonic sort of s[0, P), P a power of two
 __device__ __forceinline__ void block_sort_desc(u64* s, int P) {
   __syncthreads();
@@ -210,43 +167,10 @@ __device__ int block_topk(const Fetch& F, int n, int k, u64* skeys, int* hist, i
     m = n;
   } else {
     // radix select of the threshold key T: k - need keys are > T, and the first `need` keys == T are taken
-    uint32_t prefix = 0u, pmask = 0u;
-    int need = k;
-    for (int pass = 0; pass < 3; ++pass) {
-      const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
-      const uint32_t dmask = pass == 2 ? 0x3FFu : 0x7FFu;
-      for (int b = tid; b < TK_BINS; b += BLK) hist[b] = 0;
-      __syncthreads();
-      for (int i0 = tid * TK_PER; i0 < n; i0 += TK_STEP) {
-        const int cnt = min(TK_PER, n - i0);
-        uint32_t kk[TK_PER];
-        F(i0, cnt, kk);
-#pragma unroll
-        for (int e = 0; e < TK_PER; ++e)
-          if (e < cnt && (kk[e] & pmask) == prefix) atomicAdd(&hist[(kk[e] >> shift) & dmask], 1);
-      }
-      __syncthreads();
-      // thread t owns bins 2047-2t and 2046-2t: an exclusive scan in thread order counts the keys in higher bins
-      const int hi = TK_BINS - 1 - 2 * tid;
-      const int ch = hist[hi], cl = hist[hi - 1];
-      int tot;
-      const int above = block_excl_scan(ch + cl, misc, &tot);
-      if (above < need && need <= above + ch) {
-        misc[16] = hi;
-        misc[17] = above;
-      } else if (above + ch < need && need <= above + ch + cl) {
-        misc[16] = hi - 1;
-        misc[17] = above + ch;
-      }
-      __syncthreads();
-      need -= misc[17];
-      prefix |= (uint32_t)misc[16] << shift;
-      pmask |= dmask << shift;
-      __syncthreads();
-    }
+    int need;
+    const uint32_t T = block_radix_threshold(F, n, k, hist, misc, &need);
     // ordered compaction: keys > T go to [0, k - need) in any order (the sort below orders them), the first `need`
     // keys == T in index order to [k - need, k)
-    const uint32_t T = prefix;
     const int ngt = k - need;
     int gt_done = 0, ties_done = 0;
     for (int base = 0; base < n; base += TK_STEP) {
