@@ -304,16 +304,11 @@ extern "C" int tdn_nms(const float* boxes, const float* scores, int N, float iou
   TDN_LAUNCH_CHECK();
   TDN_LAUNCH(nms_mask_kernel, dim3(nblk, nblk), dim3(64), 0, st, sboxes, N, iou_thr, nblk, mask);
   TDN_LAUNCH_CHECK();
-  const bool one_wave = getenv("TDN_NMS_ONEWAVE") && getenv("TDN_NMS_ONEWAVE")[0] == '1';   // A/B runs
+  const char* ow = tdn_knob_present("TDN_NMS_ONEWAVE");
+  const bool one_wave = ow && ow[0] == '1';   // A/B runs
   if (nblk <= NMS_BLOCK_MAX_NBLK && !one_wave) {
     const size_t lds = nms_scan_block_lds(nblk);
-    static tdn_attr_once attr_once;
-    if (attr_once.need()) {
-      hipError_t e = hipFuncSetAttribute((const void*)nms_scan_block_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(nms scan LDS) failed: %s", hipGetErrorString(e));
-      attr_once.mark();
-    }
+    if (tdn_allow_lds<nms_scan_block_kernel>(160 * 1024, "nms_scan_block") < 0) return -1;
     TDN_LAUNCH(nms_scan_block_kernel, dim3(1), dim3(1024), lds, st, mask, order, N, nblk, keep, kept_idx,
                        num_kept);
   } else {

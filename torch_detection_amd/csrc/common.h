@@ -40,6 +40,7 @@ void tdn_set_error(const char* fmt, ...);
 // being recorded (tdn_plan_begin ... tdn_plan_end) the launch is ALSO kept, with all its arguments by value, as a
 // closure that tdn_plan_run can issue again on the same stream: a prepared step is then one C call that enqueues the
 // whole launch list, instead of ~230 trips through the host-side operator layer.
+#include <atomic>
 #include <functional>
 bool tdn_plan_recording();
 void tdn_plan_push(hipStream_t stream, std::function<void(hipStream_t)> fn);
@@ -163,15 +164,31 @@ static __device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];
 
 __host__ __device__ __forceinline__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// hipFuncSetAttribute (dynamic LDS beyond 64 KB) applies to ONE device: remembered per kernel instantiation AND device
-// (`static tdn_attr_once once; if (once.need()) { ...set...; once.mark(); }`), so that a second GPU used from the same
-// process does not launch without it.
-struct tdn_attr_once {
-  bool done[64] = {};
-  int dev = 0;
-  bool need() {
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { dev = -1; return true; }
-    return !done[dev];
-  }
-  void mark() { if (dev >= 0) done[dev] = true; }
-};
+// ---- run-time knobs ---------------------------------------------------------------------------
+// The library's only two readers of the environment (DESIGN.md "Run-time knobs" lists every name).  A knob is read on
+// every call: tests and sweeps flip them between launches of one process.
+// The raw value if `name` is set — an empty string counts as set — else nullptr.  Mostly used as a yes / no.
+static inline const char* tdn_knob_present(const char* name) { return getenv(name); }
+// atoi of the value; `dflt` if the knob is unset or empty
+static inline int tdn_knob_int(const char* name, int dflt) {
+  const char* e = tdn_knob_present(name);
+  return (e && *e) ? atoi(e) : dflt;
+}
+
+// ---- dynamic LDS beyond 64 KB -----------------------------------------------------------------
+// hipFuncSetAttribute applies to ONE device, so it is remembered per kernel instantiation (the template argument) AND
+// per device: a second GPU used from the same process does not launch without it.  The device index is a local and
+// the flags are atomics: one autograd thread per GPU may come through here at the same time.
+// Returns 1 when the attribute was set by this call (first launch of `Kernel` on this device), 0 when it already
+// was, -1 with the error set.
+template <auto Kernel>
+static int tdn_allow_lds(int bytes, const char* what) {
+  static std::atomic<bool> done[64];
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;   // unknown device: set it every time
+  if (dev >= 0 && done[dev].load(std::memory_order_acquire)) return 0;
+  const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(%s, %d B LDS) failed: %s", what, bytes, hipGetErrorString(e));
+  if (dev >= 0) done[dev].store(true, std::memory_order_release);
+  return 1;
+}

@@ -1914,17 +1914,12 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
 template <bool BWD, bool F16, bool MB = false, int HEAD = 0>
 static int launch_block64(BlockParams& p, hipStream_t stream) {
   constexpr int lds = 81920;
-  static tdn_attr_once attr_once;
-  if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)bottleneck64_kernel<BWD, F16, MB, HEAD>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(%d B LDS) failed: %s", lds, hipGetErrorString(e));
-    attr_once.mark();
-    if (getenv("TDN_DEBUG_OCC")) {
-      int nb = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)bottleneck64_kernel<BWD, F16, MB, HEAD>, 256, lds);
-      fprintf(stderr, "[tdn] bottleneck64<%d,%d,%d,%d>: %d B LDS, %d workgroups/CU\n", (int)BWD, (int)F16, (int)MB, (int)HEAD, lds, nb);
-    }
+  const int first = tdn_allow_lds<bottleneck64_kernel<BWD, F16, MB, HEAD>>(lds, "bottleneck64");
+  if (first < 0) return first;
+  if (first && tdn_knob_present("TDN_DEBUG_OCC")) {
+    int nb = -1;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)bottleneck64_kernel<BWD, F16, MB, HEAD>, 256, lds);
+    fprintf(stderr, "[tdn] bottleneck64<%d,%d,%d,%d>: %d B LDS, %d workgroups/CU\n", (int)BWD, (int)F16, (int)MB, (int)HEAD, lds, nb);
   }
   TDN_LAUNCH((bottleneck64_kernel<BWD, F16, MB, HEAD>), dim3(p.nwg_pad), dim3(256), lds, stream, p);
   TDN_LAUNCH_CHECK();
@@ -1939,13 +1934,7 @@ extern "C" int tdn_debug_block_trace(void* buf) { g_blk_trace = (unsigned long l
 template <bool BWD, bool F16, bool MB = false>
 static int launch_block128(BlockParams& p, hipStream_t stream) {
   constexpr int lds = 163840;
-  static tdn_attr_once attr_once;
-  if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)bottleneck128_kernel<BWD, F16, MB>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(%d B LDS) failed: %s", lds, hipGetErrorString(e));
-    attr_once.mark();
-  }
+  if (tdn_allow_lds<bottleneck128_kernel<BWD, F16, MB>>(lds, "bottleneck128") < 0) return -1;
   TDN_LAUNCH((bottleneck128_kernel<BWD, F16, MB>), dim3(p.nwg_pad), dim3(512), lds, stream, p);
   TDN_LAUNCH_CHECK();
   return 0;
@@ -1958,8 +1947,8 @@ static int launch_block128(BlockParams& p, hipStream_t stream) {
 // (R101 at 4 images per GPU: two chains of two; TDN_IMG_SPLIT_M below the layer2 size) take 10 rows and gain a third
 // (both images of 100 x 168: 57.4 -> 38.7 us).  TDN_BLOCK128_TH=8 / 10 forces one.
 static int block128_th(const BlockParams& p) {
-  const char* e = getenv("TDN_BLOCK128_TH");
-  if (e && *e) return atoi(e) == 10 ? 10 : 8;
+  const char* e = tdn_knob_present("TDN_BLOCK128_TH");
+  if (e && *e) return atoi(e) == 10 ? 10 : 8;   // any other value, a non-number included, forces 8
   const int tx = ceil_div(p.W, 16);
   const int r8 = ceil_div(p.N * tx * ceil_div(p.H, 8), 256) * 8;
   const int r10 = ceil_div(p.N * tx * ceil_div(p.H, 10), 256) * 10;
@@ -1969,13 +1958,7 @@ static int block128_th(const BlockParams& p) {
 template <bool BWD, bool F16, bool MB = false>
 static int launch_block128t(BlockParams& p, hipStream_t stream) {
   constexpr int lds = 163840;
-  static tdn_attr_once attr_once;
-  if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)bottleneck128t_kernel<BWD, F16, MB>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(%d B LDS) failed: %s", lds, hipGetErrorString(e));
-    attr_once.mark();
-  }
+  if (tdn_allow_lds<bottleneck128t_kernel<BWD, F16, MB>>(lds, "bottleneck128t") < 0) return -1;
   p.tiles_y = ceil_div(p.H, 10);
   p.ntiles = p.N * p.tiles_x * p.tiles_y;
   p.nwg_pad = (p.ntiles + 7) & ~7;

@@ -23,7 +23,7 @@
 // ds_read_b128 for every tap shift.  A patch whose width is not a multiple of 16 lets some fragments straddle two patch
 // rows (two runs of pixels whose slots can collide pairwise: a 2-way conflict on those fragments only) — the planner
 // weighs that against the pixels a multiple-of-16 width would waste on maps such as 50 x 84.
-#include "common.h"
+#include "conv_host.h"
 #include <type_traits>
 
 struct HaloParams {
@@ -548,55 +548,49 @@ __global__ __launch_bounds__((WM * WN + NWL) * 64, ((WM * WN + NWL) >= 16 ? 4 : 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static void hdiv_init(unsigned d, unsigned* mul, unsigned* shr) {
-  if (d <= 1) { *mul = 0; *shr = 0; return; }
-  unsigned lg = 0;
-  while ((1ull << lg) < d) ++lg;
-  const unsigned pw = 31 + lg;
-  *mul = (unsigned)(((1ull << pw) + d - 1) / d);
-  *shr = pw - 32;
-}
-
-// Tile configurations: {FM, FN, WM, WN, NST, XI9}; BM = 16 FM WM pixels, BN = 16 FN WN channels, WM WN waves, NST-deep
+// Tile configurations, one row per tile: X(id, FM, FN, WM, WN, NST, XI9, NWL); BM = 16 FM WM pixels, BN = 16 FN WN channels, WM WN waves, NST-deep
 // weight ring, XI9 activation pieces per wave and K-step (3x3 only).  Separate tables for 3x3 and 1x1 layers: the
 // LDS split between patch images and the weight ring differs (a 3x3 needs two patch images of 9 K-steps each, a 1x1
 // streams one pixel-tile chunk per K-step through an NST - 1 deep ring of its own).
-struct HaloCfg { int fm, fn, wm, wn, nst, xi9, nwl = 0; };
-static const HaloCfg kHalo3[] = {
-    {4, 4, 2, 2, 7, 2},   // 0  128 x 128, 4 waves, 6 weight tiles (96 KB) in flight: mid-size layers, one workgroup per CU
-    {4, 4, 4, 2, 4, 1},   // 1  256 x 128, 8 waves: large-M layers
-    {4, 4, 4, 1, 4, 2},   // 2  256 x  64, 4 waves: Cout = 64 at large M (layer1)
-    {4, 2, 2, 2, 5, 1},   // 3  128 x  64, 4 waves (wave tile 64 x 32)
-    {2, 4, 2, 2, 7, 1},   // 4   64 x 128, 4 waves (wave tile 32 x 64): smallest-M layers
-    {4, 4, 2, 2, 3, 1},   // 5  configuration 0 with the shallow ring (A/B)
-    {2, 4, 4, 2, 7, 1},   // 6  128 x 128, 8 waves (wave tile 32 x 64)
-    {4, 4, 4, 2, 3, 1},   // 7  configuration 1 with the shallow ring (A/B)
-    {4, 4, 2, 2, 7, 2, 4},   // 8  128 x 128, 4 consumer + 4 loader waves
-    {2, 4, 2, 2, 7, 1, 4},   // 9   64 x 128, 4 consumer + 4 loader waves
-    {4, 2, 2, 2, 5, 1, 4},   // 10 128 x  64, 4 consumer + 4 loader waves
-    {4, 4, 2, 2, 4, 1, 4},   // 11 configuration 8 with a 4-deep ring
-    {4, 4, 4, 2, 4, 2, 4},   // 12 256 x 128, 8 consumer + 4 loader waves (3 waves per SIMD: <= 168 registers)
-    {4, 2, 2, 4, 4, 1, 8},   // 13 128 x 128, 8 consumer (wave tile 64 x 32) + 8 loader waves: <= 128 registers
-    {4, 2, 2, 4, 4, 1, 4},   // 14 128 x 128, 8 consumer (wave tile 64 x 32) + 4 loader waves: <= 168 registers
-    {2, 4, 4, 2, 4, 1, 4},   // 15 128 x 128, 8 consumer (wave tile 32 x 64) + 4 loader waves
-};
-static const HaloCfg kHalo1[] = {
-    {4, 4, 2, 2, 5, 1},   // 0  128 x 128, 4 waves
-    {2, 4, 4, 2, 5, 1},   // 1  128 x 128, 8 waves (wave tile 32 x 64)
-    {4, 4, 4, 1, 4, 1},   // 2  256 x  64, 4 waves: Cout = 64
-    {4, 2, 2, 2, 5, 1},   // 3  128 x  64, 4 waves
-    {2, 4, 2, 2, 6, 1},   // 4   64 x 128, 4 waves
-    {4, 4, 2, 2, 3, 1},   // 5  configuration 0 with the shallow ring (A/B)
-    {4, 4, 4, 2, 3, 1},   // 6  256 x 128, 8 waves
-    {2, 4, 2, 4, 4, 1},   // 7   64 x 256, 8 waves
-    {4, 4, 2, 2, 5, 1, 4},   // 8  128 x 128, 4 consumer + 4 loader waves
-    {2, 4, 2, 2, 6, 1, 4},   // 9   64 x 128, 4 consumer + 4 loader waves
-    {4, 2, 2, 2, 5, 1, 4},   // 10 128 x  64, 4 consumer + 4 loader waves
-    {4, 4, 2, 2, 3, 1, 4},   // 11 configuration 8 with the shallow ring
-    {4, 2, 2, 2, 5, 1, 8},   // 12 128 x  64, 4 consumer + 8 loader waves
-    {2, 4, 2, 2, 6, 1, 8},   // 13  64 x 128, 4 consumer + 8 loader waves
-    {2, 2, 2, 2, 6, 1, 8},   // 14  64 x  64, 4 consumer + 8 loader waves (wave tile 32 x 32)
-};
+// NWL: dedicated loader waves (0: the consumer waves load).  kHalo3[] / kHalo1[] (the planner's view) and the switches
+// of halo_dispatch3 / halo_dispatch1 (the instantiations) are generated from these lists.
+#define TDN_HALO3_CFGS(X) \
+  X(0, 4, 4, 2, 2, 7, 2, 0)   /* 128 x 128, 4 waves, 6 weight tiles (96 KB) in flight: mid-size layers, one workgroup per CU */  \
+  X(1, 4, 4, 4, 2, 4, 1, 0)   /* 256 x 128, 8 waves: large-M layers */                                                           \
+  X(2, 4, 4, 4, 1, 4, 2, 0)   /* 256 x  64, 4 waves: Cout = 64 at large M (layer1) */                                            \
+  X(3, 4, 2, 2, 2, 5, 1, 0)   /* 128 x  64, 4 waves (wave tile 64 x 32) */                                                       \
+  X(4, 2, 4, 2, 2, 7, 1, 0)   /* 64 x 128, 4 waves (wave tile 32 x 64): smallest-M layers */                                     \
+  X(5, 4, 4, 2, 2, 3, 1, 0)   /* configuration 0 with the shallow ring (A/B) */                                                  \
+  X(6, 2, 4, 4, 2, 7, 1, 0)   /* 128 x 128, 8 waves (wave tile 32 x 64) */                                                       \
+  X(7, 4, 4, 4, 2, 3, 1, 0)   /* configuration 1 with the shallow ring (A/B) */                                                  \
+  X(8, 4, 4, 2, 2, 7, 2, 4)   /* 128 x 128, 4 consumer + 4 loader waves */                                                       \
+  X(9, 2, 4, 2, 2, 7, 1, 4)   /* 64 x 128, 4 consumer + 4 loader waves */                                                        \
+  X(10, 4, 2, 2, 2, 5, 1, 4)  /* 128 x  64, 4 consumer + 4 loader waves */                                                       \
+  X(11, 4, 4, 2, 2, 4, 1, 4)  /* configuration 8 with a 4-deep ring */                                                           \
+  X(12, 4, 4, 4, 2, 4, 2, 4)  /* 256 x 128, 8 consumer + 4 loader waves (3 waves per SIMD: <= 168 registers) */                  \
+  X(13, 4, 2, 2, 4, 4, 1, 8)  /* 128 x 128, 8 consumer (wave tile 64 x 32) + 8 loader waves: <= 128 registers */                 \
+  X(14, 4, 2, 2, 4, 4, 1, 4)  /* 128 x 128, 8 consumer (wave tile 64 x 32) + 4 loader waves: <= 168 registers */                 \
+  X(15, 2, 4, 4, 2, 4, 1, 4)  /* 128 x 128, 8 consumer (wave tile 32 x 64) + 4 loader waves */
+#define TDN_HALO1_CFGS(X) \
+  X(0, 4, 4, 2, 2, 5, 1, 0)   /* 128 x 128, 4 waves */                                         \
+  X(1, 2, 4, 4, 2, 5, 1, 0)   /* 128 x 128, 8 waves (wave tile 32 x 64) */                     \
+  X(2, 4, 4, 4, 1, 4, 1, 0)   /* 256 x  64, 4 waves: Cout = 64 */                              \
+  X(3, 4, 2, 2, 2, 5, 1, 0)   /* 128 x  64, 4 waves */                                         \
+  X(4, 2, 4, 2, 2, 6, 1, 0)   /* 64 x 128, 4 waves */                                          \
+  X(5, 4, 4, 2, 2, 3, 1, 0)   /* configuration 0 with the shallow ring (A/B) */                \
+  X(6, 4, 4, 4, 2, 3, 1, 0)   /* 256 x 128, 8 waves */                                         \
+  X(7, 2, 4, 2, 4, 4, 1, 0)   /* 64 x 256, 8 waves */                                          \
+  X(8, 4, 4, 2, 2, 5, 1, 4)   /* 128 x 128, 4 consumer + 4 loader waves */                     \
+  X(9, 2, 4, 2, 2, 6, 1, 4)   /* 64 x 128, 4 consumer + 4 loader waves */                      \
+  X(10, 4, 2, 2, 2, 5, 1, 4)  /* 128 x  64, 4 consumer + 4 loader waves */                     \
+  X(11, 4, 4, 2, 2, 3, 1, 4)  /* configuration 8 with the shallow ring */                      \
+  X(12, 4, 2, 2, 2, 5, 1, 8)  /* 128 x  64, 4 consumer + 8 loader waves */                     \
+  X(13, 2, 4, 2, 2, 6, 1, 8)  /* 64 x 128, 4 consumer + 8 loader waves */                      \
+  X(14, 2, 2, 2, 2, 6, 1, 8)  /* 64 x  64, 4 consumer + 8 loader waves (wave tile 32 x 32) */
+struct HaloCfg { int fm, fn, wm, wn, nst, xi9, nwl; };
+#define TDN_HALO_ROW(id, fm, fn, wm, wn, nst, xi9, nwl) {fm, fn, wm, wn, nst, xi9, nwl},
+static const HaloCfg kHalo3[] = {TDN_HALO3_CFGS(TDN_HALO_ROW)};
+static const HaloCfg kHalo1[] = {TDN_HALO1_CFGS(TDN_HALO_ROW)};
 static const int kNumHalo3 = (int)(sizeof(kHalo3) / sizeof(kHalo3[0]));
 static const int kNumHalo1 = (int)(sizeof(kHalo1) / sizeof(kHalo1[0]));
 static inline const HaloCfg& halo_cfg(int k, int id) { return k == 3 ? kHalo3[id] : kHalo1[id]; }
@@ -605,11 +599,6 @@ struct HaloPlan {
   int cfg, TH, TW, pitch, hrows, xbuf, nt_per_wg;
   size_t lds;
 };
-
-static int halo_env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && *e) ? atoi(e) : dflt;
-}
 
 // Patch shape for a BM-pixel tile on an H x W map: least wasted work over TW (multiples of 2; widths that are not a
 // multiple of 16 let fragments straddle patch rows and cost a wider LDS pitch), TH = BM / TW.  Cost per image =
@@ -639,7 +628,7 @@ struct HaloShape {
 };
 
 // TDN_HALO: bit 0 = 3x3 layers, bit 1 = 1x1 layers through the halo kernel (default both); 0 = generic kernel only
-static int halo_mode() { return halo_env_int("TDN_HALO", 3); }
+static int halo_mode() { return tdn_knob_int("TDN_HALO", 3); }
 
 // Choose configuration, patch, residency.  Returns false when the halo kernel does not apply.
 static bool halo_make_plan(const HaloShape& s, HaloPlan* pl) {
@@ -661,12 +650,12 @@ static bool halo_make_plan(const HaloShape& s, HaloPlan* pl) {
     // 192 x 256 tile alone (167 vs 175 us) but the whole step is 0.7-0.9 % SLOWER with it (three interleaved pairs on
     // one box: 469.8 vs 473.1 img/s) — it runs beside the FPN's nine-tap weight-gradient group and co-runs worse.
     // TDN_HALO_BIG=1 selects it.
-    if (M >= 100000) cfg = halo_env_int("TDN_HALO_BIG", 0) ? 1 : -1;
+    if (M >= 100000) cfg = tdn_knob_int("TDN_HALO_BIG", 0) ? 1 : -1;
     else if (M >= 6000 && M < 30000) cfg = 11;      // layer2 per image, layer3 / P4 per batch: 128 x 128, 4 + 4 waves
     else if (M < 6000 && s.Cin >= 256 && (s.Cin >= 512 || M >= 3000))
       cfg = 10;   // layer3 / layer4 per image: 128 x 64, 4 + 4 waves (P5's 256-channel conv, M = 2,100: generic 13 vs 16 us)
   }
-  cfg = halo_env_int(s.k == 3 ? "TDN_HALO_CFG3" : "TDN_HALO_CFG1", cfg);
+  cfg = tdn_knob_int(s.k == 3 ? "TDN_HALO_CFG3" : "TDN_HALO_CFG1", cfg);
   if (cfg < 0 || cfg >= (s.k == 3 ? kNumHalo3 : kNumHalo1)) return false;   // (-1: not taken)
   const HaloCfg& c = halo_cfg(s.k, cfg);
   const int bm = c.fm * c.wm * 16, bn = c.fn * c.wn * 16;
@@ -678,7 +667,7 @@ static bool halo_make_plan(const HaloShape& s, HaloPlan* pl) {
   } else {
     pl->TH = 0;
     halo_pick_patch(s.H, s.W, s.halo, bm, &pl->TH, &pl->TW, &pl->pitch, &pl->hrows);
-    const int th = halo_env_int("TDN_HALO_TH", 0), tw = halo_env_int("TDN_HALO_TW", 0);
+    const int th = tdn_knob_int("TDN_HALO_TH", 0), tw = tdn_knob_int("TDN_HALO_TW", 0);
     if (th > 0 && tw > 0 && th * tw <= bm && tw % 2 == 0) {
       pl->TH = th; pl->TW = tw;
       pl->pitch = tw + 2 * s.halo;
@@ -695,11 +684,11 @@ static bool halo_make_plan(const HaloShape& s, HaloPlan* pl) {
   // (activation-stationary, nt > 1) need all of them.
   const int xmin = s.k == 3 ? (nchunks < 2 ? nchunks : 2) : (nchunks < c.nst - 1 ? nchunks : c.nst - 1);
   pl->xbuf = xmin;
-  if (xchunk * nchunks + wring <= budget && halo_env_int("TDN_HALO_XBUF", 0) != 2) pl->xbuf = nchunks;
+  if (xchunk * nchunks + wring <= budget && tdn_knob_int("TDN_HALO_XBUF", 0) != 2) pl->xbuf = nchunks;
   const int ntn = s.Cout / bn;
   int nt = 1;
   if (s.k == 1 && pl->xbuf == nchunks && ntn >= 4 && M <= 20000) nt = 2;   // conv3 of layer3 / layer4: two passes
-  nt = halo_env_int("TDN_HALO_NT", nt);
+  nt = tdn_knob_int("TDN_HALO_NT", nt);
   if (nt < 1 || ntn % nt != 0 || pl->xbuf != nchunks) nt = 1;
   pl->nt_per_wg = nt;
   pl->lds = xchunk * pl->xbuf + wring;
@@ -711,59 +700,29 @@ static bool halo_make_plan(const HaloShape& s, HaloPlan* pl) {
 
 template <int FM, int FN, int WM, int WN, int NST, int NTAPS, int XI9, bool F16, int ABL = 0, int NWL = 0>
 static int halo_launch(const HaloParams& p, size_t lds, hipStream_t stream) {
-  static tdn_attr_once attr_once;
-  if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_halo_kernel<FM, FN, WM, WN, NST, NTAPS, XI9, F16, ABL, NWL>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(halo kernel LDS) failed: %s", hipGetErrorString(e));
-    attr_once.mark();
-  }
+  if (tdn_allow_lds<conv_halo_kernel<FM, FN, WM, WN, NST, NTAPS, XI9, F16, ABL, NWL>>(160 * 1024, "conv_halo") < 0)
+    return -1;
   dim3 grid(p.nwg_pad, 1, 1), block((WM * WN + NWL) * 64, 1, 1);
   TDN_LAUNCH((conv_halo_kernel<FM, FN, WM, WN, NST, NTAPS, XI9, F16, ABL, NWL>), grid, block, lds, stream, p);
   TDN_LAUNCH_CHECK();
   return 0;
 }
 
+#define TDN_HALO3_CASE(id, fm, fn, wm, wn, nst, xi9, nwl) \
+  case id: return halo_launch<fm, fn, wm, wn, nst, 9, xi9, F16, 0, nwl>(p, lds, stream);
+#define TDN_HALO1_CASE(id, fm, fn, wm, wn, nst, xi9, nwl) \
+  case id: return halo_launch<fm, fn, wm, wn, nst, 1, xi9, F16, 0, nwl>(p, lds, stream);
 template <bool F16>
 static int halo_dispatch3(int cfg, const HaloParams& p, size_t lds, hipStream_t stream) {
-  switch (cfg) {   // kHalo3
-    case 0: return halo_launch<4, 4, 2, 2, 7, 9, 2, F16>(p, lds, stream);
-    case 1: return halo_launch<4, 4, 4, 2, 4, 9, 1, F16>(p, lds, stream);
-    case 2: return halo_launch<4, 4, 4, 1, 4, 9, 2, F16>(p, lds, stream);
-    case 3: return halo_launch<4, 2, 2, 2, 5, 9, 1, F16>(p, lds, stream);
-    case 4: return halo_launch<2, 4, 2, 2, 7, 9, 1, F16>(p, lds, stream);
-    case 5: return halo_launch<4, 4, 2, 2, 3, 9, 1, F16>(p, lds, stream);
-    case 6: return halo_launch<2, 4, 4, 2, 7, 9, 1, F16>(p, lds, stream);
-    case 7: return halo_launch<4, 4, 4, 2, 3, 9, 1, F16>(p, lds, stream);
-    case 8: return halo_launch<4, 4, 2, 2, 7, 9, 2, F16, 0, 4>(p, lds, stream);
-    case 9: return halo_launch<2, 4, 2, 2, 7, 9, 1, F16, 0, 4>(p, lds, stream);
-    case 10: return halo_launch<4, 2, 2, 2, 5, 9, 1, F16, 0, 4>(p, lds, stream);
-    case 11: return halo_launch<4, 4, 2, 2, 4, 9, 1, F16, 0, 4>(p, lds, stream);
-    case 12: return halo_launch<4, 4, 4, 2, 4, 9, 2, F16, 0, 4>(p, lds, stream);
-    case 13: return halo_launch<4, 2, 2, 4, 4, 9, 1, F16, 0, 8>(p, lds, stream);
-    case 14: return halo_launch<4, 2, 2, 4, 4, 9, 1, F16, 0, 4>(p, lds, stream);
-    case 15: return halo_launch<2, 4, 4, 2, 4, 9, 1, F16, 0, 4>(p, lds, stream);
+  switch (cfg) {
+    TDN_HALO3_CFGS(TDN_HALO3_CASE)
     default: TDN_CHECK(false, "bad 3x3 halo config %d", cfg); return -1;
   }
 }
 template <bool F16>
 static int halo_dispatch1(int cfg, const HaloParams& p, size_t lds, hipStream_t stream) {
-  switch (cfg) {   // kHalo1
-    case 0: return halo_launch<4, 4, 2, 2, 5, 1, 1, F16>(p, lds, stream);
-    case 1: return halo_launch<2, 4, 4, 2, 5, 1, 1, F16>(p, lds, stream);
-    case 2: return halo_launch<4, 4, 4, 1, 4, 1, 1, F16>(p, lds, stream);
-    case 3: return halo_launch<4, 2, 2, 2, 5, 1, 1, F16>(p, lds, stream);
-    case 4: return halo_launch<2, 4, 2, 2, 6, 1, 1, F16>(p, lds, stream);
-    case 5: return halo_launch<4, 4, 2, 2, 3, 1, 1, F16>(p, lds, stream);
-    case 6: return halo_launch<4, 4, 4, 2, 3, 1, 1, F16>(p, lds, stream);
-    case 7: return halo_launch<2, 4, 2, 4, 4, 1, 1, F16>(p, lds, stream);
-    case 8: return halo_launch<4, 4, 2, 2, 5, 1, 1, F16, 0, 4>(p, lds, stream);
-    case 9: return halo_launch<2, 4, 2, 2, 6, 1, 1, F16, 0, 4>(p, lds, stream);
-    case 10: return halo_launch<4, 2, 2, 2, 5, 1, 1, F16, 0, 4>(p, lds, stream);
-    case 11: return halo_launch<4, 4, 2, 2, 3, 1, 1, F16, 0, 4>(p, lds, stream);
-    case 12: return halo_launch<4, 2, 2, 2, 5, 1, 1, F16, 0, 8>(p, lds, stream);
-    case 13: return halo_launch<2, 4, 2, 2, 6, 1, 1, F16, 0, 8>(p, lds, stream);
-    case 14: return halo_launch<2, 2, 2, 2, 6, 1, 1, F16, 0, 8>(p, lds, stream);
+  switch (cfg) {
+    TDN_HALO1_CFGS(TDN_HALO1_CASE)
     default: TDN_CHECK(false, "bad 1x1 halo config %d", cfg); return -1;
   }
 }
@@ -793,13 +752,13 @@ static void halo_fill(HaloParams& p, const HaloShape& s, const HaloPlan& pl) {
   p.nchunks = s.Cin / 64; p.xbuf = pl.xbuf; p.x_resident = pl.xbuf >= p.nchunks ? 1 : 0;
   p.wt_row = s.wt_row; p.Ktap = s.Ktap;
   for (int i = 0; i < 9; ++i) p.taps[i] = s.taps[i];
-  hdiv_init((unsigned)p.ngroups_n, &p.ng_mul, &p.ng_shr);
-  hdiv_init((unsigned)p.tiles_img, &p.ti_mul, &p.ti_shr);
-  hdiv_init((unsigned)p.tiles_w, &p.tw_mul, &p.tw_shr);
-  hdiv_init((unsigned)p.pitch, &p.pit_mul, &p.pit_shr);
-  hdiv_init((unsigned)p.TW, &p.TW_mul, &p.TW_shr);
-  hdiv_init((unsigned)(s.H * s.W), &p.hw_mul, &p.hw_shr);
-  hdiv_init((unsigned)s.W, &p.w_mul, &p.w_shr);
+  fast_div_init((unsigned)p.ngroups_n, &p.ng_mul, &p.ng_shr);
+  fast_div_init((unsigned)p.tiles_img, &p.ti_mul, &p.ti_shr);
+  fast_div_init((unsigned)p.tiles_w, &p.tw_mul, &p.tw_shr);
+  fast_div_init((unsigned)p.pitch, &p.pit_mul, &p.pit_shr);
+  fast_div_init((unsigned)p.TW, &p.TW_mul, &p.TW_shr);
+  fast_div_init((unsigned)(s.H * s.W), &p.hw_mul, &p.hw_shr);
+  fast_div_init((unsigned)s.W, &p.w_mul, &p.w_shr);
 }
 
 static int halo_run(HaloParams& p, const HaloShape& s, const HaloPlan& pl, int dtype, hipStream_t stream) {
@@ -811,8 +770,9 @@ static int halo_run(HaloParams& p, const HaloShape& s, const HaloPlan& pl, int d
     for (int t = 0; t < 9; ++t)
       TDN_CHECK(((p.taps[t] >> 8) & 0xff) == ((p.taps[t % 3] >> 8) & 0xff) && (p.taps[t] >> 16) == t,
                 "halo plan: taps are not (kh, kw) ordered");
-#ifdef TDN_TRACE_BUILD   // timing-only ablation builds of two configurations (make TRACE=1): wrong results by construction
-    if (const int abl = halo_env_int("TDN_HALO_ABL", 0)) {
+    // Twins of rows 0, 11 and 1 of TDN_HALO3_CFGS under symbols of their own (template argument ABL).
+#ifdef TDN_TRACE_BUILD   // timing-only ablation builds (make TRACE=1): wrong results by construction
+    if (const int abl = tdn_knob_int("TDN_HALO_ABL", 0)) {
       if (pl.cfg == 0 && abl == 1) return halo_launch<4, 4, 2, 2, 7, 9, 2, false, 1>(p, pl.lds, stream);
       if (pl.cfg == 0 && abl == 2) return halo_launch<4, 4, 2, 2, 7, 9, 2, false, 2>(p, pl.lds, stream);
       if (pl.cfg == 0 && abl == 3) return halo_launch<4, 4, 2, 2, 7, 9, 2, false, 3>(p, pl.lds, stream);
@@ -825,9 +785,10 @@ static int halo_run(HaloParams& p, const HaloShape& s, const HaloPlan& pl, int d
     }
 #endif
     // TDN_TAG_DOMINANT (set by bench.py around exactly the launches it brackets with HIP events): the same code under
-    // a symbol of its own (template argument ABL = 9 changes nothing but the name), so that rocprofv3 --stats lists
-    // those launches — neck.fpn_convs.0 forward and its dgrad — on a line of their own
-    if (pl.cfg == 1 && dtype != TDN_F16 && p.M >= 100000 && p.Cout == 256 && p.nchunks == 4 && getenv("TDN_TAG_DOMINANT"))
+    // a symbol of its own (ABL = 9 changes nothing but the name), so that rocprofv3 --stats lists those launches —
+    // neck.fpn_convs.0 forward and its dgrad — on a line of their own
+    if (pl.cfg == 1 && dtype != TDN_F16 && p.M >= 100000 && p.Cout == 256 && p.nchunks == 4 &&
+        tdn_knob_present("TDN_TAG_DOMINANT"))
       return halo_launch<4, 4, 4, 2, 4, 9, 1, false, 9>(p, pl.lds, stream);
     if (dtype == TDN_F16) return halo_dispatch3<true>(pl.cfg, p, pl.lds, stream);
     return halo_dispatch3<false>(pl.cfg, p, pl.lds, stream);
@@ -836,90 +797,53 @@ static int halo_run(HaloParams& p, const HaloShape& s, const HaloPlan& pl, int d
   return halo_dispatch1<false>(pl.cfg, p, pl.lds, stream);
 }
 
-static void halo_epilogue(HaloParams& p, const tdn_epilogue* ep) {
-  p.scale = nullptr; p.shift = nullptr; p.addend = nullptr; p.mask = nullptr;
-  p.addend_mode = TDN_ADD_NONE; p.addend_h = 0; p.addend_w = 0; p.relu = 0; p.out_f32 = 0;
-  if (!ep) return;
-  p.out_f32 = ep->out_f32 ? 1 : 0;
-  p.scale = ep->scale; p.shift = ep->shift; p.relu = ep->relu;
-  p.mask = (const bf16_t*)ep->mask_src;
-  if (ep->addend_mode != TDN_ADD_NONE) {
-    p.addend = (const bf16_t*)ep->addend;
-    p.addend_mode = ep->addend_mode;
-    p.addend_h = ep->addend_h;
-    p.addend_w = ep->addend_w;
-  }
+// The conv as the halo kernel sees it.  kind 0: forward; 1: input gradient — the same conv over g with the per-tap
+// transposed weights w_dgrad[Cin][kh][kw][Cout] (tap (kh, kw) reads g at (h + pad - kh d, w + pad - kw d)).
+// False: the halo kernel has no form of this conv (strided 3x3, strided input gradient).
+static bool halo_shape(int kind, int N, int H, int W, int Cin, int Cout, int k, int stride, int pad, HaloShape* s) {
+  if (kind == 0 ? (k == 3 && stride != 1) : stride != 1) return false;
+  const int d = conv_dil(k, pad), sign = kind == 0 ? 1 : -1;
+  s->N = N; s->Hin = H; s->Win = W; s->k = k; s->sa = stride;
+  s->H = conv_out_sz(H, k, stride, pad); s->W = conv_out_sz(W, k, stride, pad);
+  s->Cin = kind == 0 ? Cin : Cout; s->Cout = kind == 0 ? Cout : Cin;
+  s->halo = k == 3 ? d : 0;
+  s->wt_row = k * k * s->Cin; s->Ktap = s->Cin;
+  for (int i = 0; i < 9; ++i) s->taps[i] = pack_tap(0, 0, 0);
+  if (k == 3)
+    for (int kh = 0; kh < 3; ++kh)
+      for (int kw = 0; kw < 3; ++kw) s->taps[kh * 3 + kw] = pack_tap(sign * (kh * d - pad), sign * (kw * d - pad), kh * 3 + kw);
+  return true;
 }
 
-static inline int halo_pack_tap(int dh, int dw, int widx) { return (dh + 64) | ((dw + 64) << 8) | (widx << 16); }
+static int halo_conv(int kind, const void* in, const void* wt, void* out, int N, int H, int W, int Cin, int Cout, int k,
+                     int stride, int pad, const tdn_epilogue* ep, int dtype, hipStream_t stream) {
+  HaloShape s;
+  HaloPlan pl;
+  if (!halo_shape(kind, N, H, W, Cin, Cout, k, stride, pad, &s) || !halo_make_plan(s, &pl)) return 0;
+  HaloParams p;
+  if (conv_fill_epilogue(p, ep, s.H, s.W)) return -1;
+  p.in = (const bf16_t*)in; p.wt = (const bf16_t*)wt; p.out = (bf16_t*)out;
+  const int rc = halo_run(p, s, pl, dtype, stream);
+  return rc < 0 ? rc : 1;
+}
 
-// Forward conv through the halo kernel.  Returns 1 if launched, 0 if the shape is left to conv_igemm.hip, < 0 on error.
-// (The epilogue was validated by the caller: fill_epilogue of conv_igemm.hip.)
+// Forward conv / stride-1 input gradient through the halo kernel.  Each returns 1 if launched, 0 if the shape is left
+// to conv_igemm.hip, < 0 on error.
 int tdn_halo_conv_fwd(const void* x, const void* w_fwd, void* y, int N, int H, int W, int Cin, int Cout, int k,
                       int stride, int pad, const tdn_epilogue* ep, int dtype, hipStream_t stream) {
-  if (k == 3 && stride != 1) return 0;
-  HaloShape s;
-  const int d = k == 3 ? pad : 1;
-  s.N = N; s.Hin = H; s.Win = W; s.Cin = Cin; s.Cout = Cout; s.k = k; s.sa = stride;
-  s.H = k == 3 ? H : (H - 1) / stride + 1;
-  s.W = k == 3 ? W : (W - 1) / stride + 1;
-  s.halo = k == 3 ? d : 0;
-  s.wt_row = k * k * Cin; s.Ktap = Cin;
-  for (int i = 0; i < 9; ++i) s.taps[i] = halo_pack_tap(0, 0, 0);
-  if (k == 3)
-    for (int kh = 0; kh < 3; ++kh)
-      for (int kw = 0; kw < 3; ++kw) s.taps[kh * 3 + kw] = halo_pack_tap(kh * d - pad, kw * d - pad, kh * 3 + kw);
-  HaloPlan pl;
-  if (!halo_make_plan(s, &pl)) return 0;
-  HaloParams p;
-  halo_epilogue(p, ep);
-  p.in = (const bf16_t*)x; p.wt = (const bf16_t*)w_fwd; p.out = (bf16_t*)y;
-  const int rc = halo_run(p, s, pl, dtype, stream);
-  return rc < 0 ? rc : 1;
+  return halo_conv(0, x, w_fwd, y, N, H, W, Cin, Cout, k, stride, pad, ep, dtype, stream);
 }
-
-// Stride-1 input gradient: the same conv over g with the per-tap transposed weights w_dgrad[Cin][kh][kw][Cout]
-// (tap (kh, kw) reads g at (h + pad - kh d, w + pad - kw d)).
 int tdn_halo_conv_dgrad(const void* g, const void* w_dgrad, void* dx, int N, int H, int W, int Cin, int Cout, int k,
                         int stride, int pad, const tdn_epilogue* ep, int dtype, hipStream_t stream) {
-  if (stride != 1) return 0;
-  HaloShape s;
-  const int d = k == 3 ? pad : 1;
-  s.N = N; s.H = H; s.W = W; s.Hin = H; s.Win = W; s.Cin = Cout; s.Cout = Cin; s.k = k; s.sa = 1;
-  s.halo = k == 3 ? d : 0;
-  s.wt_row = k * k * Cout; s.Ktap = Cout;
-  for (int i = 0; i < 9; ++i) s.taps[i] = halo_pack_tap(0, 0, 0);
-  if (k == 3)
-    for (int kh = 0; kh < 3; ++kh)
-      for (int kw = 0; kw < 3; ++kw) s.taps[kh * 3 + kw] = halo_pack_tap(pad - kh * d, pad - kw * d, kh * 3 + kw);
-  HaloPlan pl;
-  if (!halo_make_plan(s, &pl)) return 0;
-  HaloParams p;
-  halo_epilogue(p, ep);
-  p.in = (const bf16_t*)g; p.wt = (const bf16_t*)w_dgrad; p.out = (bf16_t*)dx;
-  const int rc = halo_run(p, s, pl, dtype, stream);
-  return rc < 0 ? rc : 1;
+  return halo_conv(1, g, w_dgrad, dx, N, H, W, Cin, Cout, k, stride, pad, ep, dtype, stream);
 }
 
 // What tdn_conv2d_plan reports for a shape the halo kernel takes: o[3..6] = BM, BN, 64, workgroups.
 int tdn_halo_plan(int kind, int N, int H, int W, int Cin, int Cout, int k, int stride, int pad, int32_t* o) {
   HaloShape s;
-  const int d = k == 3 ? pad : 1;
-  if (kind == 0) {
-    if (k == 3 && stride != 1) return 0;
-    s.N = N; s.Hin = H; s.Win = W; s.Cin = Cin; s.Cout = Cout; s.k = k; s.sa = stride;
-    s.H = k == 3 ? H : (H - 1) / stride + 1;
-    s.W = k == 3 ? W : (W - 1) / stride + 1;
-  } else {
-    if (stride != 1) return 0;
-    s.N = N; s.H = H; s.W = W; s.Hin = H; s.Win = W; s.Cin = Cout; s.Cout = Cin; s.k = k; s.sa = 1;
-  }
-  s.halo = k == 3 ? d : 0;
   HaloPlan pl;
-  if (!halo_make_plan(s, &pl)) return 0;
+  if (!halo_shape(kind, N, H, W, Cin, Cout, k, stride, pad, &s) || !halo_make_plan(s, &pl)) return 0;
   HaloParams p;
-  for (int i = 0; i < 9; ++i) s.taps[i] = halo_pack_tap(0, 0, 0);
-  s.wt_row = 0; s.Ktap = 0;
   halo_fill(p, s, pl);
   const HaloCfg& c = halo_cfg(k, pl.cfg);
   o[3] = c.fm * c.wm * 16; o[4] = c.fn * c.wn * 16; o[5] = 64; o[6] = p.nwg_pad; o[7] = 1;

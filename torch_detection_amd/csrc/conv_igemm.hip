@@ -12,7 +12,7 @@
 //
 // A "class" is a sub-lattice of output pixels sharing one tap list: forward and stride-1 dgrad have one
 // class; stride-2 dgrad has four output-parity classes (gather form, no atomics, no zero-insertion).
-#include "common.h"
+#include "conv_host.h"
 
 // conv_halo.hip: LDS-resident activation patch kernel for 3x3 / 1x1 convs (stride-1 3x3, any 1x1 forward; stride-1
 // input gradients).  Each returns 1 when it launched, 0 when the shape stays with the generic kernel below.
@@ -30,16 +30,7 @@ struct GemmClass {
   unsigned mul_hw, shr_hw, mul_w, shr_w;   // exact division of m < 2^31 by Ha*Wa and by Wa: umulhi + shift
 };
 
-// n / d for 0 <= n < 2^31 as umulhi(n, mul) >> shr (mul == 0 encodes d == 1): the row -> (image, y, x) split of every
-// loader row and every epilogue pixel costs 2 multiplies instead of two ~35-instruction integer divisions.
-static void fast_div_init(unsigned d, unsigned* mul, unsigned* shr) {
-  if (d <= 1) { *mul = 0; *shr = 0; return; }
-  unsigned lg = 0;
-  while ((1ull << lg) < d) ++lg;             // ceil(log2(d))
-  const unsigned p = 31 + lg;
-  *mul = (unsigned)(((1ull << p) + d - 1) / d);
-  *shr = p - 32;
-}
+// n / d with the (mul, shr) pair of fast_div_init (conv_host.h)
 __device__ __forceinline__ int fast_div(int n, unsigned mul, unsigned shr) {
   return mul ? (int)(__umulhi((unsigned)n, mul) >> shr) : n;
 }
@@ -722,100 +713,120 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline int pack_tap(int dh, int dw, int widx) { return (dh + 64) | ((dw + 64) << 8) | (widx << 16); }
 static inline void class_divisors(GemmClass& c) {
   fast_div_init((unsigned)(c.Ha * c.Wa), &c.mul_hw, &c.shr_hw);
   fast_div_init((unsigned)c.Wa, &c.mul_w, &c.shr_w);
 }
 
-// Tile configurations. LDS = NSTAGE * (BM + BN) * BK * 2 bytes.  The production library (libtdn.so) instantiates ids
-// 0, 1, 2, 3, 25 and 46 (plus the tagged twin of 3 and the stem's 128x64x32) — the set choose_cfg picks from; every
-// other row (alternates of the round-1/2 sweeps, timing-only ablation MODEs, TAG-2 cycle-stamp builds) exists only in
-// libtdn_trace.so (`make TRACE=1`, loaded by the scripts with TDN_LIB=libtdn_trace.so).  One source, one ISA.  MODE 0: LDS-DMA of the next K-step right after the
-// barrier, fragments read per sub-step; MODE 6: fragment reads software-pipelined under the MFMAs; MODE 3/4/7/8:
-// timing-only ablations (wrong results); tag 2: cycle-stamp tracing build (tdn_debug_trace, scripts/trace_gemm.py).
-struct GemmCfg { int bm, bn, bk, wm, wn, nstage, mode, tag, kg = 1; };
-static const GemmCfg kCfgs[] = {
-    {64, 64, 64, 2, 2, 2, 0, 0},     // 0   32 KB, 256 thr: Cout = 64 layers, tiny grids
-    {64, 128, 64, 2, 2, 2, 6, 0},    // 1   48 KB, 256 thr: mid-size layers
-    {128, 128, 64, 2, 2, 2, 6, 0},   // 2   64 KB, 256 thr: large-M, Cout = 128
-    {192, 256, 64, 2, 4, 2, 6, 0},   // 3  112 KB, 512 thr: large-M, Cout % 256 == 0 (fewest L2->LDS bytes per flop)
-    {64, 128, 64, 2, 2, 2, 0, 0},    // 4  alternates kept for scripts/conv_bench.py sweeps
-    {64, 128, 64, 2, 2, 3, 0, 0},    // 5
-    {64, 64, 64, 2, 2, 4, 0, 0},     // 6
-    {128, 128, 64, 2, 2, 2, 0, 0},   // 7
-    {128, 64, 64, 2, 2, 2, 0, 0},    // 8
-    {64, 256, 64, 2, 2, 2, 0, 0},    // 9
-    {128, 256, 64, 2, 4, 2, 0, 0},   // 10
-    {256, 128, 64, 4, 2, 3, 6, 0},   // 11
-    {192, 256, 64, 2, 4, 2, 3, 0},   // 12 ablation: no loads in the K loop
-    {192, 256, 64, 2, 4, 2, 4, 0},   // 13 ablation: loads only
-    {192, 256, 64, 2, 4, 2, 7, 0},   // 14 ablation: MFMA only
-    {192, 256, 64, 2, 4, 2, 8, 0},   // 15 ablation: LDS fragment reads only
-    {64, 64, 64, 2, 2, 2, 0, 2},     // 16 trace builds of 0, 1, 6, 3
-    {64, 128, 64, 2, 2, 2, 6, 2},    // 17
-    {64, 64, 64, 2, 2, 4, 0, 2},     // 18
-    {192, 256, 64, 2, 4, 2, 6, 2},   // 19
-    {64, 64, 64, 2, 2, 2, 4, 2},     // 20 traced ablations of the small tile: loads only (2- and 4-deep ring)
-    {64, 64, 64, 2, 2, 4, 4, 2},     // 21
-    {64, 64, 64, 2, 2, 2, 3, 2},     // 22 no loads in the K loop
-    {64, 64, 64, 2, 2, 4, 3, 2},     // 23
-    {64, 64, 64, 2, 2, 2, 0, 0, 4},  // 24 in-workgroup split-K: 4 groups x 4 waves, 128 KB
-    {64, 64, 64, 2, 2, 2, 0, 0, 2},  // 25 2 groups x 4 waves, 64 KB
-    {64, 128, 64, 2, 2, 2, 6, 0, 2}, // 26 2 groups x 4 waves, 96 KB
-    {64, 128, 64, 2, 2, 2, 0, 0, 2}, // 27
-    {128, 128, 64, 2, 2, 2, 6, 0, 2},  // 28 2 groups x 4 waves, 128 KB
-    {64, 64, 64, 2, 2, 2, 0, 2, 4},  // 29 trace build of 24
-    {64, 64, 64, 2, 2, 2, 6, 0, 4},  // 30
-    {192, 256, 64, 2, 4, 2, 4, 2},   // 31 traced loads-only: 8 waves
-    {256, 256, 64, 4, 4, 2, 4, 2},   // 32 traced loads-only: 16 waves
-    {256, 256, 64, 4, 4, 2, 0, 2},   // 33 traced full kernel, 16 waves, MODE 0
-    {256, 256, 64, 4, 4, 2, 6, 2},   // 34 traced full kernel, 16 waves, MODE 6
-    {128, 256, 64, 2, 8, 2, 4, 2},   // 35 traced loads-only: 16 waves, 96 KB
-    {128, 256, 64, 2, 8, 2, 6, 2},   // 36 traced full, 16 waves
-    {64, 64, 64, 2, 2, 2, 9, 2},     // 37 traced loads-only through registers (vs 20: LDS-DMA)
-    {64, 128, 64, 2, 2, 2, 9, 2},    // 38
-    {64, 128, 64, 2, 2, 2, 4, 2},    // 39 traced loads-only LDS-DMA, 64x128
-    {192, 256, 64, 2, 4, 2, 9, 2},   // 40 traced loads-only through registers, big tile (vs 31)
-    {64, 128, 64, 2, 4, 2, 6, 2},    // 41 traced 8-wave small tiles
-    {64, 64, 64, 2, 4, 2, 0, 2},     // 42
-    {128, 128, 64, 2, 4, 2, 6, 2},   // 43
-    {64, 128, 64, 2, 4, 2, 6, 0},    // 44 the same, untraced
-    {64, 64, 64, 2, 4, 2, 0, 0},     // 45
-    {128, 128, 64, 2, 4, 2, 6, 0},   // 46 production: 8 waves, 64 KB — mid-size layers with >= 128 such tiles
-    {64, 64, 64, 2, 2, 2, 10, 2},    // 47 traced loads-only, buffer_load ... lds (vs 20)
-    {64, 64, 64, 2, 2, 4, 10, 2},    // 48 (vs 21)
-    {192, 256, 64, 2, 4, 2, 10, 2},  // 49 (vs 31)
-    {64, 64, 128, 2, 2, 2, 0, 0},    // 50 BK = 128: twice the work per ~1300-cycle K-step
-    {64, 128, 128, 2, 2, 2, 0, 0},   // 51
-    {128, 128, 128, 2, 4, 2, 0, 0},  // 52
-    {64, 64, 128, 2, 2, 2, 0, 2},    // 53 traced 50
-    {64, 128, 128, 2, 4, 2, 0, 0},   // 54 8 waves
-    {192, 256, 64, 2, 4, 2, 11, 0},  // 55 staggered DMA issue (vs 3): K-step 2700 -> 2430 cycles traced, no gain in-step
-    {192, 256, 64, 2, 4, 2, 11, 2},  // 56 traced
-    {128, 128, 64, 2, 4, 2, 11, 0},  // 57 (vs 46)
-    {256, 64, 64, 4, 2, 2, 6, 0},    // 58 tall tiles for Cout = 64 layers: the 8 KB weight tile shared by 256 pixels
-    {192, 64, 64, 2, 2, 2, 6, 0},    // 59
-    {128, 64, 64, 2, 2, 2, 6, 0},    // 60
-    {256, 64, 64, 4, 2, 3, 6, 0},    // 61
-    {128, 64, 64, 2, 2, 3, 6, 0},    // 62
-};
+// Tile configurations, one row per tile: X(id, BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, set).
+// LDS = KG * NSTAGE * (BM + BN) * BK * 2 bytes.  set P: production tile — the set choose_cfg picks from — built into
+// both libraries and for both element types (libtdn.so holds these, the TAG-1 twin of 3 and the stem's 128x64x32);
+// set T (alternates of the round-1/2 sweeps, timing-only ablation MODEs, TAG-2 cycle-stamp builds): bf16 only and
+// only in libtdn_trace.so (`make TRACE=1`, loaded by the scripts with TDN_LIB=libtdn_trace.so).  One source, one ISA.
+// kCfgs[] (the planner's and tdn_conv2d_plan's view) and the switches of dispatch_gemm (the instantiations) are both
+// generated from this list; the ids are the row numbers that scripts/, profiles/ and the tests use.
+// MODE 0: LDS-DMA of the next K-step right after the barrier, fragments read per sub-step; MODE 6: fragment reads
+// software-pipelined under the MFMAs; MODE 3/4/7/8: timing-only ablations (wrong results); TAG 2: cycle-stamp tracing
+// build (tdn_debug_trace, scripts/trace_gemm.py).
+#define TDN_GEMM_CFGS(X) \
+  X(0, 64, 64, 64, 2, 2, 2, 0, 0, 1, P)             /* 32 KB, 256 thr: Cout = 64 layers, tiny grids */                                    \
+  X(1, 64, 128, 64, 2, 2, 2, 6, 0, 1, P)            /* 48 KB, 256 thr: mid-size layers */                                                 \
+  X(2, 128, 128, 64, 2, 2, 2, 6, 0, 1, P)           /* 64 KB, 256 thr: large-M, Cout = 128 */                                             \
+  X(3, 192, 256, 64, 2, 4, 2, 6, 0, 1, P)           /* 112 KB, 512 thr: large-M, Cout % 256 == 0 (fewest L2->LDS bytes per flop) */       \
+  X(4, 64, 128, 64, 2, 2, 2, 0, 0, 1, T)            /* alternates kept for scripts/conv_bench.py sweeps */                                \
+  X(5, 64, 128, 64, 2, 2, 3, 0, 0, 1, T)                                                                                                  \
+  X(6, 64, 64, 64, 2, 2, 4, 0, 0, 1, T)                                                                                                   \
+  X(7, 128, 128, 64, 2, 2, 2, 0, 0, 1, T)                                                                                                 \
+  X(8, 128, 64, 64, 2, 2, 2, 0, 0, 1, T)                                                                                                  \
+  X(9, 64, 256, 64, 2, 2, 2, 0, 0, 1, T)                                                                                                  \
+  X(10, 128, 256, 64, 2, 4, 2, 0, 0, 1, T)                                                                                                \
+  X(11, 256, 128, 64, 4, 2, 3, 6, 0, 1, T)                                                                                                \
+  X(12, 192, 256, 64, 2, 4, 2, 3, 0, 1, T)          /* ablation: no loads in the K loop */                                                \
+  X(13, 192, 256, 64, 2, 4, 2, 4, 0, 1, T)          /* ablation: loads only */                                                            \
+  X(14, 192, 256, 64, 2, 4, 2, 7, 0, 1, T)          /* ablation: MFMA only */                                                             \
+  X(15, 192, 256, 64, 2, 4, 2, 8, 0, 1, T)          /* ablation: LDS fragment reads only */                                               \
+  X(16, 64, 64, 64, 2, 2, 2, 0, 2, 1, T)            /* trace builds of 0, 1, 6, 3 */                                                      \
+  X(17, 64, 128, 64, 2, 2, 2, 6, 2, 1, T)                                                                                                 \
+  X(18, 64, 64, 64, 2, 2, 4, 0, 2, 1, T)                                                                                                  \
+  X(19, 192, 256, 64, 2, 4, 2, 6, 2, 1, T)                                                                                                \
+  X(20, 64, 64, 64, 2, 2, 2, 4, 2, 1, T)            /* traced ablations of the small tile: loads only (2- and 4-deep ring) */             \
+  X(21, 64, 64, 64, 2, 2, 4, 4, 2, 1, T)                                                                                                  \
+  X(22, 64, 64, 64, 2, 2, 2, 3, 2, 1, T)            /* no loads in the K loop */                                                          \
+  X(23, 64, 64, 64, 2, 2, 4, 3, 2, 1, T)                                                                                                  \
+  X(24, 64, 64, 64, 2, 2, 2, 0, 0, 4, T)            /* in-workgroup split-K: 4 groups x 4 waves, 128 KB */                                \
+  X(25, 64, 64, 64, 2, 2, 2, 0, 0, 2, P)            /* 2 groups x 4 waves, 64 KB */                                                       \
+  X(26, 64, 128, 64, 2, 2, 2, 6, 0, 2, T)           /* 2 groups x 4 waves, 96 KB */                                                       \
+  X(27, 64, 128, 64, 2, 2, 2, 0, 0, 2, T)                                                                                                 \
+  X(28, 128, 128, 64, 2, 2, 2, 6, 0, 2, T)          /* 2 groups x 4 waves, 128 KB */                                                      \
+  X(29, 64, 64, 64, 2, 2, 2, 0, 2, 4, T)            /* trace build of 24 */                                                               \
+  X(30, 64, 64, 64, 2, 2, 2, 6, 0, 4, T)                                                                                                  \
+  X(31, 192, 256, 64, 2, 4, 2, 4, 2, 1, T)          /* traced loads-only: 8 waves */                                                      \
+  X(32, 256, 256, 64, 4, 4, 2, 4, 2, 1, T)          /* traced loads-only: 16 waves */                                                     \
+  X(33, 256, 256, 64, 4, 4, 2, 0, 2, 1, T)          /* traced full kernel, 16 waves, MODE 0 */                                            \
+  X(34, 256, 256, 64, 4, 4, 2, 6, 2, 1, T)          /* traced full kernel, 16 waves, MODE 6 */                                            \
+  X(35, 128, 256, 64, 2, 8, 2, 4, 2, 1, T)          /* traced loads-only: 16 waves, 96 KB */                                              \
+  X(36, 128, 256, 64, 2, 8, 2, 6, 2, 1, T)          /* traced full, 16 waves */                                                           \
+  X(37, 64, 64, 64, 2, 2, 2, 9, 2, 1, T)            /* traced loads-only through registers (vs 20: LDS-DMA) */                            \
+  X(38, 64, 128, 64, 2, 2, 2, 9, 2, 1, T)                                                                                                 \
+  X(39, 64, 128, 64, 2, 2, 2, 4, 2, 1, T)           /* traced loads-only LDS-DMA, 64x128 */                                               \
+  X(40, 192, 256, 64, 2, 4, 2, 9, 2, 1, T)          /* traced loads-only through registers, big tile (vs 31) */                           \
+  X(41, 64, 128, 64, 2, 4, 2, 6, 2, 1, T)           /* traced 8-wave small tiles */                                                       \
+  X(42, 64, 64, 64, 2, 4, 2, 0, 2, 1, T)                                                                                                  \
+  X(43, 128, 128, 64, 2, 4, 2, 6, 2, 1, T)                                                                                                \
+  X(44, 64, 128, 64, 2, 4, 2, 6, 0, 1, T)           /* the same, untraced */                                                              \
+  X(45, 64, 64, 64, 2, 4, 2, 0, 0, 1, T)                                                                                                  \
+  X(46, 128, 128, 64, 2, 4, 2, 6, 0, 1, P)          /* production: 8 waves, 64 KB — mid-size layers with >= 128 such tiles */             \
+  X(47, 64, 64, 64, 2, 2, 2, 10, 2, 1, T)           /* traced loads-only, buffer_load ... lds (vs 20) */                                  \
+  X(48, 64, 64, 64, 2, 2, 4, 10, 2, 1, T)           /* (vs 21) */                                                                         \
+  X(49, 192, 256, 64, 2, 4, 2, 10, 2, 1, T)         /* (vs 31) */                                                                         \
+  X(50, 64, 64, 128, 2, 2, 2, 0, 0, 1, P)           /* BK = 128: twice the work per ~1300-cycle K-step */                                 \
+  X(51, 64, 128, 128, 2, 2, 2, 0, 0, 1, T)                                                                                                \
+  X(52, 128, 128, 128, 2, 4, 2, 0, 0, 1, T)                                                                                               \
+  X(53, 64, 64, 128, 2, 2, 2, 0, 2, 1, T)           /* traced 50 */                                                                       \
+  X(54, 64, 128, 128, 2, 4, 2, 0, 0, 1, T)          /* 8 waves */                                                                         \
+  X(55, 192, 256, 64, 2, 4, 2, 11, 0, 1, T)         /* staggered DMA issue (vs 3): K-step 2700 -> 2430 cycles traced, no gain in-step */  \
+  X(56, 192, 256, 64, 2, 4, 2, 11, 2, 1, T)         /* traced */                                                                          \
+  X(57, 128, 128, 64, 2, 4, 2, 11, 0, 1, T)         /* (vs 46) */                                                                         \
+  X(58, 256, 64, 64, 4, 2, 2, 6, 0, 1, T)           /* tall tiles for Cout = 64 layers: the 8 KB weight tile shared by 256 pixels */      \
+  X(59, 192, 64, 64, 2, 2, 2, 6, 0, 1, T)                                                                                                 \
+  X(60, 128, 64, 64, 2, 2, 2, 6, 0, 1, T)                                                                                                 \
+  X(61, 256, 64, 64, 4, 2, 3, 6, 0, 1, T)                                                                                                 \
+  X(62, 128, 64, 64, 2, 2, 3, 6, 0, 1, T)           
+struct GemmCfg { int bm, bn, bk, wm, wn, nstage, mode, tag, kg; bool prod; };
+#define TDN_CFG_PROD_P true
+#define TDN_CFG_PROD_T false
+#define TDN_CFG_ROW(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg, set) {bm, bn, bk, wm, wn, nstage, mode, tag, kg, TDN_CFG_PROD_##set},
+static const GemmCfg kCfgs[] = {TDN_GEMM_CFGS(TDN_CFG_ROW)};
+#define TDN_CFG_ID(id, ...) id,
+static constexpr int kCfgIds[] = {TDN_GEMM_CFGS(TDN_CFG_ID)};
 static const int kNumCfgs = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
+constexpr bool cfg_ids_are_row_numbers() {
+  for (int i = 0; i < (int)(sizeof(kCfgIds) / sizeof(kCfgIds[0])); ++i)
+    if (kCfgIds[i] != i) return false;
+  return true;
+}
+static_assert(cfg_ids_are_row_numbers(), "TDN_GEMM_CFGS: the id column must count 0, 1, 2, ...");
+#ifdef TDN_TRACE_BUILD
+static const bool kTraceBuild = true;
+#else
+static const bool kTraceBuild = false;
+#endif
+
+// a forced generic tile (tests, sweeps) is in effect: it also keeps the conv away from the halo kernel.  An empty
+// value counts and reads as config 0.
+static bool gemm_cfg_forced() { return tdn_knob_present("TDN_GEMM_CFG") != nullptr; }
 
 static int choose_cfg(int maxM, int ngemm, int kgemm, int grouped = 0, int ktap = 64) {
   if (grouped) return 0;   // block-diagonal grouped conv: one 64-channel block per N tile
-  if (const char* env = getenv("TDN_GEMM_CFG")) {
-    const int id = atoi(env);
-#ifdef TDN_TRACE_BUILD
-    const bool built = true;
-#else
-    const bool built = id == 0 || id == 1 || id == 2 || id == 3 || id == 25 || id == 46 || id == 50;   // production tiles
-#endif
-    if (id >= 0 && id < kNumCfgs && built && ngemm % kCfgs[id].bn == 0 && ktap % kCfgs[id].bk == 0) return id;
+  if (gemm_cfg_forced()) {
+    const int id = tdn_knob_int("TDN_GEMM_CFG", 0);
+    if (id >= 0 && id < kNumCfgs && (kTraceBuild || kCfgs[id].prod) && ngemm % kCfgs[id].bn == 0 &&
+        ktap % kCfgs[id].bk == 0)
+      return id;
   }
 #ifdef TDN_TRACE_BUILD
   // experiments (libtdn_trace.so): TDN_CFG_RULE="M:N:K:cfg,M:N:K:cfg,..." picks a configuration for exactly that GEMM
-  if (const char* rule = getenv("TDN_CFG_RULE")) {
+  if (const char* rule = tdn_knob_present("TDN_CFG_RULE")) {
     const char* q = rule;
     while (*q) {
       int m_ = 0, n_ = 0, k_ = 0, id = -1;
@@ -827,23 +838,25 @@ static int choose_cfg(int maxM, int ngemm, int kgemm, int grouped = 0, int ktap 
     }
   }
 #endif
+  // sweep-only overrides of the thresholds below; a set but empty value reads as 0
+  auto sweep = [](const char* name, int dflt) { return tdn_knob_present(name) ? tdn_knob_int(name, 0) : dflt; };
   // Measured on MI355X over the R50-FPN shapes (scripts/conv_bench.py; profiles/convbench_*.log): several small
   // co-resident workgroups per CU (64-pixel tiles, 2-deep ring, 32-48 KB LDS) beat one large deeply pipelined
   // workgroup on almost every shape; only the very large-M 3x3 convs prefer the 256x128 8-wave tile.
-  const int big_minm = getenv("TDN_T192_MINM") ? atoi(getenv("TDN_T192_MINM")) : 24000;
+  const int big_minm = sweep("TDN_T192_MINM", 24000);
   if (ngemm % 256 == 0 && maxM >= big_minm) return 3;   // 192x256, 8 waves: fewest L2->LDS bytes per flop
   // few tiles and a long K loop (layer4, the top FPN levels): every CU holds at most two 4-wave workgroups and the
   // LDS-DMA stream starves (~4 B/clk per loading wave) — recruit a second wave group along K (in-workgroup split-K).
   // Cutting K over several workgroups with an exchange through memory lost to the unsplit tiles on every such layer
   // (layer4 3x3: 28 us unsplit, 32 / 37 us XCD-local / agent scope): it multiplies the per-workgroup fixed cost.
-  const int kg_tiles = getenv("TDN_KG_TILES") ? atoi(getenv("TDN_KG_TILES")) : 512;
-  const int kg_kmin = getenv("TDN_KG_KMIN") ? atoi(getenv("TDN_KG_KMIN")) : 2048;
+  const int kg_tiles = sweep("TDN_KG_TILES", 512);
+  const int kg_kmin = sweep("TDN_KG_KMIN", 2048);
   if ((long)ceil_div(maxM, 64) * (ngemm / 64) <= kg_tiles && kgemm >= kg_kmin) return 25;
   // at most about one 64x64 tile per CU and a K loop of 16-31 steps (layer3's 1024 -> 256 convs and the dgrad of its
   // 256 -> 1024 ones, per image: 264 tiles): 128-deep K-steps halve the barriers of a workgroup that has its CU to
   // itself.  Whole-step A/B on one box, three interleaved pairs: +0.6-0.9 %; the same tile on the neighbouring shapes
   // (528 tiles, or K = 512, or K = 2048 where the K groups above already apply) is neutral to -0.7 %.
-  const int bk128_tiles = getenv("TDN_BK128_TILES") ? atoi(getenv("TDN_BK128_TILES")) : 300;
+  const int bk128_tiles = sweep("TDN_BK128_TILES", 300);
   // 1x1 convs only: with several taps a 128-deep chunk changes the (chunk outer, taps inner) summation order
   if (kgemm == ktap && (long)ceil_div(maxM, 64) * (ngemm / 64) <= bk128_tiles && kgemm >= 1024 && ktap % 128 == 0)
     return 50;
@@ -854,8 +867,8 @@ static int choose_cfg(int maxM, int ngemm, int kgemm, int grouped = 0, int ktap 
     // chain) the 132-tile layers of layer3 (M = 8400, N = 256) run faster as 528 64x64 workgroups: whole-step A/B on
     // one box, threshold 128 -> 396 img/s, 140..200 -> 402, 268 and up -> 395 and falling.  The thresholds are
     // overridable (TDN_T128_MIN, TDN_T64_MIN, TDN_KG_TILES, TDN_KG_KMIN, TDN_T192_MINM) for such sweeps.
-    const int t128_min = getenv("TDN_T128_MIN") ? atoi(getenv("TDN_T128_MIN")) : 200;
-    const int t64_min = getenv("TDN_T64_MIN") ? atoi(getenv("TDN_T64_MIN")) : 300;
+    const int t128_min = sweep("TDN_T128_MIN", 200);
+    const int t64_min = sweep("TDN_T64_MIN", 300);
     if ((long)ceil_div(maxM, 128) * (ngemm / 128) >= t128_min) return 46;
     const long t64 = (long)ceil_div(maxM, 64) * (ngemm / 128);
     return t64 >= t64_min ? 1 : 0;
@@ -881,19 +894,15 @@ static int launch_gemm(GemmParams& p, int maxM, hipStream_t stream) {
   const int ntiles = ceil_div(maxM, BM) * p.tiles_n;
   p.nwg_pad = (ntiles + 7) & ~7;
   constexpr size_t lds = (size_t)KG * NSTAGE * (BM + BN) * BK * 2;
-  static tdn_attr_once attr_once;
-  if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_kernel<BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, F16>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(%d B LDS) failed: %s", (int)lds, hipGetErrorString(e));
-    attr_once.mark();
-    if (getenv("TDN_DEBUG_OCC")) {
-      int nb = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &nb, (const void*)conv_gemm_kernel<BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, F16>, WM * WN * KG * 64, lds);
-      fprintf(stderr, "[tdn] conv_gemm<%d,%d,%d,%d,%d,%d,%d,%d,%d,%s>: %d B LDS, %d workgroups/CU\n", BM, BN, BK, WM,
-              WN, NSTAGE, MODE, TAG, KG, F16 ? "f16" : "bf16", (int)lds, nb);
-    }
+  const int first =
+      tdn_allow_lds<conv_gemm_kernel<BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, F16>>((int)lds, "conv_gemm");
+  if (first < 0) return first;
+  if (first && tdn_knob_present("TDN_DEBUG_OCC")) {
+    int nb = -1;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &nb, (const void*)conv_gemm_kernel<BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, F16>, WM * WN * KG * 64, lds);
+    fprintf(stderr, "[tdn] conv_gemm<%d,%d,%d,%d,%d,%d,%d,%d,%d,%s>: %d B LDS, %d workgroups/CU\n", BM, BN, BK, WM,
+            WN, NSTAGE, MODE, TAG, KG, F16 ? "f16" : "bf16", (int)lds, nb);
   }
   if (TAG == 2) {
     TDN_CHECK(g_trace_buf && (long long)p.nwg_pad * p.ncls * 256 <= g_trace_bytes,
@@ -906,140 +915,60 @@ static int launch_gemm(GemmParams& p, int maxM, hipStream_t stream) {
   return 0;
 }
 
+// Tile `ID` of TDN_GEMM_CFGS.
+template <int ID, int BM, int BN, int BK, int WM, int WN, int NSTAGE, int MODE, int TAG, int KG, bool F16>
+static int launch_cfg(GemmParams& p, int maxM, hipStream_t stream) {
+  if constexpr (ID == 3 && !F16) {
+    // TDN_TAG_DOMINANT (set by bench.py around exactly the launches it brackets with HIP events): same code under
+    // the TAG-1 symbol, so rocprofv3 --stats lists those launches on a line of their own
+    if (maxM >= 100000 && p.Cout == 256 && p.cls[0].ntaps * p.Ktap == 2304 && tdn_knob_present("TDN_TAG_DOMINANT"))
+      return launch_gemm<BM, BN, BK, WM, WN, NSTAGE, MODE, 1, KG, F16>(p, maxM, stream);
+  }
+  return launch_gemm<BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, F16>(p, maxM, stream);
+}
+
+// switch cases from TDN_GEMM_CFGS: set P rows (both element types, both libraries), then set T rows (bf16, and only
+// in the trace build: alternates, ablations and cycle-stamp builds).  P before T keeps the kernels in the order the
+// compiler has always emitted them, so the code object can be compared with an older build section by section.
+#define TDN_CFG_IF_P_P(...) __VA_ARGS__
+#define TDN_CFG_IF_P_T(...)
+#define TDN_CFG_IF_T_P(...)
+#ifdef TDN_TRACE_BUILD
+#define TDN_CFG_IF_T_T(...) __VA_ARGS__
+#else
+#define TDN_CFG_IF_T_T(...)
+#endif
+#define TDN_CFG_CASE(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg) \
+  case id: return launch_cfg<id, bm, bn, bk, wm, wn, nstage, mode, tag, kg, F16>(p, maxM, stream);
+#define TDN_CFG_CASE_P(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg, set) \
+  TDN_CFG_IF_P_##set(TDN_CFG_CASE(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg))
+#define TDN_CFG_CASE_T(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg, set) \
+  TDN_CFG_IF_T_##set(TDN_CFG_CASE(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg))
+
 static int dispatch_gemm(GemmParams& p, int maxM, hipStream_t stream, int dtype) {
   if (maxM <= 0) return 0;
+  const int id = choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap);
   if (dtype == TDN_F16) {   // fp16 operands: the production tile set only
-    const int id = choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap);
+    constexpr bool F16 = true;
     switch (id) {
-      case 0: return launch_gemm<64, 64, 64, 2, 2, 2, 0, 0, 1, true>(p, maxM, stream);
-      case 1: return launch_gemm<64, 128, 64, 2, 2, 2, 6, 0, 1, true>(p, maxM, stream);
-      case 2: return launch_gemm<128, 128, 64, 2, 2, 2, 6, 0, 1, true>(p, maxM, stream);
-      case 3: return launch_gemm<192, 256, 64, 2, 4, 2, 6, 0, 1, true>(p, maxM, stream);
-      case 25: return launch_gemm<64, 64, 64, 2, 2, 2, 0, 0, 2, true>(p, maxM, stream);
-      case 46: return launch_gemm<128, 128, 64, 2, 4, 2, 6, 0, 1, true>(p, maxM, stream);
-      case 50: return launch_gemm<64, 64, 128, 2, 2, 2, 0, 0, 1, true>(p, maxM, stream);
+      TDN_GEMM_CFGS(TDN_CFG_CASE_P)
       default: TDN_CHECK(false, "GEMM config %d (TDN_GEMM_CFG) has no TDN_F16 build", id); return -1;
     }
   }
-  switch (choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap)) {
-    case 0: return launch_gemm<64, 64, 64, 2, 2, 2, 0>(p, maxM, stream);
-    case 1: return launch_gemm<64, 128, 64, 2, 2, 2, 6>(p, maxM, stream);
-    case 2: return launch_gemm<128, 128, 64, 2, 2, 2, 6>(p, maxM, stream);
-    case 3:
-      // TDN_TAG_DOMINANT (set by bench.py around exactly the launches it brackets with HIP events): same code under
-      // the TAG-1 symbol, so rocprofv3 --stats lists those launches on a line of their own
-      if (maxM >= 100000 && p.Cout == 256 && p.cls[0].ntaps * p.Ktap == 2304 && getenv("TDN_TAG_DOMINANT"))
-        return launch_gemm<192, 256, 64, 2, 4, 2, 6, 1>(p, maxM, stream);
-      return launch_gemm<192, 256, 64, 2, 4, 2, 6>(p, maxM, stream);
-    case 25: return launch_gemm<64, 64, 64, 2, 2, 2, 0, 0, 2>(p, maxM, stream);
-    case 46: return launch_gemm<128, 128, 64, 2, 4, 2, 6, 0>(p, maxM, stream);
-    case 50: return launch_gemm<64, 64, 128, 2, 2, 2, 0, 0>(p, maxM, stream);
-#ifdef TDN_TRACE_BUILD   // alternates, ablations and cycle-stamp builds: libtdn_trace.so only (make TRACE=1)
-    case 4: return launch_gemm<64, 128, 64, 2, 2, 2, 0>(p, maxM, stream);
-    case 5: return launch_gemm<64, 128, 64, 2, 2, 3, 0>(p, maxM, stream);
-    case 6: return launch_gemm<64, 64, 64, 2, 2, 4, 0>(p, maxM, stream);
-    case 7: return launch_gemm<128, 128, 64, 2, 2, 2, 0>(p, maxM, stream);
-    case 8: return launch_gemm<128, 64, 64, 2, 2, 2, 0>(p, maxM, stream);
-    case 9: return launch_gemm<64, 256, 64, 2, 2, 2, 0>(p, maxM, stream);
-    case 10: return launch_gemm<128, 256, 64, 2, 4, 2, 0>(p, maxM, stream);
-    case 11: return launch_gemm<256, 128, 64, 4, 2, 3, 6>(p, maxM, stream);
-    case 12: return launch_gemm<192, 256, 64, 2, 4, 2, 3>(p, maxM, stream);
-    case 13: return launch_gemm<192, 256, 64, 2, 4, 2, 4>(p, maxM, stream);
-    case 14: return launch_gemm<192, 256, 64, 2, 4, 2, 7>(p, maxM, stream);
-    case 15: return launch_gemm<192, 256, 64, 2, 4, 2, 8>(p, maxM, stream);
-    case 16: return launch_gemm<64, 64, 64, 2, 2, 2, 0, 2>(p, maxM, stream);
-    case 17: return launch_gemm<64, 128, 64, 2, 2, 2, 6, 2>(p, maxM, stream);
-    case 18: return launch_gemm<64, 64, 64, 2, 2, 4, 0, 2>(p, maxM, stream);
-    case 19: return launch_gemm<192, 256, 64, 2, 4, 2, 6, 2>(p, maxM, stream);
-    case 20: return launch_gemm<64, 64, 64, 2, 2, 2, 4, 2>(p, maxM, stream);
-    case 21: return launch_gemm<64, 64, 64, 2, 2, 4, 4, 2>(p, maxM, stream);
-    case 22: return launch_gemm<64, 64, 64, 2, 2, 2, 3, 2>(p, maxM, stream);
-    case 23: return launch_gemm<64, 64, 64, 2, 2, 4, 3, 2>(p, maxM, stream);
-    case 24: return launch_gemm<64, 64, 64, 2, 2, 2, 0, 0, 4>(p, maxM, stream);
-    case 26: return launch_gemm<64, 128, 64, 2, 2, 2, 6, 0, 2>(p, maxM, stream);
-    case 27: return launch_gemm<64, 128, 64, 2, 2, 2, 0, 0, 2>(p, maxM, stream);
-    case 28: return launch_gemm<128, 128, 64, 2, 2, 2, 6, 0, 2>(p, maxM, stream);
-    case 29: return launch_gemm<64, 64, 64, 2, 2, 2, 0, 2, 4>(p, maxM, stream);
-    case 30: return launch_gemm<64, 64, 64, 2, 2, 2, 6, 0, 4>(p, maxM, stream);
-    case 31: return launch_gemm<192, 256, 64, 2, 4, 2, 4, 2>(p, maxM, stream);
-    case 32: return launch_gemm<256, 256, 64, 4, 4, 2, 4, 2>(p, maxM, stream);
-    case 33: return launch_gemm<256, 256, 64, 4, 4, 2, 0, 2>(p, maxM, stream);
-    case 34: return launch_gemm<256, 256, 64, 4, 4, 2, 6, 2>(p, maxM, stream);
-    case 35: return launch_gemm<128, 256, 64, 2, 8, 2, 4, 2>(p, maxM, stream);
-    case 36: return launch_gemm<128, 256, 64, 2, 8, 2, 6, 2>(p, maxM, stream);
-    case 37: return launch_gemm<64, 64, 64, 2, 2, 2, 9, 2>(p, maxM, stream);
-    case 38: return launch_gemm<64, 128, 64, 2, 2, 2, 9, 2>(p, maxM, stream);
-    case 39: return launch_gemm<64, 128, 64, 2, 2, 2, 4, 2>(p, maxM, stream);
-    case 40: return launch_gemm<192, 256, 64, 2, 4, 2, 9, 2>(p, maxM, stream);
-    case 41: return launch_gemm<64, 128, 64, 2, 4, 2, 6, 2>(p, maxM, stream);
-    case 42: return launch_gemm<64, 64, 64, 2, 4, 2, 0, 2>(p, maxM, stream);
-    case 43: return launch_gemm<128, 128, 64, 2, 4, 2, 6, 2>(p, maxM, stream);
-    case 44: return launch_gemm<64, 128, 64, 2, 4, 2, 6, 0>(p, maxM, stream);
-    case 45: return launch_gemm<64, 64, 64, 2, 4, 2, 0, 0>(p, maxM, stream);
-    case 47: return launch_gemm<64, 64, 64, 2, 2, 2, 10, 2>(p, maxM, stream);
-    case 48: return launch_gemm<64, 64, 64, 2, 2, 4, 10, 2>(p, maxM, stream);
-    case 49: return launch_gemm<192, 256, 64, 2, 4, 2, 10, 2>(p, maxM, stream);
-    case 51: return launch_gemm<64, 128, 128, 2, 2, 2, 0, 0>(p, maxM, stream);
-    case 52: return launch_gemm<128, 128, 128, 2, 4, 2, 0, 0>(p, maxM, stream);
-    case 53: return launch_gemm<64, 64, 128, 2, 2, 2, 0, 2>(p, maxM, stream);
-    case 54: return launch_gemm<64, 128, 128, 2, 4, 2, 0, 0>(p, maxM, stream);
-    case 55: return launch_gemm<192, 256, 64, 2, 4, 2, 11, 0>(p, maxM, stream);
-    case 56: return launch_gemm<192, 256, 64, 2, 4, 2, 11, 2>(p, maxM, stream);
-    case 57: return launch_gemm<128, 128, 64, 2, 4, 2, 11, 0>(p, maxM, stream);
-    case 58: return launch_gemm<256, 64, 64, 4, 2, 2, 6, 0>(p, maxM, stream);
-    case 59: return launch_gemm<192, 64, 64, 2, 2, 2, 6, 0>(p, maxM, stream);
-    case 60: return launch_gemm<128, 64, 64, 2, 2, 2, 6, 0>(p, maxM, stream);
-    case 61: return launch_gemm<256, 64, 64, 4, 2, 3, 6, 0>(p, maxM, stream);
-    case 62: return launch_gemm<128, 64, 64, 2, 2, 3, 6, 0>(p, maxM, stream);
-#endif
+  constexpr bool F16 = false;
+  switch (id) {
+    TDN_GEMM_CFGS(TDN_CFG_CASE_P)
+    TDN_GEMM_CFGS(TDN_CFG_CASE_T)
     default: TDN_CHECK(false, "bad GEMM config id"); return -1;
   }
 }
 
-static int fill_epilogue(GemmParams& p, const tdn_epilogue* ep, int Hout, int Wout) {
-  p.scale = nullptr; p.shift = nullptr; p.addend = nullptr; p.mask = nullptr;
-  p.addend_mode = TDN_ADD_NONE; p.addend_h = 0; p.addend_w = 0; p.relu = 0; p.out_f32 = 0;
-  if (!ep) return 0;
-  p.out_f32 = ep->out_f32 ? 1 : 0;
-  p.scale = ep->scale;
-  p.shift = ep->shift;
-  p.relu = ep->relu;
-  p.mask = (const bf16_t*)ep->mask_src;
-  if (ep->addend_mode != TDN_ADD_NONE) {
-    TDN_CHECK(ep->addend != nullptr, "epilogue: addend_mode %d with NULL addend", ep->addend_mode);
-    p.addend = (const bf16_t*)ep->addend;
-    p.addend_mode = ep->addend_mode;
-    p.addend_h = ep->addend_h;
-    p.addend_w = ep->addend_w;
-    if (ep->addend_mode == TDN_ADD_UP2X)
-      TDN_CHECK(ep->addend_h * 2 == Hout && ep->addend_w * 2 == Wout,
-                "epilogue UP2X: addend %dx%d is not half of output %dx%d", ep->addend_h, ep->addend_w, Hout, Wout);
-    if (ep->addend_mode == TDN_ADD_SUMPOOL2)
-      TDN_CHECK(ep->addend_h == Hout * 2 && ep->addend_w == Wout * 2,
-                "epilogue SUMPOOL2: addend %dx%d is not twice the output %dx%d", ep->addend_h, ep->addend_w, Hout, Wout);
-    TDN_CHECK(ep->addend_mode >= 0 && ep->addend_mode <= 3, "epilogue: bad addend_mode %d", ep->addend_mode);
-  }
-  return 0;
-}
-
 static int check_conv_shape(int N, int H, int W, int Cin, int Cout, int k, int stride, int pad, int dtype) {
-  TDN_CHECK(dtype == TDN_BF16 || dtype == TDN_F16, "dtype %d is neither TDN_BF16 nor TDN_F16", dtype);
+  TDN_CHECK_DTYPE(dtype);
   TDN_CHECK(N > 0 && H > 0 && W > 0, "bad tensor shape N=%d H=%d W=%d", N, H, W);
-  TDN_CHECK(k == 1 || k == 3, "kernel size %d not supported (1 or 3)", k);
-  TDN_CHECK(stride == 1 || stride == 2, "stride %d not supported (1 or 2)", stride);
-  // "same" convolutions only.  For k = 3 the padding IS the dilation, exactly as conv3x3_group builds them
-  // (padding = dilation, models/utils/layers.py:20-32): pad = d means taps at (-d, 0, +d)
-  TDN_CHECK((k == 1 && pad == 0) || (k == 3 && pad >= 1 && pad <= 32),
-            "pad %d not supported for k=%d (1x1: 0; 3x3: pad = dilation in 1..32)", pad, k);
-  TDN_CHECK(Cin % 64 == 0 && Cout % 64 == 0, "channels must be multiples of 64 (Cin=%d Cout=%d)", Cin, Cout);
+  if (conv_check_rules(k, stride, pad, Cin, Cout)) return -1;
   TDN_CHECK((int64_t)N * H * W < (1ll << 31) / 4, "tensor too large for 32-bit pixel indexing");
   return 0;
-}
-
-// dilation of a "same" conv (see check_conv_shape) and its output size
-static inline int conv_dil(int k, int pad) { return k == 3 ? pad : 1; }
-static inline int conv_out_sz(int H, int k, int stride, int pad) {
-  return (H + 2 * pad - (conv_dil(k, pad) * (k - 1) + 1)) / stride + 1;
 }
 
 static void build_fwd(GemmParams& p, int N, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
@@ -1093,8 +1022,8 @@ extern "C" int tdn_conv2d_fwd(const void* x, const void* w_fwd, void* y, int N, 
   GemmParams p;
   build_fwd(p, N, H, W, Cin, Cout, k, stride, pad);
   p.in = (const bf16_t*)x; p.wt = (const bf16_t*)w_fwd; p.out = (bf16_t*)y;
-  if (fill_epilogue(p, ep, p.Hout, p.Wout)) return -1;
-  if (!getenv("TDN_GEMM_CFG")) {   // a forced generic tile (tests, sweeps) keeps the generic kernel
+  if (conv_fill_epilogue(p, ep, p.Hout, p.Wout)) return -1;
+  if (!gemm_cfg_forced()) {
     const int h = tdn_halo_conv_fwd(x, w_fwd, y, N, H, W, Cin, Cout, k, stride, pad, ep, dtype, (hipStream_t)stream);
     if (h != 0) return h < 0 ? h : 0;
   }
@@ -1109,8 +1038,8 @@ extern "C" int tdn_conv2d_dgrad(const void* g, const void* w_dgrad, void* dx, in
   GemmParams p;
   const int maxM = build_dgrad(p, N, H, W, Cin, Cout, k, stride, pad);
   p.in = (const bf16_t*)g; p.wt = (const bf16_t*)w_dgrad; p.out = (bf16_t*)dx;
-  if (fill_epilogue(p, ep, p.Hout, p.Wout)) return -1;
-  if (!getenv("TDN_GEMM_CFG")) {
+  if (conv_fill_epilogue(p, ep, p.Hout, p.Wout)) return -1;
+  if (!gemm_cfg_forced()) {
     const int h = tdn_halo_conv_dgrad(g, w_dgrad, dx, N, H, W, Cin, Cout, k, stride, pad, ep, dtype,
                                       (hipStream_t)stream);
     if (h != 0) return h < 0 ? h : 0;
@@ -1137,7 +1066,7 @@ extern "C" int tdn_gconv2d_fwd(const void* x, const void* w_fwd, void* y, int N,
   build_fwd(p, N, H, W, C, C, k, stride, pad);
   p.grouped = 1; p.Ktap = 64; p.wt_row = k * k * 64;
   p.in = (const bf16_t*)x; p.wt = (const bf16_t*)w_fwd; p.out = (bf16_t*)y;
-  if (fill_epilogue(p, ep, p.Hout, p.Wout)) return -1;
+  if (conv_fill_epilogue(p, ep, p.Hout, p.Wout)) return -1;
   return dispatch_gemm(p, p.cls[0].M, (hipStream_t)stream, dtype);
 }
 
@@ -1149,7 +1078,7 @@ extern "C" int tdn_gconv2d_dgrad(const void* g, const void* w_dgrad, void* dx, i
   const int maxM = build_dgrad(p, N, H, W, C, C, k, stride, pad);
   p.grouped = 1; p.Ktap = 64; p.wt_row = k * k * 64;
   p.in = (const bf16_t*)g; p.wt = (const bf16_t*)w_dgrad; p.out = (bf16_t*)dx;
-  if (fill_epilogue(p, ep, p.Hout, p.Wout)) return -1;
+  if (conv_fill_epilogue(p, ep, p.Hout, p.Wout)) return -1;
   return dispatch_gemm(p, maxM, (hipStream_t)stream, dtype);
 }
 
@@ -1157,7 +1086,7 @@ extern "C" int tdn_gconv2d_dgrad(const void* g, const void* w_dgrad, void* dx, i
 // row kh: 8 consecutive pixels x 4 channels = 32 contiguous bf16 (kw = 7 and c = 3 carry zero weights).
 extern "C" int tdn_stem_conv_fwd(const void* xp, const void* w_stem, void* y, int N, int H, int W, int Cout,
                                  const tdn_epilogue* ep, int dtype, void* stream) {
-  TDN_CHECK(dtype == TDN_BF16 || dtype == TDN_F16, "dtype %d is neither TDN_BF16 nor TDN_F16", dtype);
+  TDN_CHECK_DTYPE(dtype);
   TDN_CHECK(xp && w_stem && y, "tdn_stem_conv_fwd: NULL tensor pointer");
   TDN_CHECK(H % 2 == 0 && W % 2 == 0 && H > 0 && W > 0 && N > 0, "stem needs even H, W (got %dx%d)", H, W);
   TDN_CHECK(Cout % 64 == 0, "stem Cout must be a multiple of 64");
@@ -1170,7 +1099,7 @@ extern "C" int tdn_stem_conv_fwd(const void* xp, const void* w_stem, void* y, in
   for (int kh = 0; kh < 7; ++kh) c.taps[kh] = pack_tap(kh, 0, kh);
   class_divisors(c);
   p.in = (const bf16_t*)xp; p.wt = (const bf16_t*)w_stem; p.out = (bf16_t*)y;
-  if (fill_epilogue(p, ep, Ho, Wo)) return -1;
+  if (conv_fill_epilogue(p, ep, Ho, Wo)) return -1;
   if (dtype == TDN_F16) return launch_gemm<128, 64, 32, 2, 2, 3, 0, 0, 1, true>(p, c.M, (hipStream_t)stream);
   return launch_gemm<128, 64, 32, 2, 2, 3>(p, c.M, (hipStream_t)stream);
 }
@@ -1196,6 +1125,6 @@ extern "C" int tdn_conv2d_plan(int kind, int N, int H, int W, int Cin, int Cout,
   o[0] = Mtot; o[1] = p.Cout; o[2] = p.cls[0].ntaps * p.Ktap; o[3] = t.bm; o[4] = t.bn; o[5] = t.bk;
   o[6] = (ceil_div(maxM, t.bm) * (p.Cout / t.bn) + 7) & ~7; o[7] = p.ncls; o[8] = 1; o[9] = p.ncls;
   o[10] = p.cls[0].ntaps; o[11] = 1; o[12] = taps_tot; o[13] = p.Hout; o[14] = p.Wout; o[15] = maxM;
-  if (!getenv("TDN_GEMM_CFG")) (void)tdn_halo_plan(kind, N, H, W, Cin, Cout, k, stride, pad, o);   // o[8] >= 100: halo kernel
+  if (!gemm_cfg_forced()) (void)tdn_halo_plan(kind, N, H, W, Cin, Cout, k, stride, pad, o);   // o[8] >= 100: halo kernel
   return 0;
 }

@@ -17,7 +17,7 @@
 // work list of one launch spans all members (descriptors travel in the kernel-argument block), members whose
 // reduction fits one workgroup per tile write their gradient directly, and the remaining slabs, the BN gamma / beta
 // and bias gradients of EVERY member are reduced by one finalize launch, in a fixed order (deterministic).
-#include "common.h"
+#include "conv_host.h"
 #include <limits.h>
 #include <string.h>
 #include <type_traits>
@@ -818,34 +818,26 @@ __global__ __launch_bounds__(256) void wgrad_finalize_group_kernel(const FinGrou
 // ---------------------------------------------------------------------------------------------
 // host side: geometry, plan, launches
 // ---------------------------------------------------------------------------------------------
-// "same" convs: for k = 3 the padding is the dilation (conv3x3_group: padding = dilation, layers.py:20-32)
-static int conv_dil(int k, int pad) { return k == 3 ? pad : 1; }
-static int conv_out(int H, int k, int stride, int pad) {
-  return (H + 2 * pad - (conv_dil(k, pad) * (k - 1) + 1)) / stride + 1;
-}
-
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && *e) ? atoi(e) : dflt;
-}
-
 // Tile shapes of the tap-per-tile kernel: {co, ci, wave rows, wave cols, ring depth} and, for the planner's cost
 // model, the workgroups of that shape a CU holds (LDS: NST * 64 * (co + ci) * 2 bytes of 160 KB; 32 waves) and the
 // cycles one 64-pixel K-step takes with the CU that full.  The kernel is bound by its LDS-DMA stream, and a CU moves
 // ~16 / 30 / 36 / 41 B/clk with 4 / 8 / 12 / >= 16 loading waves (scripts/trace_gemm.py), shared by its
 // workgroups.
+// One row per shape: X(id, co, ci, wave rows, wave cols, ring depth, per_cu, step_clk); kTapShapes[] (the planner's view)
+// and the switch of launch_tap (the instantiations) are generated from this list.
+#define TDN_TAP_SHAPES(X) \
+  X(0, 64, 32, 2, 2, 2, 6, 1800)    /* stem (Ktap = 32) */  \
+  X(1, 64, 64, 2, 2, 2, 5, 2000)                            \
+  X(2, 64, 64, 2, 2, 3, 3, 1365)                            \
+  X(3, 128, 64, 2, 2, 2, 3, 2050)                           \
+  X(4, 128, 64, 2, 2, 3, 2, 1640)                           \
+  X(5, 256, 64, 4, 2, 2, 2, 2000)                           \
+  X(6, 256, 64, 4, 2, 3, 1, 1460)                           \
+  X(7, 128, 128, 2, 2, 2, 2, 2180)                          \
+  X(8, 256, 128, 4, 2, 2, 1, 1750)
 struct TapShape { int bmw, bnw, wm, wn, nst, per_cu, step_clk; };
-static const TapShape kTapShapes[] = {
-    {64, 32, 2, 2, 2, 6, 1800},     // 0  stem (Ktap = 32)
-    {64, 64, 2, 2, 2, 5, 2000},     // 1
-    {64, 64, 2, 2, 3, 3, 1365},     // 2
-    {128, 64, 2, 2, 2, 3, 2050},    // 3
-    {128, 64, 2, 2, 3, 2, 1640},    // 4
-    {256, 64, 4, 2, 2, 2, 2000},    // 5
-    {256, 64, 4, 2, 3, 1, 1460},    // 6
-    {128, 128, 2, 2, 2, 2, 2180},   // 7
-    {256, 128, 4, 2, 2, 1, 1750},   // 8
-};
+#define TDN_TAP_ROW(id, bmw, bnw, wm, wn, nst, per_cu, step_clk) {bmw, bnw, wm, wn, nst, per_cu, step_clk},
+static const TapShape kTapShapes[] = {TDN_TAP_SHAPES(TDN_TAP_ROW)};
 static const int kNumTapShapes = (int)(sizeof(kTapShapes) / sizeof(kTapShapes[0]));
 static const int kT9StepClk = 2600;   // nine-tap kernel: 72 MFMAs per wave and K-step, one 8-wave workgroup per CU
 
@@ -874,13 +866,9 @@ static int item_geometry(const tdn_wgrad_item& it, ItemPlan& g) {
   } else {
     TDN_CHECK(it.kind == TDN_WGRAD_CONV || it.kind == TDN_WGRAD_GCONV, "wgrad item: bad kind %d", it.kind);
     const int k = it.k, stride = it.stride, pad = it.pad;
-    TDN_CHECK(k == 1 || k == 3, "kernel size %d not supported", k);
-    TDN_CHECK(stride == 1 || stride == 2, "stride %d not supported", stride);
-    TDN_CHECK((k == 1 && pad == 0) || (k == 3 && pad >= 1 && pad <= 32), "pad %d not supported for k=%d", pad, k);
-    TDN_CHECK(it.Cin % 64 == 0 && it.Cout % 64 == 0, "channels must be multiples of 64 (Cin=%d Cout=%d)", it.Cin,
-              it.Cout);
+    if (conv_check_rules(k, stride, pad, it.Cin, it.Cout)) return -1;
     g.Hin = it.H; g.Win = it.W; g.Cpix = it.Cin; g.Ktap = it.Cin;
-    g.Ho = conv_out(it.H, k, stride, pad); g.Wo = conv_out(it.W, k, stride, pad);
+    g.Ho = conv_out_sz(it.H, k, stride, pad); g.Wo = conv_out_sz(it.W, k, stride, pad);
     g.Cout = it.Cout; g.sa = stride; g.ntaps = k * k;
     g.tapgen = k | (pad << 8) | (conv_dil(k, pad) << 16);
     g.map_mode = 0;
@@ -975,14 +963,14 @@ static double model_group(const std::vector<ItemPlan>& plans, const std::vector<
 static int plan_group(const tdn_wgrad_item* items, int n, std::vector<ItemPlan>& plans, int64_t* ws_floats) {
   TDN_CHECK(items != nullptr && n > 0, "wgrad group: no items");
   plans.resize(n);
-  const int t9_mode = env_int("TDN_WGRAD9", 1);   // 0: never use the nine-tap kernel
-  const int t9_64 = env_int("TDN_WGRAD9_64", 1);
-  const int shape_env = env_int("TDN_WGRAD_SHAPE", -1);   // force kTapShapes[id] where it divides the member
-  const int s256 = env_int("TDN_WGRAD_S256", 8), s128 = env_int("TDN_WGRAD_S128", 4), s64 = env_int("TDN_WGRAD_S64", 2);
-  const int s256f = env_int("TDN_WGRAD_S256F", 5);   // 256-channel members whose Cin does not divide the s256 tile
-  const int uniform = env_int("TDN_WGRAD_UNIFORM", 0);   // 1: one tile shape per group (fewest launches)
-  const int tmin_tap = env_int("TDN_WGRAD_TMIN", 24), tmin_t9 = env_int("TDN_WGRAD9_TMIN", 32);
-  const int direct_ok = env_int("TDN_WGRAD_DIRECT", 1);
+  const int t9_mode = tdn_knob_int("TDN_WGRAD9", 1);   // 0: never use the nine-tap kernel
+  const int t9_64 = tdn_knob_int("TDN_WGRAD9_64", 1);
+  const int shape_env = tdn_knob_int("TDN_WGRAD_SHAPE", -1);   // force kTapShapes[id] where it divides the member
+  const int s256 = tdn_knob_int("TDN_WGRAD_S256", 8), s128 = tdn_knob_int("TDN_WGRAD_S128", 4), s64 = tdn_knob_int("TDN_WGRAD_S64", 2);
+  const int s256f = tdn_knob_int("TDN_WGRAD_S256F", 5);   // 256-channel members whose Cin does not divide the s256 tile
+  const int uniform = tdn_knob_int("TDN_WGRAD_UNIFORM", 0);   // 1: one tile shape per group (fewest launches)
+  const int tmin_tap = tdn_knob_int("TDN_WGRAD_TMIN", 24), tmin_t9 = tdn_knob_int("TDN_WGRAD9_TMIN", 32);
+  const int direct_ok = tdn_knob_int("TDN_WGRAD_DIRECT", 1);
   int min_bmw = 256;
   for (int i = 0; i < n; ++i) {
     ItemPlan& g = plans[i];
@@ -1028,8 +1016,8 @@ static int plan_group(const tdn_wgrad_item* items, int n, std::vector<ItemPlan>&
   }
   std::vector<std::vector<int>> lists;
   launch_lists(plans, lists);
-  const double dmin = env_int("TDN_WGRAD_DMIN", 40000), dmax = env_int("TDN_WGRAD_DMAX", 400000);
-  const int fixed_t = env_int("TDN_WGRAD_T", 0);   // sweeps: the same K-steps per split for every member
+  const double dmin = tdn_knob_int("TDN_WGRAD_DMIN", 40000), dmax = tdn_knob_int("TDN_WGRAD_DMAX", 400000);
+  const int fixed_t = tdn_knob_int("TDN_WGRAD_T", 0);   // sweeps: the same K-steps per split for every member
   // the search below costs ~a millisecond per group: its result (D) is remembered per (member shapes, knobs)
   uint64_t key = 1469598103934665603ull;
   auto mix = [&key](int64_t v) { key = (key ^ (uint64_t)v) * 1099511628211ull; };
@@ -1084,13 +1072,7 @@ static int plan_group(const tdn_wgrad_item* items, int n, std::vector<ItemPlan>&
 template <int BMW, int BNW, int WM, int WN, int NST, bool F16>
 static int launch_tap_t(const WgGroup& grp, int nblocks, hipStream_t stream) {
   constexpr size_t lds = (size_t)NST * 64 * (BMW + BNW) * 2;
-  static tdn_attr_once attr_once;
-  if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wgrad_group_kernel<BMW, BNW, WM, WN, NST, F16>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(%d B LDS) failed: %s", (int)lds, hipGetErrorString(e));
-    attr_once.mark();
-  }
+  if (tdn_allow_lds<conv_wgrad_group_kernel<BMW, BNW, WM, WN, NST, F16>>((int)lds, "conv_wgrad_group") < 0) return -1;
   TDN_LAUNCH((conv_wgrad_group_kernel<BMW, BNW, WM, WN, NST, F16>), dim3(nblocks), dim3(WM * WN * 64), lds,
                      stream, grp);
   TDN_LAUNCH_CHECK();
@@ -1099,16 +1081,10 @@ static int launch_tap_t(const WgGroup& grp, int nblocks, hipStream_t stream) {
 
 template <bool F16>
 static int launch_tap(int shape, const WgGroup& grp, int nblocks, hipStream_t stream) {
+#define TDN_TAP_CASE(id, bmw, bnw, wm, wn, nst, per_cu, step_clk) \
+  case id: return launch_tap_t<bmw, bnw, wm, wn, nst, F16>(grp, nblocks, stream);
   switch (shape) {
-    case 0: return launch_tap_t<64, 32, 2, 2, 2, F16>(grp, nblocks, stream);
-    case 1: return launch_tap_t<64, 64, 2, 2, 2, F16>(grp, nblocks, stream);
-    case 2: return launch_tap_t<64, 64, 2, 2, 3, F16>(grp, nblocks, stream);
-    case 3: return launch_tap_t<128, 64, 2, 2, 2, F16>(grp, nblocks, stream);
-    case 4: return launch_tap_t<128, 64, 2, 2, 3, F16>(grp, nblocks, stream);
-    case 5: return launch_tap_t<256, 64, 4, 2, 2, F16>(grp, nblocks, stream);
-    case 6: return launch_tap_t<256, 64, 4, 2, 3, F16>(grp, nblocks, stream);
-    case 7: return launch_tap_t<128, 128, 2, 2, 2, F16>(grp, nblocks, stream);
-    case 8: return launch_tap_t<256, 128, 4, 2, 2, F16>(grp, nblocks, stream);
+    TDN_TAP_SHAPES(TDN_TAP_CASE)
     default: tdn_set_error("wgrad: bad tile shape id %d", shape); return -1;
   }
 }
@@ -1116,13 +1092,7 @@ static int launch_tap(int shape, const WgGroup& grp, int nblocks, hipStream_t st
 template <bool F16, int WMR>
 static int launch_t9(const WgGroup& grp, int nblocks, hipStream_t stream) {
   constexpr size_t lds = 2 * (size_t)(64 * (64 * WMR) + 3 * 72 * 128);
-  static tdn_attr_once attr_once;
-  if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wgrad9_group_kernel<F16, WMR>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(%d B LDS) failed: %s", (int)lds, hipGetErrorString(e));
-    attr_once.mark();
-  }
+  if (tdn_allow_lds<conv_wgrad9_group_kernel<F16, WMR>>((int)lds, "conv_wgrad9_group") < 0) return -1;
   TDN_LAUNCH((conv_wgrad9_group_kernel<F16, WMR>), dim3(nblocks), dim3(WMR * 128), lds, stream, grp);
   TDN_LAUNCH_CHECK();
   return 0;
@@ -1142,7 +1112,7 @@ static void fill_item(WgItem& d, const tdn_wgrad_item& it, const ItemPlan& g, fl
 }
 
 extern "C" int64_t tdn_wgrad_group_workspace(const tdn_wgrad_item* items, int n, int dtype) {
-  if (dtype != TDN_BF16 && dtype != TDN_F16) { tdn_set_error("dtype %d is neither TDN_BF16 nor TDN_F16", dtype); return -1; }
+  TDN_CHECK_DTYPE(dtype);
   std::vector<ItemPlan> plans;
   int64_t fl = 0;
   if (plan_group(items, n, plans, &fl)) return -1;
@@ -1151,7 +1121,7 @@ extern "C" int64_t tdn_wgrad_group_workspace(const tdn_wgrad_item* items, int n,
 
 extern "C" int tdn_wgrad_group_plan(const tdn_wgrad_item* items, int n, int dtype, int32_t* per_item,
                                     int32_t* totals) {
-  TDN_CHECK(dtype == TDN_BF16 || dtype == TDN_F16, "dtype %d is neither TDN_BF16 nor TDN_F16", dtype);
+  TDN_CHECK_DTYPE(dtype);
   std::vector<ItemPlan> plans;
   int64_t fl = 0;
   if (plan_group(items, n, plans, &fl)) return -1;
@@ -1180,7 +1150,7 @@ extern "C" int tdn_wgrad_group_plan(const tdn_wgrad_item* items, int n, int dtyp
 
 extern "C" int tdn_wgrad_group(const tdn_wgrad_item* items, int n, void* workspace, int64_t workspace_bytes,
                                int dtype, void* stream_) {
-  TDN_CHECK(dtype == TDN_BF16 || dtype == TDN_F16, "dtype %d is neither TDN_BF16 nor TDN_F16", dtype);
+  TDN_CHECK_DTYPE(dtype);
   hipStream_t stream = (hipStream_t)stream_;
   std::vector<ItemPlan> plans;
   int64_t fl = 0;
@@ -1195,7 +1165,7 @@ extern "C" int tdn_wgrad_group(const tdn_wgrad_item* items, int n, void* workspa
     WgGroup grp;
     memset(&grp, 0, sizeof(grp));
     grp.nitems = (int)L.size();
-    grp.reserved = env_int("TDN_WGRAD9_STAGGER", 1);   // nine-tap kernel: staggered LDS-DMA issue (see the kernel)
+    grp.reserved = tdn_knob_int("TDN_WGRAD9_STAGGER", 1);   // nine-tap kernel: staggered LDS-DMA issue (see the kernel)
     int blk = 0;
     for (int j = 0; j < WG_MAXI + 2; ++j) grp.blk_start[j] = INT_MAX;
     for (int j = 0; j < (int)L.size(); ++j) {

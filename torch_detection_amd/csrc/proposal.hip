@@ -411,18 +411,6 @@ __global__ __launch_bounds__(1024) void rpn_merge_kernel(const RpnArgs P, const 
 
 static inline int64_t align256(int64_t x) { return (x + 255) & ~255ll; }
 
-// LDS beyond 64 KB: attribute once per kernel and device
-#define TDN_BIG_LDS(kernel)                                                                                       \
-  do {                                                                                                            \
-    static tdn_attr_once attr_once;                                                                               \
-    if (attr_once.need()) {                                                                                       \
-      hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,          \
-                                         160 * 1024);                                                             \
-      TDN_CHECK(e == hipSuccess, "hipFuncSetAttribute(" #kernel ") failed: %s", hipGetErrorString(e));            \
-      attr_once.mark();                                                                                           \
-    }                                                                                                             \
-  } while (0)
-
 struct RpnPlan {
   RpnArgs P;
   int B, S, maxcap;
@@ -523,12 +511,12 @@ extern "C" int tdn_rpn_proposals(const tdn_rpn_level* levels, int nlevels, int B
   TDN_LAUNCH(nms_mask_seg_kernel, dim3(pitch, pitch, p.S), dim3(64), 0, st, (const float*)seg_box,
              (const int*)seg_start, (const int*)seg_count, cfg->nms_thr, pitch, mask);
   TDN_LAUNCH_CHECK();
-  TDN_BIG_LDS(nms_scan_seg_kernel);
+  if (tdn_allow_lds<nms_scan_seg_kernel>(160 * 1024, "nms_scan_seg") < 0) return -1;
   TDN_LAUNCH(nms_scan_seg_kernel, dim3(p.S), dim3(BLK), nms_scan_block_lds(pitch), st,
              (const unsigned long long*)mask, (const int*)nullptr, (const int*)seg_start, (const int*)seg_count, pitch,
              (uint8_t*)nullptr, kept, num_kept);
   TDN_LAUNCH_CHECK();
-  TDN_BIG_LDS(rpn_merge_kernel);
+  if (tdn_allow_lds<rpn_merge_kernel>(160 * 1024, "rpn_merge") < 0) return -1;
   TDN_LAUNCH(rpn_merge_kernel, dim3(p.B), dim3(BLK), MERGE_LDS, st, p.P, (const f32x4_t*)seg_box,
              (const uint32_t*)seg_key, (const int*)seg_aidx, (const int*)seg_start, (const int64_t*)kept,
              (const int*)num_kept, proposals, anchor_idx, counts);
@@ -607,7 +595,7 @@ extern "C" int tdn_batched_nms(const float* boxes, const float* scores, int N, c
   TDN_LAUNCH(nms_mask_seg_kernel, dim3(pitch, pitch, S), dim3(64), 0, st, (const float*)sboxes,
              (const int*)seg_start, (const int*)seg_count, iou_thr, pitch, mask);
   TDN_LAUNCH_CHECK();
-  TDN_BIG_LDS(nms_scan_seg_kernel);
+  if (tdn_allow_lds<nms_scan_seg_kernel>(160 * 1024, "nms_scan_seg") < 0) return -1;
   TDN_LAUNCH(nms_scan_seg_kernel, dim3(S), dim3(BLK), nms_scan_block_lds(pitch), st, (const unsigned long long*)mask,
              (const int*)order, (const int*)seg_start, (const int*)seg_count, pitch, keep, kept_idx, counts);
   TDN_LAUNCH_CHECK();
