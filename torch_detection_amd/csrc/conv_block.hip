@@ -17,7 +17,14 @@
 // costs as much as the kernel boundary it replaces (MI355X_MICROARCH.md, "handoff-flag" 2-5 us vs "boundary" 1.5 us);
 // inside one workgroup the hand-off is a ds_write + s_barrier.
 //
-// Workgroup = 8 x 16 output pixels (256 threads, two workgroups per CU, 80 KB of LDS each):
+// Three kernels, one per (C, tile) — each with its own LDS map and counted waits, described above it:
+//   bottleneck64_kernel     C = 64  (layer1; HEAD: its first block with the 1x1 downsample), 8 x 16 tiles, 256 threads,
+//                           two workgroups per CU with 80 KB of LDS each
+//   bottleneck128_kernel    C = 128 (layer2), 8 x 16 tiles, 512 threads, one workgroup per CU with all 160 KB
+//   bottleneck128t_kernel   C = 128, 10 x 16 tiles ("tall"): one round of workgroups where 8 x 16 needs two
+// The host side below them is shared: one launch template, one map from (C, tile height, BWD, F16, MB, HEAD) to the
+// instantiation, one place that computes the tile counts.
+// The phases, for the 8 x 16 tile (the tall tile has 12 x 18 halo pixels and 10 rows):
 //   phase 1  H1[10x18 halo pixels][C]  = epi1(W1[C][4C] . A[halo][4C])      A streamed global -> LDS by LDS-DMA, K-steps of 64
 //   phase 2  H2[8x16][C]               = epi2(sum_taps W2[C][tap][C] . H1[pixel + tap][C])   H1 read in place with tap shifts
 //   phase 3  OUT[8x16][4C]             = epi3(W3[4C][C] . H2 + A[pixel])
@@ -128,6 +135,28 @@ __device__ __forceinline__ unsigned gather_word4(unsigned byte, int fq) {
 // timing-dependent mismatch at 525 co-resident workgroups, never at small grids.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// ---- small pieces the three kernels share (the schedules themselves are per kernel: DESIGN.md §5c) ----
+// 16-byte-chunk XOR swizzles of the LDS images
+__device__ __forceinline__ int swz_w8(int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); }    // 128-B weight rows, 8 channels per lane
+__device__ __forceinline__ int swz_w16(int row) { return ((row >> 1) & 1) | (((row >> 4) & 3) << 1); }   // 128-B weight rows, 16 channels per lane
+__device__ __forceinline__ int f256(int R) { return ((R >> 1) & 7) << 1; }                               // 256-B pixel rows (C = 128)
+// pick element fq of a 4-entry register array (every lane holds all entries after the gathers): lets the four lanes
+// of a pixel column store four different fragments' words with ONE instruction instead of one lane storing four times
+__device__ __forceinline__ unsigned sel4(int fq, unsigned a0, unsigned a1, unsigned a2, unsigned a3) {
+  return fq == 0 ? a0 : (fq == 1 ? a1 : (fq == 2 ? a2 : a3));
+}
+// per-channel affine of an epilogue: folded BN in the forward pass (NULL: 1 / 0); the backward pass has none — the
+// same fma(acc, 1, 0) as conv_gemm_kernel computes for a NULL scale / shift, with constant operands
+template <bool BWD>
+__device__ __forceinline__ void load_affine(const float* scp, const float* shp, int ch, f32x4_t& sc, f32x4_t& sh) {
+  sc = (!BWD && scp) ? *(const f32x4_t*)(scp + ch) : (f32x4_t){1.f, 1.f, 1.f, 1.f};
+  sh = (!BWD && shp) ? *(const f32x4_t*)(shp + ch) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
+}
+// 64-byte rows (phase 1 K-steps): four rows per 256-byte bank line; this chunk swizzle keeps the ds_read_b128 lane
+// groups (rows {0-3, 12-15} with k-chunk kq, rows {4-11} with kq + 1) on 16 distinct slots
+__device__ __forceinline__ int swz64(int R) { return (4 - ((R >> 2) & 3)) & 3; }       // pixel row R
+__device__ __forceinline__ int swz64_w(int n) { return (4 - ((n >> 3) & 3)) & 3; }     // 64-byte weight row n (rows n, n + 4 of a lane: same swizzle)
+
 // HEAD (the stage's first block, resnet.py:130-136 with stride 1: layer1.0): the block input has C channels and the
 // residual branch is a 1x1 conv + BN of it.  Forward: phase 1 runs over K = C (two K-steps), the addend of phase 3 is
 // the downsample branch — read from p.ad (computed by a conv launch of its own), or computed here when p.wd is given.
@@ -184,9 +213,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   const int y0 = ty * TH, x0 = tx * TW;
   const int64_t img_pix0 = (int64_t)img * H * W;
 
-  auto swz_w8 = [](int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); };    // 128-B rows, 8 channels per lane
-  auto swz_w16 = [](int row) { return ((row >> 1) & 1) | (((row >> 4) & 3) << 1); };   // 128-B rows, 16 channels per lane
-
   // ---- conv2 weight taps: 64 rows x 128 B each, two LDS-DMA instructions per wave ----
   const int lrow8 = lane >> 3, lchunk8 = lane & 7;
   auto tap_off = [](int t) { return t < 2 ? T_OFF + t * TAP_BYTES : (t < 7 ? (t - 2) * TAP_BYTES : T_OFF + (t - 7) * TAP_BYTES); };
@@ -202,9 +228,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   load_tap(0);
   load_tap(1);
 
-  // ---- phase 1 loader state: 32-channel K-steps, 64-byte rows, 16 rows per LDS-DMA instruction ----
-  // 64-byte rows: four rows per 256-byte bank line; chunk swizzle f(row) = (4 - ((row >> 2) & 3)) & 3 keeps the
-  // ds_read_b128 lane groups (rows {0-3, 12-15} with k-chunk kq, rows {4-11} with kq + 1) on 16 distinct slots
+  // ---- phase 1 loader state: 32-channel K-steps, 64-byte rows (swz64), 16 rows per LDS-DMA instruction ----
   const int lrow16 = lane >> 2, lchunk4 = lane & 3;
   const char* zero = (const char*)g_zero_page + lchunk4 * 16;
   const char* xsrc[3];
@@ -215,19 +239,19 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
     const int hy = R / HWD, hx = R - hy * HWD;
     const int y = y0 - 1 + hy, x = x0 - 1 + hx;
     const bool ok = (R < PH) && ((unsigned)y < (unsigned)H) && ((unsigned)x < (unsigned)W);
-    const int swz = (4 - ((R >> 2) & 3)) & 3;
+    const int swz = swz64(R);
     xsrc[it] = (const char*)p.a + ((img_pix0 + (int64_t)y * W + x) * CA + ((lchunk4 ^ swz) * 8)) * 2;
     xok |= ok ? (1u << it) : 0u;
   }
   const char* w1src;
   {
     const int n = wave * 16 + lrow16;
-    w1src = (const char*)p.w1 + ((int64_t)n * CA) * 2 + ((lchunk4 ^ ((4 - ((n >> 3) & 3)) & 3)) * 16);
+    w1src = (const char*)p.w1 + ((int64_t)n * CA) * 2 + ((lchunk4 ^ swz64_w(n)) * 16);
   }
   const char* wdsrc = nullptr;
   if constexpr (DSB) {
     const int n = wave * 16 + lrow16;
-    wdsrc = (const char*)p.wd + ((int64_t)n * CA) * 2 + ((lchunk4 ^ ((4 - ((n >> 3) & 3)) & 3)) * 16);
+    wdsrc = (const char*)p.wd + ((int64_t)n * CA) * 2 + ((lchunk4 ^ swz64_w(n)) * 16);
   }
   auto load_step = [&](int kc) {   // K-step kc (32 channels) into ring slot kc % NSLOT
     char* sX = smem + (kc % NSLOT) * SLOT;
@@ -247,18 +271,9 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   const int pi = fr < 4 ? 2 * fr : (fr >= 12 ? 2 * (fr - 8) : 2 * (fr - 4) + 1);
   const int cb8 = wn * 32 + fq * 8;     // this lane's 8 consecutive channels of the C-wide outputs
 
-  // pick element fq of a 4-entry register array (every lane holds all entries after the gathers): lets the four lanes
-  // of a pixel column store four different fragments' words with ONE instruction instead of one lane storing four times
-  auto sel4 = [&](unsigned a0, unsigned a1, unsigned a2, unsigned a3) { return fq == 0 ? a0 : (fq == 1 ? a1 : (fq == 2 ? a2 : a3)); };
-  // per-channel affine of an epilogue: folded BN in the forward pass (NULL: 1 / 0); the backward pass has none — the
-  // same fma(acc, 1, 0) as conv_gemm_kernel computes for a NULL scale / shift, with constant operands
-  auto load_affine = [&](const float* scp, const float* shp, int ch, f32x4_t& sc, f32x4_t& sh) {
-    sc = (!BWD && scp) ? *(const f32x4_t*)(scp + ch) : (f32x4_t){1.f, 1.f, 1.f, 1.f};
-    sh = (!BWD && shp) ? *(const f32x4_t*)(shp + ch) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  };
   f32x4_t sc1v[2], sh1v[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) load_affine(p.sc1, p.sh1, cb8 + 4 * i, sc1v[i], sh1v[i]);
+  for (int i = 0; i < 2; ++i) load_affine<BWD>(p.sc1, p.sh1, cb8 + 4 * i, sc1v[i], sh1v[i]);
   // backward: ReLU-mask operands of the phase 1 epilogue, requested before the K loop
   bf16x8_t mk1[MB ? 1 : 6];
   unsigned mw1[MB ? 6 : 1];      // MB: the pixel's 32-channel word of the h2 > 0 bit plane (this lane's byte: fq)
@@ -469,7 +484,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int j = r * 4 + fq;
-        const unsigned w = r == 0 ? sel4(b1w[0], b1w[1], b1w[2], b1w[3]) : sel4(b1w[4], b1w[5], 0u, 0u);
+        const unsigned w = r == 0 ? sel4(fq, b1w[0], b1w[1], b1w[2], b1w[3]) : sel4(fq, b1w[4], b1w[5], 0u, 0u);
         const int R = wm * 96 + j * 16 + fr;
         const int hy = R / HWD, hx = R - hy * HWD;
         const bool st = j < 6 && ((st1 >> j) & 1u);
@@ -574,7 +589,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   f32x4_t sc2v[2], sh2v[2];
   if constexpr (DSK) {   // requested a barrier early and touched right behind b3's vmcnt(0): see below
 #pragma unroll
-    for (int i = 0; i < 2; ++i) load_affine(p.sc2, p.sh2, cb8 + 4 * i, sc2v[i], sh2v[i]);
+    for (int i = 0; i < 2; ++i) load_affine<BWD>(p.sc2, p.sh2, cb8 + 4 * i, sc2v[i], sh2v[i]);
   }
   load_tap(7);
   load_tap(8);
@@ -636,7 +651,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   }
   if constexpr (!DSK) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) load_affine(p.sc2, p.sh2, cb8 + 4 * i, sc2v[i], sh2v[i]);
+    for (int i = 0; i < 2; ++i) load_affine<BWD>(p.sc2, p.sh2, cb8 + 4 * i, sc2v[i], sh2v[i]);
   }
   tap_compute(7);
   tap_compute(8);
@@ -685,11 +700,11 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
     }
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) load_affine(p.sc3, p.sh3, chw + 4 * i, sc3v[i], sh3v[i]);
+  for (int i = 0; i < 4; ++i) load_affine<BWD>(p.sc3, p.sh3, chw + 4 * i, sc3v[i], sh3v[i]);
   f32x4_t scdv[DSK ? 4 : 1], shdv[DSK ? 4 : 1];
   if constexpr (DSK) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) load_affine(p.scd, p.shd, chw + 4 * i, scdv[i], shdv[i]);
+    for (int i = 0; i < 4; ++i) load_affine<BWD>(p.scd, p.shd, chw + 4 * i, scdv[i], shdv[i]);
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // b5: H2 complete, conv3 weights landed
 
@@ -706,7 +721,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
       if (p.b2) {   // h2 > 0 words: lane fq stores tile row wm * 4 + fq's word of its pixel column
         const int y = y0 + wm * 4 + fq, x = x0 + pi;
         *((y < H && x < W) ? p.b2 + (img_pix0 + (int64_t)y * W + x) * (C / 32) + wn : (unsigned*)g_blk_sink) =
-            sel4(b2w[0], b2w[1], b2w[2], b2w[3]);
+            sel4(fq, b2w[0], b2w[1], b2w[2], b2w[3]);
       }
     }
   };
@@ -879,10 +894,10 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
           asm volatile("" : "+v"(ch1));
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) load_affine(p.sc3, p.sh3, ch1 + 4 * i, sc3v[i], sh3v[i]);
+        for (int i = 0; i < 4; ++i) load_affine<BWD>(p.sc3, p.sh3, ch1 + 4 * i, sc3v[i], sh3v[i]);
         if constexpr (DSK) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) load_affine(p.scd, p.shd, ch1 + 4 * i, scdv[i], shdv[i]);
+          for (int i = 0; i < 4; ++i) load_affine<BWD>(p.scd, p.shd, ch1 + 4 * i, scdv[i], shdv[i]);
         }
         if constexpr (!DSK) store_o2();   // h2 / g1 to HBM: behind every load a later wait counts
       }
@@ -905,7 +920,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
           const int y = y0 + wm * 4 + fq, x = x0 + fr;
           unsigned* dst = (y < H && x < W) ? p.b3 + (img_pix0 + (int64_t)y * W + x) * (C4 / 32) + wn * 2 + nc * (C / 16)
                                            : (unsigned*)g_blk_sink;
-          *(u32x2_t*)dst = (u32x2_t){sel4(lo[0], lo[1], lo[2], lo[3]), sel4(hi[0], hi[1], hi[2], hi[3])};
+          *(u32x2_t*)dst = (u32x2_t){sel4(fq, lo[0], lo[1], lo[2], lo[3]), sel4(fq, hi[0], hi[1], hi[2], hi[3])};
         }
       }
     }
@@ -969,10 +984,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
   const int y0 = ty * TH, x0 = tx * TW;
   const int64_t img_pix0 = (int64_t)img * H * W;
 
-  auto swz_w8 = [](int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); };
-  auto swz_w16 = [](int row) { return ((row >> 1) & 1) | (((row >> 4) & 3) << 1); };
-  auto f256 = [](int R) { return ((R >> 1) & 7) << 1; };
-
   // ---- weight units ----
   const int lrow8 = lane >> 3, lchunk8 = lane & 7;
   auto unit_off = [](int u) { return RING + ((u + 5) % 7) * UB; };
@@ -1032,16 +1043,9 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
   const int pi = fr < 4 ? 2 * fr : (fr >= 12 ? 2 * (fr - 8) : 2 * (fr - 4) + 1);
   const int cb8 = wn * 32 + fq * 8;
 
-  // pick element fq of a 4-entry register array (every lane holds all entries after the gathers): lets the four lanes
-  // of a pixel column store four different fragments' words with ONE instruction instead of one lane storing four times
-  auto sel4 = [&](unsigned a0, unsigned a1, unsigned a2, unsigned a3) { return fq == 0 ? a0 : (fq == 1 ? a1 : (fq == 2 ? a2 : a3)); };
-  auto load_affine = [&](const float* scp, const float* shp, int ch, f32x4_t& sc, f32x4_t& sh) {
-    sc = (!BWD && scp) ? *(const f32x4_t*)(scp + ch) : (f32x4_t){1.f, 1.f, 1.f, 1.f};
-    sh = (!BWD && shp) ? *(const f32x4_t*)(shp + ch) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  };
   f32x4_t sc1v[2], sh1v[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) load_affine(p.sc1, p.sh1, cb8 + 4 * i, sc1v[i], sh1v[i]);
+  for (int i = 0; i < 2; ++i) load_affine<BWD>(p.sc1, p.sh1, cb8 + 4 * i, sc1v[i], sh1v[i]);
   bf16x8_t mk1[MB ? 1 : 6];
   unsigned mw1[MB ? 6 : 1];      // MB: the pixel's 32-channel word of the h2 > 0 bit plane (this lane's byte: fq)
   if constexpr (BWD) {
@@ -1161,7 +1165,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int j = r * 4 + fq;
-        const unsigned w = r == 0 ? sel4(b1w[0], b1w[1], b1w[2], b1w[3]) : sel4(b1w[4], b1w[5], 0u, 0u);
+        const unsigned w = r == 0 ? sel4(fq, b1w[0], b1w[1], b1w[2], b1w[3]) : sel4(fq, b1w[4], b1w[5], 0u, 0u);
         const int R = wm * 96 + j * 16 + fr;
         const int hy = R / HWD, hx = R - hy * HWD;
         const bool st = j < 6 && ((st1 >> j) & 1u);
@@ -1271,12 +1275,12 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
   if constexpr (!BWD) load_ad1();
   f32x4_t sc3v[4], sh3v[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) load_affine(p.sc3, p.sh3, chw + 4 * i, sc3v[i], sh3v[i]);
+  for (int i = 0; i < 4; ++i) load_affine<BWD>(p.sc3, p.sh3, chw + 4 * i, sc3v[i], sh3v[i]);
   unsigned b2w[4];
   {
     f32x4_t sc2v[2], sh2v[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) load_affine(p.sc2, p.sh2, cb8 + 4 * i, sc2v[i], sh2v[i]);
+    for (int i = 0; i < 2; ++i) load_affine<BWD>(p.sc2, p.sh2, cb8 + 4 * i, sc2v[i], sh2v[i]);
     asm volatile("" ::: "memory");   // the loads above stay in front of the unit below
     load_unit(24);
 #pragma unroll
@@ -1316,7 +1320,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
       if (p.b2) {   // h2 > 0 words: lane fq stores tile row wm * 4 + fq's word of its pixel column
         const int y = y0 + wm * 4 + fq, x = x0 + pi;
         *((y < H && x < W) ? p.b2 + (img_pix0 + (int64_t)y * W + x) * (C / 32) + wn : (unsigned*)g_blk_sink) =
-            sel4(b2w[0], b2w[1], b2w[2], b2w[3]);
+            sel4(fq, b2w[0], b2w[1], b2w[2], b2w[3]);
       }
     }
   }
@@ -1402,7 +1406,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
     if (nc == 0) {
       if constexpr (BWD) { load_ad1(); load_mask3(1); }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) load_affine(p.sc3, p.sh3, 256 + chw + 4 * i, sc3v[i], sh3v[i]);
+      for (int i = 0; i < 4; ++i) load_affine<BWD>(p.sc3, p.sh3, 256 + chw + 4 * i, sc3v[i], sh3v[i]);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -1423,7 +1427,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
         const int y = y0 + wm * 4 + fq, x = x0 + pi;
         unsigned* dst = (y < H && x < W) ? p.b3 + (img_pix0 + (int64_t)y * W + x) * (C4 / 32) + wn * 2 + nc * (C / 16)
                                          : (unsigned*)g_blk_sink;
-        *(u32x2_t*)dst = (u32x2_t){sel4(lo[0], lo[1], lo[2], lo[3]), sel4(hi[0], hi[1], hi[2], hi[3])};
+        *(u32x2_t*)dst = (u32x2_t){sel4(fq, lo[0], lo[1], lo[2], lo[3]), sel4(fq, hi[0], hi[1], hi[2], hi[3])};
       }
     }
     // b7: units 22..25 landed.  Behind unit 25 this wave has issued 8 + 8 addend and mask loads (backward without bit
@@ -1484,9 +1488,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
   const int y0 = ty * TH, x0 = tx * TW;
   const int64_t img_pix0 = (int64_t)img * H * W;
 
-  auto swz_w8 = [](int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); };
-  auto f256 = [](int R) { return ((R >> 1) & 7) << 1; };
-
   // ---- weight units ----
   const int lrow8 = lane >> 3, lchunk8 = lane & 7;
   auto unit_off = [](int u) { return (u + 5) % 6 < 5 ? RING + ((u + 5) % 6) * UB : RING + 4 * P1SLOT; };
@@ -1545,14 +1546,12 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
   const int pi = fr < 4 ? 2 * fr : (fr >= 12 ? 2 * (fr - 8) : 2 * (fr - 4) + 1);
   const int cb8 = wn * 32 + fq * 8;
 
-  auto sel4 = [&](unsigned a0, unsigned a1, unsigned a2, unsigned a3) { return fq == 0 ? a0 : (fq == 1 ? a1 : (fq == 2 ? a2 : a3)); };
-  auto load_affine = [&](const float* scp, const float* shp, int ch, f32x4_t& sc, f32x4_t& sh) {
-    sc = (!BWD && scp) ? *(const f32x4_t*)(scp + ch) : (f32x4_t){1.f, 1.f, 1.f, 1.f};
-    sh = (!BWD && shp) ? *(const f32x4_t*)(shp + ch) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  };
+  // this kernel's own copy of sel4: with the file-scope one its two forward instantiations come out 32 / 24 bytes shorter, in
+  // another instruction order (profiles/r06_block_kernel_refactor_checks.md)
+  auto sel4_t = [&](unsigned a0, unsigned a1, unsigned a2, unsigned a3) { return fq == 0 ? a0 : (fq == 1 ? a1 : (fq == 2 ? a2 : a3)); };
   f32x4_t sc1v[2], sh1v[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) load_affine(p.sc1, p.sh1, cb8 + 4 * i, sc1v[i], sh1v[i]);
+  for (int i = 0; i < 2; ++i) load_affine<BWD>(p.sc1, p.sh1, cb8 + 4 * i, sc1v[i], sh1v[i]);
   bf16x8_t mk1[MB ? 1 : NF1];
   unsigned mw1[MB ? NF1 : 1];
   if constexpr (BWD) {
@@ -1669,7 +1668,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int j = r * 4 + fq;
-        const unsigned w = r == 0 ? sel4(b1w[0], b1w[1], b1w[2], b1w[3]) : sel4(b1w[4], b1w[5], b1w[6], 0u);
+        const unsigned w = r == 0 ? sel4_t(b1w[0], b1w[1], b1w[2], b1w[3]) : sel4_t(b1w[4], b1w[5], b1w[6], 0u);
         const int R = wm * (NF1 * 16) + j * 16 + fr;
         const int hy = R / HWD, hx = R - hy * HWD;
         const bool st = j < NF1 && ((st1 >> j) & 1u);
@@ -1744,12 +1743,12 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
   lds_barrier();   // b4: H1 is dead; the slot of unit 17 is free
   f32x4_t sc3v[2], sh3v[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) load_affine(p.sc3, p.sh3, cb8 + 4 * i, sc3v[i], sh3v[i]);
+  for (int i = 0; i < 2; ++i) load_affine<BWD>(p.sc3, p.sh3, cb8 + 4 * i, sc3v[i], sh3v[i]);
   unsigned b2w[8];
   {
     f32x4_t sc2v[2], sh2v[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) load_affine(p.sc2, p.sh2, cb8 + 4 * i, sc2v[i], sh2v[i]);
+    for (int i = 0; i < 2; ++i) load_affine<BWD>(p.sc2, p.sh2, cb8 + 4 * i, sc2v[i], sh2v[i]);
     asm volatile("" ::: "memory");   // the loads above stay in front of the unit below
     load_unit(23);
 #pragma unroll
@@ -1790,8 +1789,8 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
       if (p.b2) {   // h2 > 0 words: lane fq stores tile row wm * 5 + fq's word of its pixel column, lane 0's group row 4's
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-          const unsigned w = r == 0 ? sel4(b2w[0], b2w[1], b2w[2], b2w[3]) : b2w[4];
-          const int pj = r == 0 ? (int)sel4((unsigned)pixj[0], (unsigned)pixj[1], (unsigned)pixj[2], (unsigned)pixj[3]) : pixj[4];
+          const unsigned w = r == 0 ? sel4_t(b2w[0], b2w[1], b2w[2], b2w[3]) : b2w[4];
+          const int pj = r == 0 ? (int)sel4_t((unsigned)pixj[0], (unsigned)pixj[1], (unsigned)pixj[2], (unsigned)pixj[3]) : pixj[4];
           const bool st = pj >= 0 && (r == 0 || fq == 0);
           *(st ? p.b2 + (int64_t)pj * (C / 32) + wn : (unsigned*)g_blk_sink) = w;
         }
@@ -1889,7 +1888,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
       asm volatile("" : "+s"(qn));
       load_ops3(qn);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) load_affine(p.sc3, p.sh3, qn * 128 + cb8 + 4 * i, sc3v[i], sh3v[i]);
+      for (int i = 0; i < 2; ++i) load_affine<BWD>(p.sc3, p.sh3, qn * 128 + cb8 + 4 * i, sc3v[i], sh3v[i]);
     }
 #pragma unroll
     for (int j = 0; j < NF2; ++j)
@@ -1898,8 +1897,8 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
       if (p.b3) {   // x > 0 words of this pass's 128 channels: word q * 4 + wn of the pixel
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-          const unsigned w = r == 0 ? sel4(b3w[0], b3w[1], b3w[2], b3w[3]) : b3w[4];
-          const int pj = r == 0 ? (int)sel4((unsigned)pixj[0], (unsigned)pixj[1], (unsigned)pixj[2], (unsigned)pixj[3]) : pixj[4];
+          const unsigned w = r == 0 ? sel4_t(b3w[0], b3w[1], b3w[2], b3w[3]) : b3w[4];
+          const int pj = r == 0 ? (int)sel4_t((unsigned)pixj[0], (unsigned)pixj[1], (unsigned)pixj[2], (unsigned)pixj[3]) : pixj[4];
           const bool st = pj >= 0 && (r == 0 || fq == 0);
           *(st ? p.b3 + (int64_t)pj * (C4 / 32) + q * 4 + wn : (unsigned*)g_blk_sink) = w;
         }
@@ -1911,33 +1910,66 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-template <bool BWD, bool F16, bool MB = false, int HEAD = 0>
-static int launch_block64(BlockParams& p, hipStream_t stream) {
-  constexpr int lds = 81920;
-  const int first = tdn_allow_lds<bottleneck64_kernel<BWD, F16, MB, HEAD>>(lds, "bottleneck64");
-  if (first < 0) return first;
-  if (first && tdn_knob_present("TDN_DEBUG_OCC")) {
-    int nb = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)bottleneck64_kernel<BWD, F16, MB, HEAD>, 256, lds);
-    fprintf(stderr, "[tdn] bottleneck64<%d,%d,%d,%d>: %d B LDS, %d workgroups/CU\n", (int)BWD, (int)F16, (int)MB, (int)HEAD, lds, nb);
-  }
-  TDN_LAUNCH((bottleneck64_kernel<BWD, F16, MB, HEAD>), dim3(p.nwg_pad), dim3(256), lds, stream, p);
-  TDN_LAUNCH_CHECK();
-  return 0;
-}
-
 #ifdef TDN_TRACE_BUILD
 static unsigned long long* g_blk_trace = nullptr;
 extern "C" int tdn_debug_block_trace(void* buf) { g_blk_trace = (unsigned long long*)buf; return 0; }   // >= 128 B per workgroup
 #endif
 
-template <bool BWD, bool F16, bool MB = false>
-static int launch_block128(BlockParams& p, hipStream_t stream) {
-  constexpr int lds = 163840;
-  if (tdn_allow_lds<bottleneck128_kernel<BWD, F16, MB>>(lds, "bottleneck128") < 0) return -1;
-  TDN_LAUNCH((bottleneck128_kernel<BWD, F16, MB>), dim3(p.nwg_pad), dim3(512), lds, stream, p);
+// One launch: LDS opt-in of this instantiation on this device, the launch, its check.  PRINT_OCC (the C = 64 kernel,
+// the one with two workgroups per CU to lose): its occupancy is printed at its first launch under TDN_DEBUG_OCC, under
+// the kernel's template flags BWD, F16, MB, HEAD.
+template <auto Kernel, int THREADS, int LDS, bool PRINT_OCC = false, int BWD = 0, int F16 = 0, int MB = 0, int HEAD = 0>
+static int launch_block(const BlockParams& p, hipStream_t stream, const char* what) {
+  const int first = tdn_allow_lds<Kernel>(LDS, what);
+  if (first < 0) return first;
+  if (PRINT_OCC && first && tdn_knob_present("TDN_DEBUG_OCC")) {
+    int nb = -1;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)Kernel, THREADS, LDS);
+    fprintf(stderr, "[tdn] %s<%d,%d,%d,%d>: %d B LDS, %d workgroups/CU\n", what, BWD, F16, MB, HEAD, LDS, nb);
+  }
+  TDN_LAUNCH(Kernel, dim3(p.nwg_pad), dim3(THREADS), LDS, stream, p);
   TDN_LAUNCH_CHECK();
   return 0;
+}
+
+// (C, tile height, dtype) -> kernel, for one <BWD, MB, HEAD>.  The head block exists for C = 64 only.
+template <bool BWD, bool MB, int HEAD>
+static int dispatch_block_cf(const BlockParams& p, int C, int th, bool f16, hipStream_t stream) {
+  if constexpr (HEAD == 0) {
+    if (C == 128 && th == 10) {
+      if (f16) return launch_block<bottleneck128t_kernel<BWD, true, MB>, 512, 163840>(p, stream, "bottleneck128t");
+      return launch_block<bottleneck128t_kernel<BWD, false, MB>, 512, 163840>(p, stream, "bottleneck128t");
+    }
+    if (C == 128) {
+      if (f16) return launch_block<bottleneck128_kernel<BWD, true, MB>, 512, 163840>(p, stream, "bottleneck128");
+      return launch_block<bottleneck128_kernel<BWD, false, MB>, 512, 163840>(p, stream, "bottleneck128");
+    }
+  }
+  if (f16) return launch_block<bottleneck64_kernel<BWD, true, MB, HEAD>, 256, 81920, true, BWD, 1, MB, HEAD>(p, stream, "bottleneck64");
+  return launch_block<bottleneck64_kernel<BWD, false, MB, HEAD>, 256, 81920, true, BWD, 0, MB, HEAD>(p, stream, "bottleneck64");
+}
+
+// The one map from (C, tile height, BWD, F16, MB, HEAD) to an instantiation.  head: 0, or 1 (downsample branch given)
+// / 2 (computed in the launch).  The compiler emits the kernels in the order in which these rows first name them, and
+// every kernel's pc-relative words depend on that order: a new row goes to the END (profiles/
+// r06_block_kernel_refactor_checks.md compares the code object with the previous one byte for byte).
+static int dispatch_block(const BlockParams& p, int C, int th, int dtype, bool bwd, bool mb, int head, hipStream_t stream) {
+  const bool f16 = dtype == TDN_F16;
+  if (!head) {
+    if (!bwd) return dispatch_block_cf<false, false, 0>(p, C, th, f16, stream);
+    if (mb) return dispatch_block_cf<true, true, 0>(p, C, th, f16, stream);
+    return dispatch_block_cf<true, false, 0>(p, C, th, f16, stream);
+  }
+  if (!bwd) {
+    if (head == 2) return dispatch_block_cf<false, false, 2>(p, C, th, f16, stream);
+    return dispatch_block_cf<false, false, 1>(p, C, th, f16, stream);
+  }
+  if (mb) {
+    if (head == 2) return dispatch_block_cf<true, true, 2>(p, C, th, f16, stream);
+    return dispatch_block_cf<true, true, 1>(p, C, th, f16, stream);
+  }
+  if (head == 2) return dispatch_block_cf<true, false, 2>(p, C, th, f16, stream);
+  return dispatch_block_cf<true, false, 1>(p, C, th, f16, stream);
 }
 
 // Tile height of the C = 128 kernels for this launch: 8 or 10 rows, whichever takes fewer workgroup-rounds x rows on
@@ -1946,32 +1978,22 @@ static int launch_block128(BlockParams& p, hipStream_t stream) {
 // (525.7 vs 526.5 img/s) while a single image alone is 10 % faster with 8 rows; launches of two or more images
 // (R101 at 4 images per GPU: two chains of two; TDN_IMG_SPLIT_M below the layer2 size) take 10 rows and gain a third
 // (both images of 100 x 168: 57.4 -> 38.7 us).  TDN_BLOCK128_TH=8 / 10 forces one.
-static int block128_th(const BlockParams& p) {
+static int block128_th(int N, int H, int W) {
   const char* e = tdn_knob_present("TDN_BLOCK128_TH");
   if (e && *e) return atoi(e) == 10 ? 10 : 8;   // any other value, a non-number included, forces 8
-  const int tx = ceil_div(p.W, 16);
-  const int r8 = ceil_div(p.N * tx * ceil_div(p.H, 8), 256) * 8;
-  const int r10 = ceil_div(p.N * tx * ceil_div(p.H, 10), 256) * 10;
+  const int tx = ceil_div(W, 16);
+  const int r8 = ceil_div(N * tx * ceil_div(H, 8), 256) * 8;
+  const int r10 = ceil_div(N * tx * ceil_div(H, 10), 256) * 10;
   return r10 < r8 ? 10 : 8;
-}
-
-template <bool BWD, bool F16, bool MB = false>
-static int launch_block128t(BlockParams& p, hipStream_t stream) {
-  constexpr int lds = 163840;
-  if (tdn_allow_lds<bottleneck128t_kernel<BWD, F16, MB>>(lds, "bottleneck128t") < 0) return -1;
-  p.tiles_y = ceil_div(p.H, 10);
-  p.ntiles = p.N * p.tiles_x * p.tiles_y;
-  p.nwg_pad = (p.ntiles + 7) & ~7;
-  TDN_LAUNCH((bottleneck128t_kernel<BWD, F16, MB>), dim3(p.nwg_pad), dim3(512), lds, stream, p);
-  TDN_LAUNCH_CHECK();
-  return 0;
 }
 
 extern "C" int tdn_bottleneck_supported(int H, int W, int C, int stride, int dilation) {
   return ((C == 64 || C == 128) && stride == 1 && dilation == 1 && H > 0 && W > 0) ? 1 : 0;
 }
 
-static int block_common(BlockParams& p, const tdn_bottleneck_args* a, int dtype) {
+// Checks every entry point shares, the tensors of the three convs, and the tiling: th = tile height of this launch
+// (16 columns wide), from which all tile counts follow — nothing patches them later.
+static int block_common(BlockParams& p, int& th, const tdn_bottleneck_args* a, int dtype) {
   TDN_CHECK_DTYPE(dtype);
   TDN_CHECK(a != nullptr, "bottleneck: NULL argument block");
   TDN_CHECK(a->N > 0 && a->H > 0 && a->W > 0, "bottleneck: bad tensor shape N=%d H=%d W=%d", a->N, a->H, a->W);
@@ -1982,7 +2004,8 @@ static int block_common(BlockParams& p, const tdn_bottleneck_args* a, int dtype)
   p.a = (const bf16_t*)a->in; p.w1 = (const bf16_t*)a->w1; p.w2 = (const bf16_t*)a->w2; p.w3 = (const bf16_t*)a->w3;
   p.o1 = (bf16_t*)a->out1; p.o2 = (bf16_t*)a->out2; p.o3 = (bf16_t*)a->out3;
   p.N = a->N; p.H = a->H; p.W = a->W;
-  p.tiles_x = ceil_div(a->W, 16); p.tiles_y = ceil_div(a->H, 8);
+  th = a->C == 128 ? block128_th(a->N, a->H, a->W) : 8;
+  p.tiles_x = ceil_div(a->W, 16); p.tiles_y = ceil_div(a->H, th);
   p.ntiles = a->N * p.tiles_x * p.tiles_y;
   p.nwg_pad = (p.ntiles + 7) & ~7;
 #ifdef TDN_TRACE_BUILD
@@ -1990,53 +2013,36 @@ static int block_common(BlockParams& p, const tdn_bottleneck_args* a, int dtype)
 #endif
   return 0;
 }
+// forward: folded BN of the three convs; the bit planes are optional outputs
+static void block_affine(BlockParams& p, const tdn_bottleneck_args* a) {
+  p.sc1 = a->scale1; p.sh1 = a->shift1; p.sc2 = a->scale2; p.sh2 = a->shift2; p.sc3 = a->scale3; p.sh3 = a->shift3;
+}
+// backward: 16-bit mask sources, or the bit planes the forward pass wrote
+static void block_masks(BlockParams& p, const tdn_bottleneck_args* a) {
+  p.m1 = (const bf16_t*)a->mask1; p.m2 = (const bf16_t*)a->mask2; p.m3 = (const bf16_t*)a->mask3;
+}
+static void block_bits(BlockParams& p, const tdn_bottleneck_args* a) {
+  p.b1 = (unsigned*)a->bits1; p.b2 = (unsigned*)a->bits2; p.b3 = (unsigned*)a->bits3;
+}
 
 extern "C" int tdn_bottleneck_fwd(const tdn_bottleneck_args* a, int dtype, void* stream) {
   BlockParams p;
-  if (block_common(p, a, dtype)) return -1;
-  p.sc1 = a->scale1; p.sh1 = a->shift1; p.sc2 = a->scale2; p.sh2 = a->shift2; p.sc3 = a->scale3; p.sh3 = a->shift3;
-  p.b1 = (unsigned*)a->bits1; p.b2 = (unsigned*)a->bits2; p.b3 = (unsigned*)a->bits3;   // optional outputs
-  if (a->C == 128) {
-    if (block128_th(p) == 10) {
-      if (dtype == TDN_F16) return launch_block128t<false, true>(p, (hipStream_t)stream);
-      return launch_block128t<false, false>(p, (hipStream_t)stream);
-    }
-    if (dtype == TDN_F16) return launch_block128<false, true>(p, (hipStream_t)stream);
-    return launch_block128<false, false>(p, (hipStream_t)stream);
-  }
-  if (dtype == TDN_F16) return launch_block64<false, true>(p, (hipStream_t)stream);
-  return launch_block64<false, false>(p, (hipStream_t)stream);
+  int th;
+  if (block_common(p, th, a, dtype)) return -1;
+  block_affine(p, a);
+  block_bits(p, a);
+  return dispatch_block(p, a->C, th, dtype, false, false, 0, (hipStream_t)stream);
 }
 
 extern "C" int tdn_bottleneck_dgrad(const tdn_bottleneck_args* a, int dtype, void* stream) {
   BlockParams p;
-  if (block_common(p, a, dtype)) return -1;
-  p.m1 = (const bf16_t*)a->mask1; p.m2 = (const bf16_t*)a->mask2; p.m3 = (const bf16_t*)a->mask3;
-  p.b1 = (unsigned*)a->bits1; p.b2 = (unsigned*)a->bits2; p.b3 = (unsigned*)a->bits3;
+  int th;
+  if (block_common(p, th, a, dtype)) return -1;
+  block_masks(p, a);
+  block_bits(p, a);
   const bool mb = a->bits1 || a->bits2 || a->bits3;
-  if (mb) {
-    TDN_CHECK(a->bits1 && a->bits2 && a->bits3, "bottleneck dgrad: all three bit planes or none");
-    if (a->C == 128) {
-      if (block128_th(p) == 10) {
-        if (dtype == TDN_F16) return launch_block128t<true, true, true>(p, (hipStream_t)stream);
-        return launch_block128t<true, false, true>(p, (hipStream_t)stream);
-      }
-      if (dtype == TDN_F16) return launch_block128<true, true, true>(p, (hipStream_t)stream);
-      return launch_block128<true, false, true>(p, (hipStream_t)stream);
-    }
-    if (dtype == TDN_F16) return launch_block64<true, true, true>(p, (hipStream_t)stream);
-    return launch_block64<true, false, true>(p, (hipStream_t)stream);
-  }
-  if (a->C == 128) {
-    if (block128_th(p) == 10) {
-      if (dtype == TDN_F16) return launch_block128t<true, true>(p, (hipStream_t)stream);
-      return launch_block128t<true, false>(p, (hipStream_t)stream);
-    }
-    if (dtype == TDN_F16) return launch_block128<true, true>(p, (hipStream_t)stream);
-    return launch_block128<true, false>(p, (hipStream_t)stream);
-  }
-  if (dtype == TDN_F16) return launch_block64<true, true>(p, (hipStream_t)stream);
-  return launch_block64<true, false>(p, (hipStream_t)stream);
+  if (mb) TDN_CHECK(a->bits1 && a->bits2 && a->bits3, "bottleneck dgrad: all three bit planes or none");
+  return dispatch_block(p, a->C, th, dtype, true, mb, 0, (hipStream_t)stream);
 }
 
 // ---- head block (layer1.0): C input channels, 1x1 downsample on the residual branch ----
@@ -2046,49 +2052,34 @@ extern "C" int tdn_bottleneck_head_supported(int H, int W, int Cin, int C, int s
 
 extern "C" int tdn_bottleneck_head_fwd(const tdn_bottleneck_head_args* a, int dtype, void* stream) {
   BlockParams p;
+  int th;
   TDN_CHECK(a != nullptr, "bottleneck head: NULL argument block");
-  if (block_common(p, &a->b, dtype)) return -1;
+  if (block_common(p, th, &a->b, dtype)) return -1;
   TDN_CHECK(a->b.C == 64, "bottleneck head: C=%d is not built (64)", a->b.C);
   TDN_CHECK((a->addend != nullptr) != (a->wd != nullptr),
             "bottleneck head fwd: give either the downsample branch (addend) or its weights (wd), not both / neither");
   TDN_CHECK(a->b.bits3 == nullptr, "bottleneck head fwd: there is no bits3 plane (the block input is not masked)");
-  p.sc1 = a->b.scale1; p.sh1 = a->b.shift1; p.sc2 = a->b.scale2; p.sh2 = a->b.shift2; p.sc3 = a->b.scale3; p.sh3 = a->b.shift3;
-  p.b1 = (unsigned*)a->b.bits1; p.b2 = (unsigned*)a->b.bits2;
+  block_affine(p, &a->b);
+  block_bits(p, &a->b);      // bits3 is NULL
   p.ad = (const bf16_t*)a->addend;
-  if (a->wd) {
-    p.wd = (const bf16_t*)a->wd; p.scd = a->scale_d; p.shd = a->shift_d;
-    if (dtype == TDN_F16) return launch_block64<false, true, false, 2>(p, (hipStream_t)stream);
-    return launch_block64<false, false, false, 2>(p, (hipStream_t)stream);
-  }
-  if (dtype == TDN_F16) return launch_block64<false, true, false, 1>(p, (hipStream_t)stream);
-  return launch_block64<false, false, false, 1>(p, (hipStream_t)stream);
+  if (a->wd) { p.wd = (const bf16_t*)a->wd; p.scd = a->scale_d; p.shd = a->shift_d; }
+  return dispatch_block(p, 64, th, dtype, false, false, a->wd ? 2 : 1, (hipStream_t)stream);
 }
 
 extern "C" int tdn_bottleneck_head_dgrad(const tdn_bottleneck_head_args* a, int dtype, void* stream) {
   BlockParams p;
+  int th;
   TDN_CHECK(a != nullptr, "bottleneck head: NULL argument block");
-  if (block_common(p, &a->b, dtype)) return -1;
+  if (block_common(p, th, &a->b, dtype)) return -1;
   TDN_CHECK(a->b.C == 64, "bottleneck head: C=%d is not built (64)", a->b.C);
   TDN_CHECK((a->addend != nullptr) != (a->wd != nullptr),
             "bottleneck head dgrad: give either the downsample conv's input gradient (addend) or its w_dgrad (wd)");
   TDN_CHECK(a->b.mask3 == nullptr && a->b.bits3 == nullptr, "bottleneck head dgrad: the block input gradient takes no mask");
-  p.m1 = (const bf16_t*)a->b.mask1; p.m2 = (const bf16_t*)a->b.mask2;
-  p.b1 = (unsigned*)a->b.bits1; p.b2 = (unsigned*)a->b.bits2;
+  block_masks(p, &a->b);     // mask3 and bits3 are NULL
+  block_bits(p, &a->b);
   p.ad = (const bf16_t*)a->addend;
   p.wd = (const bf16_t*)a->wd;
-  if (a->b.bits1 || a->b.bits2) {
-    TDN_CHECK(a->b.bits1 && a->b.bits2, "bottleneck head dgrad: both bit planes or none");
-    if (a->wd) {
-      if (dtype == TDN_F16) return launch_block64<true, true, true, 2>(p, (hipStream_t)stream);
-      return launch_block64<true, false, true, 2>(p, (hipStream_t)stream);
-    }
-    if (dtype == TDN_F16) return launch_block64<true, true, true, 1>(p, (hipStream_t)stream);
-    return launch_block64<true, false, true, 1>(p, (hipStream_t)stream);
-  }
-  if (a->wd) {
-    if (dtype == TDN_F16) return launch_block64<true, true, false, 2>(p, (hipStream_t)stream);
-    return launch_block64<true, false, false, 2>(p, (hipStream_t)stream);
-  }
-  if (dtype == TDN_F16) return launch_block64<true, true, false, 1>(p, (hipStream_t)stream);
-  return launch_block64<true, false, false, 1>(p, (hipStream_t)stream);
+  const bool mb = a->b.bits1 || a->b.bits2;
+  if (mb) TDN_CHECK(a->b.bits1 && a->b.bits2, "bottleneck head dgrad: both bit planes or none");
+  return dispatch_block(p, 64, th, dtype, true, mb, a->wd ? 2 : 1, (hipStream_t)stream);
 }
