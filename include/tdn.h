@@ -576,6 +576,66 @@ int tdn_sample_rois(const float* proposals, const int32_t* counts, const float* 
                     int32_t* pos_gt_inds, int32_t* num_pos, int32_t* num_neg, void* workspace,
                     int64_t workspace_bytes, void* stream);
 
+/* ---- losses of the dense anchor heads (RPN, RetinaNet) and of the RoI box head, with their gradients (DESIGN.md §4e:
+ *      sigmoid BCE / focal + smooth L1 over the level-major anchors of tdn_anchor_target; softmax CE + smooth L1 over
+ *      the rows of tdn_sample_rois) ----
+ * Head outputs are TDN_F32 / TDN_BF16 / TDN_F16, read in place; targets are the fp32 / int64 tensors the target entry
+ * points write.  Per-element work is fp32, sums are fp64 in an order fixed by the shapes (no float atomics: block
+ * partials in the workspace, added in index order by the last launch).  An element whose weight is exactly 0 is never
+ * evaluated: loss 0, gradient 0, whatever its logit.  The divisor is read on the device (tdn_loss_avg), so nothing
+ * synchronises with the host.  losses fp32 [2] = (loss_cls, loss_bbox); avg_out fp32 [1] = the divisor, which the
+ * backward entry points take back as avg_in together with the cotangent g fp32 [2].  Forward: two launches; backward:
+ * one.  Workspaces: the *_workspace_bytes() query, 256-aligned. */
+#define TDN_LOSS_MAX_LEVELS 8
+#define TDN_LOSS_MAX_CLASSES 1024
+#define TDN_LOSS_MAX_ROWS (1 << 20)     /* anchors per image / RoI rows */
+#define TDN_LOSS_MAX_AVG 64             /* elements per avg_factor tensor */
+typedef struct tdn_loss_level {
+  const void* cls;            /* (B, A*C, H, W) logits: class channel a*C + c */
+  const void* reg;            /* (B, 4A, H, W) deltas: box channel 4a + j */
+  void* dcls;                 /* backward only: gradients, laid out as cls / reg */
+  void* dreg;
+  int32_t H, W;
+  int32_t cls_nhwc, reg_nhwc; /* 0: NCHW-contiguous memory, 1: channels_last (N, H, W, C) memory */
+} tdn_loss_level;
+typedef struct tdn_loss_config {
+  int32_t dtype;              /* TDN_BF16 / TDN_F16 / TDN_F32, of every head output and gradient */
+  int32_t num_anchors;        /* A */
+  int32_t num_classes;        /* C: label k in 1..C is one-hot on class channel k-1, 0 is background */
+  int32_t focal;              /* 0: binary cross entropy, 1: focal with gamma, alpha */
+  float beta;                 /* smooth L1 knee, > 0 */
+  float gamma, alpha;
+  int32_t reserved;
+} tdn_loss_config;
+typedef struct tdn_loss_avg {
+  const int32_t* a;           /* mode 1: divisor = max(1, sum a[0..na) + sum b[0..nb)) as fp32, summed on the device */
+  const int32_t* b;
+  int32_t na, nb;             /* 0..TDN_LOSS_MAX_AVG each */
+  int32_t mode;               /* 0: value; 1: the tensors; 2 (RoI head only): rows with label_weights > 0, at least 1 */
+  float value;                /* mode 0: finite and > 0 */
+} tdn_loss_avg;
+/* labels int64 [B][N], label_weights fp32 [B][N], bbox_targets / bbox_weights fp32 [B][N][4], N = sum H*W*A over the
+ * levels in order, anchor (h*W + w)*A + a within a level; one level tensor holds fewer than 2^31 elements. */
+int64_t tdn_loss_dense_workspace_bytes(const tdn_loss_level* levels, int num_levels, int B, const tdn_loss_config* cfg);
+int tdn_loss_dense_fwd(const tdn_loss_level* levels, int num_levels, int B, const tdn_loss_config* cfg,
+                       const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                       const float* bbox_weights, const tdn_loss_avg* avg, float* losses, float* avg_out,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int tdn_loss_dense_bwd(const tdn_loss_level* levels, int num_levels, int B, const tdn_loss_config* cfg,
+                       const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                       const float* bbox_weights, const float* g, const float* avg_in, void* stream);
+/* cls [R][C] softmax logits (class 0 background), reg [R][reg_cols], reg_cols = 4C (row r regresses columns
+ * 4*labels[r] ..) or 4; labels int64 [R], label_weights fp32 [R], bbox_targets / bbox_weights fp32 [R][4].  A row whose
+ * label is outside [0, C) counts as weight 0. */
+int64_t tdn_loss_roi_workspace_bytes(int R);
+int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols, const int64_t* labels,
+                     const float* label_weights, const float* bbox_targets, const float* bbox_weights, float beta,
+                     const tdn_loss_avg* avg, float* losses, float* avg_out, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int tdn_loss_roi_bwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols, const int64_t* labels,
+                     const float* label_weights, const float* bbox_targets, const float* bbox_weights, float beta,
+                     const float* g, const float* avg_in, void* dcls, void* dreg, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

@@ -4,7 +4,8 @@ Drop-in surface (same names as the reference's ``models`` package): ``BACKBONES`
 ``FPN``, ``PAFPN``, ``ConvModule``, the conv/norm builders and init helpers, plus the steps either side of it
 (``ImageTransforms`` device-side batch staging, box ops, ``bbox_normalize`` / ``bbox_denormalize``,
 ``bbox2delta`` / ``delta2bbox``, ``batched_nms`` and ``rpn_proposals``, the training targets ``assign_max_iou`` /
-``sample_assigned`` / ``anchor_target`` / ``sample_rois``, then ``rois_from_proposals``, ``roi_align``,
+``sample_assigned`` / ``anchor_target`` / ``sample_rois`` and the losses that consume them (``rpn_loss`` /
+``anchor_head_loss`` / ``bbox_head_loss``), then ``rois_from_proposals``, ``roi_align``,
 ``map_roi_levels`` and ``SingleRoIExtractor``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
@@ -25,5 +26,7 @@ from .functional import invalidate_packed  # noqa: F401
 from .box import (AnchorGenerator, anchor_pyramid, batched_nms, bbox2delta, bbox_denormalize,  # noqa: F401
                   bbox_normalize, bbox_overlaps, delta2bbox, nms, nms_mask, rpn_proposals)
 from .target import anchor_target, assign_max_iou, sample_assigned, sample_rois  # noqa: F401
+from .losses import (AnchorHeadLossFunction, BBoxHeadLossFunction, anchor_head_loss,  # noqa: F401
+                     bbox_head_loss, rpn_loss)
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)

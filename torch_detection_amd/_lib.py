@@ -26,6 +26,10 @@ ROI_MAX_SAMPLES = 512
 TARGET_MAX_GT = 256
 TARGET_MAX_BOXES = 1 << 20
 TARGET_MAX_NUM = 8192
+LOSS_MAX_LEVELS = 8
+LOSS_MAX_CLASSES = 1024
+LOSS_MAX_ROWS = 1 << 20
+LOSS_MAX_AVG = 64
 ADD_NONE, ADD_SAME, ADD_UP2X, ADD_SUMPOOL2 = 0, 1, 2, 3
 
 c_void_p = ctypes.c_void_p
@@ -122,6 +126,31 @@ class TargetConfig(ctypes.Structure):
 
 
 _TC = ctypes.POINTER(TargetConfig)
+
+
+class LossLevel(ctypes.Structure):
+    """Mirror of ``tdn_loss_level`` (include/tdn.h)."""
+    _fields_ = [("cls", c_void_p), ("reg", c_void_p), ("dcls", c_void_p), ("dreg", c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("cls_nhwc", ctypes.c_int32),
+                ("reg_nhwc", ctypes.c_int32)]
+
+
+class LossConfig(ctypes.Structure):
+    """Mirror of ``tdn_loss_config`` (include/tdn.h)."""
+    _fields_ = [("dtype", ctypes.c_int32), ("num_anchors", ctypes.c_int32), ("num_classes", ctypes.c_int32),
+                ("focal", ctypes.c_int32), ("beta", c_float), ("gamma", c_float), ("alpha", c_float),
+                ("reserved", ctypes.c_int32)]
+
+
+class LossAvg(ctypes.Structure):
+    """Mirror of ``tdn_loss_avg`` (include/tdn.h)."""
+    _fields_ = [("a", c_void_p), ("b", c_void_p), ("na", ctypes.c_int32), ("nb", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("value", c_float)]
+
+
+_LL = ctypes.POINTER(LossLevel)
+_LC = ctypes.POINTER(LossConfig)
+_LA = ctypes.POINTER(LossAvg)
 
 
 class RoiLevel(ctypes.Structure):
@@ -229,6 +258,15 @@ SIGNATURES = {
                           [c_i64, c_void_p]),
     "tdn_sample_rois_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "tdn_sample_rois": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, _TC] + [c_void_p] * 10 + [c_i64, c_void_p]),
+    "tdn_loss_dense_workspace_bytes": (c_i64, [_LL, c_int, c_int, _LC]),
+    "tdn_loss_dense_fwd": (c_int, [_LL, c_int, c_int, _LC] + [c_void_p] * 4 + [_LA, c_void_p, c_void_p, c_void_p, c_i64,
+                                                                              c_void_p]),
+    "tdn_loss_dense_bwd": (c_int, [_LL, c_int, c_int, _LC] + [c_void_p] * 7),
+    "tdn_loss_roi_workspace_bytes": (c_i64, [c_int]),
+    "tdn_loss_roi_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4 +
+                         [c_float, _LA, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "tdn_loss_roi_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4 +
+                         [c_float] + [c_void_p] * 5),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),

@@ -1,0 +1,650 @@
+// Losses of the dense anchor heads (sigmoid BCE / focal + smooth L1) and of the RoI box head (softmax CE + smooth L1)
+// with their gradients (gfx950; DESIGN.md §4e has the spec, tests/loss_ref.py restates it).
+//
+// Per-element work is fp32 with explicit __f*_rn arithmetic (this file is compiled with -ffp-contract=off); sums are
+// fp64.  Which lane, wave and workgroup an element goes to depends on the shapes alone; a workgroup's partial goes to
+// the workspace with a plain store and the last launch adds the partials in index order, so two runs agree bit for
+// bit.  An element whose weight is exactly 0 is not evaluated.  No float atomics, no host synchronisation, no
+// allocation; every launch goes through TDN_LAUNCH.
+#include "common.h"
+#include <string.h>
+
+namespace {
+
+constexpr int LT = 1024;          // threads per workgroup: 16 waves, four per SIMD
+constexpr int LWAVES = LT / 64;
+constexpr int LMAX_BLOCKS = 256;  // one workgroup per CU at most: that many partials for the last launch
+constexpr int PART = 4;           // doubles per partial: loss_cls, loss_bbox, rows with weight > 0, unused
+constexpr int MAXSEG = 2 * TDN_LOSS_MAX_LEVELS;
+
+// ---- elementwise spec ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float e_neg_abs(float z) { return expf(-fabsf(z)); }
+__device__ __forceinline__ float softplus(float z) { return __fadd_rn(fmaxf(z, 0.f), log1pf(e_neg_abs(z))); }
+__device__ __forceinline__ float sigmoid(float z) {
+  const float e = e_neg_abs(z);
+  const float d = __fadd_rn(1.f, e);
+  return z >= 0.f ? __fdiv_rn(1.f, d) : __fdiv_rn(e, d);
+}
+
+struct ClsParams {
+  int focal;
+  float gamma, alpha, one_minus_alpha;
+};
+
+// GRAD: d loss / d logit, else the loss; t: the element's class is the anchor's label
+template <bool GRAD>
+__device__ __forceinline__ float cls_elem(float x, bool t, const ClsParams& P) {
+  if (!P.focal) {
+    if (GRAD) return t ? -sigmoid(-x) : sigmoid(x);
+    return t ? softplus(-x) : softplus(x);
+  }
+  if (t) {
+    const float mod = __fmul_rn(P.alpha, expf(-__fmul_rn(P.gamma, softplus(x))));
+    if (!GRAD) return __fmul_rn(mod, softplus(-x));
+    const float inner = __fadd_rn(__fmul_rn(__fmul_rn(P.gamma, sigmoid(x)), softplus(-x)), sigmoid(-x));
+    return -__fmul_rn(mod, inner);
+  }
+  const float mod = __fmul_rn(P.one_minus_alpha, expf(-__fmul_rn(P.gamma, softplus(-x))));
+  if (!GRAD) return __fmul_rn(mod, softplus(x));
+  const float inner = __fadd_rn(__fmul_rn(__fmul_rn(P.gamma, sigmoid(-x)), softplus(x)), sigmoid(x));
+  return __fmul_rn(mod, inner);
+}
+
+template <bool GRAD>
+__device__ __forceinline__ float smooth_l1(float pred, float target, float beta) {
+  const float d = __fsub_rn(pred, target);
+  const float ad = fabsf(d);
+  if (ad < beta) return GRAD ? __fdiv_rn(d, beta) : __fdiv_rn(__fmul_rn(__fmul_rn(0.5f, d), d), beta);
+  if (GRAD) return d > 0.f ? 1.f : (d < 0.f ? -1.f : d);      // NaN stays NaN
+  return __fsub_rn(ad, __fmul_rn(0.5f, beta));
+}
+
+// ---- storage types ------------------------------------------------------------------------------------------------
+template <int DT> struct Elem;
+template <> struct Elem<TDN_F32> {
+  typedef float T;
+  static constexpr int V = 4;
+  static __device__ __forceinline__ float ld(T v) { return v; }
+  static __device__ __forceinline__ T st(float v) { return v; }
+};
+template <> struct Elem<TDN_BF16> {
+  typedef bf16_t T;
+  static constexpr int V = 8;
+  static __device__ __forceinline__ float ld(T v) { return (float)v; }
+  static __device__ __forceinline__ T st(float v) { return (bf16_t)v; }
+};
+template <> struct Elem<TDN_F16> {
+  typedef f16_t T;
+  static constexpr int V = 8;
+  static __device__ __forceinline__ float ld(T v) { return (float)v; }
+  static __device__ __forceinline__ T st(float v) { return (f16_t)v; }
+};
+
+template <typename T, int V>
+struct alignas(16) Vec {
+  T v[V];
+};
+
+// ---- block reduction of the fp64 accumulators -----------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// lanes -> xor tree, waves -> wave 0 .. 15 in order; thread 0 stores the workgroup's partial
+__device__ __forceinline__ void block_partial(double a0, double a1, double a2, double* __restrict__ partials) {
+  __shared__ double red[LWAVES][3];
+  a0 = wave_sum(a0);
+  a1 = wave_sum(a1);
+  a2 = wave_sum(a2);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[wave][0] = a0;
+    red[wave][1] = a1;
+    red[wave][2] = a2;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int w = 0; w < LWAVES; ++w) {
+      s0 += red[w][0];
+      s1 += red[w][1];
+      s2 += red[w][2];
+    }
+    double* p = partials + (size_t)blockIdx.x * PART;
+    p[0] = s0;
+    p[1] = s1;
+    p[2] = s2;
+    p[3] = 0.0;
+  }
+}
+
+// ---- dense heads ----------------------------------------------------------------------------------------------------
+// One segment = one head tensor of one level, walked as the flat array it is in memory, in chunks of V elements
+// (16 bytes).  Chunk indices run through all segments; a workgroup takes 1024 consecutive chunks per grid stride.
+struct DenseSeg {
+  const void* x;
+  void* dx;
+  uint32_t n;        // elements
+  uint32_t nchunks;
+  int64_t chunk0;    // index of the segment's first chunk
+  int32_t Ch, HW;    // channels, H*W
+  int32_t nhwc;      // memory order: 0 (b, c, p), 1 (b, p, c)
+  int32_t reg;       // 0: class logits, 1: box deltas
+  int32_t off;       // index of the level's first anchor within an image
+  int32_t vec;       // x (and dx) are 16-byte aligned
+};
+struct DenseArgs {
+  DenseSeg seg[MAXSEG];
+  int32_t nseg;
+  int64_t nchunks;
+  const int64_t* labels;
+  const float* lw;
+  const float* bt;
+  const float* bw;
+  int32_t N, A, C;
+  float beta;
+  ClsParams P;
+};
+
+template <int DT, bool GRAD>
+__device__ __forceinline__ double dense_chunk(const DenseSeg& S, const DenseArgs& A, uint32_t lc, float s_cls,
+                                              float s_reg) {
+  typedef Elem<DT> E;
+  typedef typename E::T T;
+  constexpr int V = E::V;
+  const uint32_t m0 = lc * (uint32_t)V;
+  const int cnt = (int)min((uint32_t)V, S.n - m0);
+  const T* xp = (const T*)S.x + m0;
+  Vec<T, V> in, out;
+  if (S.vec && cnt == V) {
+    in = *(const Vec<T, V>*)xp;
+  } else {
+#pragma unroll
+    for (int e = 0; e < V; ++e) in.v[e] = e < cnt ? xp[e] : E::st(0.f);
+  }
+  // coordinates of the chunk's first element; the following elements advance them
+  const int div = S.reg ? 4 : A.C;               // channels per anchor
+  uint32_t b, c, p;
+  if (S.nhwc) {
+    const uint32_t q = m0 / (uint32_t)S.Ch;
+    c = m0 - q * (uint32_t)S.Ch;
+    b = q / (uint32_t)S.HW;
+    p = q - b * (uint32_t)S.HW;
+  } else {
+    const uint32_t q = m0 / (uint32_t)S.HW;
+    p = m0 - q * (uint32_t)S.HW;
+    b = q / (uint32_t)S.Ch;
+    c = q - b * (uint32_t)S.Ch;
+  }
+  int a = (int)c / div, k = (int)c - a * div;
+  int last_idx = -1;
+  float last_w = 0.f;
+  long long last_lab = 0;
+  double sum = 0.0;                              // the chunk's elements in memory order
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    float res = 0.f;
+    if (e < cnt) {
+      const int idx = (int)b * A.N + S.off + (int)p * A.A + a;     // < 64 * 2^20
+      const float x = E::ld(in.v[e]);
+      if (S.reg) {
+        const float w = A.bw[(size_t)idx * 4 + k];
+        if (w != 0.f) {
+          const float v = smooth_l1<GRAD>(x, A.bt[(size_t)idx * 4 + k], A.beta);
+          if (GRAD) res = __fmul_rn(__fmul_rn(w, v), s_reg);
+          else sum += (double)__fmul_rn(w, v);
+        }
+      } else {
+        if (idx != last_idx) {
+          last_idx = idx;
+          last_w = A.lw[idx];
+          if (last_w != 0.f) last_lab = A.labels[idx];
+        }
+        if (last_w != 0.f) {
+          const float v = cls_elem<GRAD>(x, last_lab == (long long)k + 1, A.P);
+          if (GRAD) res = __fmul_rn(__fmul_rn(last_w, v), s_cls);
+          else sum += (double)__fmul_rn(last_w, v);
+        }
+      }
+      if (S.nhwc) {
+        ++c; ++k;
+        if (k == div) { k = 0; ++a; }
+        if (c == (uint32_t)S.Ch) {
+          c = 0; a = 0; k = 0; ++p;
+          if (p == (uint32_t)S.HW) { p = 0; ++b; }
+        }
+      } else {
+        ++p;
+        if (p == (uint32_t)S.HW) {
+          p = 0; ++c; ++k;
+          if (k == div) { k = 0; ++a; }
+          if (c == (uint32_t)S.Ch) { c = 0; a = 0; k = 0; ++b; }
+        }
+      }
+    }
+    if (GRAD) out.v[e] = E::st(res);
+  }
+  if (GRAD) {
+    T* dp = (T*)S.dx + m0;
+    if (S.vec && cnt == V) {
+      *(Vec<T, V>*)dp = out;
+    } else {
+#pragma unroll
+      for (int e = 0; e < V; ++e)
+        if (e < cnt) dp[e] = out.v[e];
+    }
+  }
+  return sum;
+}
+
+template <int DT, bool GRAD>
+__global__ __launch_bounds__(LT) void loss_dense_kernel(const DenseArgs A, const float* __restrict__ g,
+                                                        const float* __restrict__ avg, double* __restrict__ partials) {
+  float s_cls = 0.f, s_reg = 0.f;
+  if (GRAD) {
+    const float d = avg[0];
+    s_cls = __fdiv_rn(g[0], d);
+    s_reg = __fdiv_rn(g[1], d);
+  }
+  double acc_cls = 0.0, acc_reg = 0.0;
+  for (int64_t g0 = (int64_t)blockIdx.x * LT; g0 < A.nchunks; g0 += (int64_t)gridDim.x * LT) {
+    const int64_t gc = g0 + threadIdx.x;
+    for (int s = 0; s < A.nseg; ++s) {                     // s is uniform: the segment comes through scalar loads
+      const DenseSeg& S = A.seg[s];
+      if (S.chunk0 + S.nchunks <= g0 || S.chunk0 >= g0 + LT) continue;
+      if (gc >= S.chunk0 && gc < S.chunk0 + S.nchunks) {
+        const double sum = dense_chunk<DT, GRAD>(S, A, (uint32_t)(gc - S.chunk0), s_cls, s_reg);
+        acc_cls += S.reg ? 0.0 : sum;            // selects, not a branch: both accumulators stay in registers
+        acc_reg += S.reg ? sum : 0.0;
+      }
+    }
+  }
+  if (!GRAD) block_partial(acc_cls, acc_reg, 0.0, partials);
+}
+
+// ---- last launch: partials in index order, divisor, one rounding ------------------------------------------------------
+struct AvgArgs {
+  const int32_t* a;
+  const int32_t* b;
+  int32_t na, nb, mode;
+  float value;
+};
+
+__global__ __launch_bounds__(LMAX_BLOCKS) void loss_finalize_kernel(const double* __restrict__ partials, int nparts,
+                                                                    const AvgArgs V, float* __restrict__ losses,
+                                                                    float* __restrict__ avg_out) {
+  __shared__ double stage[LMAX_BLOCKS][3];
+  const int t = threadIdx.x;
+  if (t < nparts) {
+    stage[t][0] = partials[(size_t)t * PART + 0];
+    stage[t][1] = partials[(size_t)t * PART + 1];
+    stage[t][2] = partials[(size_t)t * PART + 2];
+  }
+  __syncthreads();
+  if (t != 0) return;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int i = 0; i < nparts; ++i) {
+    s0 += stage[i][0];
+    s1 += stage[i][1];
+    s2 += stage[i][2];
+  }
+  float avg;
+  if (V.mode == 0) {
+    avg = V.value;
+  } else {
+    long long n = 0;
+    if (V.mode == 1) {
+      for (int i = 0; i < V.na; ++i) n += V.a[i];
+      for (int i = 0; i < V.nb; ++i) n += V.b[i];
+    } else {
+      n = (long long)s2;                         // a count of rows: exact in fp64
+    }
+    avg = (float)(n < 1 ? 1ll : n);
+  }
+  losses[0] = (float)(s0 / (double)avg);
+  losses[1] = (float)(s1 / (double)avg);
+  avg_out[0] = avg;
+}
+
+// ---- RoI box head ---------------------------------------------------------------------------------------------------
+// One wavefront per row; lane l holds columns l, l + 64, ... (at most 16).  S is added in fp64: lane-local in column
+// order, then the xor tree, then rounded once to fp32.
+constexpr int RCOLS = TDN_LOSS_MAX_CLASSES / 64;
+
+struct RoiArgs {
+  const void* cls;
+  const void* reg;
+  void* dcls;
+  void* dreg;
+  const int64_t* labels;
+  const float* lw;
+  const float* bt;
+  const float* bw;
+  int32_t R, C, reg_cols;
+  float beta;
+};
+
+template <int DT, bool GRAD>
+__global__ __launch_bounds__(LT) void loss_roi_kernel(const RoiArgs A, const float* __restrict__ g,
+                                                      const float* __restrict__ avg, double* __restrict__ partials) {
+  typedef Elem<DT> E;
+  typedef typename E::T T;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float s_cls = 0.f, s_reg = 0.f;
+  if (GRAD) {
+    const float d = avg[0];
+    s_cls = __fdiv_rn(g[0], d);
+    s_reg = __fdiv_rn(g[1], d);
+  }
+  double acc_cls = 0.0, acc_reg = 0.0, acc_cnt = 0.0;
+  const int C = A.C;
+  for (int r = blockIdx.x * LWAVES + wave; r < A.R; r += gridDim.x * LWAVES) {
+    const float w = A.lw[r];
+    const long long lab = A.labels[r];
+    if (!GRAD && lane == 0 && w > 0.f) acc_cnt += 1.0;
+    const bool live = w != 0.f && lab >= 0 && lab < C;         // wave-uniform
+    const int il = (int)lab;
+    const T* xr = (const T*)A.cls + (size_t)r * C;
+    T* dr = GRAD ? (T*)A.dcls + (size_t)r * C : nullptr;
+    T* br = GRAD ? (T*)A.dreg + (size_t)r * A.reg_cols : nullptr;
+    if (!live) {
+      if (GRAD) {
+        for (int c = lane; c < C; c += 64) dr[c] = E::st(0.f);
+        for (int c = lane; c < A.reg_cols; c += 64) br[c] = E::st(0.f);
+      }
+      continue;
+    }
+    float x[RCOLS];
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < RCOLS; ++j) {
+      const int c = lane + 64 * j;
+      x[j] = c < C ? E::ld(xr[c]) : -INFINITY;
+      m = fmaxf(m, x[j]);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    double sd = 0.0;
+    float zl = 0.f;                                            // z of the label's column, on the lane that holds it
+#pragma unroll
+    for (int j = 0; j < RCOLS; ++j) {
+      const int c = lane + 64 * j;
+      if (c < C) {
+        const float z = __fsub_rn(x[j], m);
+        x[j] = expf(z);
+        sd += (double)x[j];
+        if (c == il) zl = z;
+      }
+    }
+    const float S = (float)wave_sum(sd);
+    if (!GRAD) {
+      if (lane == (il & 63)) acc_cls += (double)__fmul_rn(w, __fsub_rn(logf(S), zl));
+    } else {
+#pragma unroll
+      for (int j = 0; j < RCOLS; ++j) {
+        const int c = lane + 64 * j;
+        if (c < C) {
+          const float d = __fsub_rn(__fdiv_rn(x[j], S), c == il ? 1.f : 0.f);
+          dr[c] = E::st(__fmul_rn(__fmul_rn(w, d), s_cls));
+        }
+      }
+    }
+    // box columns of the row's label (class-specific) or the four there are
+    const int col0 = A.reg_cols == 4 ? 0 : 4 * il;
+    if (GRAD) {
+      for (int c = lane; c < A.reg_cols; c += 64)
+        if (c < col0 || c >= col0 + 4) br[c] = E::st(0.f);
+    }
+    if (lane < 4) {
+      const float bw = A.bw[(size_t)r * 4 + lane];
+      float res = 0.f;
+      if (bw != 0.f) {
+        const float pred = E::ld(((const T*)A.reg)[(size_t)r * A.reg_cols + col0 + lane]);
+        const float v = smooth_l1<GRAD>(pred, A.bt[(size_t)r * 4 + lane], A.beta);
+        if (GRAD) res = __fmul_rn(__fmul_rn(bw, v), s_reg);
+        else acc_reg += (double)__fmul_rn(bw, v);
+      }
+      if (GRAD) br[col0 + lane] = E::st(res);
+    }
+  }
+  if (!GRAD) block_partial(acc_cls, acc_reg, acc_cnt, partials);
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------
+inline int64_t align256(int64_t x) { return (x + 255) & ~255ll; }
+
+int elem_bytes(int dtype) { return dtype == TDN_F32 ? 4 : 2; }
+
+int check_avg(const char* who, const tdn_loss_avg* avg, bool roi, AvgArgs* out) {
+  TDN_CHECK(avg != nullptr, "%s: NULL avg", who);
+  TDN_CHECK(avg->mode == 0 || avg->mode == 1 || (roi && avg->mode == 2), "%s: avg mode %d", who, avg->mode);
+  if (avg->mode == 0) TDN_CHECK(avg->value > 0.f && avg->value < INFINITY, "%s: avg value must be finite and > 0", who);
+  if (avg->mode == 1) {
+    TDN_CHECK(avg->na >= 0 && avg->na <= TDN_LOSS_MAX_AVG && avg->nb >= 0 && avg->nb <= TDN_LOSS_MAX_AVG,
+              "%s: an avg tensor has more than %d elements", who, TDN_LOSS_MAX_AVG);
+    TDN_CHECK((avg->na == 0 || avg->a) && (avg->nb == 0 || avg->b), "%s: NULL avg tensor", who);
+  }
+  out->a = avg->a;
+  out->b = avg->b;
+  out->na = avg->mode == 1 ? avg->na : 0;
+  out->nb = avg->mode == 1 ? avg->nb : 0;
+  out->mode = avg->mode;
+  out->value = avg->value;
+  return 0;
+}
+
+// fills the segment table; returns the number of workgroups, or -1 with the error set
+int dense_plan(const char* who, const tdn_loss_level* levels, int L, int B, const tdn_loss_config* cfg, bool grad,
+               DenseArgs* D) {
+  TDN_CHECK(levels && cfg, "%s: NULL argument", who);
+  TDN_CHECK(L >= 1 && L <= TDN_LOSS_MAX_LEVELS, "%s: %d levels (1..%d)", who, L, TDN_LOSS_MAX_LEVELS);
+  TDN_CHECK(B >= 1 && B <= 64, "%s: B=%d out of 1..64", who, B);
+  TDN_CHECK(cfg->dtype == TDN_F32 || cfg->dtype == TDN_BF16 || cfg->dtype == TDN_F16, "%s: dtype %d", who, cfg->dtype);
+  TDN_CHECK(cfg->num_anchors >= 1 && cfg->num_classes >= 1 && cfg->num_classes <= TDN_LOSS_MAX_CLASSES,
+            "%s: A=%d, C=%d (C in 1..%d)", who, cfg->num_anchors, cfg->num_classes, TDN_LOSS_MAX_CLASSES);
+  TDN_CHECK(cfg->beta > 0.f && cfg->beta < INFINITY, "%s: beta must be finite and > 0", who);
+  if (cfg->focal)
+    TDN_CHECK(cfg->gamma >= 0.f && cfg->gamma < INFINITY && cfg->alpha >= 0.f && cfg->alpha <= 1.f,
+              "%s: focal needs gamma >= 0 and alpha in [0, 1]", who);
+  memset(D, 0, sizeof(*D));
+  const int A = cfg->num_anchors, C = cfg->num_classes;
+  const int V = 16 / elem_bytes(cfg->dtype);
+  int64_t N = 0, chunk = 0;
+  int ns = 0;
+  for (int l = 0; l < L; ++l) {
+    const tdn_loss_level& lv = levels[l];
+    TDN_CHECK(lv.H >= 1 && lv.W >= 1, "%s: level %d is %d x %d", who, l, lv.H, lv.W);
+    const int64_t HW = (int64_t)lv.H * lv.W;
+    TDN_CHECK(lv.cls && lv.reg && (!grad || (lv.dcls && lv.dreg)), "%s: level %d: NULL pointer", who, l);
+    for (int k = 0; k < 2; ++k) {
+      const int64_t Ch = k ? 4ll * A : (int64_t)A * C;
+      const int64_t n = (int64_t)B * Ch * HW;
+      TDN_CHECK(n < (1ll << 31), "%s: level %d holds %lld elements (2^31 or more)", who, l, (long long)n);
+      DenseSeg& S = D->seg[ns++];
+      S.x = k ? lv.reg : lv.cls;
+      S.dx = k ? lv.dreg : lv.dcls;
+      S.n = (uint32_t)n;
+      S.nchunks = (uint32_t)((n + V - 1) / V);
+      S.chunk0 = chunk;
+      S.Ch = (int32_t)Ch;
+      S.HW = (int32_t)HW;
+      S.nhwc = (k ? lv.reg_nhwc : lv.cls_nhwc) ? 1 : 0;
+      S.reg = k;
+      S.off = (int32_t)N;
+      S.vec = (((uintptr_t)S.x | (grad ? (uintptr_t)S.dx : 0)) & 15) == 0;
+      chunk += S.nchunks;
+    }
+    N += HW * A;
+    TDN_CHECK(N <= TDN_LOSS_MAX_ROWS, "%s: more than %d anchors per image", who, TDN_LOSS_MAX_ROWS);
+  }
+  D->nseg = ns;
+  D->nchunks = chunk;
+  D->N = (int32_t)N;
+  D->A = A;
+  D->C = C;
+  D->beta = cfg->beta;
+  D->P.focal = cfg->focal ? 1 : 0;
+  D->P.gamma = cfg->gamma;
+  D->P.alpha = cfg->alpha;
+  D->P.one_minus_alpha = 1.f - cfg->alpha;
+  const int64_t blocks = (chunk + LT - 1) / LT;
+  return (int)(blocks < LMAX_BLOCKS ? blocks : LMAX_BLOCKS);
+}
+
+int roi_blocks(int R) {
+  const int b = (R + LWAVES - 1) / LWAVES;
+  return b < 1 ? 1 : (b < LMAX_BLOCKS ? b : LMAX_BLOCKS);
+}
+
+int check_roi(const char* who, int dtype, int R, int C, int reg_cols, float beta) {
+  TDN_CHECK(dtype == TDN_F32 || dtype == TDN_BF16 || dtype == TDN_F16, "%s: dtype %d", who, dtype);
+  TDN_CHECK(R >= 0 && R <= TDN_LOSS_MAX_ROWS, "%s: R=%d out of 0..%d", who, R, TDN_LOSS_MAX_ROWS);
+  TDN_CHECK(C >= 1 && C <= TDN_LOSS_MAX_CLASSES, "%s: C=%d out of 1..%d", who, C, TDN_LOSS_MAX_CLASSES);
+  TDN_CHECK(reg_cols == 4 || reg_cols == 4 * C, "%s: bbox_pred has %d columns, neither 4 nor 4C", who, reg_cols);
+  TDN_CHECK(beta > 0.f && beta < INFINITY, "%s: beta must be finite and > 0", who);
+  return 0;
+}
+
+#define LOSS_LAUNCH_DT(kernel, GRAD, dtype, grid, st, ...)                                             \
+  do {                                                                                                 \
+    if ((dtype) == TDN_F32) TDN_LAUNCH((kernel<TDN_F32, GRAD>), grid, dim3(LT), 0, st, __VA_ARGS__);    \
+    else if ((dtype) == TDN_F16) TDN_LAUNCH((kernel<TDN_F16, GRAD>), grid, dim3(LT), 0, st, __VA_ARGS__); \
+    else TDN_LAUNCH((kernel<TDN_BF16, GRAD>), grid, dim3(LT), 0, st, __VA_ARGS__);                       \
+  } while (0)
+
+}  // namespace
+
+extern "C" int64_t tdn_loss_dense_workspace_bytes(const tdn_loss_level* levels, int num_levels, int B,
+                                                  const tdn_loss_config* cfg) {
+  if (!levels || !cfg || num_levels < 1 || num_levels > TDN_LOSS_MAX_LEVELS || B < 1 || B > 64) return -1;
+  if (cfg->dtype != TDN_F32 && cfg->dtype != TDN_BF16 && cfg->dtype != TDN_F16) return -1;
+  if (cfg->num_anchors < 1 || cfg->num_classes < 1 || cfg->num_classes > TDN_LOSS_MAX_CLASSES) return -1;
+  const int V = 16 / elem_bytes(cfg->dtype);
+  int64_t chunks = 0, N = 0;
+  for (int l = 0; l < num_levels; ++l) {
+    if (levels[l].H < 1 || levels[l].W < 1) return -1;
+    const int64_t HW = (int64_t)levels[l].H * levels[l].W;
+    const int64_t ncls = (int64_t)B * cfg->num_anchors * cfg->num_classes * HW, nreg = (int64_t)B * 4 * cfg->num_anchors * HW;
+    if (ncls >= (1ll << 31) || nreg >= (1ll << 31)) return -1;
+    chunks += (ncls + V - 1) / V + (nreg + V - 1) / V;
+    N += HW * cfg->num_anchors;
+    if (N > TDN_LOSS_MAX_ROWS) return -1;
+  }
+  const int64_t blocks = (chunks + LT - 1) / LT;
+  return align256((blocks < LMAX_BLOCKS ? blocks : LMAX_BLOCKS) * PART * 8);
+}
+
+extern "C" int tdn_loss_dense_fwd(const tdn_loss_level* levels, int num_levels, int B, const tdn_loss_config* cfg,
+                                  const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                                  const float* bbox_weights, const tdn_loss_avg* avg, float* losses, float* avg_out,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_loss_dense_fwd";
+  DenseArgs D;
+  AvgArgs V;
+  const int blocks = dense_plan(who, levels, num_levels, B, cfg, false, &D);
+  if (blocks < 0 || check_avg(who, avg, false, &V) != 0) return -1;
+  TDN_CHECK(labels && label_weights && bbox_targets && bbox_weights && losses && avg_out && workspace,
+            "%s: NULL pointer", who);
+  TDN_CHECK(workspace_bytes >= (int64_t)blocks * PART * 8, "%s: workspace too small", who);
+  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  D.labels = labels;
+  D.lw = label_weights;
+  D.bt = bbox_targets;
+  D.bw = bbox_weights;
+  double* partials = (double*)workspace;
+  const float* none = nullptr;
+  LOSS_LAUNCH_DT(loss_dense_kernel, false, cfg->dtype, dim3(blocks), stream, D, none, none, partials);
+  TDN_LAUNCH_CHECK();
+  TDN_LAUNCH(loss_finalize_kernel, dim3(1), dim3(LMAX_BLOCKS), 0, stream, (const double*)partials, blocks, V, losses,
+             avg_out);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tdn_loss_dense_bwd(const tdn_loss_level* levels, int num_levels, int B, const tdn_loss_config* cfg,
+                                  const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                                  const float* bbox_weights, const float* g, const float* avg_in, void* stream) {
+  const char* who = "tdn_loss_dense_bwd";
+  DenseArgs D;
+  const int blocks = dense_plan(who, levels, num_levels, B, cfg, true, &D);
+  if (blocks < 0) return -1;
+  TDN_CHECK(labels && label_weights && bbox_targets && bbox_weights && g && avg_in, "%s: NULL pointer", who);
+  D.labels = labels;
+  D.lw = label_weights;
+  D.bt = bbox_targets;
+  D.bw = bbox_weights;
+  double* none = nullptr;
+  LOSS_LAUNCH_DT(loss_dense_kernel, true, cfg->dtype, dim3(blocks), stream, D, g, avg_in, none);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int64_t tdn_loss_roi_workspace_bytes(int R) {
+  if (R < 0 || R > TDN_LOSS_MAX_ROWS) return -1;
+  return align256((int64_t)roi_blocks(R) * PART * 8);
+}
+
+extern "C" int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
+                                const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                                const float* bbox_weights, float beta, const tdn_loss_avg* avg, float* losses,
+                                float* avg_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_loss_roi_fwd";
+  AvgArgs V;
+  if (check_roi(who, dtype, R, C, reg_cols, beta) != 0 || check_avg(who, avg, true, &V) != 0) return -1;
+  TDN_CHECK(losses && avg_out && workspace, "%s: NULL pointer", who);
+  TDN_CHECK(R == 0 || (cls && reg && labels && label_weights && bbox_targets && bbox_weights), "%s: NULL pointer", who);
+  const int blocks = roi_blocks(R);
+  TDN_CHECK(workspace_bytes >= (int64_t)blocks * PART * 8, "%s: workspace too small", who);
+  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  RoiArgs A;
+  memset(&A, 0, sizeof(A));
+  A.cls = cls;
+  A.reg = reg;
+  A.labels = labels;
+  A.lw = label_weights;
+  A.bt = bbox_targets;
+  A.bw = bbox_weights;
+  A.R = R;
+  A.C = C;
+  A.reg_cols = reg_cols;
+  A.beta = beta;
+  double* partials = (double*)workspace;
+  const float* none = nullptr;
+  LOSS_LAUNCH_DT(loss_roi_kernel, false, dtype, dim3(blocks), stream, A, none, none, partials);
+  TDN_LAUNCH_CHECK();
+  TDN_LAUNCH(loss_finalize_kernel, dim3(1), dim3(LMAX_BLOCKS), 0, stream, (const double*)partials, blocks, V, losses,
+             avg_out);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tdn_loss_roi_bwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
+                                const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                                const float* bbox_weights, float beta, const float* g, const float* avg_in, void* dcls,
+                                void* dreg, void* stream) {
+  const char* who = "tdn_loss_roi_bwd";
+  if (check_roi(who, dtype, R, C, reg_cols, beta) != 0) return -1;
+  if (R == 0) return 0;
+  TDN_CHECK(cls && reg && labels && label_weights && bbox_targets && bbox_weights && g && avg_in && dcls && dreg,
+            "%s: NULL pointer", who);
+  RoiArgs A;
+  memset(&A, 0, sizeof(A));
+  A.cls = cls;
+  A.reg = reg;
+  A.dcls = dcls;
+  A.dreg = dreg;
+  A.labels = labels;
+  A.lw = label_weights;
+  A.bt = bbox_targets;
+  A.bw = bbox_weights;
+  A.R = R;
+  A.C = C;
+  A.reg_cols = reg_cols;
+  A.beta = beta;
+  double* none = nullptr;
+  LOSS_LAUNCH_DT(loss_roi_kernel, true, dtype, dim3(roi_blocks(R)), stream, A, g, avg_in, none);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
