@@ -554,7 +554,7 @@ def test_bbox_deltas(ops, guard, T):
     guard.clean()
 
 
-@pytest.mark.parametrize("sizes", [[1500], [0, 1, 700], [300, 0, 1, 2, 2000, 64, 65, 129, 4096, 17]])
+@pytest.mark.parametrize("sizes", [[1500], [0, 1, 700], [300, 0, 1, 2, 2000, 64, 65, 129, 4096, 17], [0, 0]])
 def test_batched_nms(ops, guard, T, sizes):
     PR.test_batched_nms_vs_oracle(T, sizes)
     guard.clean()

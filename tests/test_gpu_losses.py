@@ -427,6 +427,15 @@ def test_guarded_roi(T, guard, dt):
         _clean(guard, ["bbox_head_loss_fwd", "bbox_head_loss_bwd"])
 
 
+def test_guarded_roi_no_rows(T, guard):
+    """R = 0 still runs one workgroup and the last launch: losses of 0, a divisor of 1."""
+    from torch_detection_amd import loss_ops
+    z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device="cuda")
+    losses, avg = loss_ops.bbox_head_loss_fwd(z(0, 5), z(0, 20), z(0, dt=torch.int64), z(0), z(0, 4), z(0, 4), None, 1.0)
+    _clean(guard, [])
+    assert losses.tolist() == [0.0, 0.0] and avg.tolist() == [1.0]
+
+
 def test_every_loss_entry_point_ran_under_the_guard():
     """Counts what the guarded tests above did IN THIS RUN (run the file as a whole): every public wrapper of
     loss_ops.py returned under the guard, and every tdn_loss*_workspace_bytes query was answered at its exact size

@@ -315,6 +315,45 @@ def test_guarded_sample_rois(T, guard):
         _clean(guard, ["sample_rois"])
 
 
+def test_guarded_placeholder_regions(T, guard):
+    """The shapes at which a workspace region would be empty and holds one placeholder element instead (DESIGN.md
+    §5d): no ground truths, no anchors, no proposals.  The answers follow from the spec without the oracle."""
+    anchors = torch.tensor([[0, 0, 9, 9], [5, 5, 20, 20], [30, 30, 40, 45], [2, 3, 11, 12], [50, 50, 60, 60]],
+                           dtype=torch.float32, device="cuda")
+    ish = torch.tensor([(100, 100), (80, 90)], dtype=torch.int32, device="cuda")
+    none = torch.zeros(2, dtype=torch.int32, device="cuda")
+    # G = 0: every anchor is a negative, num = 4 of the 5 are sampled
+    got = T.anchor_target(anchors, None, torch.zeros(2, 0, 4, device="cuda"), none, ish, num=4)
+    _clean(guard, [])
+    labels, lw, bt, bwt, npos, nneg, assigned = [g.cpu() for g in got]
+    assert assigned.shape == (2, 5) and bool((assigned == 0).all()) and bool((labels == 0).all())
+    assert npos.tolist() == [0, 0] and nneg.tolist() == [4, 4] and lw.sum(1).tolist() == [4.0, 4.0]
+    assert bool((bt == 0).all()) and bool((bwt == 0).all())
+    # N = 0: empty outputs, counts of 0
+    gt = torch.tensor([[[0, 0, 9, 9], [30, 30, 40, 45], [60, 10, 80, 25]], [[5, 5, 20, 20], [0, 0, 0, 0], [0, 0, 0, 0]]],
+                      dtype=torch.float32, device="cuda")
+    cnt = torch.tensor([3, 1], dtype=torch.int32, device="cuda")
+    got = T.anchor_target(torch.zeros(0, 4, device="cuda"), None, gt, cnt, ish, num=4)
+    _clean(guard, [])
+    assert got[0].shape == (2, 0) and got[2].shape == (2, 0, 4) and got[4].tolist() == [0, 0] and got[5].tolist() == [0, 0]
+    # P = 0 with the ground truths added: each is its own positive, in index order, with a zero target
+    lab = torch.tensor([[7, 8, 9], [3, 0, 0]], dtype=torch.int64, device="cuda")
+    got = T.sample_rois(torch.zeros(2, 0, 5, device="cuda"), none, gt, lab, cnt, num=8, pos_fraction=0.5)
+    _clean(guard, [])
+    rois, labels, lw, bt, bwt, inds, npos, nneg = [g.cpu() for g in got]
+    assert npos.tolist() == [3, 1] and nneg.tolist() == [0, 0]
+    assert torch.equal(rois[:3, 1:], gt[0].cpu()) and rois[:3, 0].tolist() == [0, 0, 0] and bool((rois[3:8, 0] == -1).all())
+    assert torch.equal(rois[8, 1:], gt[1, 0].cpu()) and rois[8, 0] == 1 and bool((rois[9:, 0] == -1).all())
+    assert labels.tolist() == [7, 8, 9, 0, 0, 0, 0, 0, 3, 0, 0, 0, 0, 0, 0, 0]
+    assert inds.tolist() == [0, 1, 2, -1, -1, -1, -1, -1, 0, -1, -1, -1, -1, -1, -1, -1]
+    assert lw.tolist() == [float(i >= 0) for i in inds.tolist()] and bool((bt == 0).all())
+    assert bwt[:, 0].tolist() == lw.tolist()
+    # and without them there is no candidate at all
+    got = T.sample_rois(torch.zeros(2, 0, 5, device="cuda"), none, gt, lab, cnt, num=8, add_gt_as_proposals=False)
+    _clean(guard, [])
+    assert got[6].tolist() == [0, 0] and got[7].tolist() == [0, 0] and bool((got[0][:, 0] == -1).all())
+
+
 def test_every_target_entry_point_ran_under_the_guard():
     """Counts what the three tests above did IN THIS RUN (run the file as a whole): every public wrapper of
     target_ops.py returned under the guard, and every workspace query of the target block of include/tdn.h was

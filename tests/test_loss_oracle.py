@@ -197,6 +197,32 @@ def test_struct_mirrors_match_the_header(tmp_path):
     assert lib.tdn_loss_roi_workspace_bytes(-1) < 0
 
 
+def test_workspace_sizes_are_the_design_table():
+    """DESIGN.md §5d worked by hand: 32 bytes per workgroup of the forward launch, rounded up to 256."""
+    from torch_detection_amd import _lib
+    lib = _lib.load()
+    # RoI head: a workgroup takes 16 rows, 256 workgroups at most
+    assert lib.tdn_loss_roi_workspace_bytes(1031) == 2304              # 65 workgroups: 2080 -> 2304
+    assert lib.tdn_loss_roi_workspace_bytes(0) == 256                  # still one workgroup
+    assert lib.tdn_loss_roi_workspace_bytes(1 << 20) == 256 * 32
+    assert lib.tdn_loss_roi_workspace_bytes((1 << 20) + 1) == -1 and lib.tdn_loss_roi_workspace_bytes(-1) == -1
+    # dense heads, B = 2, A = 3, C = 80, levels 13 x 21 and 7 x 11: a workgroup takes 1024 chunks of 16 bytes.
+    # fp32 (4 per chunk): 131040 / 4 + 6552 / 4 + 36960 / 4 + 1848 / 4 = 32760 + 1638 + 9240 + 462 = 44100 chunks,
+    # 44 workgroups: 1408 -> 1536.  bf16 (8 per chunk): 16380 + 819 + 4620 + 231 = 22050 chunks, 22: 704 -> 768
+    lv = (_lib.LossLevel * 2)()
+    (lv[0].H, lv[0].W), (lv[1].H, lv[1].W) = (13, 21), (7, 11)        # a size query does not look at the pointers
+    cfg = _lib.LossConfig(dtype=_lib.TDN_F32, num_anchors=3, num_classes=80, beta=1.0)
+    assert lib.tdn_loss_dense_workspace_bytes(lv, 2, 2, ctypes.byref(cfg)) == 1536
+    cfg.dtype = _lib.TDN_BF16
+    assert lib.tdn_loss_dense_workspace_bytes(lv, 2, 2, ctypes.byref(cfg)) == 768
+    assert lib.tdn_loss_dense_workspace_bytes(lv, 2, 65, ctypes.byref(cfg)) == -1
+    assert lib.tdn_loss_dense_workspace_bytes(lv, 9, 2, ctypes.byref(cfg)) == -1
+    cfg.num_classes = 1025
+    assert lib.tdn_loss_dense_workspace_bytes(lv, 2, 2, ctypes.byref(cfg)) == -1
+    cfg.num_classes, lv[1].W = 80, 0
+    assert lib.tdn_loss_dense_workspace_bytes(lv, 2, 2, ctypes.byref(cfg)) == -1
+
+
 def test_host_refusals_need_no_gpu():
     import torch_detection_amd as T
     cls, reg, labels, lw, bt, bw = [[torch.from_numpy(a) for a in v] if isinstance(v, list) else torch.from_numpy(v)

@@ -70,6 +70,16 @@ def test_nms_known_answers():
     assert np.array_equal(k1, k2) and np.array_equal(kk1[:c], kk2)
 
 
+def test_nms_workspace_size_is_the_design_table():
+    """DESIGN.md §5d worked by hand (host arithmetic: no device is touched)."""
+    from torch_detection_amd import _lib
+    lib = _lib.load()
+    # N = 200, 4 column blocks: rank and order 800 -> 1024 each, sboxes 3200 -> 3328, mask 200 * 4 * 8 = 6400, 256 spare
+    assert lib.tdn_nms_workspace(200) == 2 * 1024 + 3328 + 6400 + 256
+    assert lib.tdn_nms_workspace(1) == 4 * 256 + 256
+    assert lib.tdn_nms_workspace(0) == 256 and lib.tdn_nms_workspace(-1) == 256
+
+
 def test_bbox_norm_oracle_vs_reference_golden(golden_dir=None):
     """Box delta (de)normalisation: the numpy restatement reproduces vectors captured from the reference's own
     datasets/utils/bbox.py:118-166 bit for bit (this row IS pinned by the reference)."""

@@ -172,3 +172,28 @@ def test_rpn_host_validation_without_a_gpu():
     lv[1].dtype = 1                                          # TDN_F16 is not an input type here
     assert lib.tdn_rpn_proposals_workspace(lv, 2, 2, ctypes.byref(cfg)) < 0
     assert lib.tdn_batched_nms_workspace(10000, 3) > 0 and lib.tdn_batched_nms_workspace(-1, 3) < 0
+
+
+def test_workspace_sizes_are_the_design_table():
+    """DESIGN.md §5d worked by hand: every region rounded up to 256 bytes, in the table's order."""
+    from torch_detection_amd import _lib
+    lib = _lib.load()
+    # batched NMS, N = 1000, S = 5, pitch = ceil(1000 / 64) = 16:
+    # order 4000 -> 4096, sboxes 16000 -> 16128, seg_start and seg_count 20 -> 256 each, mask 1000 * 16 * 8 = 128000
+    assert lib.tdn_batched_nms_workspace(1000, 5) == 4096 + 16128 + 2 * 256 + 128000
+    # the placeholders: N = 0 counts as one row (pitch 1), S = 0 as one segment: five regions of 256
+    assert lib.tdn_batched_nms_workspace(0, 3) == 5 * 256 and lib.tdn_batched_nms_workspace(0, 0) == 5 * 256
+    assert lib.tdn_batched_nms_workspace(10, -1) == -1
+    # RPN, B = 2, levels 50 x 84 and 13 x 21 with A = 3, nms_pre = 2000: cap = (2000, 819), R = 2 * 2819 = 5638 rows,
+    # S = 4 segments, pitch = ceil(2000 / 64) = 32:
+    # seg_box 90208 -> 90368, seg_key and seg_aidx 22552 -> 22784 each, kept 45104 -> 45312,
+    # seg_start / seg_count / num_kept 16 -> 256 each, mask 5638 * 32 * 8 = 1443328
+    lv = (_lib.RpnLevel * 2)()
+    for v, (h, w) in zip(lv, [(50, 84), (13, 21)]):
+        v.dtype, v.H, v.W, v.A = _lib.TDN_BF16, h, w, 3
+        v.logits = v.deltas = v.anchors = 256                # never dereferenced on the host
+    cfg = _lib.RpnConfig(nms_pre=2000, nms_post=2000, max_num=2000, nms_thr=0.7)
+    assert lib.tdn_rpn_proposals_workspace(lv, 2, 2, ctypes.byref(cfg)) == 90368 + 2 * 22784 + 45312 + 3 * 256 + 1443328
+    lv[0].H = lv[1].H = 0                                    # every level empty: one placeholder row, pitch 1
+    assert lib.tdn_rpn_proposals_workspace(lv, 2, 2, ctypes.byref(cfg)) == 8 * 256
+    assert lib.tdn_rpn_proposals_workspace(lv, 2, 0, ctypes.byref(cfg)) == -1

@@ -191,3 +191,13 @@ def test_roi_host_validation_without_a_gpu():
     assert lib.tdn_roi_align_fwd(lv, 2, 2, 64, None, 0, ctypes.byref(cfg), None, None) < 0
     assert lib.tdn_roi_align_bwd_workspace(1000) >= 1000 * 48 and lib.tdn_roi_align_bwd_workspace(-1) < 0
     assert lib.tdn_roi_map_levels(None, 0, 9, 56.0, None, None) < 0
+
+
+def test_bwd_workspace_size_is_the_design_table():
+    """DESIGN.md §5d worked by hand: a 32-byte record and a 16-byte geometry vector per row, each region rounded up
+    to 256 bytes."""
+    from torch_detection_amd import _lib
+    lib = _lib.load()
+    assert lib.tdn_roi_align_bwd_workspace(1001) == 32256 + 16128      # 32032 -> 126 * 256, 16016 -> 63 * 256
+    assert lib.tdn_roi_align_bwd_workspace(0) == 2 * 256               # R = 0 counts as one row
+    assert lib.tdn_roi_align_bwd_workspace(-1) == -1 and lib.tdn_roi_align_bwd_workspace(1 << 31) == -1

@@ -40,6 +40,28 @@ def test_package_exports_the_four_entry_points_and_mirrors_the_header(tmp_path):
     assert lib.tdn_sample_rois_workspace_bytes(2, 2000, 100, 1) > lib.tdn_sample_rois_workspace_bytes(2, 2000, 100, 0) > 0
 
 
+def test_workspace_sizes_are_the_design_table():
+    """DESIGN.md §5d worked by hand: every region rounded up to 256 bytes, in the table's order."""
+    from torch_detection_amd import _lib
+    lib = _lib.load()
+    # assignment, B = 3, G = 70: colmax and first are 210 words = 840 -> 1024 bytes each; G = 0 counts as one column
+    assert lib.tdn_assign_max_iou_workspace_bytes(3, 70) == 2 * 1024
+    assert lib.tdn_assign_max_iou_workspace_bytes(2, 0) == 2 * 256
+    assert lib.tdn_assign_max_iou_workspace_bytes(0, 4) == -1 and lib.tdn_assign_max_iou_workspace_bytes(2, -1) == -1
+    # anchor_target, B = 3, N = 1000, G = 70: the assignment words, then two masks of 3000 -> 3072 bytes
+    assert lib.tdn_anchor_target_workspace_bytes(3, 1000, 70) == 2 * 1024 + 2 * 3072
+    assert lib.tdn_anchor_target_workspace_bytes(2, 0, 0) == 2 * 256 + 2 * 256          # N = 0 counts as one box
+    assert lib.tdn_anchor_target_workspace_bytes(2, (1 << 20) + 1, 4) == -1
+    assert lib.tdn_anchor_target_workspace_bytes(2, -1, 4) == -1
+    # sample_rois, B = 2, P = 2000, G = 100: assignment words 800 -> 1024 each; with the ground truths added Nc = 2100:
+    # assigned 4200 * 4 = 16800 -> 16896, masks 4200 -> 4352 each; without, Nc = 2000: 16000 -> 16128, 4000 -> 4096
+    assert lib.tdn_sample_rois_workspace_bytes(2, 2000, 100, 1) == 2 * 1024 + 16896 + 2 * 4352
+    assert lib.tdn_sample_rois_workspace_bytes(2, 2000, 100, 0) == 2 * 1024 + 16128 + 2 * 4096
+    assert lib.tdn_sample_rois_workspace_bytes(2, 0, 0, 1) == 2 * 256 + 256 + 2 * 256   # Nc = 0 counts as one box
+    assert lib.tdn_sample_rois_workspace_bytes(2, (1 << 20) - 255, 4, 0) == -1
+    assert lib.tdn_sample_rois_workspace_bytes(65, 10, 4, 0) == -1
+
+
 # ---- an independent restatement in torch (mmdetection's formulation: (G, N) overlaps, max over both axes) ----------
 def torch_iou(a, b):
     lt = torch.max(a[:, None, :2], b[None, :, :2])

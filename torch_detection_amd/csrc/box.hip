@@ -36,10 +36,8 @@ extern "C" int tdn_anchor_grid(const float* base_anchors, int A, int featH, int 
   TDN_CHECK(total < (1ll << 30), "tdn_anchor_grid: too many anchors");
   if (total == 0) return 0;
   TDN_CHECK(base_anchors && anchors, "tdn_anchor_grid: NULL pointer");
-  int grid = (int)((total + 255) / 256);
-  if (grid > 4096) grid = 4096;
-  TDN_LAUNCH(anchor_grid_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, base_anchors, A, featH,
-                     featW, stride, valid_h, valid_w, anchors, valid);
+  TDN_LAUNCH(anchor_grid_kernel, dim3(tdn_grid_1d(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, base_anchors, A,
+             featH, featW, stride, valid_h, valid_w, anchors, valid);
   TDN_LAUNCH_CHECK();
   return 0;
 }
@@ -99,9 +97,8 @@ extern "C" int tdn_anchor_pyramid(const tdn_anchor_level* levels, int nlevels, f
   L.total = (int)total;
   if (total == 0) return 0;
   TDN_CHECK(anchors != nullptr, "tdn_anchor_pyramid: NULL output");
-  int grid = (int)((total + 255) / 256);
-  if (grid > 4096) grid = 4096;
-  TDN_LAUNCH(anchor_pyramid_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, L, anchors, valid);
+  TDN_LAUNCH(anchor_pyramid_kernel, dim3(tdn_grid_1d(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, L, anchors,
+             valid);
   TDN_LAUNCH_CHECK();
   return 0;
 }
@@ -264,13 +261,13 @@ __global__ __launch_bounds__(1024) void nms_scan_block_kernel(const unsigned lon
   nms_scan_block(mask, order, N, nblk, nblk, keep, kept_idx, num_kept, sm);
 }
 
-static inline int64_t align256(int64_t x) { return (x + 255) & ~255ll; }
-
-extern "C" int64_t tdn_nms_workspace(int N) {
-  if (N <= 0) return 256;
-  const int64_t nblk = (N + 63) / 64;
-  return align256((int64_t)N * 4) * 2 + align256((int64_t)N * 16) + align256((int64_t)N * nblk * 8) + 256;
+struct NmsWs { int *rank, *order; float* sboxes; unsigned long long* mask; int64_t bytes; };
+static NmsWs nms_layout(int N, void* base) {   // N >= 1; a braced list is evaluated left to right
+  tdn_carver c{(char*)base, 0};
+  return {c.take<int>(N), c.take<int>(N), c.take<float>(4ll * N),
+          c.take<unsigned long long>((int64_t)N * ((N + 63) / 64)), c.off + 256};   // one spare block, as ever
 }
+extern "C" int64_t tdn_nms_workspace(int N) { return N <= 0 ? 256 : nms_layout(N, nullptr).bytes; }
 
 extern "C" int tdn_nms(const float* boxes, const float* scores, int N, float iou_thr, uint8_t* keep,
                        int64_t* kept_idx, int32_t* num_kept, void* workspace, int64_t workspace_bytes,
@@ -283,37 +280,32 @@ extern "C" int tdn_nms(const float* boxes, const float* scores, int N, float iou
     return 0;
   }
   TDN_CHECK(boxes && scores && keep && kept_idx && workspace, "tdn_nms: NULL pointer");
-  TDN_CHECK(workspace_bytes >= tdn_nms_workspace(N), "tdn_nms: workspace too small");
-  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "tdn_nms: workspace must be 256-byte aligned");
+  const NmsWs w = nms_layout(N, workspace);
+  if (tdn_check_ws("tdn_nms", workspace, workspace_bytes, w.bytes) != 0) return -1;
   const int nblk = (N + 63) / 64;
-  char* ws = (char*)workspace;
-  int* rank = (int*)ws; ws += align256((int64_t)N * 4);
-  int* order = (int*)ws; ws += align256((int64_t)N * 4);
-  float* sboxes = (float*)ws; ws += align256((int64_t)N * 16);
-  unsigned long long* mask = (unsigned long long*)ws;
-  TDN_MEMSET_ASYNC(rank, 0, (size_t)N * 4, st);
+  TDN_MEMSET_ASYNC(w.rank, 0, (size_t)N * 4, st);
   const int nb = (N + 255) / 256;
   int jsplit = 1024 / nb;  // aim for ~1024 blocks
   if (jsplit < 1) jsplit = 1;
   if (jsplit > (N + 1023) / 1024) jsplit = (N + 1023) / 1024;
   const int jchunk = ((N + jsplit - 1) / jsplit + 1023) / 1024 * 1024;
   jsplit = (N + jchunk - 1) / jchunk;
-  TDN_LAUNCH(nms_rank_kernel, dim3(nb, jsplit), dim3(256), 0, st, scores, N, jchunk, rank);
+  TDN_LAUNCH(nms_rank_kernel, dim3(nb, jsplit), dim3(256), 0, st, scores, N, jchunk, w.rank);
   TDN_LAUNCH_CHECK();
-  TDN_LAUNCH(nms_scatter_kernel, dim3(nb), dim3(256), 0, st, boxes, rank, N, order, sboxes);
+  TDN_LAUNCH(nms_scatter_kernel, dim3(nb), dim3(256), 0, st, boxes, (const int*)w.rank, N, w.order, w.sboxes);
   TDN_LAUNCH_CHECK();
-  TDN_LAUNCH(nms_mask_kernel, dim3(nblk, nblk), dim3(64), 0, st, sboxes, N, iou_thr, nblk, mask);
+  TDN_LAUNCH(nms_mask_kernel, dim3(nblk, nblk), dim3(64), 0, st, (const float*)w.sboxes, N, iou_thr, nblk, w.mask);
   TDN_LAUNCH_CHECK();
   const char* ow = tdn_knob_present("TDN_NMS_ONEWAVE");
   const bool one_wave = ow && ow[0] == '1';   // A/B runs
   if (nblk <= NMS_BLOCK_MAX_NBLK && !one_wave) {
     const size_t lds = nms_scan_block_lds(nblk);
     if (tdn_allow_lds<nms_scan_block_kernel>(160 * 1024, "nms_scan_block") < 0) return -1;
-    TDN_LAUNCH(nms_scan_block_kernel, dim3(1), dim3(1024), lds, st, mask, order, N, nblk, keep, kept_idx,
-                       num_kept);
+    TDN_LAUNCH(nms_scan_block_kernel, dim3(1), dim3(1024), lds, st, (const unsigned long long*)w.mask,
+               (const int*)w.order, N, nblk, keep, kept_idx, num_kept);
   } else {
-    TDN_LAUNCH(nms_scan_kernel, dim3(1), dim3(64), (size_t)nblk * 8, st, mask, order, N, nblk, keep, kept_idx,
-                       num_kept);
+    TDN_LAUNCH(nms_scan_kernel, dim3(1), dim3(64), (size_t)nblk * 8, st, (const unsigned long long*)w.mask,
+               (const int*)w.order, N, nblk, keep, kept_idx, num_kept);
   }
   TDN_LAUNCH_CHECK();
   return 0;
@@ -347,10 +339,9 @@ extern "C" int tdn_bbox_normalize(float* bbox, int64_t rows, const float* means4
   TDN_CHECK(rows >= 0 && means4 && stds4, "tdn_bbox_normalize: bad arguments");
   if (rows == 0) return 0;
   TDN_CHECK(bbox != nullptr, "tdn_bbox_normalize: NULL bbox");
-  const f32x4_t m = {means4[0], means4[1], means4[2], means4[3]}, s = {stds4[0], stds4[1], stds4[2], stds4[3]};
-  int64_t grid = (rows + 255) / 256;
-  if (grid > 4096) grid = 4096;
-  TDN_LAUNCH(bbox_normalize_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, bbox, rows, m, s);
+  const f32x4_t m = host_f4(means4), s = host_f4(stds4);   // by value: a recorded launch must not keep the pointers
+  TDN_LAUNCH(bbox_normalize_kernel, dim3(tdn_grid_1d(rows, 256, 4096)), dim3(256), 0, (hipStream_t)stream, bbox, rows,
+             m, s);
   TDN_LAUNCH_CHECK();
   return 0;
 }
@@ -361,10 +352,9 @@ extern "C" int tdn_bbox_denormalize(const float* bbox, float* out, int64_t rows,
   const int64_t n4 = rows * (cols / 4);
   if (n4 == 0) return 0;
   TDN_CHECK(bbox && out, "tdn_bbox_denormalize: NULL pointer");
-  const f32x4_t m = {means4[0], means4[1], means4[2], means4[3]}, s = {stds4[0], stds4[1], stds4[2], stds4[3]};
-  int64_t grid = (n4 + 255) / 256;
-  if (grid > 4096) grid = 4096;
-  TDN_LAUNCH(bbox_denormalize_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, bbox, out, n4, m, s);
+  const f32x4_t m = host_f4(means4), s = host_f4(stds4);
+  TDN_LAUNCH(bbox_denormalize_kernel, dim3(tdn_grid_1d(n4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, bbox, out,
+             n4, m, s);
   TDN_LAUNCH_CHECK();
   return 0;
 }

@@ -175,6 +175,37 @@ static inline int tdn_knob_int(const char* name, int dflt) {
   return (e && *e) ? atoi(e) : dflt;
 }
 
+// ---- host helpers of the detection-head files -----------------------------------------------------
+static inline f32x4_t host_f4(const float* v) { return (f32x4_t){v[0], v[1], v[2], v[3]}; }
+// blocks of `block` threads for n items of a grid-stride kernel: at least 1, at most `cap`
+static inline int tdn_grid_1d(int64_t n, int block, int cap) {
+  const int64_t g = (n + block - 1) / block;
+  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
+static inline int tdn_check_batch(const char* who, int B) {
+  TDN_CHECK(B >= 1 && B <= 64, "%s: B=%d out of 1..64", who, B);
+  return 0;
+}
+// A caller's workspace is laid out by ONE function per entry point (nms_layout, rpn_layout, ...): it carves the regions
+// in order, each from a 256-byte boundary, and returns their pointers with the total.  With a null base the pointers
+// are null and the pass is the size query; with the caller's pointer it is the launch path.
+static inline int64_t align256(int64_t x) { return (x + 255) & ~255ll; }
+struct tdn_carver {
+  char* base;
+  int64_t off;
+  template <class T>
+  T* take(int64_t count) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += align256(count * (int64_t)sizeof(T));
+    return p;
+  }
+};
+static inline int tdn_check_ws(const char* who, const void* workspace, int64_t workspace_bytes, int64_t need) {
+  TDN_CHECK(workspace && workspace_bytes >= need, "%s: workspace too small", who);
+  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  return 0;
+}
+
 // ---- dynamic LDS beyond 64 KB -----------------------------------------------------------------
 // hipFuncSetAttribute applies to ONE device, so it is remembered per kernel instantiation (the template argument) AND
 // per device: a second GPU used from the same process does not launch without it.  The device index is a local and

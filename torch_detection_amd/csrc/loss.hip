@@ -413,7 +413,12 @@ __global__ __launch_bounds__(LT) void loss_roi_kernel(const RoiArgs A, const flo
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
-inline int64_t align256(int64_t x) { return (x + 255) & ~255ll; }
+// the one workspace of this file: a partial per workgroup of the forward launch
+struct PartialsWs { double* partials; int64_t bytes; };
+PartialsWs partials_layout(int blocks, void* base) {   // a braced list is evaluated left to right
+  tdn_carver c{(char*)base, 0};
+  return {c.take<double>((int64_t)blocks * PART), c.off};
+}
 
 int elem_bytes(int dtype) { return dtype == TDN_F32 ? 4 : 2; }
 
@@ -435,36 +440,28 @@ int check_avg(const char* who, const tdn_loss_avg* avg, bool roi, AvgArgs* out) 
   return 0;
 }
 
-// fills the segment table; returns the number of workgroups, or -1 with the error set
-int dense_plan(const char* who, const tdn_loss_level* levels, int L, int B, const tdn_loss_config* cfg, bool grad,
-               DenseArgs* D) {
+// The shape half of the plan, all the size query needs: checks of everything the sizes depend on, the segment table
+// without its pointers, the anchor and chunk totals.  Returns the number of workgroups, or -1 with the error set.
+int dense_shape(const char* who, const tdn_loss_level* levels, int L, int B, const tdn_loss_config* cfg, DenseArgs* D) {
   TDN_CHECK(levels && cfg, "%s: NULL argument", who);
   TDN_CHECK(L >= 1 && L <= TDN_LOSS_MAX_LEVELS, "%s: %d levels (1..%d)", who, L, TDN_LOSS_MAX_LEVELS);
-  TDN_CHECK(B >= 1 && B <= 64, "%s: B=%d out of 1..64", who, B);
+  if (tdn_check_batch(who, B) != 0) return -1;
   TDN_CHECK(cfg->dtype == TDN_F32 || cfg->dtype == TDN_BF16 || cfg->dtype == TDN_F16, "%s: dtype %d", who, cfg->dtype);
   TDN_CHECK(cfg->num_anchors >= 1 && cfg->num_classes >= 1 && cfg->num_classes <= TDN_LOSS_MAX_CLASSES,
             "%s: A=%d, C=%d (C in 1..%d)", who, cfg->num_anchors, cfg->num_classes, TDN_LOSS_MAX_CLASSES);
-  TDN_CHECK(cfg->beta > 0.f && cfg->beta < INFINITY, "%s: beta must be finite and > 0", who);
-  if (cfg->focal)
-    TDN_CHECK(cfg->gamma >= 0.f && cfg->gamma < INFINITY && cfg->alpha >= 0.f && cfg->alpha <= 1.f,
-              "%s: focal needs gamma >= 0 and alpha in [0, 1]", who);
   memset(D, 0, sizeof(*D));
-  const int A = cfg->num_anchors, C = cfg->num_classes;
-  const int V = 16 / elem_bytes(cfg->dtype);
+  const int A = cfg->num_anchors, C = cfg->num_classes, V = 16 / elem_bytes(cfg->dtype);
   int64_t N = 0, chunk = 0;
   int ns = 0;
   for (int l = 0; l < L; ++l) {
     const tdn_loss_level& lv = levels[l];
     TDN_CHECK(lv.H >= 1 && lv.W >= 1, "%s: level %d is %d x %d", who, l, lv.H, lv.W);
     const int64_t HW = (int64_t)lv.H * lv.W;
-    TDN_CHECK(lv.cls && lv.reg && (!grad || (lv.dcls && lv.dreg)), "%s: level %d: NULL pointer", who, l);
     for (int k = 0; k < 2; ++k) {
       const int64_t Ch = k ? 4ll * A : (int64_t)A * C;
       const int64_t n = (int64_t)B * Ch * HW;
       TDN_CHECK(n < (1ll << 31), "%s: level %d holds %lld elements (2^31 or more)", who, l, (long long)n);
       DenseSeg& S = D->seg[ns++];
-      S.x = k ? lv.reg : lv.cls;
-      S.dx = k ? lv.dreg : lv.dcls;
       S.n = (uint32_t)n;
       S.nchunks = (uint32_t)((n + V - 1) / V);
       S.chunk0 = chunk;
@@ -473,7 +470,6 @@ int dense_plan(const char* who, const tdn_loss_level* levels, int L, int B, cons
       S.nhwc = (k ? lv.reg_nhwc : lv.cls_nhwc) ? 1 : 0;
       S.reg = k;
       S.off = (int32_t)N;
-      S.vec = (((uintptr_t)S.x | (grad ? (uintptr_t)S.dx : 0)) & 15) == 0;
       chunk += S.nchunks;
     }
     N += HW * A;
@@ -484,13 +480,32 @@ int dense_plan(const char* who, const tdn_loss_level* levels, int L, int B, cons
   D->N = (int32_t)N;
   D->A = A;
   D->C = C;
-  D->beta = cfg->beta;
-  D->P.focal = cfg->focal ? 1 : 0;
-  D->P.gamma = cfg->gamma;
-  D->P.alpha = cfg->alpha;
-  D->P.one_minus_alpha = 1.f - cfg->alpha;
   const int64_t blocks = (chunk + LT - 1) / LT;
   return (int)(blocks < LMAX_BLOCKS ? blocks : LMAX_BLOCKS);
+}
+
+// The pointer half: the loss parameters and each segment's tensors.  Same return value.
+int dense_plan(const char* who, const tdn_loss_level* levels, int L, int B, const tdn_loss_config* cfg, bool grad,
+               DenseArgs* D) {
+  const int blocks = dense_shape(who, levels, L, B, cfg, D);
+  if (blocks < 0) return -1;
+  TDN_CHECK(cfg->beta > 0.f && cfg->beta < INFINITY, "%s: beta must be finite and > 0", who);
+  if (cfg->focal)
+    TDN_CHECK(cfg->gamma >= 0.f && cfg->gamma < INFINITY && cfg->alpha >= 0.f && cfg->alpha <= 1.f,
+              "%s: focal needs gamma >= 0 and alpha in [0, 1]", who);
+  for (int l = 0; l < L; ++l) {
+    const tdn_loss_level& lv = levels[l];
+    TDN_CHECK(lv.cls && lv.reg && (!grad || (lv.dcls && lv.dreg)), "%s: level %d: NULL pointer", who, l);
+    for (int k = 0; k < 2; ++k) {
+      DenseSeg& S = D->seg[2 * l + k];
+      S.x = k ? lv.reg : lv.cls;
+      S.dx = k ? lv.dreg : lv.dcls;
+      S.vec = (((uintptr_t)S.x | (grad ? (uintptr_t)S.dx : 0)) & 15) == 0;
+    }
+  }
+  D->beta = cfg->beta;
+  D->P = {cfg->focal ? 1 : 0, cfg->gamma, cfg->alpha, 1.f - cfg->alpha};
+  return blocks;
 }
 
 int roi_blocks(int R) {
@@ -518,22 +533,9 @@ int check_roi(const char* who, int dtype, int R, int C, int reg_cols, float beta
 
 extern "C" int64_t tdn_loss_dense_workspace_bytes(const tdn_loss_level* levels, int num_levels, int B,
                                                   const tdn_loss_config* cfg) {
-  if (!levels || !cfg || num_levels < 1 || num_levels > TDN_LOSS_MAX_LEVELS || B < 1 || B > 64) return -1;
-  if (cfg->dtype != TDN_F32 && cfg->dtype != TDN_BF16 && cfg->dtype != TDN_F16) return -1;
-  if (cfg->num_anchors < 1 || cfg->num_classes < 1 || cfg->num_classes > TDN_LOSS_MAX_CLASSES) return -1;
-  const int V = 16 / elem_bytes(cfg->dtype);
-  int64_t chunks = 0, N = 0;
-  for (int l = 0; l < num_levels; ++l) {
-    if (levels[l].H < 1 || levels[l].W < 1) return -1;
-    const int64_t HW = (int64_t)levels[l].H * levels[l].W;
-    const int64_t ncls = (int64_t)B * cfg->num_anchors * cfg->num_classes * HW, nreg = (int64_t)B * 4 * cfg->num_anchors * HW;
-    if (ncls >= (1ll << 31) || nreg >= (1ll << 31)) return -1;
-    chunks += (ncls + V - 1) / V + (nreg + V - 1) / V;
-    N += HW * cfg->num_anchors;
-    if (N > TDN_LOSS_MAX_ROWS) return -1;
-  }
-  const int64_t blocks = (chunks + LT - 1) / LT;
-  return align256((blocks < LMAX_BLOCKS ? blocks : LMAX_BLOCKS) * PART * 8);
+  DenseArgs D;
+  const int blocks = dense_shape("tdn_loss_dense_workspace_bytes", levels, num_levels, B, cfg, &D);
+  return blocks < 0 ? -1 : partials_layout(blocks, nullptr).bytes;
 }
 
 extern "C" int tdn_loss_dense_fwd(const tdn_loss_level* levels, int num_levels, int B, const tdn_loss_config* cfg,
@@ -547,17 +549,16 @@ extern "C" int tdn_loss_dense_fwd(const tdn_loss_level* levels, int num_levels, 
   if (blocks < 0 || check_avg(who, avg, false, &V) != 0) return -1;
   TDN_CHECK(labels && label_weights && bbox_targets && bbox_weights && losses && avg_out && workspace,
             "%s: NULL pointer", who);
-  TDN_CHECK(workspace_bytes >= (int64_t)blocks * PART * 8, "%s: workspace too small", who);
-  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  const PartialsWs w = partials_layout(blocks, workspace);
+  if (tdn_check_ws(who, workspace, workspace_bytes, w.bytes) != 0) return -1;
   D.labels = labels;
   D.lw = label_weights;
   D.bt = bbox_targets;
   D.bw = bbox_weights;
-  double* partials = (double*)workspace;
   const float* none = nullptr;
-  LOSS_LAUNCH_DT(loss_dense_kernel, false, cfg->dtype, dim3(blocks), stream, D, none, none, partials);
+  LOSS_LAUNCH_DT(loss_dense_kernel, false, cfg->dtype, dim3(blocks), stream, D, none, none, w.partials);
   TDN_LAUNCH_CHECK();
-  TDN_LAUNCH(loss_finalize_kernel, dim3(1), dim3(LMAX_BLOCKS), 0, stream, (const double*)partials, blocks, V, losses,
+  TDN_LAUNCH(loss_finalize_kernel, dim3(1), dim3(LMAX_BLOCKS), 0, stream, (const double*)w.partials, blocks, V, losses,
              avg_out);
   TDN_LAUNCH_CHECK();
   return 0;
@@ -583,7 +584,7 @@ extern "C" int tdn_loss_dense_bwd(const tdn_loss_level* levels, int num_levels, 
 
 extern "C" int64_t tdn_loss_roi_workspace_bytes(int R) {
   if (R < 0 || R > TDN_LOSS_MAX_ROWS) return -1;
-  return align256((int64_t)roi_blocks(R) * PART * 8);
+  return partials_layout(roi_blocks(R), nullptr).bytes;
 }
 
 extern "C" int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
@@ -596,8 +597,8 @@ extern "C" int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int
   TDN_CHECK(losses && avg_out && workspace, "%s: NULL pointer", who);
   TDN_CHECK(R == 0 || (cls && reg && labels && label_weights && bbox_targets && bbox_weights), "%s: NULL pointer", who);
   const int blocks = roi_blocks(R);
-  TDN_CHECK(workspace_bytes >= (int64_t)blocks * PART * 8, "%s: workspace too small", who);
-  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  const PartialsWs w = partials_layout(blocks, workspace);
+  if (tdn_check_ws(who, workspace, workspace_bytes, w.bytes) != 0) return -1;
   RoiArgs A;
   memset(&A, 0, sizeof(A));
   A.cls = cls;
@@ -610,11 +611,10 @@ extern "C" int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int
   A.C = C;
   A.reg_cols = reg_cols;
   A.beta = beta;
-  double* partials = (double*)workspace;
   const float* none = nullptr;
-  LOSS_LAUNCH_DT(loss_roi_kernel, false, dtype, dim3(blocks), stream, A, none, none, partials);
+  LOSS_LAUNCH_DT(loss_roi_kernel, false, dtype, dim3(blocks), stream, A, none, none, w.partials);
   TDN_LAUNCH_CHECK();
-  TDN_LAUNCH(loss_finalize_kernel, dim3(1), dim3(LMAX_BLOCKS), 0, stream, (const double*)partials, blocks, V, losses,
+  TDN_LAUNCH(loss_finalize_kernel, dim3(1), dim3(LMAX_BLOCKS), 0, stream, (const double*)w.partials, blocks, V, losses,
              avg_out);
   TDN_LAUNCH_CHECK();
   return 0;

@@ -88,16 +88,12 @@ __global__ void delta2bbox_kernel(const float* __restrict__ rois, const float* _
   }
 }
 
-static f32x4_t host_f4(const float* v) { return (f32x4_t){v[0], v[1], v[2], v[3]}; }
-
 extern "C" int tdn_bbox2delta(const float* proposals, const float* gt, int64_t N, const float* means4,
                               const float* stds4, float* deltas, void* stream) {
   TDN_CHECK(N >= 0 && means4 && stds4, "tdn_bbox2delta: bad arguments");
   if (N == 0) return 0;
   TDN_CHECK(proposals && gt && deltas, "tdn_bbox2delta: NULL pointer");
-  int64_t grid = (N + 255) / 256;
-  if (grid > 4096) grid = 4096;
-  TDN_LAUNCH(bbox2delta_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, proposals, gt, N,
+  TDN_LAUNCH(bbox2delta_kernel, dim3(tdn_grid_1d(N, 256, 4096)), dim3(256), 0, (hipStream_t)stream, proposals, gt, N,
              host_f4(means4), host_f4(stds4), deltas);
   TDN_LAUNCH_CHECK();
   return 0;
@@ -114,10 +110,8 @@ extern "C" int tdn_delta2bbox(const float* rois, const float* deltas, int64_t N,
   TDN_CHECK(!max_shape || (max_shape[0] > 0 && max_shape[1] > 0), "tdn_delta2bbox: bad max_shape");
   if (N == 0) return 0;
   TDN_CHECK(rois && deltas && out, "tdn_delta2bbox: NULL pointer");
-  int64_t grid = (N * C + 255) / 256;
-  if (grid > 4096) grid = 4096;
-  TDN_LAUNCH(delta2bbox_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, rois, deltas, N, C,
-             host_f4(means4), host_f4(stds4), max_ratio_of(wh_ratio_clip), max_shape ? max_shape[0] : -1,
+  TDN_LAUNCH(delta2bbox_kernel, dim3(tdn_grid_1d(N * C, 256, 4096)), dim3(256), 0, (hipStream_t)stream, rois, deltas, N,
+             C, host_f4(means4), host_f4(stds4), max_ratio_of(wh_ratio_clip), max_shape ? max_shape[0] : -1,
              max_shape ? max_shape[1] : -1, out);
   TDN_LAUNCH_CHECK();
   return 0;
@@ -409,8 +403,6 @@ __global__ __launch_bounds__(1024) void rpn_merge_kernel(const RpnArgs P, const 
   if (tid == 0) counts[b] = m;
 }
 
-static inline int64_t align256(int64_t x) { return (x + 255) & ~255ll; }
-
 struct RpnPlan {
   RpnArgs P;
   int B, S, maxcap;
@@ -420,7 +412,7 @@ struct RpnPlan {
 static int rpn_plan(const tdn_rpn_level* levels, int nlevels, int B, const tdn_rpn_config* cfg, RpnPlan* out) {
   TDN_CHECK(levels && cfg, "tdn_rpn_proposals: NULL levels / config");
   TDN_CHECK(nlevels >= 1 && nlevels <= TDN_RPN_MAX_LEVELS, "tdn_rpn_proposals: 1..%d levels", TDN_RPN_MAX_LEVELS);
-  TDN_CHECK(B >= 1 && B <= 64, "tdn_rpn_proposals: B=%d out of 1..64", B);
+  if (tdn_check_batch("tdn_rpn_proposals", B) != 0) return -1;
   TDN_CHECK(cfg->nms_pre >= 0 && cfg->nms_post >= 1 && cfg->max_num >= 1 && cfg->max_num <= TDN_RPN_MAX_NUM,
             "tdn_rpn_proposals: bad nms_pre / nms_post / max_num");
   TDN_CHECK(cfg->min_bbox_size >= 0.f && cfg->nms_thr == cfg->nms_thr, "tdn_rpn_proposals: bad min_bbox_size / nms_thr");
@@ -472,17 +464,22 @@ static int rpn_plan(const tdn_rpn_level* levels, int nlevels, int B, const tdn_r
   return 0;
 }
 
-static int64_t rpn_ws_bytes(const RpnPlan& p) {
-  const int64_t R = p.rows > 0 ? p.rows : 1;
-  return align256(R * 16) + align256(R * 4) * 2 + align256(R * 8) + align256((int64_t)p.S * 4) * 3 +
-         align256(R * p.P.pitch * 8);
+struct RpnWs {
+  f32x4_t* seg_box; uint32_t* seg_key; int* seg_aidx; int64_t* kept;
+  int *seg_start, *seg_count, *num_kept; u64* mask; int64_t bytes;
+};
+static RpnWs rpn_layout(const RpnPlan& p, void* base) {   // a braced list is evaluated left to right
+  const int64_t R = p.rows > 0 ? p.rows : 1;   // every level empty: one placeholder row
+  tdn_carver c{(char*)base, 0};
+  return {c.take<f32x4_t>(R), c.take<uint32_t>(R), c.take<int>(R), c.take<int64_t>(R),
+          c.take<int>(p.S), c.take<int>(p.S), c.take<int>(p.S), c.take<u64>(R * p.P.pitch), c.off};
 }
 
 extern "C" int64_t tdn_rpn_proposals_workspace(const tdn_rpn_level* levels, int nlevels, int B,
                                                const tdn_rpn_config* cfg) {
   RpnPlan p;
   if (rpn_plan(levels, nlevels, B, cfg, &p) != 0) return -1;
-  return rpn_ws_bytes(p);
+  return rpn_layout(p, nullptr).bytes;
 }
 
 extern "C" int tdn_rpn_proposals(const tdn_rpn_level* levels, int nlevels, int B, const int32_t* img_shapes,
@@ -491,35 +488,25 @@ extern "C" int tdn_rpn_proposals(const tdn_rpn_level* levels, int nlevels, int B
   RpnPlan p;
   if (rpn_plan(levels, nlevels, B, cfg, &p) != 0) return -1;
   TDN_CHECK(img_shapes && proposals && anchor_idx && counts && workspace, "tdn_rpn_proposals: NULL pointer");
-  TDN_CHECK(workspace_bytes >= rpn_ws_bytes(p), "tdn_rpn_proposals: workspace too small");
-  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "tdn_rpn_proposals: workspace must be 256-byte aligned");
+  const RpnWs w = rpn_layout(p, workspace);
+  if (tdn_check_ws("tdn_rpn_proposals", workspace, workspace_bytes, w.bytes) != 0) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t R = p.rows > 0 ? p.rows : 1;
   const int pitch = p.P.pitch;
-  char* ws = (char*)workspace;
-  f32x4_t* seg_box = (f32x4_t*)ws; ws += align256(R * 16);
-  uint32_t* seg_key = (uint32_t*)ws; ws += align256(R * 4);
-  int* seg_aidx = (int*)ws; ws += align256(R * 4);
-  int64_t* kept = (int64_t*)ws; ws += align256(R * 8);
-  int* seg_start = (int*)ws; ws += align256((int64_t)p.S * 4);
-  int* seg_count = (int*)ws; ws += align256((int64_t)p.S * 4);
-  int* num_kept = (int*)ws; ws += align256((int64_t)p.S * 4);
-  unsigned long long* mask = (unsigned long long*)ws;
-  TDN_LAUNCH(rpn_topk_decode_kernel, dim3(p.S), dim3(BLK), TOPK_LDS, st, p.P, img_shapes, seg_box, seg_key, seg_aidx,
-             seg_start, seg_count);
+  TDN_LAUNCH(rpn_topk_decode_kernel, dim3(p.S), dim3(BLK), TOPK_LDS, st, p.P, img_shapes, w.seg_box, w.seg_key,
+             w.seg_aidx, w.seg_start, w.seg_count);
   TDN_LAUNCH_CHECK();
-  TDN_LAUNCH(nms_mask_seg_kernel, dim3(pitch, pitch, p.S), dim3(64), 0, st, (const float*)seg_box,
-             (const int*)seg_start, (const int*)seg_count, cfg->nms_thr, pitch, mask);
+  TDN_LAUNCH(nms_mask_seg_kernel, dim3(pitch, pitch, p.S), dim3(64), 0, st, (const float*)w.seg_box,
+             (const int*)w.seg_start, (const int*)w.seg_count, cfg->nms_thr, pitch, w.mask);
   TDN_LAUNCH_CHECK();
   if (tdn_allow_lds<nms_scan_seg_kernel>(160 * 1024, "nms_scan_seg") < 0) return -1;
   TDN_LAUNCH(nms_scan_seg_kernel, dim3(p.S), dim3(BLK), nms_scan_block_lds(pitch), st,
-             (const unsigned long long*)mask, (const int*)nullptr, (const int*)seg_start, (const int*)seg_count, pitch,
-             (uint8_t*)nullptr, kept, num_kept);
+             (const unsigned long long*)w.mask, (const int*)nullptr, (const int*)w.seg_start, (const int*)w.seg_count,
+             pitch, (uint8_t*)nullptr, w.kept, w.num_kept);
   TDN_LAUNCH_CHECK();
   if (tdn_allow_lds<rpn_merge_kernel>(160 * 1024, "rpn_merge") < 0) return -1;
-  TDN_LAUNCH(rpn_merge_kernel, dim3(p.B), dim3(BLK), MERGE_LDS, st, p.P, (const f32x4_t*)seg_box,
-             (const uint32_t*)seg_key, (const int*)seg_aidx, (const int*)seg_start, (const int64_t*)kept,
-             (const int*)num_kept, proposals, anchor_idx, counts);
+  TDN_LAUNCH(rpn_merge_kernel, dim3(p.B), dim3(BLK), MERGE_LDS, st, p.P, (const f32x4_t*)w.seg_box,
+             (const uint32_t*)w.seg_key, (const int*)w.seg_aidx, (const int*)w.seg_start, (const int64_t*)w.kept,
+             (const int*)w.num_kept, proposals, anchor_idx, counts);
   TDN_LAUNCH_CHECK();
   return 0;
 }
@@ -560,11 +547,15 @@ static int nms_seg_pitch(int N) {
   return m > 0 ? (m + 63) / 64 : 1;
 }
 
+struct SegNmsWs { int* order; float* sboxes; int *seg_start, *seg_count; u64* mask; int64_t bytes; };
+static SegNmsWs seg_nms_layout(int N, int S, void* base) {
+  const int64_t n = N > 0 ? N : 1, s = S > 0 ? S : 1;   // placeholders: no region is empty
+  tdn_carver c{(char*)base, 0};
+  return {c.take<int>(n), c.take<float>(n * 4), c.take<int>(s), c.take<int>(s), c.take<u64>(n * nms_seg_pitch(N)),
+          c.off};
+}
 extern "C" int64_t tdn_batched_nms_workspace(int N, int S) {
-  if (N < 0 || S < 0) return -1;
-  const int64_t n = N > 0 ? N : 1;
-  return align256(n * 4) + align256(n * 16) + align256((int64_t)(S > 0 ? S : 1) * 4) * 2 +
-         align256(n * nms_seg_pitch(N) * 8);
+  return (N < 0 || S < 0) ? -1 : seg_nms_layout(N, S, nullptr).bytes;
 }
 
 extern "C" int tdn_batched_nms(const float* boxes, const float* scores, int N, const int64_t* seg_offsets, int S,
@@ -579,25 +570,18 @@ extern "C" int tdn_batched_nms(const float* boxes, const float* scores, int N, c
   }
   if (S == 0) return 0;
   TDN_CHECK(seg_offsets && counts && workspace && (N == 0 || (boxes && scores)), "tdn_batched_nms: NULL pointer");
-  TDN_CHECK(workspace_bytes >= tdn_batched_nms_workspace(N, S), "tdn_batched_nms: workspace too small");
-  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "tdn_batched_nms: workspace must be 256-byte aligned");
-  const int64_t n = N > 0 ? N : 1;
+  const SegNmsWs w = seg_nms_layout(N, S, workspace);
+  if (tdn_check_ws("tdn_batched_nms", workspace, workspace_bytes, w.bytes) != 0) return -1;
   const int pitch = nms_seg_pitch(N);
-  char* ws = (char*)workspace;
-  int* order = (int*)ws; ws += align256(n * 4);
-  float* sboxes = (float*)ws; ws += align256(n * 16);
-  int* seg_start = (int*)ws; ws += align256((int64_t)S * 4);
-  int* seg_count = (int*)ws; ws += align256((int64_t)S * 4);
-  unsigned long long* mask = (unsigned long long*)ws;
   TDN_LAUNCH(nms_seg_sort_kernel, dim3(S), dim3(BLK), (size_t)TDN_NMS_SEG_MAX * 8, st, boxes, scores, N, seg_offsets,
-             order, sboxes, seg_start, seg_count);
+             w.order, w.sboxes, w.seg_start, w.seg_count);
   TDN_LAUNCH_CHECK();
-  TDN_LAUNCH(nms_mask_seg_kernel, dim3(pitch, pitch, S), dim3(64), 0, st, (const float*)sboxes,
-             (const int*)seg_start, (const int*)seg_count, iou_thr, pitch, mask);
+  TDN_LAUNCH(nms_mask_seg_kernel, dim3(pitch, pitch, S), dim3(64), 0, st, (const float*)w.sboxes,
+             (const int*)w.seg_start, (const int*)w.seg_count, iou_thr, pitch, w.mask);
   TDN_LAUNCH_CHECK();
   if (tdn_allow_lds<nms_scan_seg_kernel>(160 * 1024, "nms_scan_seg") < 0) return -1;
-  TDN_LAUNCH(nms_scan_seg_kernel, dim3(S), dim3(BLK), nms_scan_block_lds(pitch), st, (const unsigned long long*)mask,
-             (const int*)order, (const int*)seg_start, (const int*)seg_count, pitch, keep, kept_idx, counts);
+  TDN_LAUNCH(nms_scan_seg_kernel, dim3(S), dim3(BLK), nms_scan_block_lds(pitch), st, (const unsigned long long*)w.mask,
+             (const int*)w.order, (const int*)w.seg_start, (const int*)w.seg_count, pitch, keep, kept_idx, counts);
   TDN_LAUNCH_CHECK();
   return 0;
 }

@@ -347,8 +347,6 @@ __global__ __launch_bounds__(ROI_BLK) void roi_align_bwd_kernel(const RoiLevels 
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------
-static inline int64_t roi_align256(int64_t x) { return (x + 255) & ~255ll; }
-
 static int roi_plan(const char* fn, const tdn_roi_level* lv, int L, int B, int C, const tdn_roi_config* cfg,
                     RoiLevels* P) {
   TDN_CHECK(lv && cfg, "%s: NULL levels / config", fn);
@@ -404,10 +402,7 @@ static int roi_plan(const char* fn, const tdn_roi_level* lv, int L, int B, int C
   return 0;
 }
 
-static int grid_of(int64_t n, int blk) {
-  int64_t g = (n + blk - 1) / blk;
-  return (int)(g > 65536 ? 65536 : (g < 1 ? 1 : g));
-}
+static int grid_of(int64_t n, int blk) { return tdn_grid_1d(n, blk, 65536); }
 
 extern "C" int tdn_roi_map_levels(const float* rois, int64_t R, int nlevels, float finest_scale, int64_t* levels,
                                   void* stream) {
@@ -438,10 +433,14 @@ extern "C" int tdn_roi_align_fwd(const tdn_roi_level* feats, int nlevels, int B,
   return 0;
 }
 
+struct RoiBwdWs { RoiRec* rec; f32x4_t* geo; int64_t bytes; };
+static RoiBwdWs roi_bwd_layout(int64_t R, void* base) {   // a braced list is evaluated left to right
+  const int64_t n = R > 0 ? R : 1;             // R = 0 still launches the gradient kernel
+  tdn_carver c{(char*)base, 0};
+  return {c.take<RoiRec>(n), c.take<f32x4_t>(n), c.off};
+}
 extern "C" int64_t tdn_roi_align_bwd_workspace(int64_t R) {
-  if (R < 0 || R >= (1ll << 31)) return -1;
-  const int64_t n = R > 0 ? R : 1;
-  return roi_align256(n * (int64_t)sizeof(RoiRec)) + roi_align256(n * 16);
+  return (R < 0 || R >= (1ll << 31)) ? -1 : roi_bwd_layout(R, nullptr).bytes;
 }
 
 extern "C" int tdn_roi_align_bwd(const tdn_roi_level* grads, int nlevels, int B, int C, const float* rois, int64_t R,
@@ -452,19 +451,16 @@ extern "C" int tdn_roi_align_bwd(const tdn_roi_level* grads, int nlevels, int B,
   TDN_CHECK(R >= 0 && R < (1ll << 31), "tdn_roi_align_bwd: bad R");
   TDN_CHECK(R == 0 || (rois && dout && ((uintptr_t)dout & 15) == 0),
             "tdn_roi_align_bwd: NULL or misaligned rois / dout");
-  TDN_CHECK(workspace && workspace_bytes >= tdn_roi_align_bwd_workspace(R), "tdn_roi_align_bwd: workspace too small");
-  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "tdn_roi_align_bwd: workspace must be 256-byte aligned");
+  const RoiBwdWs w = roi_bwd_layout(R, workspace);
+  if (tdn_check_ws("tdn_roi_align_bwd", workspace, workspace_bytes, w.bytes) != 0) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t n = R > 0 ? R : 1;
-  RoiRec* rec = (RoiRec*)workspace;
-  f32x4_t* geo = (f32x4_t*)((char*)workspace + roi_align256(n * (int64_t)sizeof(RoiRec)));
   if (R > 0) {
-    TDN_LAUNCH(roi_prep_kernel, dim3(grid_of(R, 256)), dim3(256), 0, st, P, rois, R, rec, geo);
+    TDN_LAUNCH(roi_prep_kernel, dim3(grid_of(R, 256)), dim3(256), 0, st, P, rois, R, w.rec, w.geo);
     TDN_LAUNCH_CHECK();
   }
   const int dt = grads[0].dtype;
-  TDN_LAUNCH_T(roi_align_bwd_kernel, dt, dim3(P.blk_off[nlevels]), dim3(ROI_BLK), st, P, (const RoiRec*)rec,
-               (const f32x4_t*)geo, R, (const bf16_t*)dout);
+  TDN_LAUNCH_T(roi_align_bwd_kernel, dt, dim3(P.blk_off[nlevels]), dim3(ROI_BLK), st, P, (const RoiRec*)w.rec,
+               (const f32x4_t*)w.geo, R, (const bf16_t*)dout);
   TDN_LAUNCH_CHECK();
   return 0;
 }

@@ -392,15 +392,23 @@ __global__ __launch_bounds__(1024) void sample_rois_fill_kernel(const FillArgs A
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------
-static inline int64_t align256(int64_t x) { return (x + 255) & ~255ll; }
-static f32x4_t host_f4(const float* v) { return (f32x4_t){v[0], v[1], v[2], v[3]}; }
-
-static int check_common(const char* who, int B, int64_t N, int G, const tdn_target_config* cfg) {
-  TDN_CHECK(cfg != nullptr, "%s: NULL config", who);
-  TDN_CHECK(B >= 1 && B <= 64, "%s: B=%d out of 1..64", who, B);
+// the ranges every entry point and every size query accepts
+static int check_dims(const char* who, int B, int64_t N, int G) {
+  if (tdn_check_batch(who, B) != 0) return -1;
   TDN_CHECK(N >= 0 && N <= TDN_TARGET_MAX_BOXES, "%s: %lld boxes per image (max %d)", who, (long long)N,
             TDN_TARGET_MAX_BOXES);
   TDN_CHECK(G >= 0 && G <= TDN_TARGET_MAX_GT, "%s: G=%d ground truths per image (max %d)", who, G, TDN_TARGET_MAX_GT);
+  return 0;
+}
+// sample_rois: P proposals leave room for the ground truths it may add
+static int check_props(const char* who, int P) {
+  TDN_CHECK(P >= 0 && P <= TDN_TARGET_MAX_BOXES - TDN_TARGET_MAX_GT, "%s: P=%d out of range", who, P);
+  return 0;
+}
+
+static int check_common(const char* who, int B, int64_t N, int G, const tdn_target_config* cfg) {
+  TDN_CHECK(cfg != nullptr, "%s: NULL config", who);
+  if (check_dims(who, B, N, G) != 0) return -1;
   TDN_CHECK(cfg->pos_iou_thr == cfg->pos_iou_thr && cfg->neg_iou_thr == cfg->neg_iou_thr &&
                 cfg->min_pos_iou == cfg->min_pos_iou, "%s: NaN threshold", who);
   return 0;
@@ -414,14 +422,25 @@ static int check_sampling(const char* who, const tdn_target_config* cfg) {
   return 0;
 }
 
-// colmax and first: [B][G] words each
-static int64_t assign_ws_bytes(int B, int G) { return 2 * align256((int64_t)B * (G > 0 ? G : 1) * 4); }
+// ---- workspaces (a braced list is evaluated left to right) ------------------------------------------------------
+struct AssignWs { int64_t words; uint32_t* colmax; int* first; int64_t bytes; };   // `words` of each
+static AssignWs assign_layout(int B, int G, void* base) {
+  const int64_t words = (int64_t)B * (G > 0 ? G : 1);
+  tdn_carver c{(char*)base, 0};
+  return {words, c.take<uint32_t>(words), c.take<int>(words), c.off};
+}
+// anchor_target and sample_rois: the assignment words first, then assigned (sample_rois only: anchor_target's is an
+// output of the call), then the two masks
+struct SampleWs { AssignWs a; int32_t* assigned; uint8_t *pos_mask, *neg_mask; int64_t bytes; };
+static SampleWs sample_layout(int B, int64_t N, int G, bool with_assigned, void* base) {
+  const AssignWs a = assign_layout(B, G, base);
+  const int64_t n = (int64_t)B * (N > 0 ? N : 1);
+  tdn_carver c{(char*)base, a.bytes};
+  return {a, with_assigned ? c.take<int32_t>(n) : nullptr, c.take<uint8_t>(n), c.take<uint8_t>(n), c.off};
+}
 
 static int run_assign(const BoxSrc& S, const int32_t* gt_counts, int B, int N, int G, const tdn_target_config* cfg,
-                      int32_t* assigned, float* max_overlaps, char* ws, hipStream_t st) {
-  const int64_t words = (int64_t)B * (G > 0 ? G : 1);
-  uint32_t* colmax = (uint32_t*)ws;
-  int* first = (int*)(ws + align256(words * 4));
+                      int32_t* assigned, float* max_overlaps, const AssignWs& w, hipStream_t st) {
   AssignArgs A;
   A.S = S;
   A.gt_counts = gt_counts;
@@ -431,16 +450,17 @@ static int run_assign(const BoxSrc& S, const int32_t* gt_counts, int B, int N, i
   A.pos_thr = cfg->pos_iou_thr;
   A.neg_thr = cfg->neg_iou_thr;
   A.min_pos = cfg->min_pos_iou;
-  TDN_LAUNCH(target_clear_kernel, dim3((int)((words + 255) / 256)), dim3(256), 0, st, colmax, first, (int)words);
+  TDN_LAUNCH(target_clear_kernel, dim3((int)((w.words + 255) / 256)), dim3(256), 0, st, w.colmax, w.first,
+             (int)w.words);
   TDN_LAUNCH_CHECK();
   const dim3 grid((N + P1_THREADS * P1_PER - 1) / (P1_THREADS * P1_PER), B);
-  TDN_LAUNCH(assign_pass1_kernel, grid, dim3(P1_THREADS), 0, st, A, assigned, max_overlaps, colmax);
+  TDN_LAUNCH(assign_pass1_kernel, grid, dim3(P1_THREADS), 0, st, A, assigned, max_overlaps, w.colmax);
   TDN_LAUNCH_CHECK();
   if (G == 0) return 0;                        // every participating box is already 0
-  TDN_LAUNCH(assign_pass2_kernel, grid, dim3(P1_THREADS), 0, st, A, assigned, (const uint32_t*)colmax, first);
+  TDN_LAUNCH(assign_pass2_kernel, grid, dim3(P1_THREADS), 0, st, A, assigned, (const uint32_t*)w.colmax, w.first);
   TDN_LAUNCH_CHECK();
   if (!A.all) {
-    TDN_LAUNCH(assign_first_kernel, dim3(B), dim3(MAXG), 0, st, (const int*)first, gt_counts, N, G, assigned);
+    TDN_LAUNCH(assign_first_kernel, dim3(B), dim3(MAXG), 0, st, (const int*)w.first, gt_counts, N, G, assigned);
     TDN_LAUNCH_CHECK();
   }
   return 0;
@@ -463,8 +483,8 @@ static BoxSrc anchor_src(const float* boxes, int64_t box_stride, const uint8_t* 
 }
 
 extern "C" int64_t tdn_assign_max_iou_workspace_bytes(int B, int G) {
-  if (B < 1 || B > 64 || G < 0 || G > TDN_TARGET_MAX_GT) return -1;
-  return assign_ws_bytes(B, G);
+  if (check_dims("tdn_assign_max_iou_workspace_bytes", B, 0, G) != 0) return -1;
+  return assign_layout(B, G, nullptr).bytes;
 }
 
 extern "C" int tdn_assign_max_iou(const float* boxes, int64_t box_stride, const uint8_t* valid, int64_t valid_stride,
@@ -477,10 +497,10 @@ extern "C" int tdn_assign_max_iou(const float* boxes, int64_t box_stride, const 
   TDN_CHECK(valid_stride == 0 || valid_stride >= N, "tdn_assign_max_iou: bad valid_stride");
   if (N == 0) return 0;
   TDN_CHECK(boxes && gt_counts && assigned && workspace && (G == 0 || gt), "tdn_assign_max_iou: NULL pointer");
-  TDN_CHECK(workspace_bytes >= assign_ws_bytes(B, G), "tdn_assign_max_iou: workspace too small");
-  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "tdn_assign_max_iou: workspace must be 256-byte aligned");
+  const AssignWs w = assign_layout(B, G, workspace);
+  if (tdn_check_ws("tdn_assign_max_iou", workspace, workspace_bytes, w.bytes) != 0) return -1;
   const BoxSrc S = anchor_src(boxes, box_stride, valid, valid_stride, gt, G, nullptr, -1);
-  return run_assign(S, gt_counts, B, N, G, cfg, assigned, max_overlaps, (char*)workspace, (hipStream_t)stream);
+  return run_assign(S, gt_counts, B, N, G, cfg, assigned, max_overlaps, w, (hipStream_t)stream);
 }
 
 static int run_select(const int32_t* assigned, int B, int N, const tdn_target_config* cfg, const int32_t* keys,
@@ -506,14 +526,9 @@ extern "C" int tdn_sample_assigned(const int32_t* assigned, int B, int N, const 
   return run_select(assigned, B, N, cfg, keys, pos_mask, neg_mask, num_pos, num_neg, (hipStream_t)stream);
 }
 
-// assignment words, then the two masks [B][N] bytes
-static int64_t anchor_ws_bytes(int B, int64_t N, int G) {
-  return assign_ws_bytes(B, G) + 2 * align256((int64_t)B * (N > 0 ? N : 1));
-}
-
 extern "C" int64_t tdn_anchor_target_workspace_bytes(int B, int N, int G) {
-  if (B < 1 || B > 64 || G < 0 || G > TDN_TARGET_MAX_GT || N < 0 || N > TDN_TARGET_MAX_BOXES) return -1;
-  return anchor_ws_bytes(B, N, G);
+  if (check_dims("tdn_anchor_target_workspace_bytes", B, N, G) != 0) return -1;
+  return sample_layout(B, N, G, false, nullptr).bytes;
 }
 
 extern "C" int tdn_anchor_target(const float* anchors, int64_t box_stride, const uint8_t* valid, int64_t valid_stride,
@@ -530,15 +545,12 @@ extern "C" int tdn_anchor_target(const float* anchors, int64_t box_stride, const
   TDN_CHECK(N == 0 || (anchors && labels && label_weights && bbox_targets && bbox_weights && assigned),
             "tdn_anchor_target: NULL pointer");
   TDN_CHECK(cfg->allowed_border < 0 || img_shapes, "tdn_anchor_target: allowed_border >= 0 needs img_shapes");
-  TDN_CHECK(workspace_bytes >= anchor_ws_bytes(B, N, G), "tdn_anchor_target: workspace too small");
-  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "tdn_anchor_target: workspace must be 256-byte aligned");
+  const SampleWs w = sample_layout(B, N, G, false, workspace);
+  if (tdn_check_ws("tdn_anchor_target", workspace, workspace_bytes, w.bytes) != 0) return -1;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  uint8_t* pos_mask = (uint8_t*)(ws + assign_ws_bytes(B, G));
-  uint8_t* neg_mask = pos_mask + align256((int64_t)B * (N > 0 ? N : 1));
   const BoxSrc S = anchor_src(anchors, box_stride, valid, valid_stride, gt, G, img_shapes, cfg->allowed_border);
-  if (N > 0 && run_assign(S, gt_counts, B, N, G, cfg, assigned, nullptr, ws, st) != 0) return -1;
-  if (run_select(assigned, B, N, cfg, keys, pos_mask, neg_mask, num_pos, num_neg, st) != 0) return -1;
+  if (N > 0 && run_assign(S, gt_counts, B, N, G, cfg, assigned, nullptr, w.a, st) != 0) return -1;
+  if (run_select(assigned, B, N, cfg, keys, w.pos_mask, w.neg_mask, num_pos, num_neg, st) != 0) return -1;
   if (N == 0) return 0;
   FillArgs F;
   F.S = S;
@@ -549,24 +561,17 @@ extern "C" int tdn_anchor_target(const float* anchors, int64_t box_stride, const
   F.num = cfg->num;
   F.means = host_f4(cfg->means);
   F.stds = host_f4(cfg->stds);
-  int gx = (N + 255) / 256;
-  if (gx > 2048) gx = 2048;
-  TDN_LAUNCH(anchor_target_fill_kernel, dim3(gx, B), dim3(256), 0, st, F, (const int32_t*)assigned,
-             (const uint8_t*)pos_mask, (const uint8_t*)neg_mask, labels, label_weights, bbox_targets, bbox_weights);
+  TDN_LAUNCH(anchor_target_fill_kernel, dim3(tdn_grid_1d(N, 256, 2048), B), dim3(256), 0, st, F,
+             (const int32_t*)assigned, (const uint8_t*)w.pos_mask, (const uint8_t*)w.neg_mask, labels, label_weights,
+             bbox_targets, bbox_weights);
   TDN_LAUNCH_CHECK();
   return 0;
 }
 
-// assignment words, assigned [B][Nc] int32, the two masks [B][Nc] bytes
-static int64_t rois_ws_bytes(int B, int64_t Nc, int G) {
-  const int64_t n = (int64_t)B * (Nc > 0 ? Nc : 1);
-  return assign_ws_bytes(B, G) + align256(n * 4) + 2 * align256(n);
-}
-
 extern "C" int64_t tdn_sample_rois_workspace_bytes(int B, int P, int G, int add_gt_as_proposals) {
-  if (B < 1 || B > 64 || G < 0 || G > TDN_TARGET_MAX_GT || P < 0 || P > TDN_TARGET_MAX_BOXES - TDN_TARGET_MAX_GT)
-    return -1;
-  return rois_ws_bytes(B, (int64_t)P + (add_gt_as_proposals ? G : 0), G);
+  const char* who = "tdn_sample_rois_workspace_bytes";
+  if (check_props(who, P) != 0 || check_dims(who, B, P, G) != 0) return -1;
+  return sample_layout(B, (int64_t)P + (add_gt_as_proposals ? G : 0), G, true, nullptr).bytes;
 }
 
 extern "C" int tdn_sample_rois(const float* proposals, const int32_t* counts, const float* gt,
@@ -575,21 +580,16 @@ extern "C" int tdn_sample_rois(const float* proposals, const int32_t* counts, co
                                float* label_weights, float* bbox_targets, float* bbox_weights, int32_t* pos_gt_inds,
                                int32_t* num_pos, int32_t* num_neg, void* workspace, int64_t workspace_bytes,
                                void* stream) {
-  TDN_CHECK(P >= 0 && P <= TDN_TARGET_MAX_BOXES - TDN_TARGET_MAX_GT, "tdn_sample_rois: P=%d out of range", P);
-  if (check_common("tdn_sample_rois", B, P, G, cfg) != 0 || check_sampling("tdn_sample_rois", cfg) != 0) return -1;
+  const char* who = "tdn_sample_rois";
+  if (check_props(who, P) != 0 || check_common(who, B, P, G, cfg) != 0 || check_sampling(who, cfg) != 0) return -1;
   const int Nc = P + (cfg->add_gt_as_proposals ? G : 0);
   TDN_CHECK(gt_counts && counts && num_pos && num_neg && workspace && (G == 0 || (gt && gt_labels)) &&
                 (P == 0 || proposals), "tdn_sample_rois: NULL pointer");
   TDN_CHECK(cfg->num == 0 || (rois && labels && label_weights && bbox_targets && bbox_weights && pos_gt_inds),
             "tdn_sample_rois: NULL output");
-  TDN_CHECK(workspace_bytes >= rois_ws_bytes(B, Nc, G), "tdn_sample_rois: workspace too small");
-  TDN_CHECK(((uintptr_t)workspace & 255) == 0, "tdn_sample_rois: workspace must be 256-byte aligned");
+  const SampleWs w = sample_layout(B, Nc, G, true, workspace);
+  if (tdn_check_ws("tdn_sample_rois", workspace, workspace_bytes, w.bytes) != 0) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t n = (int64_t)B * (Nc > 0 ? Nc : 1);
-  char* ws = (char*)workspace;
-  int32_t* assigned = (int32_t*)(ws + assign_ws_bytes(B, G));
-  uint8_t* pos_mask = (uint8_t*)assigned + align256(n * 4);
-  uint8_t* neg_mask = pos_mask + align256(n);
   BoxSrc S;
   memset(&S, 0, sizeof(S));
   S.cand = 1;
@@ -600,8 +600,8 @@ extern "C" int tdn_sample_rois(const float* proposals, const int32_t* counts, co
   S.gt = gt;
   S.G = G;
   S.border = -1;
-  if (Nc > 0 && run_assign(S, gt_counts, B, Nc, G, cfg, assigned, nullptr, ws, st) != 0) return -1;
-  if (run_select(assigned, B, Nc, cfg, keys, pos_mask, neg_mask, num_pos, num_neg, st) != 0) return -1;
+  if (Nc > 0 && run_assign(S, gt_counts, B, Nc, G, cfg, w.assigned, nullptr, w.a, st) != 0) return -1;
+  if (run_select(w.assigned, B, Nc, cfg, keys, w.pos_mask, w.neg_mask, num_pos, num_neg, st) != 0) return -1;
   if (cfg->num == 0) return 0;
   FillArgs F;
   F.S = S;
@@ -612,9 +612,9 @@ extern "C" int tdn_sample_rois(const float* proposals, const int32_t* counts, co
   F.num = cfg->num;
   F.means = host_f4(cfg->means);
   F.stds = host_f4(cfg->stds);
-  TDN_LAUNCH(sample_rois_fill_kernel, dim3(B), dim3(BLK), 0, st, F, (const int32_t*)assigned, (const uint8_t*)pos_mask,
-             (const uint8_t*)neg_mask, gt_labels, rois, labels, label_weights, bbox_targets, bbox_weights,
-             pos_gt_inds);
+  TDN_LAUNCH(sample_rois_fill_kernel, dim3(B), dim3(BLK), 0, st, F, (const int32_t*)w.assigned,
+             (const uint8_t*)w.pos_mask, (const uint8_t*)w.neg_mask, gt_labels, rois, labels, label_weights, bbox_targets,
+             bbox_weights, pos_gt_inds);
   TDN_LAUNCH_CHECK();
   return 0;
 }
