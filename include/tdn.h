@@ -636,6 +636,41 @@ int tdn_loss_roi_bwd(const void* cls, const void* reg, int dtype, int R, int C, 
                      const float* label_weights, const float* bbox_targets, const float* bbox_weights, float beta,
                      const float* g, const float* avg_in, void* dcls, void* dreg, void* stream);
 
+/* ---- test-time detections of the RoI box head: softmax + decode, per-class NMS, per-image top-k (the
+ *      project's own spec in the mmdetection-v0.x lineage of multiclass_nms / get_det_bboxes; NMS is tdn_batched_nms's
+ *      arithmetic, decode is tdn_delta2bbox's, the softmax row is tdn_loss_roi_fwd's) ----
+ * scores fp32 [N][C], column 0 background; boxes fp32 [N][box_cols], box_cols = 4 (C - 1) (class c reads columns
+ * 4 (c - 1) ..) or 4 (class-agnostic).  batch_idx: device int32 (batch_idx_bytes 4) or int64 (8) [N], or NULL for one
+ * image (B = 1); a row whose index is outside [0, B) takes no part.  Candidates of (image b, class c >= 1): the image's
+ * rows with score > score_thr; per segment greedy NMS (score desc, row asc; iou > nms_thr) as tdn_batched_nms; per image
+ * the best min(max_num, survivors) by (score desc, class asc, row asc), always in that order.
+ * Outputs (device): dets fp32 [B][max_num][5] = x1, y1, x2, y2, score; labels int64 [B][max_num] = c - 1; row_idx int64
+ * [B][max_num] = the source row; counts int32 [B]; unused rows 0 / -1 / -1.  An image with a segment of more than
+ * TDN_NMS_SEG_MAX candidates gets counts[b] = -1 and empty rows.  NaN scores are unsupported.
+ * Limits: 1 <= B <= 64, 2 <= C <= TDN_DET_MAX_CLASSES, N <= TDN_DET_MAX_ROWS, 1 <= max_num <= TDN_RPN_MAX_NUM, finite
+ * thresholds, B (C - 1) min(N, TDN_NMS_SEG_MAX) < 2^31.  Four launches; no host synchronisation, no memset, no float
+ * atomics.  workspace: tdn_multiclass_nms_workspace_bytes() bytes, 256-aligned. */
+#define TDN_DET_MAX_CLASSES 1024
+#define TDN_DET_MAX_ROWS (1 << 18)
+int64_t tdn_multiclass_nms_workspace_bytes(int N, int C, int B);
+int tdn_multiclass_nms(const float* boxes, int box_cols, const float* scores, const void* batch_idx, int batch_idx_bytes,
+                       int N, int C, int B, float score_thr, float nms_thr, int max_num, float* dets, int64_t* labels,
+                       int64_t* row_idx, int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+/* The box head's outputs to detections in five launches.  rois fp32 [R][5] = (batch_idx, x1, y1, x2, y2) as
+ * tdn_roi_align_fwd takes them (a row whose (int)batch_idx is not in [0, B) takes no part); cls [R][C] softmax logits,
+ * reg [R][reg_cols], reg_cols = 4C (class c reads columns 4c ..) or 4, both TDN_F32 / TDN_BF16 / TDN_F16; img_shapes
+ * device int32 [B][2] = (h, w): the decode's clip; scale_factors device fp32 [B] or NULL, then scale_factor (0: none):
+ * every clipped coordinate is divided by its image's factor.  dense_scores fp32 [R][C] and dense_boxes fp32
+ * [R][4 (C - 1)] (or [R][4]) are written by the first launch (rows that take no part: 0) and are what the selection
+ * reads: tdn_multiclass_nms on them with batch_idx = the rois' first column gives the same outputs bit for bit.
+ * workspace: tdn_bbox_detections_workspace_bytes() bytes, 256-aligned. */
+int64_t tdn_bbox_detections_workspace_bytes(int R, int C, int B);
+int tdn_bbox_detections(const float* rois, const void* cls, const void* reg, int dtype, int R, int C, int reg_cols, int B,
+                        const int32_t* img_shapes, const float* scale_factors, float scale_factor, const float* means4,
+                        const float* stds4, double wh_ratio_clip, float score_thr, float nms_thr, int max_num,
+                        float* dense_scores, float* dense_boxes, float* dets, int64_t* labels, int64_t* row_idx,
+                        int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

@@ -1,0 +1,455 @@
+// Test-time detections of the RoI box head: softmax + decode, per-class NMS and the per-image top-k.
+//
+// Semantics are the project's own spec in the mmdetection-v0.x lineage (multiclass_nms / get_det_bboxes), '+1' boxes,
+// strict IEEE fp32 in the spec's operation order (this file is compiled with -ffp-contract=off); the CPU restatement
+// is tests/detect_ref.py.
+//
+// multiclass_nms is four launches for any B, C and N; bbox_head_detections puts one launch in front:
+//   0 det_softmax_decode_kernel  one wavefront per RoI row: the softmax row of loss_roi_kernel (fp64 sum in the fixed
+//                                lane -> column order) and the decode of every foreground class, written once as dense
+//                                fp32 (R, C) scores and (R, 4C') boxes; everything after reads those.
+//   1 det_segment_kernel         one workgroup per (image, class): ordered compaction of the image's rows whose score
+//                                in the class's column is > score_thr, LDS bitonic sort of (key << 32 | ~row), box
+//                                gather into the segment's rows.  More than TDN_NMS_SEG_MAX candidates: count -1.
+//   2 det_nms_mask_kernel        nms_mask_block of nms_core.h on every segment: grid (column block, row block, segment).
+//   3 det_nms_scan_kernel        nms_scan_block of nms_core.h, one workgroup per segment; rows already are in key order.
+//   4 det_merge_kernel           one workgroup per image: block_topk over the classes' survivors by (score key desc,
+//                                class asc, row asc); writes the padded outputs and the count.
+// No memset, no float atomics, no inter-workgroup waits, no allocation; the integer LDS atomics of the radix select only
+// count, so every output is a pure function of the inputs.
+#include "nms_core.h"
+#include "select_core.h"
+#include "delta_core.h"
+#include <math.h>
+#include <string.h>
+
+namespace {
+
+constexpr int DET_SEG_MAX = TDN_NMS_SEG_MAX;
+constexpr int DET_WAVES = BLK / 64;
+constexpr int DET_COLS = TDN_DET_MAX_CLASSES / 64;     // columns per lane of a row's wavefront
+
+enum { IDX_NONE = 0, IDX_I32 = 1, IDX_I64 = 2, IDX_ROI = 3 };
+
+// image of row r, or -1 for a row that takes no part.  IDX_ROI: column 0 of (R, 5) rois, by roi_align's rule (the
+// truncated value must lie in [0, B); NaN does not)
+__device__ __forceinline__ int row_image(const void* idx, int kind, int64_t r, int B) {
+  if (kind == IDX_NONE) return 0;
+  if (kind == IDX_ROI) {
+    const float bf = ((const float*)idx)[r * 5];
+    return (bf > -1.f && bf < (float)B) ? (int)bf : -1;
+  }
+  const long long v = kind == IDX_I32 ? (long long)((const int32_t*)idx)[r] : (long long)((const int64_t*)idx)[r];
+  return (v >= 0 && v < B) ? (int)v : -1;
+}
+
+// ---- 0: softmax + decode, one wavefront per row -----------------------------------------------------------------
+template <int DT> struct DetElem;
+template <> struct DetElem<TDN_F32> { typedef float T; };
+template <> struct DetElem<TDN_BF16> { typedef bf16_t T; };
+template <> struct DetElem<TDN_F16> { typedef f16_t T; };
+
+struct HeadArgs {
+  const float* rois;          // (R, 5)
+  const void* cls;            // (R, C)
+  const void* reg;            // (R, reg_cols)
+  const int32_t* img_shapes;  // (B, 2)
+  const float* scales;        // (B,) or null
+  float scale;                // used when scales == null; 0: no rescale
+  int32_t R, C, reg_cols, B;
+  f32x4_t means, stds;
+  float max_ratio;
+};
+
+template <int DT>
+__global__ __launch_bounds__(BLK) void det_softmax_decode_kernel(const HeadArgs A, float* __restrict__ scores,
+                                                                 float* __restrict__ boxes) {
+  typedef typename DetElem<DT>::T T;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int C = A.C;
+  const int nbox = A.reg_cols == 4 ? 1 : C - 1;       // boxes per row of the dense output
+  for (int r = blockIdx.x * DET_WAVES + wave; r < A.R; r += gridDim.x * DET_WAVES) {
+    const float* roi = A.rois + (size_t)r * 5;
+    const int b = row_image(A.rois, IDX_ROI, r, A.B);           // wave-uniform
+    float* sr = scores + (size_t)r * C;
+    f32x4_t* br = (f32x4_t*)boxes + (size_t)r * nbox;
+    if (b < 0) {
+      for (int c = lane; c < C; c += 64) sr[c] = 0.f;
+      for (int c = lane; c < nbox; c += 64) br[c] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+      continue;
+    }
+    // softmax: the row of loss_roi_kernel, operation for operation
+    const T* xr = (const T*)A.cls + (size_t)r * C;
+    float x[DET_COLS];
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < DET_COLS; ++j) {
+      const int c = lane + 64 * j;
+      x[j] = c < C ? (float)xr[c] : -INFINITY;
+      m = fmaxf(m, x[j]);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    double sd = 0.0;
+#pragma unroll
+    for (int j = 0; j < DET_COLS; ++j) {
+      const int c = lane + 64 * j;
+      if (c < C) {
+        x[j] = expf(__fsub_rn(x[j], m));
+        sd += (double)x[j];
+      }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) sd += __shfl_xor(sd, o);
+    const float S = (float)sd;
+#pragma unroll
+    for (int j = 0; j < DET_COLS; ++j) {
+      const int c = lane + 64 * j;
+      if (c < C) sr[c] = __fdiv_rn(x[j], S);
+    }
+    // decode: box k of the row from delta columns 4(k+1).. (class-specific) or 0.. (class-agnostic)
+    const f32x4_t rb = {roi[1], roi[2], roi[3], roi[4]};
+    const int ih = A.img_shapes[2 * b], iw = A.img_shapes[2 * b + 1];
+    const float sc = A.scales ? A.scales[b] : A.scale;
+    const T* dr = (const T*)A.reg + (size_t)r * A.reg_cols + (A.reg_cols == 4 ? 0 : 4);
+    for (int k = lane; k < nbox; k += 64) {
+      f32x4_t d;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) d[e] = (float)dr[4 * k + e];
+      f32x4_t o = decode_box(rb, d, A.means, A.stds, A.max_ratio, ih, iw);
+      if (A.scales || A.scale != 0.f) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = __fdiv_rn(o[e], sc);
+      }
+      br[k] = o;
+    }
+  }
+}
+
+// ---- 1: the (image, class) segments -----------------------------------------------------------------------------
+struct DetArgs {
+  const float* boxes;         // (N, box_cols)
+  const float* scores;        // (N, C)
+  const void* idx;            // image of each row
+  int32_t idx_kind;
+  int32_t N, C, B, box_cols;
+  int32_t cap, pitch, max_num;
+  float score_thr, nms_thr;
+};
+
+constexpr size_t SEG_LDS = (size_t)DET_SEG_MAX * 8 + TK_MISC * 4;                               // 33 KB
+
+__global__ __launch_bounds__(BLK) void det_segment_kernel(const DetArgs A, f32x4_t* seg_box, uint32_t* seg_key,
+                                                          int* seg_row, int* seg_start, int* seg_count) {
+  extern __shared__ __attribute__((aligned(16))) u64 smem[];
+  u64* skeys = smem;                                  // [DET_SEG_MAX]
+  int* misc = (int*)(smem + DET_SEG_MAX);             // [TK_MISC]
+  const int tid = threadIdx.x;
+  const int s = blockIdx.x, Cf = A.C - 1;
+  const int b = s / Cf, cls = s - b * Cf + 1;         // score column of the class
+  const int start = s * A.cap;
+  // candidates in row order; a thread takes TK_PER consecutive rows, so one scan orders a whole step
+  int n = 0;
+  for (int base = 0; base < A.N; base += TK_STEP) {
+    const int r0 = base + tid * TK_PER;
+    uint32_t key[TK_PER];
+    unsigned cand = 0u;                               // bit e: row r0 + e is a candidate
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e) {
+      const int r = r0 + e;
+      key[e] = 0u;
+      if (r < A.N && row_image(A.idx, A.idx_kind, r, A.B) == b) {
+        const float sc = A.scores[(size_t)r * A.C + cls];
+        key[e] = order_key(sc);
+        cand |= sc > A.score_thr ? 1u << e : 0u;
+      }
+    }
+    int tot;
+    int pos = n + block_excl_scan(__builtin_popcount(cand), misc, &tot);
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e)
+      if (cand >> e & 1u) {
+        if (pos < DET_SEG_MAX) skeys[pos] = compose(key[e], (uint32_t)(r0 + e));
+        ++pos;
+      }
+    n += tot;
+  }
+  if (n > DET_SEG_MAX || n > A.cap) {                 // the second cannot happen: cap = min(N, DET_SEG_MAX)
+    if (tid == 0) {
+      seg_start[s] = start;
+      seg_count[s] = -1;
+    }
+    return;
+  }
+  const int P = pow2_ceil(n);
+  for (int i = n + tid; i < P; i += BLK) skeys[i] = 0ull;       // below every real key
+  block_sort_desc(skeys, P);
+  const int col = A.box_cols == 4 ? 0 : 4 * (cls - 1);
+  for (int p = tid; p < n; p += BLK) {
+    const u64 c = skeys[p];
+    const int r = (int)~(uint32_t)c;
+    seg_box[start + p] = *(const f32x4_t*)(A.boxes + (size_t)r * A.box_cols + col);
+    seg_key[start + p] = (uint32_t)(c >> 32);
+    seg_row[start + p] = r;
+  }
+  if (tid == 0) {
+    seg_start[s] = start;
+    seg_count[s] = n;
+  }
+}
+
+// ---- 2, 3: NMS of every segment (the bodies are nms_core.h's) --------------------------------------------------------
+__global__ __launch_bounds__(64) void det_nms_mask_kernel(const float* __restrict__ sboxes, const int* seg_start,
+                                                          const int* seg_count, float thr, int pitch,
+                                                          unsigned long long* __restrict__ mask) {
+  const int s = blockIdx.z, rb = blockIdx.y, cb = blockIdx.x;
+  if (cb < rb) return;
+  const int n = seg_count[s];
+  if (cb * 64 >= n) return;                           // also n <= 0; rb <= cb
+  const int64_t start = seg_start[s];
+  nms_mask_block(sboxes + start * 4, n, thr, pitch, rb, cb, mask + start * pitch);
+}
+
+// kept[start + j]: the segment-local row of survivor j; num_kept[s] = survivors, -1 for an oversized segment
+__global__ __launch_bounds__(BLK) void det_nms_scan_kernel(const unsigned long long* __restrict__ mask,
+                                                           const int* seg_start, const int* seg_count, int pitch,
+                                                           int64_t* kept, int* num_kept) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long sm[];
+  const int s = blockIdx.x;
+  const int n = seg_count[s];
+  if (n <= 0) {
+    if (threadIdx.x == 0) num_kept[s] = n < 0 ? -1 : 0;
+    return;
+  }
+  const int64_t start = seg_start[s];
+  nms_scan_block(mask + start * pitch, nullptr, n, (n + 63) / 64, pitch, nullptr, kept + start, num_kept + s, sm);
+}
+
+// ---- 4: per image, the best max_num of the classes' survivors ------------------------------------------------------
+// candidate j of an image: survivor j - cum[c] of class c, classes in order; among equal keys the candidate order is
+// (class asc, row asc), because a segment's survivors keep its (key desc, row asc) order
+struct SurvivorFetch {
+  const int* cum;           // [Cf + 1] LDS
+  int Cf, seg0, cap;
+  const int64_t* kept;
+  const uint32_t* seg_key;
+  __device__ __forceinline__ int cls(int j) const {   // the last c with cum[c] <= j
+    int lo = 0, hi = Cf - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (cum[mid] <= j) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+  }
+  __device__ __forceinline__ int row(int j, int c) const {      // row of the segment arrays
+    const int st = (seg0 + c) * cap;
+    return st + (int)kept[st + j - cum[c]];
+  }
+  __device__ __forceinline__ void operator()(int i0, int cnt, uint32_t* kk) const {
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e)
+      if (e < cnt) kk[e] = seg_key[row(i0 + e, cls(i0 + e))];
+  }
+};
+
+// dynamic LDS of det_merge_kernel: sorted keys, radix histogram, scratch, class offsets
+size_t merge_lds(int max_num, int C) {
+  return (size_t)pow2_ceil(max_num) * 8 + TK_BINS * 4 + TK_MISC * 4 + (size_t)(C + 1) * 4;
+}
+
+__global__ __launch_bounds__(BLK) void det_merge_kernel(const DetArgs A, const f32x4_t* __restrict__ seg_box,
+                                                        const uint32_t* __restrict__ seg_key,
+                                                        const int* __restrict__ seg_row,
+                                                        const int64_t* __restrict__ kept, const int* num_kept,
+                                                        float* dets, int64_t* labels, int64_t* row_idx,
+                                                        int32_t* counts) {
+  extern __shared__ __attribute__((aligned(16))) u64 smem[];
+  const int K = pow2_ceil(A.max_num);
+  u64* skeys = smem;                                  // [K]
+  int* hist = (int*)(smem + K);                       // [TK_BINS]
+  int* misc = hist + TK_BINS;                         // [TK_MISC]
+  int* cum = misc + TK_MISC;                          // [Cf + 1]
+  const int tid = threadIdx.x, b = blockIdx.x, Cf = A.C - 1;
+  // class offsets: Cf <= 1023 survivors' counts, one per thread; an oversized segment empties the image
+  const int nk = tid < Cf ? num_kept[b * Cf + tid] : 0;
+  const int bad = __syncthreads_or(nk < 0);
+  int T;
+  const int ex = block_excl_scan(nk < 0 ? 0 : nk, misc, &T);
+  if (tid < Cf) cum[tid] = ex;
+  if (tid == 0) cum[Cf] = T;
+  __syncthreads();
+  int m = 0;
+  const SurvivorFetch F{cum, Cf, b * Cf, A.cap, kept, seg_key};
+  if (!bad) m = block_topk(F, T, min(A.max_num, T), skeys, hist, misc);
+  for (int p = tid; p < A.max_num; p += BLK) {
+    float* o = dets + ((int64_t)b * A.max_num + p) * 5;
+    const int64_t q = (int64_t)b * A.max_num + p;
+    if (p < m) {
+      const int j = (int)~(uint32_t)skeys[p];
+      const int c = F.cls(j);
+      const int r = F.row(j, c);
+      const f32x4_t bx = seg_box[r];
+      const int src = seg_row[r];
+      o[0] = bx[0];
+      o[1] = bx[1];
+      o[2] = bx[2];
+      o[3] = bx[3];
+      o[4] = A.scores[(size_t)src * A.C + c + 1];     // the stored score itself (-0.0 stays -0.0)
+      labels[q] = c;
+      row_idx[q] = src;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 5; ++e) o[e] = 0.f;
+      labels[q] = -1;
+      row_idx[q] = -1;
+    }
+  }
+  if (tid == 0) counts[b] = bad ? -1 : m;
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------
+struct DetPlan {
+  DetArgs A;
+  int S;
+  int64_t rows;
+};
+
+// the checks both the query and the call depend on
+int det_plan(const char* who, int N, int C, int B, DetPlan* out) {
+  if (tdn_check_batch(who, B) != 0) return -1;
+  TDN_CHECK(C >= 2 && C <= TDN_DET_MAX_CLASSES, "%s: C=%d out of 2..%d", who, C, TDN_DET_MAX_CLASSES);
+  TDN_CHECK(N >= 0 && N <= TDN_DET_MAX_ROWS, "%s: %d rows (max %d)", who, N, TDN_DET_MAX_ROWS);
+  memset(&out->A, 0, sizeof(out->A));
+  DetArgs& A = out->A;
+  A.N = N;
+  A.C = C;
+  A.B = B;
+  A.cap = N < DET_SEG_MAX ? (N > 0 ? N : 1) : DET_SEG_MAX;    // no rows: one placeholder row per segment
+  A.pitch = (A.cap + 63) / 64;
+  out->S = B * (C - 1);
+  out->rows = (int64_t)out->S * A.cap;
+  return 0;
+}
+
+struct DetWs {
+  f32x4_t* seg_box; uint32_t* seg_key; int* seg_row; int64_t* kept;
+  int *seg_start, *seg_count, *num_kept; u64* mask; int64_t bytes;
+};
+DetWs det_layout(const DetPlan& p, void* base) {   // a braced list is evaluated left to right
+  tdn_carver c{(char*)base, 0};
+  return {c.take<f32x4_t>(p.rows), c.take<uint32_t>(p.rows), c.take<int>(p.rows), c.take<int64_t>(p.rows),
+          c.take<int>(p.S), c.take<int>(p.S), c.take<int>(p.S), c.take<u64>(p.rows * p.A.pitch), c.off};
+}
+
+// launches 1..4 on dense fp32 boxes and scores
+int det_run(const char* who, DetPlan& p, float score_thr, float nms_thr, int max_num, float* dets, int64_t* labels,
+            int64_t* row_idx, int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+  TDN_CHECK(max_num >= 1 && max_num <= TDN_RPN_MAX_NUM, "%s: max_num=%d out of 1..%d", who, max_num, TDN_RPN_MAX_NUM);
+  TDN_CHECK(score_thr - score_thr == 0.f && nms_thr - nms_thr == 0.f, "%s: score_thr / nms_thr must be finite", who);
+  TDN_CHECK(dets && labels && row_idx && counts, "%s: NULL output", who);
+  TDN_CHECK(p.rows < (1ll << 31), "%s: B * (C - 1) * min(N, %d) segment rows do not fit 31 bits", who, DET_SEG_MAX);
+  DetArgs& A = p.A;
+  A.score_thr = score_thr;
+  A.nms_thr = nms_thr;
+  A.max_num = max_num;
+  const DetWs w = det_layout(p, workspace);
+  if (tdn_check_ws(who, workspace, workspace_bytes, w.bytes) != 0) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  TDN_LAUNCH(det_segment_kernel, dim3(p.S), dim3(BLK), SEG_LDS, st, A, w.seg_box, w.seg_key, w.seg_row, w.seg_start,
+             w.seg_count);
+  TDN_LAUNCH_CHECK();
+  TDN_LAUNCH(det_nms_mask_kernel, dim3(A.pitch, A.pitch, p.S), dim3(64), 0, st, (const float*)w.seg_box,
+             (const int*)w.seg_start, (const int*)w.seg_count, nms_thr, A.pitch, w.mask);
+  TDN_LAUNCH_CHECK();
+  if (tdn_allow_lds<det_nms_scan_kernel>(160 * 1024, "det_nms_scan") < 0) return -1;
+  TDN_LAUNCH(det_nms_scan_kernel, dim3(p.S), dim3(BLK), nms_scan_block_lds(A.pitch), st,
+             (const unsigned long long*)w.mask, (const int*)w.seg_start, (const int*)w.seg_count, A.pitch, w.kept,
+             w.num_kept);
+  TDN_LAUNCH_CHECK();
+  // at most 78 KB (max_num = 8192, C = 1024); the kernel also has a few static bytes, so not the full 160 KB
+  if (tdn_allow_lds<det_merge_kernel>((int)merge_lds(TDN_RPN_MAX_NUM, TDN_DET_MAX_CLASSES), "det_merge") < 0) return -1;
+  TDN_LAUNCH(det_merge_kernel, dim3(A.B), dim3(BLK), merge_lds(max_num, A.C), st, A, (const f32x4_t*)w.seg_box,
+             (const uint32_t*)w.seg_key, (const int*)w.seg_row, (const int64_t*)w.kept, (const int*)w.num_kept, dets,
+             labels, row_idx, counts);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t tdn_multiclass_nms_workspace_bytes(int N, int C, int B) {
+  DetPlan p;
+  if (det_plan("tdn_multiclass_nms", N, C, B, &p) != 0) return -1;
+  return det_layout(p, nullptr).bytes;
+}
+
+extern "C" int tdn_multiclass_nms(const float* boxes, int box_cols, const float* scores, const void* batch_idx,
+                                  int batch_idx_bytes, int N, int C, int B, float score_thr, float nms_thr,
+                                  int max_num, float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_multiclass_nms";
+  DetPlan p;
+  if (det_plan(who, N, C, B, &p) != 0) return -1;
+  TDN_CHECK(box_cols == 4 || box_cols == 4 * (C - 1), "%s: box_cols=%d is neither 4 nor 4 * (C - 1)", who, box_cols);
+  TDN_CHECK(batch_idx ? (batch_idx_bytes == 4 || batch_idx_bytes == 8) : (B == 1 || N == 0),
+            "%s: batch_idx must be int32 or int64, or NULL for one image", who);
+  TDN_CHECK(N == 0 || (boxes && scores), "%s: NULL boxes / scores", who);
+  p.A.boxes = boxes;
+  p.A.scores = scores;
+  p.A.idx = batch_idx;
+  p.A.idx_kind = !batch_idx ? IDX_NONE : (batch_idx_bytes == 4 ? IDX_I32 : IDX_I64);
+  p.A.box_cols = box_cols;
+  return det_run(who, p, score_thr, nms_thr, max_num, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t tdn_bbox_detections_workspace_bytes(int R, int C, int B) {
+  DetPlan p;
+  if (det_plan("tdn_bbox_detections", R, C, B, &p) != 0) return -1;
+  return det_layout(p, nullptr).bytes;
+}
+
+extern "C" int tdn_bbox_detections(const float* rois, const void* cls, const void* reg, int dtype, int R, int C,
+                                   int reg_cols, int B, const int32_t* img_shapes, const float* scale_factors,
+                                   float scale_factor, const float* means4, const float* stds4, double wh_ratio_clip,
+                                   float score_thr, float nms_thr, int max_num, float* dense_scores, float* dense_boxes,
+                                   float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_bbox_detections";
+  DetPlan p;
+  if (det_plan(who, R, C, B, &p) != 0) return -1;
+  TDN_CHECK(dtype == TDN_F32 || dtype == TDN_BF16 || dtype == TDN_F16, "%s: dtype %d", who, dtype);
+  TDN_CHECK(reg_cols == 4 || reg_cols == 4 * C, "%s: reg_cols=%d is neither 4 nor 4 * C", who, reg_cols);
+  TDN_CHECK(means4 && stds4 && img_shapes, "%s: NULL means / stds / img_shapes", who);
+  TDN_CHECK(wh_ratio_clip > 0.0 && wh_ratio_clip < 1.0, "%s: wh_ratio_clip must be in (0, 1)", who);
+  TDN_CHECK(scale_factors || scale_factor == 0.f || (scale_factor > 0.f && scale_factor - scale_factor == 0.f),
+            "%s: scale_factor must be positive and finite (0: none)", who);
+  TDN_CHECK(R == 0 || (rois && cls && reg && dense_scores && dense_boxes), "%s: NULL pointer", who);
+  HeadArgs H;
+  memset(&H, 0, sizeof(H));
+  H.rois = rois;
+  H.cls = cls;
+  H.reg = reg;
+  H.img_shapes = img_shapes;
+  H.scales = scale_factors;
+  H.scale = scale_factors ? 0.f : scale_factor;
+  H.R = R;
+  H.C = C;
+  H.reg_cols = reg_cols;
+  H.B = B;
+  H.means = host_f4(means4);
+  H.stds = host_f4(stds4);
+  H.max_ratio = (float)fabs(log(wh_ratio_clip));     // as tdn_delta2bbox: in double, rounded to fp32
+  if (R > 0) {
+    const dim3 grid(tdn_grid_1d(R, DET_WAVES, 4096)), block(BLK);
+    if (dtype == TDN_F32) TDN_LAUNCH(det_softmax_decode_kernel<TDN_F32>, grid, block, 0, stream, H, dense_scores, dense_boxes);
+    else if (dtype == TDN_BF16) TDN_LAUNCH(det_softmax_decode_kernel<TDN_BF16>, grid, block, 0, stream, H, dense_scores, dense_boxes);
+    else TDN_LAUNCH(det_softmax_decode_kernel<TDN_F16>, grid, block, 0, stream, H, dense_scores, dense_boxes);
+    TDN_LAUNCH_CHECK();
+  }
+  p.A.boxes = dense_boxes;
+  p.A.scores = dense_scores;
+  p.A.idx = rois;
+  p.A.idx_kind = IDX_ROI;
+  p.A.box_cols = reg_cols == 4 ? 4 : 4 * (C - 1);
+  return det_run(who, p, score_thr, nms_thr, max_num, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
+}

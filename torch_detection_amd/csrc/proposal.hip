@@ -24,51 +24,9 @@
 #include <math.h>
 #include <string.h>
 
-typedef unsigned long long u64;
-
-// ---- keys ----------------------------------------------------------------------------------------------------
-// order-preserving: a > b (as floats, -0 == +0)  <=>  order_key(a) > order_key(b)
-__device__ __forceinline__ uint32_t order_key(float f) {
-  uint32_t u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ u64 compose(uint32_t key, uint32_t i) { return ((u64)key << 32) | (uint32_t)~i; }
-
 __device__ __forceinline__ float load_elem(const void* p, int dtype, int64_t off) {
   if (dtype == TDN_F32) return ((const float*)p)[off];
   return __uint_as_float((uint32_t)((const uint16_t*)p)[off] << 16);   // bf16 -> fp32 is exact
-}
-
-// ---- decode (spec order, one rounding per operation; the encode is in delta_core.h) ---------------------------------
-// clip_w < 0: no clipping
-__device__ __forceinline__ f32x4_t decode_box(const f32x4_t r, const f32x4_t delta, const f32x4_t means,
-                                              const f32x4_t stds, float max_ratio, int clip_h, int clip_w) {
-  f32x4_t d;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) d[e] = __fadd_rn(__fmul_rn(delta[e], stds[e]), means[e]);
-  const float dw = fminf(fmaxf(d[2], -max_ratio), max_ratio), dh = fminf(fmaxf(d[3], -max_ratio), max_ratio);
-  const float px = __fmul_rn(__fadd_rn(r[0], r[2]), 0.5f), py = __fmul_rn(__fadd_rn(r[1], r[3]), 0.5f);
-  const float pw = __fadd_rn(__fsub_rn(r[2], r[0]), 1.0f), ph = __fadd_rn(__fsub_rn(r[3], r[1]), 1.0f);
-  const float gw = __fmul_rn(pw, expf(dw)), gh = __fmul_rn(ph, expf(dh));
-  const float gx = __fadd_rn(px, __fmul_rn(pw, d[0])), gy = __fadd_rn(py, __fmul_rn(ph, d[1]));
-  const float hw = __fmul_rn(gw, 0.5f), hh = __fmul_rn(gh, 0.5f);
-  f32x4_t o;
-  o[0] = __fadd_rn(__fsub_rn(gx, hw), 0.5f);
-  o[1] = __fadd_rn(__fsub_rn(gy, hh), 0.5f);
-  o[2] = __fsub_rn(__fadd_rn(gx, hw), 0.5f);
-  o[3] = __fsub_rn(__fadd_rn(gy, hh), 0.5f);
-  if (clip_w >= 0) {
-    const float xm = (float)(clip_w - 1), ym = (float)(clip_h - 1);
-    o[0] = fminf(fmaxf(o[0], 0.f), xm);
-    o[1] = fminf(fmaxf(o[1], 0.f), ym);
-    o[2] = fminf(fmaxf(o[2], 0.f), xm);
-    o[3] = fminf(fmaxf(o[3], 0.f), ym);
-  }
-  return o;
 }
 
 __global__ void bbox2delta_kernel(const float* __restrict__ prop, const float* __restrict__ gt, int64_t N,
@@ -115,92 +73,6 @@ extern "C" int tdn_delta2bbox(const float* rois, const float* deltas, int64_t N,
              max_shape ? max_shape[1] : -1, out);
   TDN_LAUNCH_CHECK();
   return 0;
-}
-
-// ---- block-wide helpers (1024 threads; the scan and the radix select are in select_core.h) ----------------------
-// descending bitonic sort of s[0, P), P a power of two
-__device__ __forceinline__ void block_sort_desc(u64* s, int P) {
-  __syncthreads();
-  for (int size = 2; size <= P; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (P >> 1); t += BLK) {
-        const int i = 2 * t - (t & (stride - 1));
-        const int j = i + stride;
-        const u64 a = s[i], c = s[j];
-        if ((a < c) == ((i & size) == 0)) {
-          s[i] = c;
-          s[j] = a;
-        }
-      }
-      __syncthreads();
-    }
-}
-
-__host__ __device__ __forceinline__ int pow2_ceil(int m) {
-  int p = 1;
-  while (p < m) p <<= 1;
-  return p;
-}
-
-// The k highest of n keys (ties: lower index first) as composite keys (key << 32 | ~index), sorted descending into
-// skeys[0, pow2_ceil(k)) (zero padding).  F(i0, cnt, keys) fetches keys i0 .. i0+cnt-1 (cnt <= TK_PER).  Returns
-// min(n, k).  hist: TK_BINS ints of LDS, misc: TK_MISC ints.
-template <class Fetch>
-__device__ int block_topk(const Fetch& F, int n, int k, u64* skeys, int* hist, int* misc) {
-  const int tid = threadIdx.x;
-  int m;
-  if (n <= k) {
-    for (int i0 = tid * TK_PER; i0 < n; i0 += TK_STEP) {
-      const int cnt = min(TK_PER, n - i0);
-      uint32_t kk[TK_PER];
-      F(i0, cnt, kk);
-#pragma unroll
-      for (int e = 0; e < TK_PER; ++e)
-        if (e < cnt) skeys[i0 + e] = compose(kk[e], i0 + e);
-    }
-    m = n;
-  } else {
-    // radix select of the threshold key T: k - need keys are > T, and the first `need` keys == T are taken
-    int need;
-    const uint32_t T = block_radix_threshold(F, n, k, hist, misc, &need);
-    // ordered compaction: keys > T go to [0, k - need) in any order (the sort below orders them), the first `need`
-    // keys == T in index order to [k - need, k)
-    const int ngt = k - need;
-    int gt_done = 0, ties_done = 0;
-    for (int base = 0; base < n; base += TK_STEP) {
-      const int i0 = base + tid * TK_PER;
-      const int cnt = max(0, min(TK_PER, n - i0));
-      uint32_t kk[TK_PER];
-      if (cnt > 0) F(i0, cnt, kk);
-      int ng = 0, nt = 0;
-#pragma unroll
-      for (int e = 0; e < TK_PER; ++e)
-        if (e < cnt) {
-          ng += kk[e] > T ? 1 : 0;
-          nt += kk[e] == T ? 1 : 0;
-        }
-      int tot;   // both counts packed: a step holds at most 8192 of either
-      const int ex = block_excl_scan(ng | (nt << 16), misc, &tot);
-      int gpos = gt_done + (ex & 0xFFFF), tpos = ties_done + (ex >> 16);
-#pragma unroll
-      for (int e = 0; e < TK_PER; ++e)
-        if (e < cnt) {
-          if (kk[e] > T) {
-            skeys[gpos++] = compose(kk[e], i0 + e);
-          } else if (kk[e] == T) {
-            if (tpos < need) skeys[ngt + tpos] = compose(kk[e], i0 + e);
-            ++tpos;
-          }
-        }
-      gt_done += tot & 0xFFFF;
-      ties_done += tot >> 16;
-    }
-    m = k;
-  }
-  const int P = pow2_ceil(m);
-  for (int i = m + tid; i < P; i += BLK) skeys[i] = 0ull;   // below every real key
-  block_sort_desc(skeys, P);
-  return m;
 }
 
 // ---- RPN proposals ----------------------------------------------------------------------------------------------
