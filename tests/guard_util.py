@@ -215,9 +215,6 @@ class TorchProxy(object):
         op, arg = _caller(self._file)
         dtype = dtype if dtype is not None else _torch.get_default_dtype()
         self._g.calls[op] += 1
-        if op == "nms" and dtype == _torch.uint8 and interior == "poison" and arg.startswith("ws@"):
-            # ops.nms builds its workspace inline as empty(nbytes + 256): the slack is for alignment only
-            return self._g.workspace(shape[0] - 256, device, 256, op)
         return self._g.alloc(shape, dtype, device, interior, "%s: %s" % (op, arg))
 
     def empty(self, *shape, dtype=None, device=None):

@@ -175,11 +175,11 @@ MC_REFUSALS = [
     (dict(max_num=8193), "max_num must be in 1..8192"),
     (dict(score_thr=float("nan")), "score_thr must be finite"),
     (dict(nms_thr=float("inf")), "nms_thr must be finite"),
-    (dict(multi_bboxes=torch.zeros(6, 12)), r"multi_bboxes must be a contiguous float32 \(6, 8\) or \(6, 4\)"),
+    (dict(multi_bboxes=torch.zeros(6, 12)), r"multi_bboxes must be a contiguous float32 \(6, 8 or 4\)"),
     (dict(multi_bboxes=torch.zeros(5, 8)), "multi_bboxes must be a contiguous float32"),
     (dict(batch_idx=None), "batch_idx=None means one image"),
-    (dict(batch_idx=torch.zeros(6)), "batch_idx must be a contiguous int32 or int64"),
-    (dict(batch_idx=torch.zeros(5, dtype=torch.int32)), "batch_idx must be a contiguous int32 or int64"),
+    (dict(batch_idx=torch.zeros(6)), "batch_idx must be a contiguous int32 / int64"),
+    (dict(batch_idx=torch.zeros(5, dtype=torch.int32)), "batch_idx must be a contiguous int32 / int64"),
     (dict(), "multi_scores must be a CUDA tensor"),
 ]
 
@@ -201,8 +201,8 @@ def _bh(**kw):
 
 BH_REFUSALS = [
     (dict(rois=torch.zeros(6, 4)), r"rois must be a contiguous float32 \(R, 5\)"),
-    (dict(cls_score=torch.zeros(6, 3, dtype=torch.float64)), r"cls_score must be a contiguous \(6, C\)"),
-    (dict(cls_score=torch.zeros(5, 3)), r"cls_score must be a contiguous \(6, C\)"),
+    (dict(cls_score=torch.zeros(6, 3, dtype=torch.float64)), r"cls_score must be a contiguous float32 / bfloat16 / float16 \(6, C\)"),
+    (dict(cls_score=torch.zeros(5, 3)), r"cls_score must be a contiguous float32 / bfloat16 / float16 \(6, C\)"),
     (dict(img_shapes=torch.ones(2, 2, dtype=torch.int64)), "img_shapes must be a contiguous int32"),
     (dict(img_shapes=[(4, 4), (4, 4)]), "img_shapes must be a contiguous int32"),
     (dict(img_shapes=torch.ones(65, 2, dtype=torch.int32)), "number of images must be in 1..64"),
@@ -211,9 +211,9 @@ BH_REFUSALS = [
           bbox_pred=torch.zeros((1 << 18) + 1, 4)), r"rows \(max 262144\)"),
     (dict(max_per_img=0), "max_num must be in 1..8192"),
     (dict(score_thr=float("inf")), "score_thr must be finite"),
-    (dict(bbox_pred=torch.zeros(6, 8)), r"bbox_pred must be a contiguous \(6, 12\) or \(6, 4\)"),
-    (dict(bbox_pred=torch.zeros(6, 12, dtype=torch.float16)), "of cls_score's dtype"),
-    (dict(scale_factors=torch.ones(3)), "scale_factors must be None, a positive number or a contiguous float32"),
+    (dict(bbox_pred=torch.zeros(6, 8)), r"bbox_pred must be a contiguous float32 \(6, 12 or 4\)"),
+    (dict(bbox_pred=torch.zeros(6, 12, dtype=torch.float16)), r"bbox_pred must be a contiguous float32 \(6, 12 or 4\) tensor, got float16"),
+    (dict(scale_factors=torch.ones(3)), r"scale_factors must be a contiguous float32 \(2,\)"),
     (dict(scale_factors=0.0), "scale_factors must be finite and > 0"),
     (dict(scale_factors=(1.0, 1.0)), "scale_factors must be a number"),
     (dict(target_stds=(0.1, 0.1, 0.2)), "target_stds must have 4 finite entries"),
@@ -229,6 +229,15 @@ def test_bbox_head_detections_refusals(case):
     kw, msg = BH_REFUSALS[case]
     with pytest.raises(ValueError, match=msg):
         T.bbox_head_detections(**_bh(**kw))
+
+
+def test_ws_bytes_reads_a_negative_answer_as_the_librarys_refusal():
+    from torch_detection_amd import _lib
+    lib = _lib.load()
+    with pytest.raises(ValueError, match=r"^multiclass_nms: .*C=1 out of 2\.\.1024"):
+        _lib.ws_bytes(lib.tdn_multiclass_nms_workspace_bytes(10, 1, 1), "multiclass_nms")
+    n = lib.tdn_multiclass_nms_workspace_bytes(1000, 81, 2)
+    assert n > 0 and _lib.ws_bytes(n, "multiclass_nms") == n
 
 
 def test_workspace_queries_share_one_layout_and_refuse_like_the_call():

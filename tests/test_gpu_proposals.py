@@ -219,40 +219,41 @@ def test_rpn_proposals_errors(T):
     cls, reg = _head_outputs(2, levels, 1, torch.float32, False, "normal")
     ish = torch.tensor([(80, 96), (80, 96)], dtype=torch.int32).cuda()
     bad = [
-        dict(cls_scores=cls * 5, bbox_preds=reg * 5, anchors=anchors * 5),                  # 10 levels
-        dict(cls_scores=[c.half() for c in cls], bbox_preds=[d.half() for d in reg]),       # dtype
-        dict(bbox_preds=[reg[0][:, :8], reg[1]]),                                           # 4A channels
-        dict(bbox_preds=[reg[0].bfloat16(), reg[1]]),                                       # mixed dtypes
-        dict(anchors=[anchors[0][:-1], anchors[1]]),                                        # anchor rows
-        dict(img_shapes=ish[:1]),
-        dict(img_shapes=ish.float()),
-        dict(nms_pre=4097),
-        dict(nms_pre=-1),
-        dict(max_num=8193),
-        dict(max_num=0),
-        dict(nms_post=0),
-        dict(min_bbox_size=-1),
-        dict(target_stds=(1, 1, 1)),
+        (dict(cls_scores=cls * 5, bbox_preds=reg * 5, anchors=anchors * 5), "takes 1..8 levels"),      # 10 levels
+        (dict(cls_scores=[c.half() for c in cls], bbox_preds=[d.half() for d in reg]),
+         r"cls_scores\[0\] must be a float32 / bfloat16"),                                              # dtype
+        (dict(bbox_preds=[reg[0][:, :8], reg[1]]), r"bbox_preds\[0\] must be a float32 \(2, 12, 10, 12\)"),  # 4A channels
+        (dict(bbox_preds=[reg[0].bfloat16(), reg[1]]), r"bbox_preds\[0\] must be a float32 .* got bfloat16"),   # mixed dtypes
+        (dict(anchors=[anchors[0][:-1], anchors[1]]), r"anchors\[0\] must be a contiguous float32 \(360, 4\)"),  # anchor rows
+        (dict(img_shapes=ish[:1]), r"img_shapes must be a contiguous int32 \(2, 2\)"),
+        (dict(img_shapes=ish.float()), r"img_shapes must be a contiguous int32 \(2, 2\)"),
+        (dict(nms_pre=4097), "nms_pre must be in 0..4096"),
+        (dict(nms_pre=-1), "nms_pre must be in 0..4096"),
+        (dict(max_num=8193), "max_num must be in 1..8192"),
+        (dict(max_num=0), "max_num must be in 1..8192"),
+        (dict(nms_post=0), "nms_post must be >= 1"),
+        (dict(min_bbox_size=-1), "min_bbox_size must be >= 0"),
+        (dict(target_stds=(1, 1, 1)), "target_stds must have 4 finite entries"),
     ]
-    for kw in bad:
+    for kw, msg in bad:
         args = dict(cls_scores=cls, bbox_preds=reg, anchors=anchors, img_shapes=ish)
         args.update(kw)
-        with pytest.raises(ValueError):
+        with pytest.raises(ValueError, match=msg):
             T.rpn_proposals(**args)
     big = [((70, 70), 8)]                                                                   # 14700 anchors
     a_big = _pyramid(T, big)
     c_big, r_big = _head_outputs(1, big, 2, torch.float32, False, "normal")
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="14700 anchors enter NMS with nms_pre=0"):
         T.rpn_proposals(c_big, r_big, a_big, [(560, 560)], nms_pre=0)
     c65 = [torch.zeros(65, 3, 2, 2, device="cuda")]
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="number of images must be in 1..64"):
         T.rpn_proposals(c65, [torch.zeros(65, 12, 2, 2, device="cuda")], [torch.zeros(12, 4, device="cuda")],
                         [(8, 8)] * 65)
     with pytest.raises(NotImplementedError):
         T.rpn_proposals(cls, reg, anchors, ish, use_sigmoid_cls=False)
     with pytest.raises(NotImplementedError):
         T.rpn_proposals(cls, reg, anchors, ish, nms_across_levels=True)
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="a segment holds more than 4096 boxes"):
         T.batched_nms(torch.zeros(5000, 4, device="cuda"), torch.zeros(5000, device="cuda"),
                       torch.tensor([0, 5000]), 0.5)
     torch.cuda.synchronize()

@@ -279,29 +279,37 @@ def test_bad_inputs_raise_before_any_launch(T):
     fs = feats_of(B, C, C4[:2], torch.bfloat16, 21)
     rois = torch.from_numpy(mixed_rois(10, B, 22)).cuda()
     bad = [
-        lambda: T.roi_align([f.float() for f in fs], rois, 7, (4, 8)),               # fp32 features
-        lambda: T.roi_align([f.cpu() for f in fs], rois, 7, (4, 8)),                 # CPU features
-        lambda: T.roi_align([fs[0], fs[1].half()], rois, 7, (4, 8)),                 # mixed dtypes
-        lambda: T.roi_align([fs[0], fs[1][:1]], rois, 7, (4, 8)),                    # mismatched batch
-        lambda: T.roi_align([fs[0], fs[1][:, :8]], rois, 7, (4, 8)),                 # mismatched channels
-        lambda: T.roi_align([f[:, :12] for f in fs], rois, 7, (4, 8)),               # C % 8
-        lambda: T.roi_align(fs, rois, 7, (4, 8, 16)),                                # levels vs strides
-        lambda: T.roi_align(fs, rois, 17, (4, 8)),                                   # out_size
-        lambda: T.roi_align(fs, rois, 7, (4, 8), -1),                                # sampling_ratio
-        lambda: T.roi_align(fs, rois, 7, (4, 8), 2, 0),                              # finest_scale
-        lambda: T.roi_align(fs, rois[:, 1:].contiguous(), 7, (4, 8)),                # (R, 4) rois
-        lambda: T.roi_align(fs, rois.double(), 7, (4, 8)),
-        lambda: T.roi_align(fs, rois.cpu(), 7, (4, 8)),
-        lambda: T.roi_align(fs, rois.t().contiguous().t(), 7, (4, 8)),               # not contiguous
-        lambda: T.map_roi_levels(rois, 9),
-        lambda: T.SingleRoIExtractor(dict(type='RoIPool', out_size=7)),
-        lambda: T.SingleRoIExtractor(out_channels=32)(fs + fs, rois),
-        lambda: T.rois_from_proposals(torch.zeros(2, 10, 4, device="cuda"), torch.zeros(2, dtype=torch.int32,
-                                                                                        device="cuda")),
-        lambda: T.rois_from_proposals(torch.zeros(2, 10, 5, device="cuda"), torch.zeros(3, dtype=torch.int32,
-                                                                                        device="cuda")),
+        (lambda: T.roi_align([f.float() for f in fs], rois, 7, (4, 8)),
+         r"feats\[0\] must be a bfloat16 / float16"),                                               # fp32 features
+        (lambda: T.roi_align([f.cpu() for f in fs], rois, 7, (4, 8)), r"feats\[0\] must be a CUDA tensor"),  # CPU features
+        (lambda: T.roi_align([fs[0], fs[1].half()], rois, 7, (4, 8)),
+         r"feats\[1\] must be a bfloat16 .* got float16"),                                          # mixed dtypes
+        (lambda: T.roi_align([fs[0], fs[1][:1]], rois, 7, (4, 8)),
+         r"feats\[1\] must be a bfloat16 \(2, 16, H, W\)"),                                         # mismatched batch
+        (lambda: T.roi_align([fs[0], fs[1][:, :8]], rois, 7, (4, 8)),
+         r"feats\[1\] must be a bfloat16 \(2, 16, H, W\)"),                                         # mismatched channels
+        (lambda: T.roi_align([f[:, :12] for f in fs], rois, 7, (4, 8)), "C a positive multiple of 8"),  # C % 8
+        (lambda: T.roi_align(fs, rois, 7, (4, 8, 16)), "2 feature levels but 3 featmap strides"),     # levels vs strides
+        (lambda: T.roi_align(fs, rois, 17, (4, 8)), "out_size must be in 1..16"),                     # out_size
+        (lambda: T.roi_align(fs, rois, 7, (4, 8), -1), "sampling_ratio must be in 0..512"),           # sampling_ratio
+        (lambda: T.roi_align(fs, rois, 7, (4, 8), 2, 0), "finest_scale must be finite and > 0"),      # finest_scale
+        (lambda: T.roi_align(fs, rois[:, 1:].contiguous(), 7, (4, 8)),
+         r"rois must be a contiguous float32 \(R, 5\)"),                                             # (R, 4) rois
+        (lambda: T.roi_align(fs, rois.double(), 7, (4, 8)), r"rois must be a contiguous float32 \(R, 5\)"),
+        (lambda: T.roi_align(fs, rois.cpu(), 7, (4, 8)), "rois must be a CUDA tensor"),
+        (lambda: T.roi_align(fs, rois.t().contiguous().t(), 7, (4, 8)),
+         r"rois must be a contiguous float32 \(R, 5\)"),                                             # not contiguous
+        (lambda: T.map_roi_levels(rois, 9), "num_levels must be in 1..8"),
+        (lambda: T.SingleRoIExtractor(dict(type='RoIPool', out_size=7)), "roi_layer type 'RoIAlign' only"),
+        (lambda: T.SingleRoIExtractor(out_channels=32)(fs + fs, rois), "out_channels is 32"),
+        (lambda: T.rois_from_proposals(torch.zeros(2, 10, 4, device="cuda"),
+                                       torch.zeros(2, dtype=torch.int32, device="cuda")),
+         r"proposals must be a contiguous float32 \(B, M, 5\)"),
+        (lambda: T.rois_from_proposals(torch.zeros(2, 10, 5, device="cuda"),
+                                       torch.zeros(3, dtype=torch.int32, device="cuda")),
+         r"counts must be a contiguous int32 \(2,\)"),
     ]
-    for i, fn in enumerate(bad):
-        with pytest.raises(ValueError):
+    for i, (fn, msg) in enumerate(bad):
+        with pytest.raises(ValueError, match=msg):
             fn()
             pytest.fail("case %d did not raise" % i)

@@ -241,31 +241,36 @@ def test_host_refusals(T):
     pc = torch.zeros(3, dtype=torch.int32, device="cuda")
     lab = torch.zeros(3, gt.shape[1], dtype=torch.int64, device="cuda")
     bad = [
-        lambda: T.assign_max_iou(a.cpu(), gt, cnt, 0.7, 0.3),                                   # CPU tensors
-        lambda: T.assign_max_iou(a, gt.cpu(), cnt, 0.7, 0.3),
-        lambda: T.assign_max_iou(a.double(), gt, cnt, 0.7, 0.3),                                # dtypes
-        lambda: T.assign_max_iou(a, gt, cnt.long(), 0.7, 0.3),
-        lambda: T.assign_max_iou(a, gt, cnt, 0.7, (0.1, 0.3)),                                  # tuple threshold
-        lambda: T.assign_max_iou(a, gt, cnt, (0.7,), 0.3),
-        lambda: T.assign_max_iou(a, torch.zeros(3, 257, 4, device="cuda"), cnt, 0.7, 0.3),      # G over the cap
-        lambda: T.assign_max_iou(a, torch.zeros(65, 4, 4, device="cuda"),
-                                 torch.zeros(65, dtype=torch.int32, device="cuda"), 0.7, 0.3),  # B over 64
-        lambda: T.assign_max_iou(a, gt, cnt, 0.7, 0.3, valid=torch.ones(3, 5, dtype=torch.uint8, device="cuda")),
-        lambda: T.sample_assigned(assigned, 8193, 0.5),                                         # num over 8192
-        lambda: T.sample_assigned(assigned.long(), 256, 0.5),
-        lambda: T.sample_assigned(assigned.cpu(), 256, 0.5),
-        lambda: T.sample_assigned(assigned, 256, 0.5, keys=torch.zeros(3, 100, device="cuda")),
-        lambda: T.anchor_target(**dict(d, img_shapes=d["img_shapes"].float())),
-        lambda: T.anchor_target(num=8193, **d),
-        lambda: T.anchor_target(neg_iou_thr=(0.0, 0.3), **d),
-        lambda: T.anchor_target(target_stds=(1, 1, 1), **d),
-        lambda: T.sample_rois(props, pc, gt, lab, cnt, num=8193),
-        lambda: T.sample_rois(props[..., :4].contiguous(), pc, gt, lab, cnt),
-        lambda: T.sample_rois(props, pc, gt, lab.int(), cnt),
-        lambda: T.sample_rois(props.cpu(), pc, gt, lab, cnt),
+        (lambda: T.assign_max_iou(a.cpu(), gt, cnt, 0.7, 0.3), "boxes must be a CUDA tensor"),           # CPU tensors
+        (lambda: T.assign_max_iou(a, gt.cpu(), cnt, 0.7, 0.3), "gt_bboxes must be a CUDA tensor"),
+        (lambda: T.assign_max_iou(a.double(), gt, cnt, 0.7, 0.3), "boxes must be a contiguous float32"),  # dtypes
+        (lambda: T.assign_max_iou(a, gt, cnt.long(), 0.7, 0.3), "gt_counts must be a contiguous int32"),
+        (lambda: T.assign_max_iou(a, gt, cnt, 0.7, (0.1, 0.3)), "neg_iou_thr must be a number"),          # tuple threshold
+        (lambda: T.assign_max_iou(a, gt, cnt, (0.7,), 0.3), "pos_iou_thr must be a number"),
+        (lambda: T.assign_max_iou(a, torch.zeros(3, 257, 4, device="cuda"), cnt, 0.7, 0.3),
+         r"257 ground truths per image \(max 256\)"),                                                    # G over the cap
+        (lambda: T.assign_max_iou(a, torch.zeros(65, 4, 4, device="cuda"),
+                                  torch.zeros(65, dtype=torch.int32, device="cuda"), 0.7, 0.3),
+         "number of images must be in 1..64"),                                                           # B over 64
+        (lambda: T.assign_max_iou(a, gt, cnt, 0.7, 0.3, valid=torch.ones(3, 5, dtype=torch.uint8, device="cuda")),
+         r"valid must be a contiguous uint8 / bool \(3, \d+\)"),
+        (lambda: T.sample_assigned(assigned, 8193, 0.5), "num must be in 0..8192"),                       # num over 8192
+        (lambda: T.sample_assigned(assigned.long(), 256, 0.5), "assigned_gt_inds must be a contiguous int32"),
+        (lambda: T.sample_assigned(assigned.cpu(), 256, 0.5), "assigned_gt_inds must be a CUDA tensor"),
+        (lambda: T.sample_assigned(assigned, 256, 0.5, keys=torch.zeros(3, 100, device="cuda")),
+         "keys must be a contiguous int32"),
+        (lambda: T.anchor_target(**dict(d, img_shapes=d["img_shapes"].float())), "img_shapes must be a contiguous int32"),
+        (lambda: T.anchor_target(num=8193, **d), "num must be in 0..8192"),
+        (lambda: T.anchor_target(neg_iou_thr=(0.0, 0.3), **d), "neg_iou_thr must be a number"),
+        (lambda: T.anchor_target(target_stds=(1, 1, 1), **d), "target_stds must have 4 finite entries"),
+        (lambda: T.sample_rois(props, pc, gt, lab, cnt, num=8193), "num must be in 0..8192"),
+        (lambda: T.sample_rois(props[..., :4].contiguous(), pc, gt, lab, cnt),
+         r"proposals must be a contiguous float32 \(3, P, 5\)"),
+        (lambda: T.sample_rois(props, pc, gt, lab.int(), cnt), "gt_labels must be a contiguous int64"),
+        (lambda: T.sample_rois(props.cpu(), pc, gt, lab, cnt), "proposals must be a CUDA tensor"),
     ]
-    for i, f in enumerate(bad):
-        with pytest.raises(ValueError):
+    for i, (f, msg) in enumerate(bad):
+        with pytest.raises(ValueError, match=msg):
             f()
             pytest.fail("case %d was accepted" % i)
     torch.cuda.synchronize()

@@ -183,7 +183,7 @@ def _fake_ops(tmp_path):
         "    ws = _workspace(100, dev)\n"
         "    return y, keep, like, f, ws\n"
         "def nms(n, dev='cpu'):\n"
-        "    ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)\n"
+        "    ws, wp = _aligned_ws(n, dev)\n"
         "    return ws\n"
         "def _workspace(nbytes, device):\n"
         "    return torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=device)\n"
@@ -208,7 +208,7 @@ def test_proxy_guards_allocations_and_names_them(tmp_path, monkeypatch):
     assert g.calls["op"] == 4 and g.ws_calls["op"] == 1
     found = g.check()                  # y and like are never written; zeros / full / workspace are not "must write"
     assert len(found) == 2 and found[0].startswith("op: o1@3") and found[1].startswith("op: like@8")
-    w = mod.nms(1000)                  # the inline workspace of ops.nms: exact, 256-aligned size, no slack
+    w = mod.nms(1000)                  # the workspace of ops.nms: exact, 256-aligned size, no slack
     assert w.numel() == 1024 and g.ws_log[-1] == ("nms", 1000, 1024) and g.check() == []
 
 

@@ -5,6 +5,7 @@ import os
 import subprocess
 
 import numpy as np
+import pytest
 
 import proposal_ref as R
 
@@ -197,3 +198,71 @@ def test_workspace_sizes_are_the_design_table():
     lv[0].H = lv[1].H = 0                                    # every level empty: one placeholder row, pitch 1
     assert lib.tdn_rpn_proposals_workspace(lv, 2, 2, ctypes.byref(cfg)) == 8 * 256
     assert lib.tdn_rpn_proposals_workspace(lv, 2, 0, ctypes.byref(cfg)) == -1
+
+
+# ---- host refusals (no GPU: shapes, dtypes, limits and scalars come first, the device last) --------------------------
+def _refusals():
+    import torch
+    import torch_detection_amd as T
+    cls = [torch.zeros(2, 3, 10, 12), torch.zeros(2, 3, 5, 6)]
+    reg = [torch.zeros(2, 12, 10, 12), torch.zeros(2, 12, 5, 6)]
+    anchors = [torch.zeros(360, 4), torch.zeros(90, 4)]
+    ish = torch.ones(2, 2, dtype=torch.int32)
+
+    def rpn(**kw):
+        args = dict(cls_scores=cls, bbox_preds=reg, anchors=anchors, img_shapes=ish)
+        args.update(kw)
+        return lambda: T.rpn_proposals(**args)
+
+    p, gt, d = torch.zeros(7, 4), torch.zeros(7, 4), torch.zeros(7, 8)
+    s, off = torch.zeros(7), torch.tensor([0, 3, 7])
+    return [
+        (rpn(cls_scores=cls * 5, bbox_preds=reg * 5, anchors=anchors * 5), "rpn_proposals takes 1..8 levels"),
+        (rpn(cls_scores=[c.half() for c in cls], bbox_preds=[r.half() for r in reg]),
+         r"cls_scores\[0\] must be a float32 / bfloat16"),
+        (rpn(bbox_preds=[reg[0][:, :8], reg[1]]), r"bbox_preds\[0\] must be a float32 \(2, 12, 10, 12\)"),
+        (rpn(bbox_preds=[reg[0].bfloat16(), reg[1]]), r"bbox_preds\[0\] must be a float32 .* got bfloat16"),
+        (rpn(anchors=[anchors[0][:-1], anchors[1]]), r"anchors\[0\] must be a contiguous float32 \(360, 4\)"),
+        (rpn(img_shapes=ish[:1]), r"img_shapes must be a contiguous int32 \(2, 2\)"),
+        (rpn(img_shapes=ish.float()), r"img_shapes must be a contiguous int32 \(2, 2\)"),
+        (rpn(img_shapes=[(8, 8)]), "img_shapes must hold B positive"),
+        (rpn(nms_pre=4097), "nms_pre must be in 0..4096"),
+        (rpn(nms_pre=-1), "nms_pre must be in 0..4096"),
+        (rpn(max_num=8193), "max_num must be in 1..8192"),
+        (rpn(max_num=0), "max_num must be in 1..8192"),
+        (rpn(nms_post=0), "nms_post must be >= 1"),
+        (rpn(min_bbox_size=-1), "min_bbox_size must be >= 0"),
+        (rpn(nms_thr=float("nan")), "nms_thr must be finite"),
+        (rpn(target_stds=(1, 1, 1)), "target_stds must have 4 finite entries"),
+        (rpn(cls_scores=[torch.zeros(1, 3, 70, 70)], bbox_preds=[torch.zeros(1, 12, 70, 70)],
+             anchors=[torch.zeros(14700, 4)], img_shapes=[(560, 560)], nms_pre=0), "14700 anchors enter NMS with nms_pre=0"),
+        (rpn(cls_scores=[torch.zeros(65, 3, 2, 2)], bbox_preds=[torch.zeros(65, 12, 2, 2)], anchors=[torch.zeros(12, 4)],
+             img_shapes=[(8, 8)] * 65), "batch size: the number of images must be in 1..64"),
+        (rpn(), r"cls_scores\[0\] must be a CUDA tensor"),
+        (lambda: T.batched_nms(torch.zeros(5000, 4), torch.zeros(5000), torch.tensor([0, 5000]), 0.5),
+         "a segment holds more than 4096 boxes"),
+        (lambda: T.batched_nms(p, s, torch.tensor([0, 8]), 0.5), r"seg_offsets must be non-decreasing within \[0, 7\]"),
+        (lambda: T.batched_nms(p, s, off.int(), 0.5), r"seg_offsets must be a int64 \(S\+1,\)"),
+        (lambda: T.batched_nms(p, s[:6], off, 0.5), r"scores must be a contiguous float32 \(7,\)"),
+        (lambda: T.batched_nms(p, s, off, 0.5), "boxes must be a CUDA tensor"),
+        (lambda: T.bbox2delta(p, gt[:6]), r"gt must be a contiguous float32 \(7, 4\)"),
+        (lambda: T.bbox2delta(p.double(), gt), r"proposals must be a contiguous float32 \(N, 4\)"),
+        (lambda: T.bbox2delta(p, gt, stds=(1, 1, 1, float("inf"))), "stds must have 4 finite entries"),
+        (lambda: T.bbox2delta(p, gt), "proposals must be a CUDA tensor"),
+        (lambda: T.delta2bbox(p, d[:, :6].contiguous()), "deltas must have 4C columns"),
+        (lambda: T.delta2bbox(p, d[:6]), r"deltas must be a contiguous float32 \(7, 4C\)"),
+        (lambda: T.delta2bbox(p, d, wh_ratio_clip=1.0), r"wh_ratio_clip must be in \(0, 1\)"),
+        (lambda: T.delta2bbox(p, d, max_shape=(0, 10)), "max_shape must be a positive"),
+        (lambda: T.delta2bbox(p, d), "rois must be a CUDA tensor"),
+    ]
+
+
+def test_host_refusal_table_is_run_in_full():
+    assert len(_refusals()) == 33
+
+
+@pytest.mark.parametrize("case", range(33))
+def test_host_refusals_need_no_gpu(case):
+    fn, msg = _refusals()[case]
+    with pytest.raises(ValueError, match=msg):
+        fn()

@@ -5,6 +5,7 @@ import os
 import subprocess
 
 import numpy as np
+import pytest
 import torch
 
 import roi_ref as R
@@ -201,3 +202,48 @@ def test_bwd_workspace_size_is_the_design_table():
     assert lib.tdn_roi_align_bwd_workspace(1001) == 32256 + 16128      # 32032 -> 126 * 256, 16016 -> 63 * 256
     assert lib.tdn_roi_align_bwd_workspace(0) == 2 * 256               # R = 0 counts as one row
     assert lib.tdn_roi_align_bwd_workspace(-1) == -1 and lib.tdn_roi_align_bwd_workspace(1 << 31) == -1
+
+
+# ---- host refusals (no GPU: shapes, dtypes, limits and scalars come first, the device last) --------------------------
+def _refusals():
+    import torch_detection_amd as T
+    fs = [torch.zeros(2, 16, 8, 12, dtype=torch.bfloat16), torch.zeros(2, 16, 4, 6, dtype=torch.bfloat16)]
+    rois = torch.zeros(10, 5)
+    props, counts = torch.zeros(2, 10, 5), torch.zeros(2, dtype=torch.int32)
+    return [
+        (lambda: T.roi_align([f.float() for f in fs], rois, 7, (4, 8)), r"feats\[0\] must be a bfloat16 / float16"),
+        (lambda: T.roi_align([fs[0], fs[1].half()], rois, 7, (4, 8)), r"feats\[1\] must be a bfloat16 .* got float16"),
+        (lambda: T.roi_align([fs[0], fs[1][:1]], rois, 7, (4, 8)), r"feats\[1\] must be a bfloat16 \(2, 16, H, W\)"),
+        (lambda: T.roi_align([fs[0], fs[1][:, :8]], rois, 7, (4, 8)), r"feats\[1\] must be a bfloat16 \(2, 16, H, W\)"),
+        (lambda: T.roi_align([f[:, :12] for f in fs], rois, 7, (4, 8)), "C a positive multiple of 8"),
+        (lambda: T.roi_align(fs, rois, 7, (4, 8, 16)), "2 feature levels but 3 featmap strides"),
+        (lambda: T.roi_align(fs, rois, 17, (4, 8)), "out_size must be in 1..16"),
+        (lambda: T.roi_align(fs, rois, 7, (4, 8), -1), "sampling_ratio must be in 0..512"),
+        (lambda: T.roi_align(fs, rois, 7, (4, 8), 2, 0), "finest_scale must be finite and > 0"),
+        (lambda: T.roi_align(fs, rois[:, 1:].contiguous(), 7, (4, 8)), r"rois must be a contiguous float32 \(R, 5\)"),
+        (lambda: T.roi_align(fs, rois.double(), 7, (4, 8)), r"rois must be a contiguous float32 \(R, 5\)"),
+        (lambda: T.roi_align(fs, rois.t().contiguous().t(), 7, (4, 8)), r"rois must be a contiguous float32 \(R, 5\)"),
+        (lambda: T.roi_align(fs, rois, 7, (4, 8)), r"feats\[0\] must be a CUDA tensor"),
+        (lambda: T.map_roi_levels(rois, 9), "num_levels must be in 1..8"),
+        (lambda: T.map_roi_levels(rois[:, 1:].contiguous(), 4), r"rois must be a contiguous float32 \(R, 5\)"),
+        (lambda: T.map_roi_levels(rois, 4, float("inf")), "finest_scale must be finite and > 0"),
+        (lambda: T.map_roi_levels(rois, 4), "rois must be a CUDA tensor"),
+        (lambda: T.SingleRoIExtractor(dict(type='RoIPool', out_size=7)), "roi_layer type 'RoIAlign' only"),
+        (lambda: T.SingleRoIExtractor(out_channels=32)(fs + fs, rois), "out_channels is 32"),
+        (lambda: T.rois_from_proposals(props[..., :4].contiguous(), counts),
+         r"proposals must be a contiguous float32 \(B, M, 5\)"),
+        (lambda: T.rois_from_proposals(props, torch.zeros(3, dtype=torch.int32)),
+         r"counts must be a contiguous int32 \(2,\)"),
+        (lambda: T.rois_from_proposals(props, counts), "proposals must be a CUDA tensor"),
+    ]
+
+
+def test_host_refusal_table_is_run_in_full():
+    assert len(_refusals()) == 22
+
+
+@pytest.mark.parametrize("case", range(22))
+def test_host_refusals_need_no_gpu(case):
+    fn, msg = _refusals()[case]
+    with pytest.raises(ValueError, match=msg):
+        fn()

@@ -244,3 +244,60 @@ def test_sample_rois_layout():
     assert np.all(rois[16 + 13:, 0] == -1) and np.all(lw[16 + 13:] == 0) and np.all(pg[17:] == -1)    # 1 + 12 rows used
     assert set(lab[:4].tolist()) <= {5, 6, 7} and np.all(lab[4:16] == 0) and np.all(bw[:4] == 1) and np.all(bw[4:16] == 0)
     assert np.all(bt[16] == 0)                                        # a ground truth against itself
+
+
+# ---- host refusals (no GPU: shapes, dtypes, limits and scalars come first, the device last) --------------------------
+def _refusals():
+    import torch_detection_amd as T
+    a, gt, cnt = torch.zeros(100, 4), torch.zeros(3, 5, 4), torch.zeros(3, dtype=torch.int32)
+    assigned = torch.zeros(3, 100, dtype=torch.int32)
+    props, pc, lab = torch.zeros(3, 50, 5), torch.zeros(3, dtype=torch.int32), torch.zeros(3, 5, dtype=torch.int64)
+    d = dict(anchors=a, valid_flags=torch.ones(3, 100, dtype=torch.uint8), gt_bboxes=gt, gt_counts=cnt,
+             img_shapes=torch.ones(3, 2, dtype=torch.int32))
+    return [
+        (lambda: T.assign_max_iou(a.double(), gt, cnt, 0.7, 0.3), "boxes must be a contiguous float32"),
+        (lambda: T.assign_max_iou(a, gt, cnt.long(), 0.7, 0.3), r"gt_counts must be a contiguous int32 \(3,\)"),
+        (lambda: T.assign_max_iou(a, gt, cnt, 0.7, (0.1, 0.3)), "neg_iou_thr must be a number"),
+        (lambda: T.assign_max_iou(a, gt, cnt, (0.7,), 0.3), "pos_iou_thr must be a number"),
+        (lambda: T.assign_max_iou(a, gt, cnt, float("nan"), 0.3), "pos_iou_thr must be finite"),
+        (lambda: T.assign_max_iou(a, torch.zeros(3, 257, 4), cnt, 0.7, 0.3), r"257 ground truths per image \(max 256\)"),
+        (lambda: T.assign_max_iou(a, torch.zeros(65, 4, 4), torch.zeros(65, dtype=torch.int32), 0.7, 0.3),
+         "batch size: the number of images must be in 1..64"),
+        (lambda: T.assign_max_iou(a, gt[..., :3].contiguous(), cnt, 0.7, 0.3),
+         r"gt_bboxes must be a contiguous float32 \(B, G, 4\)"),
+        (lambda: T.assign_max_iou(torch.zeros(2, 100, 4), gt, cnt, 0.7, 0.3),
+         r"boxes must be a contiguous float32 \(3, N, 4\)"),
+        (lambda: T.assign_max_iou(a, gt, cnt, 0.7, 0.3, valid=torch.ones(3, 5, dtype=torch.uint8)),
+         r"valid must be a contiguous uint8 / bool \(3, 100\)"),
+        (lambda: T.assign_max_iou(a, gt, cnt, 0.7, 0.3), "boxes must be a CUDA tensor"),
+        (lambda: T.sample_assigned(assigned, 8193, 0.5), "num must be in 0..8192"),
+        (lambda: T.sample_assigned(assigned, 256, 1.5), r"pos_fraction must be in \[0, 1\]"),
+        (lambda: T.sample_assigned(assigned.long(), 256, 0.5), r"assigned_gt_inds must be a contiguous int32 \(B, N\)"),
+        (lambda: T.sample_assigned(assigned, 256, 0.5, keys=torch.zeros(3, 100)),
+         r"keys must be a contiguous int32 \(3, 100\)"),
+        (lambda: T.sample_assigned(assigned, 256, 0.5), "assigned_gt_inds must be a CUDA tensor"),
+        (lambda: T.anchor_target(**dict(d, img_shapes=d["img_shapes"].float())),
+         r"img_shapes must be a contiguous int32 \(3, 2\)"),
+        (lambda: T.anchor_target(num=8193, **d), "num must be in 0..8192"),
+        (lambda: T.anchor_target(neg_iou_thr=(0.0, 0.3), **d), "neg_iou_thr must be a number"),
+        (lambda: T.anchor_target(target_stds=(1, 1, 1), **d), "target_stds must have 4 finite entries"),
+        (lambda: T.anchor_target(**d), "anchors must be a CUDA tensor"),
+        (lambda: T.sample_rois(props, pc, gt, lab, cnt, num=8193), "num must be in 0..8192"),
+        (lambda: T.sample_rois(props[..., :4].contiguous(), pc, gt, lab, cnt),
+         r"proposals must be a contiguous float32 \(3, P, 5\)"),
+        (lambda: T.sample_rois(props, pc, gt, lab.int(), cnt), r"gt_labels must be a contiguous int64 \(3, 5\)"),
+        (lambda: T.sample_rois(props, pc, gt, lab, cnt, keys=torch.zeros(3, 50, dtype=torch.int32)),
+         r"keys must be a contiguous int32 \(3, 55\)"),                    # the ground truths are candidates too
+        (lambda: T.sample_rois(props, pc, gt, lab, cnt), "proposals must be a CUDA tensor"),
+    ]
+
+
+@pytest.mark.parametrize("case", range(26))
+def test_host_refusals_need_no_gpu(case):
+    fn, msg = _refusals()[case]
+    with pytest.raises(ValueError, match=msg):
+        fn()
+
+
+def test_host_refusal_table_is_run_in_full():
+    assert len(_refusals()) == 26

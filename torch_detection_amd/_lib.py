@@ -345,6 +345,15 @@ def check(rc, what):
         raise RuntimeError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
 
 
+def ws_bytes(nbytes, what):
+    """The answer of a ``*_workspace*()`` query of the detection heads: a negative one is a refusal (ValueError) whose
+    reason the library left in ``tdn_last_error``."""
+    if nbytes < 0:
+        msg = load().tdn_last_error()
+        raise ValueError("%s: %s" % (what, msg.decode() if msg else "?"))
+    return nbytes
+
+
 _tls = threading.local()
 
 

@@ -10,6 +10,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._args import CODES, batch, f4, integer, number, on_device, tensor
 from ._lib import ADD_NONE, ADD_SAME, ADD_SUMPOOL2, ADD_UP2X, TDN_BF16, TDN_F16, Epilogue  # noqa: F401
 
 BF16 = torch.bfloat16
@@ -748,16 +749,15 @@ def nhwc_to_nchw_f32(x):
 
 
 # ---- box ops ---------------------------------------------------------------------------------------
-def _chk_boxes(b, name):
-    if b.dtype != torch.float32 or not b.is_cuda or b.dim() != 2 or b.shape[1] != 4 or not b.is_contiguous():
-        raise ValueError("%s must be a contiguous CUDA float32 (K,4) tensor" % name)
-    _chk_dev(b, name)
+# From here to rois_from_proposals the wrappers are written in the vocabulary of _args.py: shapes,
+# dtypes, limits and scalars first, on_device(...) last; then the library, the workspace query, allocations, the call.
+F32 = torch.float32
 
 
 def anchor_grid(base_anchors, featmap_size, stride, valid_size=None):
-    _chk_boxes(base_anchors, "base_anchors")
+    A = tensor(base_anchors, "base_anchors", F32, ("A", 4))[0]
+    on_device([("base_anchors", base_anchors)])
     fh, fw = featmap_size
-    A = base_anchors.shape[0]
     vh, vw = valid_size if valid_size is not None else (fh, fw)
     dev = base_anchors.device
     anchors = torch.empty(fh * fw * A, 4, dtype=torch.float32, device=dev)
@@ -778,11 +778,12 @@ def anchor_pyramid(bases, featmap_sizes, strides, valid_sizes=None):
     arr = (_lib.AnchorLevel * n)()
     counts = []
     for l, (base, (fh, fw), st) in enumerate(zip(bases, featmap_sizes, strides)):
-        _chk_boxes(base, "base_anchors[%d]" % l)
+        A = tensor(base, "base_anchors[%d]" % l, F32, ("A", 4))[0]
         vh, vw = valid_sizes[l] if valid_sizes is not None else (fh, fw)
-        arr[l].base_anchors, arr[l].A = base.data_ptr(), base.shape[0]
+        arr[l].base_anchors, arr[l].A = base.data_ptr(), A
         arr[l].featH, arr[l].featW, arr[l].stride, arr[l].valid_h, arr[l].valid_w = int(fh), int(fw), int(st), int(vh), int(vw)
-        counts.append(int(fh) * int(fw) * base.shape[0])
+        counts.append(int(fh) * int(fw) * A)
+    on_device([("base_anchors[%d]" % l, base) for l, base in enumerate(bases)])
     dev = bases[0].device
     total = sum(counts)
     anchors = torch.empty(total, 4, dtype=torch.float32, device=dev)
@@ -793,56 +794,56 @@ def anchor_pyramid(bases, featmap_sizes, strides, valid_sizes=None):
 
 
 def bbox_iou_pairwise(a, b):
-    _chk_boxes(a, "bboxes1")
-    _chk_boxes(b, "bboxes2")
-    out = torch.empty(a.shape[0], b.shape[0], dtype=torch.float32, device=a.device)
-    _lib.check(_lib.load().tdn_bbox_iou_pairwise(_ptr(a), a.shape[0], _ptr(b), b.shape[0], _ptr(out),
-                                                 _lib.stream_ptr()), "tdn_bbox_iou_pairwise")
+    N, M = tensor(a, "bboxes1", F32, ("N", 4))[0], tensor(b, "bboxes2", F32, ("M", 4))[0]
+    on_device([("bboxes1", a), ("bboxes2", b)])
+    out = torch.empty(N, M, dtype=torch.float32, device=a.device)
+    _lib.check(_lib.load().tdn_bbox_iou_pairwise(_ptr(a), N, _ptr(b), M, _ptr(out), _lib.stream_ptr()),
+               "tdn_bbox_iou_pairwise")
     return out
 
 
-def _f4(vals):
-    vals = [float(v) for v in vals]
-    if len(vals) != 4:
+def _means_stds(means, stds):
+    """For bbox_normalize_ / bbox_denormalize, which keep the exception of the reference's own assert on the length."""
+    if len(means) != 4 or len(stds) != 4:
         raise AssertionError("means / stds must have 4 entries")
-    return (ctypes.c_float * 4)(*vals)
+    return f4(means, "means"), f4(stds, "stds")
 
 
 def bbox_normalize_(bbox, means, stds):
     """In place: bbox <- (bbox - means) / stds (datasets/utils/bbox.py:118-140). bbox: CUDA float32 (A, 4)."""
-    _chk_boxes(bbox, "bbox")
-    _lib.check(_lib.load().tdn_bbox_normalize(_ptr(bbox), bbox.shape[0], _f4(means), _f4(stds), _lib.stream_ptr()),
-               "tdn_bbox_normalize")
+    A = tensor(bbox, "bbox", F32, ("A", 4))[0]
+    means, stds = _means_stds(means, stds)
+    on_device([("bbox", bbox)])
+    _lib.check(_lib.load().tdn_bbox_normalize(_ptr(bbox), A, means, stds, _lib.stream_ptr()), "tdn_bbox_normalize")
     return bbox
 
 
 def bbox_denormalize(bbox, means, stds):
     """bbox * stds + means, means/stds tiled over the 4C columns (datasets/utils/bbox.py:143-166)."""
-    if bbox.dtype != torch.float32 or not bbox.is_cuda or bbox.dim() != 2 or not bbox.is_contiguous():
-        raise ValueError("bbox must be a contiguous CUDA float32 (A, 4C) tensor")
-    if bbox.shape[1] % 4:
+    A, cols = tensor(bbox, "bbox", F32, ("A", "4C"))
+    if cols % 4:
         raise AssertionError("bbox.shape[1] must be a multiple of 4")
+    means, stds = _means_stds(means, stds)
+    on_device([("bbox", bbox)])
     out = torch.empty_like(bbox)
-    _lib.check(_lib.load().tdn_bbox_denormalize(_ptr(bbox), _ptr(out), bbox.shape[0], bbox.shape[1], _f4(means),
-                                                _f4(stds), _lib.stream_ptr()), "tdn_bbox_denormalize")
+    _lib.check(_lib.load().tdn_bbox_denormalize(_ptr(bbox), _ptr(out), A, cols, means, stds, _lib.stream_ptr()),
+               "tdn_bbox_denormalize")
     return out
 
 
 def nms(boxes, scores, iou_thr):
-    _chk_boxes(boxes, "boxes")
-    N = boxes.shape[0]
-    if scores.dtype != torch.float32 or not scores.is_cuda or scores.numel() != N or not scores.is_contiguous():
-        raise ValueError("scores must be a contiguous CUDA float32 (N,) tensor")
+    N = tensor(boxes, "boxes", F32, ("N", 4))[0]
+    tensor(scores, "scores", F32, (N,))
+    on_device([("boxes", boxes), ("scores", scores)])
     dev = boxes.device
+    lib = _lib.load()
+    nbytes = _lib.ws_bytes(lib.tdn_nms_workspace(N), "nms")
     keep = torch.zeros(N, dtype=torch.uint8, device=dev)
     kept_idx = torch.empty(N, dtype=torch.int64, device=dev)
     num = torch.zeros(1, dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    nbytes = lib.tdn_nms_workspace(N)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    _lib.check(lib.tdn_nms(_ptr(boxes), _ptr(scores), N, float(iou_thr), _ptr(keep), _ptr(kept_idx), _ptr(num),
-                           ctypes.c_void_p(ws.data_ptr() + off), nbytes, _lib.stream_ptr()), "tdn_nms")
+    ws, wp = _aligned_ws(nbytes, dev)
+    _lib.check(lib.tdn_nms(_ptr(boxes), _ptr(scores), N, float(iou_thr), _ptr(keep), _ptr(kept_idx), _ptr(num), wp,
+                           nbytes, _lib.stream_ptr()), "tdn_nms")
     return keep, kept_idx, num
 
 
@@ -853,36 +854,40 @@ def _aligned_ws(nbytes, dev):
 
 def bbox2delta(proposals, gt, means, stds):
     """(N,4) deltas = (encode(proposals, gt) - means) / stds."""
-    _chk_boxes(proposals, "proposals")
-    _chk_boxes(gt, "gt")
-    if proposals.shape != gt.shape:
-        raise ValueError("proposals %s and gt %s differ in shape" % (tuple(proposals.shape), tuple(gt.shape)))
-    _chk_dev(gt, "gt")
+    N = tensor(proposals, "proposals", F32, ("N", 4))[0]
+    tensor(gt, "gt", F32, (N, 4))
+    means, stds = f4(means, "means"), f4(stds, "stds")
+    on_device([("proposals", proposals), ("gt", gt)])
     out = torch.empty_like(proposals)
-    _lib.check(_lib.load().tdn_bbox2delta(_ptr(proposals), _ptr(gt), proposals.shape[0], _f4(means), _f4(stds),
-                                          _ptr(out), _lib.stream_ptr()), "tdn_bbox2delta")
+    _lib.check(_lib.load().tdn_bbox2delta(_ptr(proposals), _ptr(gt), N, means, stds, _ptr(out), _lib.stream_ptr()),
+               "tdn_bbox2delta")
     return out
+
+
+def _clip(wh_ratio_clip):
+    clip = number(wh_ratio_clip, "wh_ratio_clip")
+    if not 0.0 < clip < 1.0:
+        raise ValueError("wh_ratio_clip must be in (0, 1), got %r" % clip)
+    return clip
 
 
 def delta2bbox(rois, deltas, means, stds, max_shape, wh_ratio_clip):
     """(N,4C) boxes: rois (N,4) decoded by deltas (N,4C) * stds + means, clipped to max_shape = (h, w) if given."""
-    _chk_boxes(rois, "rois")
-    if deltas.dtype != torch.float32 or not deltas.is_cuda or deltas.dim() != 2 or not deltas.is_contiguous() or \
-            deltas.shape[0] != rois.shape[0] or deltas.shape[1] == 0 or deltas.shape[1] % 4:
-        raise ValueError("deltas must be a contiguous CUDA float32 (N, 4C) tensor with N = rois.shape[0]")
-    _chk_dev(deltas, "deltas")
-    if not 0.0 < float(wh_ratio_clip) < 1.0:
-        raise ValueError("wh_ratio_clip must be in (0, 1)")
+    N = tensor(rois, "rois", F32, ("N", 4))[0]
+    cols = tensor(deltas, "deltas", F32, (N, "4C"))[1]
+    if cols == 0 or cols % 4:
+        raise ValueError("deltas must have 4C columns with C >= 1, got %d" % cols)
+    means, stds, clip = f4(means, "means"), f4(stds, "stds"), _clip(wh_ratio_clip)
     ms = None
     if max_shape is not None:
         h, w = int(max_shape[0]), int(max_shape[1])
         if h <= 0 or w <= 0:
             raise ValueError("max_shape must be a positive (h, w)")
         ms = (ctypes.c_int32 * 2)(h, w)
+    on_device([("rois", rois), ("deltas", deltas)])
     out = torch.empty_like(deltas)
-    _lib.check(_lib.load().tdn_delta2bbox(_ptr(rois), _ptr(deltas), rois.shape[0], deltas.shape[1] // 4, _f4(means),
-                                          _f4(stds), ms, float(wh_ratio_clip), _ptr(out), _lib.stream_ptr()),
-               "tdn_delta2bbox")
+    _lib.check(_lib.load().tdn_delta2bbox(_ptr(rois), _ptr(deltas), N, cols // 4, means, stds, ms, clip, _ptr(out),
+                                          _lib.stream_ptr()), "tdn_delta2bbox")
     return out
 
 
@@ -890,39 +895,29 @@ def batched_nms(boxes, scores, seg_offsets, iou_thr):
     """Greedy NMS of the contiguous segments of a CSR int64 ``seg_offsets`` (S+1,) in one call (tdn_batched_nms).
     A CPU ``seg_offsets`` is validated here and copied; a CUDA one is checked on the device (a bad segment gets
     count -1).  Returns (keep (N,) uint8, kept indices (N,) int64, counts (S,) int32); never synchronises."""
-    _chk_boxes(boxes, "boxes")
-    N = boxes.shape[0]
-    if scores.dtype != torch.float32 or not scores.is_cuda or scores.dim() != 1 or scores.numel() != N or \
-            not scores.is_contiguous():
-        raise ValueError("scores must be a contiguous CUDA float32 (N,) tensor")
-    _chk_dev(scores, "scores")
-    if not torch.is_tensor(seg_offsets) or seg_offsets.dtype != torch.int64 or seg_offsets.dim() != 1 or \
-            seg_offsets.numel() < 1:
-        raise ValueError("seg_offsets must be an int64 (S+1,) tensor")
-    dev = boxes.device
+    N = tensor(boxes, "boxes", F32, ("N", 4))[0]
+    tensor(scores, "scores", F32, (N,))
+    S = tensor(seg_offsets, "seg_offsets", torch.int64, ("S+1",), contiguous=False)[0] - 1
+    if S < 0:
+        raise ValueError("seg_offsets must hold S+1 >= 1 entries")
     if not seg_offsets.is_cuda:
         off = seg_offsets.tolist()
         if off[0] < 0 or off[-1] > N or any(b < a for a, b in zip(off, off[1:])):
             raise ValueError("seg_offsets must be non-decreasing within [0, %d]" % N)
         if any(b - a > _lib.NMS_SEG_MAX for a, b in zip(off, off[1:])):
             raise ValueError("a segment holds more than %d boxes" % _lib.NMS_SEG_MAX)
-        seg_offsets = seg_offsets.to(dev)
-    else:
-        _chk_dev(seg_offsets, "seg_offsets")
-    seg_offsets = seg_offsets.contiguous()
-    S = seg_offsets.numel() - 1
+    on_device([("boxes", boxes), ("scores", scores), ("seg_offsets", seg_offsets if seg_offsets.is_cuda else None)])
+    dev = boxes.device
+    seg_offsets = seg_offsets.to(dev).contiguous()
+    lib = _lib.load()
+    nbytes = _lib.ws_bytes(lib.tdn_batched_nms_workspace(N, S), "batched_nms")
     keep = torch.empty(N, dtype=torch.uint8, device=dev)
     kept_idx = torch.empty(N, dtype=torch.int64, device=dev)
     counts = torch.empty(S, dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    nbytes = lib.tdn_batched_nms_workspace(N, S)
     ws, wp = _aligned_ws(nbytes, dev)
     _lib.check(lib.tdn_batched_nms(_ptr(boxes), _ptr(scores), N, _ptr(seg_offsets), S, float(iou_thr), _ptr(keep),
                                    _ptr(kept_idx), _ptr(counts), wp, nbytes, _lib.stream_ptr()), "tdn_batched_nms")
     return keep, kept_idx, counts
-
-
-_RPN_DTYPES = {torch.float32: _lib.TDN_F32, torch.bfloat16: TDN_BF16}
 
 
 def rpn_proposals(cls_scores, bbox_preds, anchors, img_shapes, nms_pre, nms_post, max_num, nms_thr, min_bbox_size,
@@ -934,63 +929,48 @@ def rpn_proposals(cls_scores, bbox_preds, anchors, img_shapes, nms_pre, nms_post
     if not (1 <= L <= _lib.RPN_MAX_LEVELS) or len(bbox_preds) != L or len(anchors) != L:
         raise ValueError("rpn_proposals takes 1..%d levels with one cls_score / bbox_pred / anchors each"
                          % _lib.RPN_MAX_LEVELS)
-    B = cls_scores[0].shape[0] if cls_scores[0].dim() == 4 else -1
-    if not 1 <= B <= 64:
-        raise ValueError("rpn_proposals: batch size must be 1..64")
-    nms_pre, nms_post, max_num = int(nms_pre), int(nms_post), int(max_num)
-    if not 0 <= nms_pre <= _lib.NMS_SEG_MAX:
-        raise ValueError("nms_pre must be in 0..%d" % _lib.NMS_SEG_MAX)
-    if nms_post < 1:
-        raise ValueError("nms_post must be positive")
-    if not 1 <= max_num <= _lib.RPN_MAX_NUM:
-        raise ValueError("max_num must be in 1..%d" % _lib.RPN_MAX_NUM)
-    if float(min_bbox_size) < 0:
+    first = tensor(cls_scores[0], "cls_scores[0]", (F32, BF16), ("B", "A", "H", "W"), contiguous=False)
+    B, dtype = batch(first[0]), cls_scores[0].dtype
+    cfg = _lib.RpnConfig()
+    cfg.nms_pre = nms_pre = integer(nms_pre, "nms_pre", 0, _lib.NMS_SEG_MAX)
+    cfg.nms_post = integer(nms_post, "nms_post", 1)
+    cfg.max_num = max_num = integer(max_num, "max_num", 1, _lib.RPN_MAX_NUM)
+    cfg.nms_thr, cfg.min_bbox_size = number(nms_thr, "nms_thr"), number(min_bbox_size, "min_bbox_size")
+    if min_bbox_size < 0:
         raise ValueError("min_bbox_size must be >= 0")
-    if len(means) != 4 or len(stds) != 4:
-        raise ValueError("target_means / target_stds must have 4 entries")
-    dev = cls_scores[0].device
+    cfg.means, cfg.stds = f4(means, "target_means"), f4(stds, "target_stds")
     arr = (_lib.RpnLevel * L)()
-    for l in range(L):
-        c, d, a = cls_scores[l], bbox_preds[l], anchors[l]
-        if c.dim() != 4 or d.dim() != 4 or c.dtype not in _RPN_DTYPES or d.dtype != c.dtype or not c.is_cuda or \
-                not d.is_cuda:
-            raise ValueError("level %d: cls_score / bbox_pred must be 4-D CUDA float32 or bfloat16 tensors of one "
-                             "dtype" % l)
-        Bl, A, H, W = c.shape
-        if Bl != B or tuple(d.shape) != (B, 4 * A, H, W) or A < 1:
-            raise ValueError("level %d: cls_score %s and bbox_pred %s do not match (B, A, H, W) / (B, 4A, H, W)"
-                             % (l, tuple(c.shape), tuple(d.shape)))
-        if a.dtype != torch.float32 or not a.is_cuda or not a.is_contiguous() or tuple(a.shape) != (H * W * A, 4):
-            raise ValueError("level %d: anchors must be a contiguous CUDA float32 (%d, 4) tensor" % (l, H * W * A))
+    named = []
+    for l, (c, d, a) in enumerate(zip(cls_scores, bbox_preds, anchors)):
+        cn, dn, an = "cls_scores[%d]" % l, "bbox_preds[%d]" % l, "anchors[%d]" % l
+        _, A, H, W = tensor(c, cn, dtype, (B, "A", "H", "W"), contiguous=False) if l else first
+        if A < 1:
+            raise ValueError("%s has no anchor channel" % cn)
+        tensor(d, dn, dtype, (B, 4 * A, H, W), contiguous=False)
+        tensor(a, an, F32, (H * W * A, 4))
         if nms_pre == 0 and H * W * A > _lib.NMS_SEG_MAX:
             raise ValueError("level %d: %d anchors enter NMS with nms_pre=0 (max %d)"
                              % (l, H * W * A, _lib.NMS_SEG_MAX))
-        for t, nm in ((c, "cls_score"), (d, "bbox_pred"), (a, "anchors")):
-            _chk_dev(t, "%s[%d]" % (nm, l))
+        named += [(cn, c), (dn, d), (an, a)]
         v = arr[l]
         v.logits, v.deltas, v.anchors = c.data_ptr(), d.data_ptr(), a.data_ptr()
         v.logit_strides[:] = list(c.stride())
         v.delta_strides[:] = list(d.stride())
-        v.dtype, v.H, v.W, v.A = _RPN_DTYPES[c.dtype], H, W, A
+        v.dtype, v.H, v.W, v.A = CODES[dtype], H, W, A
+    shapes = None
     if torch.is_tensor(img_shapes):
-        if img_shapes.dtype != torch.int32 or not img_shapes.is_cuda or tuple(img_shapes.shape) != (B, 2) or \
-                not img_shapes.is_contiguous():
-            raise ValueError("img_shapes must be a contiguous CUDA int32 (B, 2) tensor of (h, w)")
-        _chk_dev(img_shapes, "img_shapes")
+        tensor(img_shapes, "img_shapes", torch.int32, (B, 2))
+        named.append(("img_shapes", img_shapes))
     else:
         shapes = [(int(h), int(w)) for h, w in img_shapes]
         if len(shapes) != B or any(h < 1 or w < 1 for h, w in shapes):
             raise ValueError("img_shapes must hold B positive (h, w) pairs")
+    on_device(named)
+    dev = cls_scores[0].device
+    if shapes is not None:
         img_shapes = torch.tensor(shapes, dtype=torch.int32).to(dev)
-    cfg = _lib.RpnConfig()
-    cfg.nms_pre, cfg.nms_post, cfg.max_num = nms_pre, nms_post, max_num
-    cfg.nms_thr, cfg.min_bbox_size = float(nms_thr), float(min_bbox_size)
-    cfg.means[:] = [float(x) for x in means]
-    cfg.stds[:] = [float(x) for x in stds]
     lib = _lib.load()
-    nbytes = lib.tdn_rpn_proposals_workspace(arr, L, B, ctypes.byref(cfg))
-    if nbytes < 0:
-        raise ValueError("rpn_proposals: %s" % lib.tdn_last_error().decode())
+    nbytes = _lib.ws_bytes(lib.tdn_rpn_proposals_workspace(arr, L, B, ctypes.byref(cfg)), "rpn_proposals")
     proposals = torch.empty(B, max_num, 5, dtype=torch.float32, device=dev)
     anchor_idx = torch.empty(B, max_num, dtype=torch.int64, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
@@ -1002,53 +982,37 @@ def rpn_proposals(cls_scores, bbox_preds, anchors, img_shapes, nms_pre, nms_post
 
 
 # ---- multi-level RoIAlign ------------------------------------------------------------------------
-def _chk_rois(rois):
-    if not torch.is_tensor(rois) or rois.dtype != torch.float32 or not rois.is_cuda or rois.dim() != 2 or \
-            rois.shape[1] != 5 or not rois.is_contiguous():
-        raise ValueError("rois must be a contiguous CUDA float32 (R, 5) tensor of (batch_idx, x1, y1, x2, y2)")
-    _chk_dev(rois, "rois")
-
-
 def _roi_config(out_size, scales, sampling_ratio, finest_scale):
-    S, sr, fs = int(out_size), int(sampling_ratio), float(finest_scale)
-    if not 1 <= S <= _lib.ROI_MAX_OUT:
-        raise ValueError("out_size must be in 1..%d" % _lib.ROI_MAX_OUT)
-    if not 0 <= sr <= _lib.ROI_MAX_SAMPLES:
-        raise ValueError("sampling_ratio must be in 0..%d" % _lib.ROI_MAX_SAMPLES)
-    if not 0.0 < fs < float("inf"):
-        raise ValueError("finest_scale must be positive")
+    cfg = _lib.RoiConfig()
+    cfg.out_size = integer(out_size, "out_size", 1, _lib.ROI_MAX_OUT)
+    cfg.sampling_ratio = integer(sampling_ratio, "sampling_ratio", 0, _lib.ROI_MAX_SAMPLES)
+    cfg.finest_scale = number(finest_scale, "finest_scale", positive=True)
     if not 1 <= len(scales) <= _lib.ROI_MAX_LEVELS:
         raise ValueError("RoIAlign takes 1..%d levels" % _lib.ROI_MAX_LEVELS)
-    cfg = _lib.RoiConfig()
-    cfg.out_size, cfg.sampling_ratio, cfg.finest_scale = S, sr, fs
-    for l, sc in enumerate(scales):
-        sc = float(ctypes.c_float(sc).value)
-        if not 0.0 < sc < float("inf"):
-            raise ValueError("level %d: spatial scale must be positive" % l)
-        cfg.scales[l] = sc
+    for l, sc in enumerate(scales):                 # positive and finite as the float the kernel reads
+        cfg.scales[l] = number(ctypes.c_float(number(sc, "scales[%d]" % l)).value, "scales[%d]" % l, positive=True)
     return cfg
+
+
+def _level_shapes(feats):
+    if not 1 <= len(feats) <= _lib.ROI_MAX_LEVELS:
+        raise ValueError("RoIAlign takes 1..%d feature levels, got %d" % (_lib.ROI_MAX_LEVELS, len(feats)))
+    B, C, _, _ = tensor(feats[0], "feats[0]", (BF16, F16), ("B", "C", "H", "W"), contiguous=False)
+    if B < 1 or C < 8 or C % 8:
+        raise ValueError("RoIAlign needs B >= 1 and C a positive multiple of 8, got B=%d C=%d" % (B, C))
+    shapes = [tuple(tensor(f, "feats[%d]" % l, feats[0].dtype, (B, C, "H", "W"), contiguous=False)[2:])
+              for l, f in enumerate(feats)]
+    if any(h < 1 or w < 1 for h, w in shapes):
+        raise ValueError("RoIAlign: empty feature map among %s" % (shapes,))
+    return B, C, feats[0].dtype, shapes
 
 
 def roi_level_shapes(feats):
     """Validate RoIAlign's feature levels (logical (B, C, H_l, W_l), 16-bit, one CUDA device, B / C / dtype shared,
     C % 8 == 0) on the host and return (B, C, dtype, [(H_l, W_l)])."""
-    if not 1 <= len(feats) <= _lib.ROI_MAX_LEVELS:
-        raise ValueError("RoIAlign takes 1..%d feature levels, got %d" % (_lib.ROI_MAX_LEVELS, len(feats)))
-    f0 = feats[0]
-    for l, f in enumerate(feats):
-        if not torch.is_tensor(f) or f.dim() != 4 or f.dtype not in _CODES or not f.is_cuda:
-            raise ValueError("level %d: features must be a 4-D CUDA bfloat16/float16 tensor, got %s" %
-                             (l, (f.dtype, str(f.device), tuple(f.shape)) if torch.is_tensor(f) else type(f)))
-        _chk_dev(f, "feats[%d]" % l)
-        if f.dtype != f0.dtype or f.shape[0] != f0.shape[0] or f.shape[1] != f0.shape[1]:
-            raise ValueError("level %d: %s %s does not match level 0's batch, channels and dtype %s %s" %
-                             (l, f.dtype, tuple(f.shape), f0.dtype, tuple(f0.shape)))
-        if f.shape[2] < 1 or f.shape[3] < 1:
-            raise ValueError("level %d: empty feature map %s" % (l, tuple(f.shape)))
-    B, C = f0.shape[0], f0.shape[1]
-    if B < 1 or C < 8 or C % 8:
-        raise ValueError("RoIAlign needs B >= 1 and C a positive multiple of 8, got B=%d C=%d" % (B, C))
-    return B, C, f0.dtype, [(f.shape[2], f.shape[3]) for f in feats]
+    out = _level_shapes(feats)
+    on_device([("feats[%d]" % l, f) for l, f in enumerate(feats)])
+    return out
 
 
 def _roi_levels(ts, dtype):
@@ -1062,17 +1026,13 @@ def _roi_levels(ts, dtype):
 
 def roi_map_levels(rois, num_levels, finest_scale=56.0):
     """(R,) int64 FPN level of every row of ``rois`` (tdn_roi_map_levels; the batch index is not looked at)."""
-    if rois.dim() == 2 and rois.shape[1] == 4:
-        raise ValueError("rois must be (R, 5) = (batch_idx, x1, y1, x2, y2)")
-    _chk_rois(rois)
-    L = int(num_levels)
-    if not 1 <= L <= _lib.ROI_MAX_LEVELS:
-        raise ValueError("num_levels must be in 1..%d" % _lib.ROI_MAX_LEVELS)
-    if not 0.0 < float(finest_scale) < float("inf"):
-        raise ValueError("finest_scale must be positive")
-    out = torch.empty(rois.shape[0], dtype=torch.int64, device=rois.device)
-    _lib.check(_lib.load().tdn_roi_map_levels(_ptr(rois), rois.shape[0], L, float(finest_scale), _ptr(out),
-                                              _lib.stream_ptr()), "tdn_roi_map_levels")
+    R = tensor(rois, "rois", F32, ("R", 5))[0]
+    L = integer(num_levels, "num_levels", 1, _lib.ROI_MAX_LEVELS)
+    fs = number(finest_scale, "finest_scale", positive=True)
+    on_device([("rois", rois)])
+    out = torch.empty(R, dtype=torch.int64, device=rois.device)
+    _lib.check(_lib.load().tdn_roi_map_levels(_ptr(rois), R, L, fs, _ptr(out), _lib.stream_ptr()),
+               "tdn_roi_map_levels")
     return out
 
 
@@ -1080,14 +1040,13 @@ def roi_align_fwd(feats, rois, out_size, scales, sampling_ratio, finest_scale):
     """Multi-level RoIAlign forward (tdn_roi_align_fwd, one launch).  ``feats``: logical (B, C, H_l, W_l) 16-bit
     tensors; NHWC memory is read in place, any other layout goes once through tdn_nchw16_to_nhwc.  Everything is
     checked here before the first launch.  Returns (R, C, S, S) in ``feats``' dtype, channels_last memory."""
-    B, C, dtype, _ = roi_level_shapes(feats)
-    _chk_rois(rois)
-    if rois.device != feats[0].device:
-        raise ValueError("rois are on %s, features on %s" % (rois.device, feats[0].device))
+    B, C, dtype, _ = _level_shapes(feats)
+    R = tensor(rois, "rois", F32, ("R", 5))[0]
     if len(scales) != len(feats):
         raise ValueError("%d feature levels but %d featmap strides" % (len(feats), len(scales)))
     cfg = _roi_config(out_size, scales, sampling_ratio, finest_scale)
-    S, R = cfg.out_size, rois.shape[0]
+    on_device([("feats[%d]" % l, f) for l, f in enumerate(feats)] + [("rois", rois)])
+    S = cfg.out_size
     xs = [to_nhwc_bf16(f, dtype) for f in feats]
     out = torch.empty(R, S, S, C, dtype=dtype, device=rois.device)
     _lib.check(_lib.load().tdn_roi_align_fwd(_roi_levels(xs, dtype), len(xs), B, C, _ptr(rois), R, ctypes.byref(cfg),
@@ -1101,13 +1060,14 @@ def roi_align_bwd(dout, rois, level_shapes, B, C, dtype, out_size, scales, sampl
     are 0."""
     cfg = _roi_config(out_size, scales, sampling_ratio, finest_scale)
     S, R = cfg.out_size, rois.shape[0]
-    if tuple(dout.shape) != (R, C, S, S) or not dout.is_cuda:
-        raise ValueError("dout must be a CUDA (%d, %d, %d, %d) tensor, got %s" % (R, C, S, S, tuple(dout.shape)))
+    if tuple(dout.shape) != (R, C, S, S):           # any dtype and strides: to_nhwc_bf16 converts
+        raise ValueError("dout must be a (%d, %d, %d, %d) tensor, got %s" % (R, C, S, S, tuple(dout.shape)))
+    on_device([("dout", dout), ("rois", rois)])
     d = to_nhwc_bf16(dout, dtype) if R > 0 else None
     dev = rois.device
-    grads = [torch.empty(B, h, w, C, dtype=dtype, device=dev) for h, w in level_shapes]
     lib = _lib.load()
-    nbytes = lib.tdn_roi_align_bwd_workspace(R)
+    nbytes = _lib.ws_bytes(lib.tdn_roi_align_bwd_workspace(R), "roi_align_bwd")
+    grads = [torch.empty(B, h, w, C, dtype=dtype, device=dev) for h, w in level_shapes]
     ws, wp = _aligned_ws(nbytes, dev)
     _lib.check(lib.tdn_roi_align_bwd(_roi_levels(grads, dtype), len(grads), B, C, _ptr(rois), R, ctypes.byref(cfg),
                                      _ptr(d), wp, nbytes, _lib.stream_ptr()), "tdn_roi_align_bwd")
@@ -1117,15 +1077,9 @@ def roi_align_bwd(dout, rois, level_shapes, B, C, dtype, out_size, scales, sampl
 def rois_from_proposals(proposals, counts):
     """(B*M, 5) rois (batch_idx, x1, y1, x2, y2) from rpn_proposals' (B, M, 5) output; rows at or past counts[b] get
     batch index -1 (tdn_rois_from_proposals; no host synchronisation)."""
-    if not torch.is_tensor(proposals) or proposals.dtype != torch.float32 or not proposals.is_cuda or \
-            proposals.dim() != 3 or proposals.shape[2] != 5 or not proposals.is_contiguous():
-        raise ValueError("proposals must be a contiguous CUDA float32 (B, M, 5) tensor")
-    B, M = proposals.shape[0], proposals.shape[1]
-    if not torch.is_tensor(counts) or counts.dtype != torch.int32 or not counts.is_cuda or \
-            tuple(counts.shape) != (B,) or not counts.is_contiguous():
-        raise ValueError("counts must be a contiguous CUDA int32 (B,) tensor")
-    _chk_dev(proposals, "proposals")
-    _chk_dev(counts, "counts")
+    B, M, _ = tensor(proposals, "proposals", F32, ("B", "M", 5))
+    tensor(counts, "counts", torch.int32, (B,))
+    on_device([("proposals", proposals), ("counts", counts)])
     rois = torch.empty(B * M, 5, dtype=torch.float32, device=proposals.device)
     _lib.check(_lib.load().tdn_rois_from_proposals(_ptr(proposals), _ptr(counts), B, M, _ptr(rois),
                                                    _lib.stream_ptr()), "tdn_rois_from_proposals")

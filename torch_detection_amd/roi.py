@@ -46,9 +46,6 @@ def roi_align(feats, rois, out_size=7, featmap_strides=(4, 8, 16, 32), sampling_
     in place, other layouts transposed once).  Rows whose batch index is outside ``[0, B)`` (the -1 padding of
     :func:`rois_from_proposals`) give zeros and no gradient.  Returns (R, C, out_size, out_size) in the features'
     dtype, channels_last.  Differentiable in ``feats``."""
-    feats = list(feats)
-    if len(feats) != len(featmap_strides):
-        raise ValueError("%d feature levels but %d featmap strides" % (len(feats), len(featmap_strides)))
     return RoIAlignFunction.apply(rois, int(out_size), tuple(featmap_strides), int(sampling_ratio),
                                   float(finest_scale), *feats)
 
