@@ -499,9 +499,62 @@ def test_gn_bad_shapes(ops, guard):
     guard.clean()
 
 
-@pytest.mark.parametrize("case", [(2, 64, 13, 21), (3, 256, 8, 12), (1, 1024, 5, 4)])
+@pytest.mark.parametrize("case", GN.BN_CASES)
 def test_bn_train_fwd_bwd(ops, guard, case):
     GN.test_bn_train_fwd_bwd(ops, case)
+    guard.clean()
+
+
+def test_bn_cases_keep_their_first_members():
+    assert GN.BN_CASES[:3] == [(2, 64, 13, 21), (3, 256, 8, 12), (1, 1024, 5, 4)]
+
+
+# the 514 x 512 row stays in: with its poisoned copies it takes about a second
+@pytest.mark.parametrize("case", GN.GEOM_CASES + [GN.BIG_CASE], ids=GN._gid)
+def test_gn_geometry(ops, guard, case):
+    if case is GN.BIG_CASE:
+        GN.test_gn_grid_stride(ops)
+    else:
+        GN.test_gn_geometry(ops, case)
+    guard.clean()
+
+
+@pytest.mark.parametrize("case", GN.BN_GEOM_CASES + [GN.BN_BIG_CASE], ids=GN._gid)
+def test_bn_train_geometry(ops, guard, case):
+    if case is GN.BN_BIG_CASE:
+        GN.test_bn_train_grid_stride(ops)
+    else:
+        GN.test_bn_train_geometry(ops, case)
+    guard.clean()
+
+
+@pytest.mark.parametrize("case", GN.COND_CASES, ids=GN._cid)
+def test_norm_ill_conditioned(ops, guard, case):
+    GN.test_gn_ill_conditioned(ops, case)
+    GN.test_bn_train_ill_conditioned(ops, case)
+    guard.clean()
+
+
+@pytest.mark.parametrize("kind", ["gn", "bn"])
+def test_norm_constant_and_opposite_groups(ops, guard, kind):
+    for shape in GN.COND_SHAPES:
+        GN.test_constant_group(ops, kind, shape)
+        GN.test_opposite_pivots(ops, kind, shape)
+    guard.clean()
+
+
+def test_norm_options(ops, guard):
+    for case in GN.BN_CASES:
+        GN.test_bn_train_fp16(ops, case)
+    for momentum in (0.25, 1.0):
+        GN.test_bn_train_momentum(ops, momentum)
+    GN.test_bn_train_no_running_stats(ops)
+    GN.test_bn_train_up2x(ops)
+    for kind in ("gn", "bn"):
+        GN.test_eps(ops, kind)
+        for dt in DTYPES:
+            GN.test_relu6(ops, kind, dt)
+        GN.test_accumulate_and_overwrite(ops, kind)
     guard.clean()
 
 

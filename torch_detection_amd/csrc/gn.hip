@@ -4,9 +4,14 @@
 // and applied after the convs of models/backbone/resnet.py (use_gn=True: :42-59, :97-119, :254-257) and of ConvModule
 // (layers.py:122-135, necks with normalize=GN), together with the residual add and ReLU that follow it.
 // Unlike eval-mode BatchNorm the statistics depend on the sample, so GN cannot be folded into the conv epilogue:
-//   forward   z = conv(x) (raw, 16-bit)  ->  [1] per-channel partial (sum, sum of squares) over pixel chunks
-//             -> [2] per (sample, group) mean / rstd, expanded to per-(sample, channel) affine (a, b)
-//             -> [3] y = relu?(z*a + b (+ addend))      (relu: 0 none, 1 ReLU, 2 ReLU6)
+//   forward   z = conv(x) (raw, 16-bit)  ->  [1] per-channel partial (sum, sum of squares) of z - K over pixel chunks,
+//                K = the channel's pivot: its value at pixel 0 of the sample (GN) / of sample 0 (BN)
+//             -> [2] per (sample, group) mean / rstd, expanded to per-(sample, channel) affine (a, b, K)
+//             -> [3] y = relu?((z - K)*a + b (+ addend))      (relu: 0 none, 1 ReLU, 2 ReLU6)
+//   Numerics of the statistics (GroupNorm): the fp32 sums are taken about the pivot, so they carry the
+//   spread of the data and not its offset: sum z^2 / cnt - mu^2 would cancel |mean|^2 / var leading digits, which a
+//   16-bit tensor can make 2^20.  The pivots are put back in double in [2].  The output is formed about the same pivot
+//   for the same reason: z*a - mu*a would round at the size of |mean| * a.
 //   backward  g = dL/dy (ReLU-masked) -> [1'] per-channel partial (sum g, sum g*xhat) -> [2'] dgamma, dbeta and the
 //             per-(sample, channel) coefficients of dz = g*A + z*B + C  ->  [3'] dz, which then feeds the ordinary
 //             conv dgrad / wgrad kernels.
@@ -25,13 +30,14 @@ struct GnGeom {
 };
 
 // [1] / [1']: partial per-channel sums over one pixel chunk of one sample.
-//   MODE 0: (sum z, sum z^2)            MODE 1: (sum g, sum g * xhat), xhat = z*rstd - mu*rstd from `stats`
+//   MODE 0: (sum d, sum d^2), d = z - K, K = z[n * pivot_stride + c] (pixel 0 of the sample, or of sample 0)
+//   MODE 1: (sum g, sum g * xhat), xhat = (z - mu) * rstd from `stats`
 // part layout: [n][chunk][2][C]
 template <int MODE, bool F16>
 __global__ __launch_bounds__(kThreads) void gn_partial_kernel(const bf16_t* __restrict__ z,
                                                                const bf16_t* __restrict__ g,
                                                                const float* __restrict__ stats, GnGeom ge,
-                                                               float* __restrict__ part) {
+                                                               int64_t pivot_stride, float* __restrict__ part) {
   __shared__ float red[kThreads][17];
   const int n = blockIdx.y, chunk = blockIdx.x;
   const int tid = threadIdx.x;
@@ -41,31 +47,36 @@ __global__ __launch_bounds__(kThreads) void gn_partial_kernel(const bf16_t* __re
   float a0[8], a1[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) a0[e] = a1[e] = 0.f;
-  float mu_r[8], rs[8];
+  float mu[8], rs[8];
   if (MODE == 1) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float mu = stats[((int64_t)n * ge.C + cl * 8 + e) * 2], r = stats[((int64_t)n * ge.C + cl * 8 + e) * 2 + 1];
-      rs[e] = r;
-      mu_r[e] = mu * r;
+      mu[e] = stats[((int64_t)n * ge.C + cl * 8 + e) * 2];
+      rs[e] = stats[((int64_t)n * ge.C + cl * 8 + e) * 2 + 1];
     }
   }
   const int64_t base = (int64_t)n * ge.HW * ge.C + cl * 8;
+  float piv[8];
+  if (MODE == 0) {
+    const bf16x8_t kv = *(const bf16x8_t*)(z + (int64_t)n * pivot_stride + cl * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) piv[e] = elem_to_f32<F16>(kv[e]);
+  }
   for (int p = p0 + pl; p < p1; p += ge.ppp) {
     const bf16x8_t zv = *(const bf16x8_t*)(z + base + (int64_t)p * ge.C);
     if (MODE == 0) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float v = elem_to_f32<F16>(zv[e]);
-        a0[e] += v;
-        a1[e] += v * v;
+        const float d = elem_to_f32<F16>(zv[e]) - piv[e];
+        a0[e] += d;
+        a1[e] += d * d;
       }
     } else {
       const bf16x8_t gv = *(const bf16x8_t*)(g + base + (int64_t)p * ge.C);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float gg = elem_to_f32<F16>(gv[e]);
-        const float xh = elem_to_f32<F16>(zv[e]) * rs[e] - mu_r[e];
+        const float xh = (elem_to_f32<F16>(zv[e]) - mu[e]) * rs[e];   // z*rstd - mu*rstd would round at |z| * rstd
         a0[e] += gg;
         a1[e] += gg * xh;
       }
@@ -84,6 +95,11 @@ __global__ __launch_bounds__(kThreads) void gn_partial_kernel(const bf16_t* __re
 #pragma unroll
     for (int e = 0; e < 8; ++e) { o[e] = red[tid][e]; o[ge.C + e] = red[tid][8 + e]; }
   }
+}
+
+// the pivot of channel c of sample n as the partial kernel read it
+__device__ __forceinline__ double pivot_of(const bf16_t* __restrict__ z, int64_t idx, int f16) {
+  return (double)(f16 ? elem_to_f32<true>(z[idx]) : elem_to_f32<false>(z[idx]));
 }
 
 // Sum of the per-chunk partials of channel c of sample n, both planes, by the KL chunk-lanes of a block (thread
@@ -111,41 +127,55 @@ __device__ __forceinline__ void chunk_totals(const float* __restrict__ part, con
 }
 
 // [2]: block (sample n, channel block of CB = max(32, cpg) channels — whole groups); chunk sums -> group mean / rstd
-// (double), then per-channel stats[n][c] = (mu, rstd) and coef[n][c] = (a, b) with y = z*a + b.
+// (double), then per-channel stats[n][c] = (mu, rstd) and the three planes coef[3][n][c] = a, b, K of y = (z - K)*a + b
+// (planes, so that a lane's 8 channels are 32 contiguous bytes of each: fewer cache lines per load than [n][c][3]).
+// With s_c = sum (z - K_c), q_c = sum (z - K_c)^2 over the HW pixels of channel c:
+//   mu = sum_c (s_c + HW K_c) / cnt,   cnt var = sum_c (q_c + 2 (K_c - mu) s_c + HW (K_c - mu)^2)
+// (the second moment about the group mean, cross terms between the channels' pivots included), in channel order.
 __global__ __launch_bounds__(kThreads) void gn_stats_kernel(const float* __restrict__ part, GnGeom ge, int CB,
+                                                            const bf16_t* __restrict__ z, int f16,
                                                             const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float eps,
                                                             float* __restrict__ stats, float* __restrict__ coef) {
   __shared__ double red[2 * kThreads];
-  __shared__ double tot[2 * kThreads];
+  __shared__ double tot[3 * kThreads];
   const int n = blockIdx.y;
   const int KL = kThreads / CB;
   const int cl = threadIdx.x % CB, kl = threadIdx.x / CB;
   const int c = blockIdx.x * CB + cl;
+  // asked for ahead of the chunk sums, so that its latency hides behind theirs
+  const double K = (kl == 0 && c < ge.C) ? pivot_of(z, (int64_t)n * ge.HW * ge.C + c, f16) : 0.0;
   double s, ss;
   chunk_totals(part, ge, n, c, cl, kl, CB, KL, c < ge.C, red, s, ss);
-  if (kl == 0) { tot[cl] = s; tot[kThreads + cl] = ss; }
+  if (kl == 0) { tot[cl] = s; tot[kThreads + cl] = ss; tot[2 * kThreads + cl] = K; }
   __syncthreads();
   if (kl == 0 && c < ge.C) {
     const int g0 = (cl / ge.cpg) * ge.cpg;
-    double gs = 0.0, gss = 0.0;
-    for (int j = 0; j < ge.cpg; ++j) { gs += tot[g0 + j]; gss += tot[kThreads + g0 + j]; }
-    const double cnt = (double)ge.HW * ge.cpg;
+    const double hw = (double)ge.HW, cnt = hw * ge.cpg;
+    double gs = 0.0;
+    for (int j = 0; j < ge.cpg; ++j) gs += tot[g0 + j] + hw * tot[2 * kThreads + g0 + j];
     const double mu = gs / cnt;
-    double var = gss / cnt - mu * mu;       // biased variance, like nn.GroupNorm
+    double m2 = 0.0;
+    for (int j = 0; j < ge.cpg; ++j) {
+      const double dk = tot[2 * kThreads + g0 + j] - mu;
+      m2 += tot[kThreads + g0 + j] + 2.0 * dk * tot[g0 + j] + hw * dk * dk;
+    }
+    double var = m2 / cnt;                  // biased variance, like nn.GroupNorm
     if (var < 0.0) var = 0.0;
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float muf = (float)mu;
-    stats[((int64_t)n * ge.C + c) * 2] = muf;
+    stats[((int64_t)n * ge.C + c) * 2] = (float)mu;
     stats[((int64_t)n * ge.C + c) * 2 + 1] = rstd;
     const float a = rstd * gamma[c];
-    coef[((int64_t)n * ge.C + c) * 2] = a;
-    coef[((int64_t)n * ge.C + c) * 2 + 1] = beta[c] - muf * a;
+    float* o = coef + (int64_t)n * ge.C + c;
+    const int64_t plane = (int64_t)ge.N * ge.C;
+    o[0] = a;
+    o[plane] = (float)((double)beta[c] - (mu - K) * (double)a);
+    o[2 * plane] = (float)K;
   }
 }
 
-// [3]: y = relu?(z*a + b (+ addend));  up_w > 0: the addend is the coarser FPN level (H/2 x W/2), read with
-// nearest-neighbour 2x upsampling (fpn.py:98-100), W = 2*up_w
+// [3]: y = relu?((z - K)*a + b (+ addend)), coef[3][n][c] = a, b, K;  up_w > 0: the addend is the coarser FPN level
+// (H/2 x W/2), read with nearest-neighbour 2x upsampling (fpn.py:98-100), W = 2*up_w
 template <bool F16>
 __global__ void gn_apply_kernel(const bf16_t* __restrict__ z, const float* __restrict__ coef,
                                 const bf16_t* __restrict__ addend, int relu, int up_w, GnGeom ge,
@@ -155,10 +185,16 @@ __global__ void gn_apply_kernel(const bf16_t* __restrict__ z, const float* __res
     const int n = (int)(i / per_n);
     const int cl = (int)(i % ge.C8);
     const bf16x8_t zv = *(const bf16x8_t*)(z + i * 8);
-    const float* cf = coef + ((int64_t)n * ge.C + cl * 8) * 2;
+    const float* cf = coef + (int64_t)n * ge.C + cl * 8;
+    const int64_t plane = (int64_t)ge.N * ge.C;
     float v[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = elem_to_f32<F16>(zv[e]) * cf[2 * e] + cf[2 * e + 1];
+    for (int h = 0; h < 2; ++h) {
+      const f32x4_t ca = *(const f32x4_t*)(cf + 4 * h), cb = *(const f32x4_t*)(cf + plane + 4 * h);
+      const f32x4_t ck = *(const f32x4_t*)(cf + 2 * plane + 4 * h);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[4 * h + e] = (elem_to_f32<F16>(zv[4 * h + e]) - ck[e]) * ca[e] + cb[e];
+    }
     if (addend) {
       int64_t ai = i;
       if (up_w > 0) {
@@ -273,7 +309,10 @@ __device__ __forceinline__ void batch_totals(const float* __restrict__ part, con
   }
 }
 
+// The pivot K_c is common to all samples (sample 0's pixel 0): mu = K_c + s / cnt, var = q / cnt - (s / cnt)^2 with
+// s, q the sums of z - K_c and its square over the batch, both of the size of the spread.
 __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const float* __restrict__ part, GnGeom ge,
+                                                            const bf16_t* __restrict__ z, int f16,
                                                             const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float eps, float momentum,
                                                             float* running_mean, float* running_var,
@@ -282,21 +321,26 @@ __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const float* __restr
   constexpr int CB = 32, KL = kThreads / CB;
   const int cl = threadIdx.x % CB, kl = threadIdx.x / CB;
   const int c = blockIdx.x * CB + cl;
+  const double K = (kl == 0 && c < ge.C) ? pivot_of(z, c, f16) : 0.0;   // ahead of the sums: its latency hides
   double s, ss;
   batch_totals(part, ge, c, cl, kl, CB, KL, c < ge.C, red, s, ss);
   if (kl != 0 || c >= ge.C) return;
   const double cnt = (double)ge.N * ge.HW;
-  const double mu = s / cnt;
-  double var = ss / cnt - mu * mu;             // biased variance normalises (nn.BatchNorm2d, training)
+  const double dm = s / cnt;
+  const double mu = K + dm;
+  double var = ss / cnt - dm * dm;             // biased variance normalises (nn.BatchNorm2d, training)
   if (var < 0.0) var = 0.0;
   const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   const float muf = (float)mu;
-  const float a = rstd * gamma[c], b = beta[c] - muf * a;
+  const float a = rstd * gamma[c], b = (float)((double)beta[c] - dm * (double)a);
   for (int n = 0; n < ge.N; ++n) {
     stats[((int64_t)n * ge.C + c) * 2] = muf;
     stats[((int64_t)n * ge.C + c) * 2 + 1] = rstd;
-    coef[((int64_t)n * ge.C + c) * 2] = a;
-    coef[((int64_t)n * ge.C + c) * 2 + 1] = b;
+    float* o = coef + (int64_t)n * ge.C + c;
+    const int64_t plane = (int64_t)ge.N * ge.C;
+    o[0] = a;
+    o[plane] = b;
+    o[2 * plane] = (float)K;
   }
   if (running_mean && running_var) {           // running statistics: unbiased variance, momentum update
     const double unb = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
@@ -349,7 +393,7 @@ int make_geom(GnGeom& ge, int N, int H, int W, int C, int G) {
   return 0;
 }
 
-// workspace: part [N][chunks][2][C] floats | coef [N][C][3] floats
+// workspace: part [N][chunks][2][C] floats | coef: 3 N C floats (forward: planes [3][N][C], backward: [N][C][3])
 int64_t ws_floats(const GnGeom& ge) { return (int64_t)ge.N * ge.chunks * 2 * ge.C + (int64_t)ge.N * ge.C * 3; }
 
 }  // namespace
@@ -380,12 +424,14 @@ extern "C" int tdn_gn_fwd(const void* z, const float* gamma, const float* beta, 
   hipStream_t st = (hipStream_t)stream;
   const dim3 gp(ge.chunks, N);
   if (dtype == TDN_F16)
-    TDN_LAUNCH((gn_partial_kernel<0, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge, part);
+    TDN_LAUNCH((gn_partial_kernel<0, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge,
+               (int64_t)ge.HW * ge.C, part);
   else
-    TDN_LAUNCH((gn_partial_kernel<0, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge, part);
+    TDN_LAUNCH((gn_partial_kernel<0, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge,
+               (int64_t)ge.HW * ge.C, part);
   const int CB = ge.cpg > 32 ? ge.cpg : 32;
-  TDN_LAUNCH(gn_stats_kernel, dim3(ceil_div(C, CB), N), dim3(kThreads), 0, st, part, ge, CB, gamma, beta, eps,
-                     stats, coef);
+  TDN_LAUNCH(gn_stats_kernel, dim3(ceil_div(C, CB), N), dim3(kThreads), 0, st, part, ge, CB, (const bf16_t*)z,
+             dtype == TDN_F16 ? 1 : 0, gamma, beta, eps, stats, coef);
   const int64_t total = (int64_t)N * ge.HW * ge.C8;
   int grid = (int)((total + kThreads - 1) / kThreads);
   if (grid > 8192) grid = 8192;
@@ -409,9 +455,11 @@ extern "C" int tdn_gn_bwd(const void* g, const void* z, const float* stats, cons
   hipStream_t st = (hipStream_t)stream;
   const dim3 gp(ge.chunks, N);
   if (dtype == TDN_F16)
-    TDN_LAUNCH((gn_partial_kernel<1, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge, part);
+    TDN_LAUNCH((gn_partial_kernel<1, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge,
+               (int64_t)0, part);
   else
-    TDN_LAUNCH((gn_partial_kernel<1, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge, part);
+    TDN_LAUNCH((gn_partial_kernel<1, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge,
+               (int64_t)0, part);
   const int CB = ge.cpg > 32 ? ge.cpg : 32;
   TDN_LAUNCH(gn_bwd_coef_kernel, dim3(ceil_div(C, CB)), dim3(kThreads), 0, st, part, ge, CB, gamma, stats,
                      coef3, dgamma, dbeta, acc);
@@ -448,11 +496,13 @@ extern "C" int tdn_bn_train_fwd(const void* z, const float* gamma, const float* 
   hipStream_t st = (hipStream_t)stream;
   const dim3 gp(ge.chunks, N);
   if (dtype == TDN_F16)
-    TDN_LAUNCH((gn_partial_kernel<0, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge, part);
+    TDN_LAUNCH((gn_partial_kernel<0, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge,
+               (int64_t)0, part);
   else
-    TDN_LAUNCH((gn_partial_kernel<0, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge, part);
-  TDN_LAUNCH(bn_stats_kernel, dim3(ceil_div(C, 32)), dim3(kThreads), 0, st, part, ge, gamma, beta, eps,
-                     momentum, running_mean, running_var, stats, coef);
+    TDN_LAUNCH((gn_partial_kernel<0, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge,
+               (int64_t)0, part);
+  TDN_LAUNCH(bn_stats_kernel, dim3(ceil_div(C, 32)), dim3(kThreads), 0, st, part, ge, (const bf16_t*)z,
+             dtype == TDN_F16 ? 1 : 0, gamma, beta, eps, momentum, running_mean, running_var, stats, coef);
   const int64_t total = (int64_t)N * ge.HW * ge.C8;
   int grid = (int)((total + kThreads - 1) / kThreads);
   if (grid > 8192) grid = 8192;
@@ -476,9 +526,11 @@ extern "C" int tdn_bn_train_bwd(const void* g, const void* z, const float* stats
   hipStream_t st = (hipStream_t)stream;
   const dim3 gp(ge.chunks, N);
   if (dtype == TDN_F16)
-    TDN_LAUNCH((gn_partial_kernel<1, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge, part);
+    TDN_LAUNCH((gn_partial_kernel<1, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge,
+               (int64_t)0, part);
   else
-    TDN_LAUNCH((gn_partial_kernel<1, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge, part);
+    TDN_LAUNCH((gn_partial_kernel<1, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge,
+               (int64_t)0, part);
   TDN_LAUNCH(bn_bwd_coef_kernel, dim3(ceil_div(C, 32)), dim3(kThreads), 0, st, part, ge, gamma, stats,
                      coef3, dgamma, dbeta, acc);
   const int64_t total = (int64_t)N * ge.HW * ge.C8;
