@@ -671,6 +671,47 @@ int tdn_bbox_detections(const float* rois, const void* cls, const void* reg, int
                         float* dense_scores, float* dense_boxes, float* dets, int64_t* labels, int64_t* row_idx,
                         int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the mask branch of Mask R-CNN: polygon mask targets, mask loss, mask paste (the project's own
+ *      spec in the mmdetection-v1 lineage of mask_target / FCNMaskHead.loss / get_seg_masks) ----
+ * Polygons: poly_xy fp32 [P][2] vertices in the network-input frame; poly_offsets int32 [Q + 1]: polygon q owns vertices
+ * [poly_offsets[q], poly_offsets[q + 1]); gt_poly_offsets int32 [B][G + 1]: ground truth j of image b owns polygons
+ * [gt_poly_offsets[b][j], gt_poly_offsets[b][j + 1]).  Every offset read on the device is clamped to its array.
+ * tdn_mask_target, one launch: row r of rois fp32 [R][5] = (batch_idx, x1, y1, x2, y2) with gt_inds int32 [R] is valid
+ * iff its truncated batch index is in [0, B) and 0 <= gt_inds[r] < G; targets uint8 [R][M][M] = 1 where the cell centre
+ * of the truncated box lies inside any polygon of the instance (even-odd per polygon, union across polygons), weights
+ * fp32 [R] = 1; an invalid row gets zeros and weight 0.  1 <= M <= TDN_MASK_MAX_SIZE, R <= TDN_LOSS_MAX_ROWS. */
+#define TDN_MASK_MAX_SIZE 56
+int tdn_mask_target(const float* rois, const int32_t* gt_inds, int R, const float* poly_xy, int P,
+                    const int32_t* poly_offsets, int Q, const int32_t* gt_poly_offsets, int B, int G, int M,
+                    uint8_t* targets, float* weights, void* stream);
+/* pred [R][C][M][M] logits, TDN_F32 / TDN_BF16 / TDN_F16, nhwc 0: NCHW-contiguous memory, 1: channels_last memory; row r
+ * reads channel labels[r] (int64, 1..C-1; C == 1: channel 0) against targets uint8 [R][M][M] with weights fp32 [R];
+ * loss fp32 [1] = sum_r w_r sum_ij bce / (D M^2), D from avg as tdn_loss_roi_fwd takes it (mode 2: rows with w > 0);
+ * avg_out fp32 [1] = D, which the backward takes as avg_in with the cotangent g fp32 [1].  A row whose weight is exactly
+ * 0 is never read; a row whose label is outside its range counts as weight 0.  dpred has pred's layout and is written
+ * in full.  Forward two launches, backward one.  R <= TDN_LOSS_MAX_ROWS, C <= TDN_LOSS_MAX_CLASSES, R C M^2 < 2^31.
+ * workspace: tdn_mask_loss_workspace_bytes() bytes, 256-aligned. */
+int64_t tdn_mask_loss_workspace_bytes(int R);
+int tdn_mask_loss_fwd(const void* pred, int dtype, int nhwc, int R, int C, int M, const uint8_t* targets,
+                      const int64_t* labels, const float* weights, const tdn_loss_avg* avg, float* loss, float* avg_out,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int tdn_mask_loss_bwd(const void* pred, int dtype, int nhwc, int R, int C, int M, const uint8_t* targets,
+                      const int64_t* labels, const float* weights, const float* g, const float* avg_in, void* dpred,
+                      void* stream);
+/* dets fp32 [B][max_num][5] and counts int32 [B] of tdn_multiclass_nms -> rois fp32 [B * max_num][5] =
+ * (b, x1 s, y1 s, x2 s, y2 s) for rows below counts[b], (-1, 0, 0, 0, 0) for the rest; s = scale_factors[b] (device
+ * fp32 [B]) or, when that is NULL, scale_factor. */
+int tdn_rois_from_detections(const float* dets, const int32_t* counts, int B, int max_num, const float* scale_factors,
+                             float scale_factor, float* rois, void* stream);
+/* pred [B * max_num][C][M][M] as above, in the row order of tdn_rois_from_detections; dets in the frame of the H x W
+ * canvas, labels int64 [B][max_num] 0-based foreground labels (channel label + 1, or 0 when C == 1), img_shapes device
+ * int32 [B][2] = (h, w) or NULL.  out uint8 [B * max_num][H][W] (packed 0) = bilinear sample of sigmoid(pred) > thr
+ * inside the truncated box, the canvas and the image, 0 elsewhere; packed 1: [B * max_num][H][8 ceil(W / 64)], bit
+ * x % 8 of byte x / 8 is pixel x.  Every byte is written.  One launch. */
+int tdn_mask_paste(const void* pred, int dtype, int nhwc, int B, int max_num, int C, int M, const float* dets,
+                   const int64_t* labels, const int32_t* counts, const int32_t* img_shapes, int H, int W, float thr,
+                   int packed, uint8_t* out, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

@@ -6,8 +6,9 @@ Drop-in surface (same names as the reference's ``models`` package): ``BACKBONES`
 ``bbox2delta`` / ``delta2bbox``, ``batched_nms`` and ``rpn_proposals``, the training targets ``assign_max_iou`` /
 ``sample_assigned`` / ``anchor_target`` / ``sample_rois`` and the losses that consume them (``rpn_loss`` /
 ``anchor_head_loss`` / ``bbox_head_loss``), then ``rois_from_proposals``, ``roi_align``,
-``map_roi_levels`` and ``SingleRoIExtractor``, and the test-time detections ``bbox_head_detections`` /
-``multiclass_nms``).  Everything computes through libtdn.so
+``map_roi_levels`` and ``SingleRoIExtractor``, the test-time detections ``bbox_head_detections`` /
+``multiclass_nms``, and the mask branch ``pack_polygons`` / ``mask_target`` / ``mask_head_loss`` /
+``rois_from_detections`` / ``mask_head_masks``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -30,5 +31,7 @@ from .target import anchor_target, assign_max_iou, sample_assigned, sample_rois 
 from .losses import (AnchorHeadLossFunction, BBoxHeadLossFunction, anchor_head_loss,  # noqa: F401
                      bbox_head_loss, rpn_loss)
 from .detect import bbox_head_detections, multiclass_nms  # noqa: F401
+from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_target,  # noqa: F401
+                   pack_polygons, rois_from_detections)
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)

@@ -32,6 +32,7 @@ LOSS_MAX_ROWS = 1 << 20
 LOSS_MAX_AVG = 64
 DET_MAX_CLASSES = 1024
 DET_MAX_ROWS = 1 << 18
+MASK_MAX_SIZE = 56
 ADD_NONE, ADD_SAME, ADD_UP2X, ADD_SUMPOOL2 = 0, 1, 2, 3
 
 c_void_p = ctypes.c_void_p
@@ -276,6 +277,15 @@ SIGNATURES = {
     "tdn_bbox_detections": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_float,
                                     ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.c_double, c_float, c_float,
                                     c_int] + [c_void_p] * 7 + [c_i64, c_void_p]),
+    "tdn_mask_target": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                c_void_p, c_void_p, c_void_p]),
+    "tdn_mask_loss_workspace_bytes": (c_i64, [c_int]),
+    "tdn_mask_loss_fwd": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p] * 3 + [_LA, c_void_p, c_void_p, c_void_p, c_i64,
+                                                                              c_void_p]),
+    "tdn_mask_loss_bwd": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p] * 7),
+    "tdn_rois_from_detections": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p]),
+    "tdn_mask_paste": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 4 + [c_int, c_int, c_float, c_int, c_void_p,
+                                                                          c_void_p]),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),
