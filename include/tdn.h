@@ -712,6 +712,73 @@ int tdn_mask_paste(const void* pred, int dtype, int nhwc, int B, int max_num, in
                    const int64_t* labels, const int32_t* counts, const int32_t* img_shapes, int H, int W, float thr,
                    int packed, uint8_t* out, void* stream);
 
+/* ---- fused SGD step: gradient-norm clip, loss unscaling, momentum update (no reference counterpart:
+ *      SURVEY row 25) ----
+ * One item per parameter: p, g and buf are fp32 device pointers to the lowest address of a dense, non-overlapping
+ * tensor of `shape` (fewer than 4 dims: leading 1s); p_stride / g_stride are element strides, buf has p's strides and
+ * is NULL when the item's group has momentum 0.  Fewer than 2^31 elements per item.  Three access paths, chosen from the
+ * strides (tdn_sgd_plan reports them):
+ *   TDN_SGD_PATH_LINEAR      p and g share one layout: 16-byte loads and stores when all three pointers are aligned
+ *   TDN_SGD_PATH_TRANSPOSED  p contiguous [O][I][kh][kw], g stored [O][kh][kw][I] (the gradient views of a reducer):
+ *                            per output channel a kh kw x I block is transposed through LDS
+ *   TDN_SGD_PATH_GENERAL     any other pair of dense permutations, element by element */
+typedef struct {
+  float* p;
+  const float* g;
+  float* buf;
+  int64_t shape[4];
+  int64_t p_stride[4];
+  int64_t g_stride[4];
+  int32_t group;             /* row of the hyper-parameter array */
+  int32_t reserved;
+} tdn_sgd_item;
+#define TDN_SGD_MAX_ITEMS (1 << 20)
+#define TDN_SGD_MAX_GROUPS 1024
+#define TDN_SGD_PATH_LINEAR 0
+#define TDN_SGD_PATH_TRANSPOSED 1
+#define TDN_SGD_PATH_GENERAL 2
+/* flags */
+#define TDN_SGD_NESTEROV 1
+#define TDN_SGD_SKIP_NONFINITE 2
+#define TDN_SGD_DYNAMIC_SCALE 4
+/* fstate: device fp32 [TDN_SGD_F_COUNT]; istate: device int32 [TDN_SGD_I_COUNT].  The caller initialises
+ * fstate[F_SCALE] (1 without loss scaling) and zeroes the rest; I_BUF_INIT != 0 says that the momentum buffers hold
+ * values (a loaded checkpoint), 0 makes the next taken step copy instead of accumulate. */
+#define TDN_SGD_F_SCALE 0
+#define TDN_SGD_F_NORM 1
+#define TDN_SGD_F_COEF 2
+#define TDN_SGD_F_SNAP_SCALE 3
+#define TDN_SGD_F_COUNT 4
+#define TDN_SGD_I_TRACKER 0
+#define TDN_SGD_I_TAKEN 1
+#define TDN_SGD_I_SKIPPED 2
+#define TDN_SGD_I_LAST_SKIPPED 3
+#define TDN_SGD_I_BUF_INIT 4
+#define TDN_SGD_I_SNAP_FIRST 5
+#define TDN_SGD_I_COUNT 8
+/* Host only.  plan8 = {table bytes, workspace bytes, workgroups of pass 1, workgroups of pass 2, norm chunks, update
+ * chunks, n, n_groups}.  table_host NULL: the size query; else a 16-byte aligned HOST buffer of table_bytes >= plan8[0]
+ * bytes that receives the table (item descriptors and the two chunk -> (item, offset) maps), which the caller copies
+ * to 256-aligned device memory once.  paths: NULL or int32 [n], the access path of every item.  Overlapping or
+ * non-dense tensors are refused. */
+int tdn_sgd_plan(const tdn_sgd_item* items, int n, int n_groups, int64_t* plan8, void* table_host, int64_t table_bytes,
+                 int32_t* paths);
+/* The step, two launches, no host synchronisation, no atomics; table (device) and plan8 (host) of one tdn_sgd_plan call.
+ * hyper: device fp32 [n_groups][3] = lr, weight decay, momentum.  Pass 1: S = sum of g^2 over all items in float64 (one
+ * partial per norm chunk in the workspace), and the snapshot of fstate[F_SCALE] / !istate[I_BUF_INIT].  Pass 2, with
+ * inv = 1 / scale, n = (float)(sqrt(S) * inv), coef = max_norm > 0 ? min(1, max_norm / (n + 1e-6)) : 1, m = coef * inv,
+ * per element, each operation rounded to fp32 on its own:
+ *   gh = g * m;  d = wd != 0 ? fma(wd, p, gh) : gh;  buf' = first step ? d : buf * mom + d;
+ *   u = nesterov ? fma(mom, buf', d) : buf'  (no buf: u = d);  p' = fma(-lr, u, p)
+ * which is torch.optim.SGD(foreach=False) bit for bit.  g is never written.  S not finite (an Inf or NaN gradient) with
+ * TDN_SGD_SKIP_NONFINITE: p and buf are left untouched, istate[I_SKIPPED] advances instead of istate[I_TAKEN].  With
+ * TDN_SGD_DYNAMIC_SCALE fstate[F_SCALE] and istate[I_TRACKER] follow torch._amp_update_scale_(growth, backoff,
+ * interval).  fstate[F_NORM] = n, fstate[F_COEF] = coef, istate[I_LAST_SKIPPED] = 0 / 1.
+ * workspace: plan8[1] bytes, 256-aligned. */
+int tdn_sgd_step(const void* table, const int64_t* plan8, const float* hyper, float* fstate, int32_t* istate,
+                 void* workspace, int64_t workspace_bytes, int flags, float max_norm, float growth, float backoff,
+                 int interval, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

@@ -8,7 +8,7 @@ Drop-in surface (same names as the reference's ``models`` package): ``BACKBONES`
 ``anchor_head_loss`` / ``bbox_head_loss``), then ``rois_from_proposals``, ``roi_align``,
 ``map_roi_levels`` and ``SingleRoIExtractor``, the test-time detections ``bbox_head_detections`` /
 ``multiclass_nms``, and the mask branch ``pack_polygons`` / ``mask_target`` / ``mask_head_loss`` /
-``rois_from_detections`` / ``mask_head_masks``).  Everything computes through libtdn.so
+``rois_from_detections`` / ``mask_head_masks``, and the fused optimizer step ``SGD``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -33,5 +33,6 @@ from .losses import (AnchorHeadLossFunction, BBoxHeadLossFunction, anchor_head_l
 from .detect import bbox_head_detections, multiclass_nms  # noqa: F401
 from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_target,  # noqa: F401
                    pack_polygons, rois_from_detections)
+from .optim import SGD  # noqa: F401
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)

@@ -33,6 +33,13 @@ LOSS_MAX_AVG = 64
 DET_MAX_CLASSES = 1024
 DET_MAX_ROWS = 1 << 18
 MASK_MAX_SIZE = 56
+SGD_MAX_ITEMS = 1 << 20
+SGD_MAX_GROUPS = 1024
+SGD_PATH_LINEAR, SGD_PATH_TRANSPOSED, SGD_PATH_GENERAL = 0, 1, 2
+SGD_NESTEROV, SGD_SKIP_NONFINITE, SGD_DYNAMIC_SCALE = 1, 2, 4
+SGD_F_SCALE, SGD_F_NORM, SGD_F_COEF, SGD_F_SNAP_SCALE, SGD_F_COUNT = 0, 1, 2, 3, 4
+SGD_I_TRACKER, SGD_I_TAKEN, SGD_I_SKIPPED, SGD_I_LAST_SKIPPED, SGD_I_BUF_INIT, SGD_I_SNAP_FIRST, SGD_I_COUNT = \
+    0, 1, 2, 3, 4, 5, 8
 ADD_NONE, ADD_SAME, ADD_UP2X, ADD_SUMPOOL2 = 0, 1, 2, 3
 
 c_void_p = ctypes.c_void_p
@@ -194,6 +201,17 @@ class BottleneckHeadArgs(ctypes.Structure):
 
 _BHA = ctypes.POINTER(BottleneckHeadArgs)
 
+
+class SgdItem(ctypes.Structure):
+    """Mirror of ``tdn_sgd_item`` (include/tdn.h): one parameter of a fused SGD step."""
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("buf", c_void_p),
+                ("shape", c_i64 * 4), ("p_stride", c_i64 * 4), ("g_stride", c_i64 * 4),
+                ("group", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+_SI = ctypes.POINTER(SgdItem)
+_I64P = ctypes.POINTER(c_i64)
+
 # name -> (restype, argtypes); must list every symbol of include/tdn.h (tests/test_abi.py checks this)
 SIGNATURES = {
     "tdn_last_error": (ctypes.c_char_p, []),
@@ -286,6 +304,9 @@ SIGNATURES = {
     "tdn_rois_from_detections": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p]),
     "tdn_mask_paste": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 4 + [c_int, c_int, c_float, c_int, c_void_p,
                                                                           c_void_p]),
+    "tdn_sgd_plan": (c_int, [_SI, c_int, c_int, _I64P, c_void_p, c_i64, ctypes.POINTER(ctypes.c_int32)]),
+    "tdn_sgd_step": (c_int, [c_void_p, _I64P, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, c_float,
+                             c_float, c_int, c_void_p]),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),
