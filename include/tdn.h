@@ -779,6 +779,55 @@ int tdn_sgd_step(const void* table, const int64_t* plan8, const float* hyper, fl
                  void* workspace, int64_t workspace_bytes, int flags, float max_norm, float growth, float backoff,
                  int interval, void* stream);
 
+/* ---- fully connected layers ---------------------------------------------------------------------------
+ * nn.Linear as the box head uses it (shared_fcs, fc_cls, fc_reg of the mmdetection-v1 SharedFCBBoxHead): 16-bit
+ * operands, fp32 accumulation on the matrix cores, one rounding of the result.  K is a multiple of 64, O is any value in
+ * 1..65536, M any value in 0..2^18; Op = O rounded up to 64.  ld* are row strides in ELEMENTS.  Nothing past row M or
+ * column O is written and nothing outside an operand's rows is read.
+ *
+ * splits: 0 lets the library cut the reduction (see tdn_linear_plan); 1..K/64 (wgrad: 1..ceil(M/64), at least 1) forces
+ * a slice count — a value above the number of 64-element chunks of the product's reduction (dgrad reduces over Op) means
+ * one chunk per slice; anything else is an error.  With more than one slice every workgroup stores an fp32 partial slab
+ * into the workspace and a finalize launch adds the slabs in slice order, then applies the epilogue: the result does not
+ * depend on the run.  workspace: tdn_linear_workspace_bytes(kind, M, O, K, splits) bytes (may be 0, then NULL is taken),
+ * 256-byte aligned; its regions, in order: the padded cotangent (dgrad / wgrad with O % 64 != 0: M x Op elements), the
+ * slabs, wgrad's column-sum slabs.  kind: 0 forward, 1 dgrad, 2 wgrad.
+ *
+ * tdn_pack_linear_weight: w fp32 [O][K] with element strides (s_o, s_k) -> w_fwd [Op][K] and, unless NULL, w_dgrad
+ *   [K][Op], each value rounded once to `dtype`, the rows / columns O..Op-1 zero.  C == K: the columns as they are;
+ *   otherwise (C | K, C % 8 == 0, hw = K / C) logical column c * hw + p goes to packed column p * C + c, so that the
+ *   forward reads a channels_last (R, S, S, C) RoI feature buffer and the dgrad writes its gradient in place.
+ * tdn_linear_plan (host only): out[0..15] = {BM, BN, BK, row tiles, column tiles, tiles, slices, chunks per slice, chunks,
+ *   workgroups of the GEMM launch, launches, 1 if a pad launch runs + 2 if the product is handed to the conv GEMM, slab bytes low 31 bits, slab bytes >> 31, workspace
+ *   bytes low 31 bits, workspace bytes >> 31}.
+ * With splits == 0, an unsplit forward / dgrad of a layer with O % 64 == 0 and dense rows (ld == row length) is computed
+ * by tdn_conv2d_fwd / tdn_conv2d_dgrad as a 1x1 conv over M pixels (same operands, same arithmetic contract; measured
+ * faster); any splits >= 1 keeps it in csrc/linear.hip.
+ * tdn_linear_fwd:   y[m][o] = act(sum_k x[m][k] * w_fwd[o][k] + bias[o]);  bias fp32 or NULL, act = ReLU if relu, y
+ *   16-bit, or fp32 if out_f32.
+ * tdn_linear_dgrad: dx[m][k] = sum_o g[m][o] * w_dgrad[k][o], then 0 where mask_src[m][k] <= 0 (mask_src: the layer's own
+ *   input, i.e. the previous layer's ReLU output, or NULL).  g rows need no alignment when O % 64 != 0 (one pad launch
+ *   copies them); otherwise g and ldg must keep rows 16-byte aligned.
+ * tdn_linear_wgrad: dw[o][j] = beta * dw[o][j] + sum_m g[m][o] * x[m][packed(j)] in fp32, dw contiguous [O][K] in the
+ *   parameter's LOGICAL column order (C as in the pack); dbias[o] = beta * dbias[o] + sum_m g[m][o] (NULL: skipped).
+ *   beta == 0 never reads dw / dbias.  M == 0 leaves beta * old.
+ * tdn_linear_relu_bwd: out[m][o] = y[m][o] > 0 ? g[m][o] : 0 on contiguous (M, O) operands: the cotangent behind a
+ *   layer's own ReLU, from its stored output y (16-bit; fp32 if y_f32).  Only a stand-alone layer needs it: in a chain
+ *   the next layer's tdn_linear_dgrad applies this mask through mask_src. */
+int tdn_pack_linear_weight(const float* w, int64_t s_o, int64_t s_k, int O, int K, int C, void* w_fwd, void* w_dgrad,
+                           int dtype, void* stream);
+int64_t tdn_linear_workspace_bytes(int kind, int M, int O, int K, int splits);
+int tdn_linear_relu_bwd(const void* g, const void* y, int y_f32, void* out, int M, int O, int dtype, void* stream);
+int tdn_linear_plan(int kind, int M, int O, int K, int splits, int32_t* out16);
+int tdn_linear_fwd(const void* x, int64_t ldx, const void* w_fwd, const float* bias, void* y, int64_t ldy, int M, int O,
+                   int K, int relu, int out_f32, int splits, void* workspace, int64_t workspace_bytes, int dtype,
+                   void* stream);
+int tdn_linear_dgrad(const void* g, int64_t ldg, const void* w_dgrad, const void* mask_src, int64_t ld_mask, void* dx,
+                     int64_t lddx, int M, int O, int K, int splits, void* workspace, int64_t workspace_bytes, int dtype,
+                     void* stream);
+int tdn_linear_wgrad(const void* x, int64_t ldx, const void* g, int64_t ldg, float* dw, float* dbias, float beta, int M,
+                     int O, int K, int C, int splits, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

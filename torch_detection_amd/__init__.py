@@ -8,12 +8,13 @@ Drop-in surface (same names as the reference's ``models`` package): ``BACKBONES`
 ``anchor_head_loss`` / ``bbox_head_loss``), then ``rois_from_proposals``, ``roi_align``,
 ``map_roi_levels`` and ``SingleRoIExtractor``, the test-time detections ``bbox_head_detections`` /
 ``multiclass_nms``, and the mask branch ``pack_polygons`` / ``mask_target`` / ``mask_head_loss`` /
-``rois_from_detections`` / ``mask_head_masks``, and the fused optimizer step ``SGD``).  Everything computes through libtdn.so
+``rois_from_detections`` / ``mask_head_masks``, the fused optimizer step ``SGD``, and the
+fully connected layers ``linear`` / ``BBoxHead`` between ``roi_align`` and the box losses).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
 
-from .registry import BACKBONES, NECKS, Registry  # noqa: F401
+from .registry import BACKBONES, HEADS, NECKS, Registry  # noqa: F401
 from .layers import (ConvModule, conv1x1_group, conv3x3_group, conv7x7_group, get_group_gn,  # noqa: F401
                      norm_layer)
 from .inits import (bias_init_with_prob, constant_init, kaiming_init, normal_init, uniform_init,  # noqa: F401
@@ -34,5 +35,7 @@ from .detect import bbox_head_detections, multiclass_nms  # noqa: F401
 from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_target,  # noqa: F401
                    pack_polygons, rois_from_detections)
 from .optim import SGD  # noqa: F401
+from .linear import LinearFunction, linear  # noqa: F401
+from .heads import BBoxHead  # noqa: F401
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)

@@ -307,6 +307,17 @@ SIGNATURES = {
     "tdn_sgd_plan": (c_int, [_SI, c_int, c_int, _I64P, c_void_p, c_i64, ctypes.POINTER(ctypes.c_int32)]),
     "tdn_sgd_step": (c_int, [c_void_p, _I64P, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, c_float,
                              c_float, c_int, c_void_p]),
+    "tdn_pack_linear_weight": (c_int, [c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                       c_void_p]),
+    "tdn_linear_workspace_bytes": (c_i64, [c_int] * 5),
+    "tdn_linear_relu_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "tdn_linear_plan": (c_int, [c_int] * 5 + [ctypes.POINTER(ctypes.c_int32)]),
+    "tdn_linear_fwd": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64] + [c_int] * 6 +
+                       [c_void_p, c_i64, c_int, c_void_p]),
+    "tdn_linear_dgrad": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64] + [c_int] * 4 +
+                         [c_void_p, c_i64, c_int, c_void_p]),
+    "tdn_linear_wgrad": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_float] + [c_int] * 5 +
+                         [c_void_p, c_i64, c_int, c_void_p]),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),

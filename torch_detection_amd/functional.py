@@ -251,10 +251,13 @@ def invalidate_packed(*modules):
     re-derives them from the fp32 parameters.  Needed after parameter or running-statistics updates that do not bump
     the tensors' version counters (``p.data.copy_()``, ``p.data.mul_()``, kernels writing through raw pointers);
     ordinary in-place updates under ``torch.no_grad()`` (what optimizers do) are picked up automatically."""
+    from .linear import forget               # imported here: linear.py imports this module
     for m in modules:
         for sub in m.modules():
             for u in sub.__dict__.get('_hip_units', {}).values():
                 u.key = None
+        for p in m.parameters():
+            forget(p)                        # packed copies made by a bare linear() call on this parameter
 
 
 class StagedImages(object):
