@@ -20,8 +20,7 @@
  *     Weights are pre-packed K-major in the same type by tdn_pack_conv_weight.
  *   - Return value: 0 = ok, negative = error; tdn_last_error() returns a
  *     thread-local message.  Nothing throws across the boundary.
- *   - Re-entrant: no global mutable state besides the thread-local error text
- *     (and the optional diagnostics buffer of tdn_debug_trace).
+ *   - Re-entrant: no global mutable state besides the thread-local error text.
  */
 #ifndef TDN_H_
 #define TDN_H_
@@ -889,11 +888,6 @@ int tdn_collate_images(const void* const* imgs, const int32_t* hw, const uint8_t
  * out[12] = chunk images held in LDS * 100 + output-channel passes per workgroup. */
 int tdn_conv2d_plan(int kind, int N, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                     int32_t* out16);
-
-/* Diagnostics only: registers a device buffer of `bytes` bytes into which the tracing builds of the conv GEMM
- * kernel (selected with the TDN_GEMM_CFG environment variable, scripts/trace_gemm.py) write 32 64-bit shader-clock
- * stamps per workgroup.  buf = NULL disables tracing.  No reference counterpart. */
-int tdn_debug_trace(void* buf, long long bytes);
 
 #ifdef __cplusplus
 }

@@ -40,7 +40,7 @@ for src, name in (
         ("bench_nohalo.json", "bench_generic_kernel_only.json"),
         ("convbench_fwd.log", "convbench_fwd.log"), ("convbench_dgrad.log", "convbench_dgrad.log"),
         ("convbench_fwd_b1.log", "convbench_fwd_b1.log"), ("ksweep_l3.log", "ksweep_l3.log"),
-        ("ksweep_p2.log", "ksweep_p2.log"), ("halo_ablate.log", "halo_ablations.log"),
+        ("ksweep_p2.log", "ksweep_p2.log"),
         ("wgrad_group_bench.log", "wgrad_group_bench.log"), ("block_bench.log", "block_bench.log")):
     cp(src, name)
 # one-line files gathered into jsonl tables

@@ -1,11 +1,9 @@
 #!/usr/bin/env python
-"""Graph-replay timing of the generic conv GEMM kernel's tile / load-path configurations (TDN_GEMM_CFG, trace build)
-on the per-image 1x1 layers of R50-FPN (the launches of the layer2-4 chains), with a bit-for-bit check against
-configuration 0 where the K order is the same (all but the K-group configurations)."""
+"""Graph-replay timing of the generic conv GEMM kernel's tile configurations (TDN_GEMM_CFG) on the per-image 1x1
+layers of R50-FPN (the launches of the layer2-4 chains), with a bit-for-bit check against configuration 0 where the
+K order is the same (all but the K-group configurations)."""
 import argparse
 import os
-
-os.environ.setdefault("TDN_LIB", "libtdn_trace.so")
 import sys
 
 import torch

@@ -82,6 +82,26 @@ def test_host_side_plans_and_errors():
     assert lib.tdn_conv2d_plan(0, 1, 8, 8, 64, 64, 5, 1, 2, o) != 0
 
 
+def test_forced_gemm_cfg_ids_name_their_tiles(monkeypatch):
+    """TDN_GEMM_CFG ids are names, not row numbers: each of the seven reports its (BM, BN, BK); an id that is not in
+    the table is left to the planner."""
+    from torch_detection_amd import _lib
+    lib = _lib.load()
+    tiles = {0: (64, 64, 64), 1: (64, 128, 64), 2: (128, 128, 64), 3: (192, 256, 64), 25: (64, 64, 64),
+             46: (128, 128, 64), 50: (64, 64, 128)}
+
+    def plan(cfg):
+        monkeypatch.setenv("TDN_GEMM_CFG", str(cfg))
+        o = (ctypes.c_int32 * 16)()
+        assert lib.tdn_conv2d_plan(0, 1, 16, 16, 256, 256, 1, 1, 0, o) == 0   # 1x1, M = 256, N = K = 256
+        return list(o)
+
+    for cfg, tile in tiles.items():
+        o = plan(cfg)
+        assert (o[3], o[4], o[5]) == tile, (cfg, o)
+    assert plan(7) == plan(99)   # a retired row and an id that never existed
+
+
 def test_launch_plan_bookkeeping_without_a_gpu():
     """tdn_plan_*: recording state machine and error reporting (no launches, no events: nothing touches a device)."""
     from torch_detection_amd import _lib

@@ -10,8 +10,8 @@ import threading
 import torch  # noqa: F401  (loads the HIP runtime first so libtdn binds to the same libamdhip64)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# TDN_LIB: another build of the library in the package directory — scripts/ use libtdn_trace.so (`make TRACE=1`: ablation
-# and cycle-stamp instantiations) for their sweeps; the package, the tests and bench.py use the product, libtdn.so
+# TDN_LIB: another build of the library in the package directory, for A/B runs of two builds (scripts/norm_bench.py);
+# the package, the tests and bench.py use the product, libtdn.so
 LIB_PATH = os.path.join(_HERE, os.path.basename(os.environ.get("TDN_LIB", "") or "libtdn.so"))
 
 TDN_BF16 = 0
@@ -356,7 +356,6 @@ SIGNATURES = {
     "tdn_plan_stats": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "tdn_plan_free": (c_int, [c_void_p]),
     "tdn_conv2d_plan": (c_int, [c_int] * 9 + [ctypes.POINTER(ctypes.c_int32)]),
-    "tdn_debug_trace": (c_int, [c_void_p, ctypes.c_longlong]),
 }
 
 _lib = None

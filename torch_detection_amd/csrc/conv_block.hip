@@ -68,22 +68,7 @@ struct BlockParams {
   const float* scd; const float* shd;
   int N, H, W;
   int tiles_x, tiles_y, ntiles, nwg_pad;
-  unsigned long long* trace;   // libtdn_trace.so only: 16 x 8-byte stamps per workgroup (scripts/block_trace.py)
 };
-
-#ifdef TDN_TRACE_BUILD
-#define BLK_STAMP(slot)                                                                                   \
-  do {                                                                                                    \
-    if (p.trace && tid == 0) p.trace[(size_t)blockIdx.x * 16 + (slot)] = __builtin_readcyclecounter();   \
-  } while (0)
-#define BLK_STAMP_RT(slot)                                                                                \
-  do {                                                                                                    \
-    if (p.trace && tid == 0) p.trace[(size_t)blockIdx.x * 16 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define BLK_STAMP(slot) do { } while (0)
-#define BLK_STAMP_RT(slot) do { } while (0)
-#endif
 
 // Store target of output pixels that lie outside the image (ragged right / bottom tiles): the epilogue's loads and
 // stores are then unconditional — address selects, no branches — so the compiler can count what is in flight behind a
@@ -203,8 +188,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   const int bid = blockIdx.x;
   const int tile = (bid & 7) * (p.nwg_pad >> 3) + (bid >> 3);   // XCD x owns a contiguous run of tiles (shared halos)
   if (tile >= p.ntiles) return;
-  BLK_STAMP(0);
-  BLK_STAMP_RT(14);
   const int H = p.H, W = p.W;
   const int tpi = p.tiles_x * p.tiles_y;
   const int img = tile / tpi;
@@ -356,8 +339,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
       if (kc == 0) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
-    if (kc == 0) BLK_STAMP(1);
-    if (kc == 4) BLK_STAMP(2);
     if constexpr (DSB) {
       if (kc + 2 < 8) load_step(kc + 2);
       else if (kc == 7) {
@@ -399,7 +380,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
     }
   }
   lds_barrier();   // b0: every wave is done reading the ring
-  BLK_STAMP(3);
   bf16x8_t tpk[DSB ? 6 : 1];   // DSB: t of this lane's six patch pixels (its 8 channels), as the downsample dgrad launch stores it
   if constexpr (DSB) {
     load_tap(4); load_tap(5); load_tap(6);
@@ -465,7 +445,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   if constexpr (DSB) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // taps 2..6 travel on
   else if constexpr (KS1 == 8) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  BLK_STAMP(4);
   // h1 / g2 to HBM: behind the barrier, so that nobody waits for the stores (DSB: behind b2, which drains the queue)
   auto store_o1 = [&]() {
 #pragma unroll
@@ -584,7 +563,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   tap_compute(1);
   if constexpr (KS1 == 8 && !DSB) lds_barrier();   // b2: [65536, 81920) is free
   else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // ... and taps 2..5 (DSB: 2..6) have landed
-  BLK_STAMP(5);
   if constexpr (DSB) store_o1();
   f32x4_t sc2v[2], sh2v[2];
   if constexpr (DSK) {   // requested a barrier early and touched right behind b3's vmcnt(0): see below
@@ -596,7 +574,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
 #pragma unroll
   for (int t = 2; t < 7; ++t) tap_compute(t);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // b3: taps 7, 8 landed; [0, 40960) is free
-  BLK_STAMP(6);
   // (the compiler waits vmcnt(0) where a load it knows about is first used; with the operands of epilogue 2 touched
   // here that wait coincides with b3's instead of draining the transfers issued at b3 / b4)
   if constexpr (DSK) asm volatile("" ::"v"(sc2v[0]), "v"(sc2v[1]), "v"(sh2v[0]), "v"(sh2v[1]));
@@ -656,7 +633,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   tap_compute(7);
   tap_compute(8);
   lds_barrier();   // b4: every wave is done with H1
-  BLK_STAMP(7);
   if constexpr (DSK) {
     load_wrows(p.w3, 64, 8, 57344);
     load_wrows(p.wd, 128, 16, 65536);
@@ -708,7 +684,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // b5: H2 complete, conv3 weights landed
 
-  BLK_STAMP(8);
   auto store_o2 = [&]() {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -775,8 +750,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
       }
       *(bf16x8_t*)(pixj[j] >= 0 ? p.o3 + (int64_t)pixj[j] * C + cb8 : (bf16_t*)g_blk_sink) = o;
     }
-    BLK_STAMP(9);
-    BLK_STAMP(10);
   } else {
 #pragma unroll
     for (int nc = 0; nc < 2; ++nc) {
@@ -878,7 +851,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
             ov[j][h][4 + e] = f32_to_elem<F16>(v[2 * h + 1][e]);
           }
       }
-      BLK_STAMP(9 + nc);
       __builtin_amdgcn_sched_barrier(0);
       if (nc == 0) {   // the second pass's operands travel while the first pass's results are stored
         if constexpr (BWD && !MB) { load_ad(1, ad1); load_mask3(1); }
@@ -925,18 +897,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_kernel(const BlockParams 
       }
     }
   }
-#ifdef TDN_TRACE_BUILD
-  BLK_STAMP(11);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  BLK_STAMP(12);
-  BLK_STAMP_RT(15);
-  if (p.trace && tid == 0) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    p.trace[(size_t)blockIdx.x * 16 + 13] = ((unsigned long long)xcc << 32) | hwid;
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -974,8 +934,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
   const int bid = blockIdx.x;
   const int tile = (bid & 7) * (p.nwg_pad >> 3) + (bid >> 3);
   if (tile >= p.ntiles) return;
-  BLK_STAMP(0);
-  BLK_STAMP_RT(14);
   const int H = p.H, W = p.W;
   const int tpi = p.tiles_x * p.tiles_y;
   const int img = tile / tpi;
@@ -1076,8 +1034,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
     if (kc <= KS1 - 3) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     else if (kc == KS1 - 2) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (kc == 0) BLK_STAMP(1);
-    if (kc == 8) BLK_STAMP(2);
     if (kc + 3 < KS1) load_step(kc + 3);
     else load_unit(kc + 3 - KS1 + 2);            // kc = 13, 14, 15 -> units 2, 3, 4 into the slots just released
     const char* sX = smem + RING + (kc & 3) * P1SLOT + (wm * 96 + fr) * 64 + ((fq ^ f_rd32) * 16);
@@ -1093,7 +1049,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
       for (int j = 0; j < 6; ++j) acc1[i][j] = mfma16<F16>(wf[i], xf[j], acc1[i][j]);
   }
   lds_barrier();   // b0: the K-step slots are free
-  BLK_STAMP(3);
   // Compiler-visible loads / stores share the vmcnt queue with the LDS-DMA stream.  They are placed where the counted
   // waits of the unit stream only ever find them OLDER than the units they may leave in flight (a count that is too
   // small over-waits; one that is too large would let a unit be read before it has landed): the phase 2 mask loads and
@@ -1239,8 +1194,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
           for (int j = 0; j < 4; ++j) mw3[nc][j] = *(const u32x2_t*)(b3r(j) + nc * (C / 16));
       }
     }
-    if (u == 0) BLK_STAMP(4);
-    if (u == 9) BLK_STAMP(5);
     const int h = u / 9, t = u - h * 9;
     const int ky = t / 3, kx = t - ky * 3;
     const int oy = BWD ? 2 - ky : ky, ox = BWD ? 2 - kx : kx;
@@ -1262,7 +1215,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
     }
   }
   lds_barrier();   // b4: H1 is dead; the slot of unit 17 is free
-  BLK_STAMP(6);
   // second pass's addend (forward; the backward pass, which also carries mask operands, has no registers to spare and
   // requests it with the second mask after the first pass), first pass's affine: in front of unit 24, so that b5's
   // counted wait covers them
@@ -1327,7 +1279,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
   // b5: H2 complete; conv3 units 18..21 landed.  Younger than unit 21 in this wave's queue: units 22..24 (6 LDS-DMA)
   // and the 4 unconditional h2 / g1 stores above (the forward's bit-plane words, if any, only make the wait stricter)
   asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  BLK_STAMP(8);
 
   // ================= phase 3: two passes of 256 channels =================
   const int lrow3 = ((wn & 1) * 64 + (fr >> 2) * 16 + (fr & 3)) * WRB;   // + 4i rows, inside row-half unit wn >> 1
@@ -1401,7 +1352,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
         }
       __builtin_amdgcn_sched_barrier(0);   // one pixel at a time: interleaving the four keeps 4 x 16 fp32 temporaries live
     }
-    BLK_STAMP(9 + nc);
     __builtin_amdgcn_sched_barrier(0);
     if (nc == 0) {
       if constexpr (BWD) { load_ad1(); load_mask3(1); }
@@ -1435,12 +1385,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128_kernel(const BlockParams
     // (sink / zero-page redirect); bit-plane words, if any, only make the wait stricter
     if (nc == 0) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(BWD ? (MB ? 16 : 24) : 8) : "memory");
   }
-#ifdef TDN_TRACE_BUILD
-  BLK_STAMP(11);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  BLK_STAMP(12);
-  BLK_STAMP_RT(15);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1910,10 +1854,6 @@ __global__ __launch_bounds__(512, 1) void bottleneck128t_kernel(const BlockParam
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-#ifdef TDN_TRACE_BUILD
-static unsigned long long* g_blk_trace = nullptr;
-extern "C" int tdn_debug_block_trace(void* buf) { g_blk_trace = (unsigned long long*)buf; return 0; }   // >= 128 B per workgroup
-#endif
 
 // One launch: LDS opt-in of this instantiation on this device, the launch, its check.  PRINT_OCC (the C = 64 kernel,
 // the one with two workgroups per CU to lose): its occupancy is printed at its first launch under TDN_DEBUG_OCC, under
@@ -2008,9 +1948,6 @@ static int block_common(BlockParams& p, int& th, const tdn_bottleneck_args* a, i
   p.tiles_x = ceil_div(a->W, 16); p.tiles_y = ceil_div(a->H, th);
   p.ntiles = a->N * p.tiles_x * p.tiles_y;
   p.nwg_pad = (p.ntiles + 7) & ~7;
-#ifdef TDN_TRACE_BUILD
-  p.trace = g_blk_trace;
-#endif
   return 0;
 }
 // forward: folded BN of the three convs; the bit planes are optional outputs

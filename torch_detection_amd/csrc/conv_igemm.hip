@@ -51,20 +51,8 @@ struct GemmParams {
   unsigned tn_mul, tn_shr;   // fast_div by tiles_n
   int ncls;
   int grouped;   // block-diagonal grouped conv: the output tile's 64 channels see only the same 64 input channels
-  unsigned long long* trace;   // TAG 2 instantiations only: 32 timestamps per workgroup (scripts/trace_gemm.py)
   GemmClass cls[4];
 };
-
-// s_memtime stamp of (workgroup, slot): wave 0 only, written at the end of the kernel from SGPR-held values would
-// perturb less, but a direct store is good enough for a +-50 cycle picture of the pipeline
-#define TDN_TRACE(slot)                                                                                       \
-  do {                                                                                                        \
-    if constexpr (TAG == 2) {                                                                                 \
-      if (p.trace && tid == 0)                                                                                \
-        p.trace[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 + (slot)] = __builtin_readcyclecounter(); \
-    }                                                                                                         \
-  } while (0)
-
 
 template <int BK>
 __device__ __forceinline__ int swz_f(int row) {
@@ -84,15 +72,16 @@ __device__ __forceinline__ void wait_vm_and_barrier() {
 // NSTAGE-deep LDS ring filled by LDS-DMA: while K-step t is multiplied, the loads of steps t+1 .. t+NSTAGE-2 stay
 // in flight (counted vmcnt, one s_barrier per K-step).
 // MODE 0: fragments read per 32-deep sub-step;  MODE 6: sub-step 1's fragment reads issued under sub-step 0's MFMAs.
-// (Measured and dropped: mid-step DMA issue, reads-first, phase-staggered wave groups, BK = 32 rings.)
-// (Register staging — global_load_dwordx4 -> VGPR -> ds_write_b128 — measured the same as LDS-DMA and was dropped.)
+// (Measured and dropped, DESIGN.md §6: mid-step DMA issue, reads-first, phase-staggered wave groups, BK = 32 rings.)
+// (Register staging — global_load_dwordx4 -> VGPR -> ds_write_b128 — measured the same as LDS-DMA and was dropped;
+// buffer_load ... lds with the hardware range check was 15-25 % slower.  DESIGN.md §6.)
 // TAG only changes the kernel's symbol name: TAG 1 is the instantiation bench.py requests (TDN_TAG_DOMINANT) for the
 // launches of the heaviest shape of the net (3x3, 256 -> 256 at M >= 100000: neck.fpn_convs.0 forward and its dgrad)
 // that it brackets with HIP events, so that rocprofv3 --stats of the same command reports exactly those launches on a
-// line of their own, directly comparable with bench.py's figure.  TAG 2: cycle-stamp tracing builds.
+// line of their own, directly comparable with bench.py's figure.
 // KG > 1: in-workgroup split-K.  The workgroup holds KG groups of WM x WN waves; group g owns its own LDS ring and
 // multiplies K-steps g, g+KG, g+2KG, ... of the SAME output tile; the KG partial accumulators are summed through LDS
-// in a fixed order and the epilogue is shared out over the groups.  Reason (scripts/trace_gemm.py): one
+// in a fixed order and the epilogue is shared out over the groups.  Reason (cycle stamps): one
 // wave sustains only ~4 B/clk of LDS-DMA however many loads it keeps in flight, a CU needs ~16 loading waves to reach
 // its ~40 B/clk L2->LDS rate, and the small-M layers (layer3/4, FPN top levels) have too few output tiles to put
 // four 4-wave workgroups on every CU — so the extra waves are recruited along K instead.
@@ -112,14 +101,12 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
   static_assert(A_IT >= 1 && B_IT >= 1 && FM >= 1 && FN >= 1, "tile too small for this wave layout");
   static_assert(BM % (RPI * NW) == 0 && BN % (RPI * NW) == 0, "loader does not tile evenly");
   static_assert(NSTAGE >= 2 && LOADS * (NSTAGE - 2) < 64, "vmcnt immediate out of range");
-  static_assert(KG == 1 || (MODE == 0 || MODE == 6 || MODE == 9 || MODE == 10 || MODE == 11),
-                "split-K groups: production schedules only");
   static_assert(KG == 1 || BM * BN * 4 <= NSTAGE * STAGE, "partial sums must fit the group's LDS ring");
   constexpr bool EARLY_EPI = FN * FM <= 8;   // small tiles: fetch scale/shift before the K loop (registers to spare)
   // WIDE: the MFMA rows of channel-fragment i are weight rows  q*4FN + 4i + e  (q = row>>2, e = row&3) of the wave's
   // channel block instead of 16i + row, so a lane's FN fragments of one pixel are 4FN CONSECUTIVE channels: the
   // epilogue then moves 8FN contiguous bytes per lane (scale/shift, residual, ReLU mask, store) instead of FN
-  // scattered 8-byte pieces — the store tail of a 192x256 tile was 11 % of the kernel (scripts/trace_gemm.py).
+  // scattered 8-byte pieces — the store tail of a 192x256 tile was 11 % of the kernel (cycle stamps).
   // The weight tile gets its own XOR swizzle (swz_w) so that this row pattern still reads LDS conflict-free.
   constexpr bool WIDE = (BK >= 64) && (FN == 2 || FN == 4);
   constexpr int CPL = 4 * FN;                // channels per lane and pixel
@@ -150,17 +137,12 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
 #pragma unroll
   for (int i = 0; i < 9; ++i) tapv = (lane == i) ? taps_s[i] : tapv;
 
-  TDN_TRACE(0);
   const int bid = blockIdx.x;
   const int tile = (bid & 7) * (p.nwg_pad >> 3) + (bid >> 3);
   const int tile_m = fast_div(tile, p.tn_mul, p.tn_shr), tile_n = tile - tile_m * p.tiles_n;
   const int m0 = tile_m * BM;
   if (m0 >= cM) return;
   const int n0 = tile_n * BN;
-  if constexpr (TAG == 2) {   // stamp 31: the first kernel-argument values have arrived (tile index known)
-    asm volatile("" ::"s"(n0), "s"(m0));
-    TDN_TRACE(31);
-  }
 
   // ---- loader thread constants ----
   const int lrow = lane / CH, lchunk = lane % CH;
@@ -253,80 +235,6 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
     }
   };
 
-#ifdef TDN_TRACE_BUILD   // alternate load paths of the ablation builds (libtdn_trace.so)
-  // ABLATION (MODE 10, timing only): the same K-step fetched with buffer_load_dwordx4 ... offen lds — a descriptor
-  // per operand whose base carries the wave-uniform part (tap displacement, channel chunk), a 32-bit per-lane offset,
-  // and the hardware range check instead of the zero page for out-of-image taps
-  unsigned a_off32[A_IT];
-#pragma unroll
-  for (int it = 0; it < A_IT; ++it)
-    a_off32[it] = a_valid[it] ? (unsigned)(a_base[it] - (const char*)p.in) : 0x80000000u;
-  auto stage_load_buf = [&](int s) {
-    char* sA = smem + s * STAGE + wave * (RPI * ROWB);
-    char* sB = sA + A_BYTES;
-    const bool live = ld_issued < T;
-    const char* a_u = (const char*)p.in;
-    const char* wt_u = (const char*)p.wt;
-    unsigned bit = 0;
-    if (live) {
-      ld_issued += KG;
-      const int tp = __builtin_amdgcn_readlane(tapv, ld_tap);
-      const int dh = (tp & 0xff) - 64, dw = ((tp >> 8) & 0xff) - 64, widx = tp >> 16;
-      a_u += ((int64_t)(dh * p.Win + dw) * p.Cpix + (ld_kc + in_kc0) * BK) * 2;
-      wt_u += ((int64_t)widx * p.Ktap + ld_kc * BK) * 2;
-      bit = 1u << ld_tap;
-#pragma unroll
-      for (int i = 0; i < KG; ++i) advance_k();
-    }
-#if defined(__HIP_DEVICE_COMPILE__)   // the buffer builtins exist for the device target only
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)a_u, 0, live ? 0x7fffffff : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)wt_u, 0, live ? 0x7fffffff : 0, 0x00020000);
-#pragma unroll
-    for (int it = 0; it < A_IT; ++it) {
-      const unsigned off = (a_valid[it] & bit) ? a_off32[it] : 0x80000000u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (TDN_LDS void*)(sA + it * (RPI * NW * ROWB)), 16, off, 0, 0, 0);
-    }
-#pragma unroll
-    for (int it = 0; it < B_IT; ++it)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (TDN_LDS void*)(sB + it * (RPI * NW * ROWB)), 16, b_off[it], 0, 0, 0);
-#else
-    (void)sA; (void)sB; (void)a_u; (void)wt_u; (void)bit;
-#endif
-  };
-
-  // ABLATION (MODE 9, timing only): the same K-step fetched with plain global_load_dwordx4 into registers and written
-  // to LDS with ds_write_b128 — every load of the step in flight at once, no LDS-DMA
-  auto stage_load_regs = [&](int s) {
-    char* sA = smem + s * STAGE + wave * (RPI * ROWB) + lane * 16;
-    char* sB = sA + A_BYTES;
-    bf16x8_t ra[A_IT], rb[B_IT];
-    const bool live = ld_issued < T;
-    int64_t uoff_a = 0;
-    const char* wt_u = (const char*)p.wt;
-    unsigned bit = 0;
-    if (live) {
-      ld_issued += KG;
-      const int tp = __builtin_amdgcn_readlane(tapv, ld_tap);
-      const int dh = (tp & 0xff) - 64, dw = ((tp >> 8) & 0xff) - 64, widx = tp >> 16;
-      uoff_a = ((int64_t)(dh * p.Win + dw) * p.Cpix + (ld_kc + in_kc0) * BK) * 2;
-      wt_u = (const char*)p.wt + ((int64_t)widx * p.Ktap + ld_kc * BK) * 2;
-      bit = 1u << ld_tap;
-#pragma unroll
-      for (int i = 0; i < KG; ++i) advance_k();
-    }
-#pragma unroll
-    for (int it = 0; it < A_IT; ++it)
-      ra[it] = *(const bf16x8_t*)((live && (a_valid[it] & bit)) ? a_base[it] + uoff_a : zero_src);
-#pragma unroll
-    for (int it = 0; it < B_IT; ++it) rb[it] = *(const bf16x8_t*)(live ? wt_u + b_off[it] : zero_src);
-#pragma unroll
-    for (int it = 0; it < A_IT; ++it) *(TDN_LDS bf16x8_t*)(TDN_LDS char*)(sA + it * (RPI * NW * ROWB)) = ra[it];
-#pragma unroll
-    for (int it = 0; it < B_IT; ++it) *(TDN_LDS bf16x8_t*)(TDN_LDS char*)(sB + it * (RPI * NW * ROWB)) = rb[it];
-  };
-
-#endif
-
   // ---- fragment reader constants ----
   const int wm = wave / WN, wn = wave % WN;
   const int fr = lane & 15, fq = lane >> 4;
@@ -379,7 +287,7 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
   // of behind the K loop (they are older than every LDS-DMA too).  Same values, same arithmetic order.
   // Only where the 16 extra registers cost no occupancy: the 64x64 4-wave tile (80 -> 96); the 128x128 8-wave tile would
   // cross 128 registers (two workgroups per CU -> one).
-  constexpr bool PRE_EPI = EARLY_EPI && FN * FM <= 4 && WIDE && OWN_BY_J && KG == 1 && TAG != 2;
+  constexpr bool PRE_EPI = EARLY_EPI && FN * FM <= 4 && WIDE && OWN_BY_J && KG == 1;
   bf16x8_t pre_add[PRE_EPI ? FM : 1][PRE_EPI ? FN / 2 : 1], pre_msk[PRE_EPI ? FM : 1][PRE_EPI ? FN / 2 : 1];
   const bool pre_have_add = PRE_EPI && p.addend_mode == TDN_ADD_SAME;
   const bool pre_have_msk = PRE_EPI && p.mask != nullptr;
@@ -405,86 +313,17 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
   }
 
   if (Tg > 0) {
-    TDN_TRACE(1);
 #pragma unroll
     for (int s = 0; s < NSTAGE - 1; ++s) stage_load(s);
-    TDN_TRACE(2);
     int slot = 0, fill = NSTAGE - 1;
     for (int t = 0; t < Tg; ++t) {
       wait_vm_and_barrier<LOADS * (NSTAGE - 2)>();   // K-step t has landed for every wave; slot (t-1) is free
-      if (t < 24) TDN_TRACE(3 + t);
       const char* sA = smem + slot * STAGE + (wm * WTM) * ROWB;
       const char* sB = smem + slot * STAGE + A_BYTES + (wn * WTN) * ROWB;
       if constexpr (MODE == 0) {
         stage_load(fill);
 #pragma unroll
         for (int kk = 0; kk < KSUB; ++kk) mfma_substep(sA, sB, kk);
-#ifdef TDN_TRACE_BUILD
-      } else if constexpr (MODE == 3) {   // ABLATION (timing only, wrong results): no loads in the K loop
-#pragma unroll
-        for (int kk = 0; kk < KSUB; ++kk) mfma_substep(sA, sB, kk);
-      } else if constexpr (MODE == 4) {   // ABLATION (timing only, wrong results): loads only, no LDS reads / MFMA
-        stage_load(fill);
-      } else if constexpr (MODE == 11) {
-        // MODE 6 with the two waves of every SIMD out of phase: waves with wm == 0 issue the next K-step's LDS-DMA
-        // before their MFMAs, the others between their two MFMA sub-steps — while one wave of a SIMD is held up
-        // issuing DMA pieces (~60-100 cycles each) its partner feeds the matrix pipe
-        static_assert(KSUB == 2 && WM == 2, "staggered DMA issue: BK = 64, two wave rows");
-        bf16x8_t wf[2][FN], xf[2][FM];
-#pragma unroll
-        for (int i = 0; i < FN; ++i) wf[0][i] = lds_read_b128(sB + i * W_STEP + rdw_off[0]);
-#pragma unroll
-        for (int j = 0; j < FM; ++j) xf[0][j] = lds_read_b128(sA + j * 16 * ROWB + rd_off[0]);
-        if (wm == 0) stage_load(fill);
-#pragma unroll
-        for (int i = 0; i < FN; ++i) wf[1][i] = lds_read_b128(sB + i * W_STEP + rdw_off[1]);
-#pragma unroll
-        for (int j = 0; j < FM; ++j) xf[1][j] = lds_read_b128(sA + j * 16 * ROWB + rd_off[1]);
-#pragma unroll
-        for (int i = 0; i < FN; ++i)
-#pragma unroll
-          for (int j = 0; j < FM; ++j) acc[i][j] = mfma16<F16>(wf[0][i], xf[0][j], acc[i][j]);
-        __builtin_amdgcn_sched_barrier(0);
-        if (wm != 0) stage_load(fill);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < FN; ++i)
-#pragma unroll
-          for (int j = 0; j < FM; ++j) acc[i][j] = mfma16<F16>(wf[1][i], xf[1][j], acc[i][j]);
-      } else if constexpr (MODE == 9) {   // ABLATION: loads only, through registers instead of LDS-DMA
-        stage_load_regs(fill);
-      } else if constexpr (MODE == 10) {  // ABLATION: loads only, buffer_load ... lds
-        stage_load_buf(fill);
-      } else if constexpr (MODE == 7) {   // ABLATION: MFMA only (fragments never re-read: pure matrix-pipe rate)
-        bf16x8_t wf[FN], xf[FM];
-#pragma unroll
-        for (int i = 0; i < FN; ++i) wf[i] = lds_read_b128(sB + i * W_STEP + rdw_off[0]);
-#pragma unroll
-        for (int j = 0; j < FM; ++j) xf[j] = lds_read_b128(sA + j * 16 * ROWB + rd_off[0]);
-        if (t == 0) {
-          for (int rep = 0; rep < T * KSUB; ++rep) {
-#pragma unroll
-            for (int i = 0; i < FN; ++i)
-#pragma unroll
-              for (int j = 0; j < FM; ++j)
-                acc[i][j] = mfma16<F16>(wf[i], xf[j], acc[i][j]);
-          }
-        }
-      } else if constexpr (MODE == 8) {   // ABLATION: LDS fragment reads only (kept live), no MFMA, no loads
-#pragma unroll
-        for (int kk = 0; kk < KSUB; ++kk) {
-#pragma unroll
-          for (int i = 0; i < FN; ++i) {
-            bf16x8_t v = lds_read_b128(sB + i * W_STEP + rdw_off[kk]);
-            asm volatile("" ::"v"(v));
-          }
-#pragma unroll
-          for (int j = 0; j < FM; ++j) {
-            bf16x8_t v = lds_read_b128(sA + j * 16 * ROWB + rd_off[kk]);
-            asm volatile("" ::"v"(v));
-          }
-        }
-#endif
       } else if constexpr (MODE == 6) {
         // software-pipelined fragments: sub-step 1's LDS reads are issued between sub-step 0's MFMAs (second
         // register set), so only ONE LDS latency per K-step is exposed; the interleave is pinned with
@@ -523,7 +362,6 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
     }
     // drain the dummy tail loads before the LDS ring / registers are reused
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    TDN_TRACE(27);
   }
 
   // ---- split-K groups: exchange the partial accumulators through LDS (the rings are idle now) ----
@@ -696,18 +534,6 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void conv_gemm_kernel(const Gemm
       }
     }
   }
-  if constexpr (TAG == 2) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    TDN_TRACE(28);
-    if (p.trace && tid == 0) {
-      unsigned hwid;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-      unsigned xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      p.trace[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 + 29] = ((unsigned long long)xcc << 32) | hwid;
-      p.trace[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 + 30] = (unsigned long long)T;
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -718,99 +544,32 @@ static inline void class_divisors(GemmClass& c) {
   fast_div_init((unsigned)c.Wa, &c.mul_w, &c.shr_w);
 }
 
-// Tile configurations, one row per tile: X(id, BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, set).
-// LDS = KG * NSTAGE * (BM + BN) * BK * 2 bytes.  set P: production tile — the set choose_cfg picks from — built into
-// both libraries and for both element types (libtdn.so holds these, the TAG-1 twin of 3 and the stem's 128x64x32);
-// set T (alternates of the round-1/2 sweeps, timing-only ablation MODEs, TAG-2 cycle-stamp builds): bf16 only and
-// only in libtdn_trace.so (`make TRACE=1`, loaded by the scripts with TDN_LIB=libtdn_trace.so).  One source, one ISA.
-// kCfgs[] (the planner's and tdn_conv2d_plan's view) and the switches of dispatch_gemm (the instantiations) are both
-// generated from this list; the ids are the row numbers that scripts/, profiles/ and the tests use.
+// Tile configurations, one row per tile: X(id, BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG).
+// LDS = KG * NSTAGE * (BM + BN) * BK * 2 bytes.  These seven are the set choose_cfg picks from, built for both element
+// types; the library also holds the TAG-1 twin of 3 and the stem's 128x64x32.  kCfgs[] (the planner's and
+// tdn_conv2d_plan's view) and the switches of dispatch_gemm (the instantiations) are both generated from this list.
+// The ids are names, not row numbers: the tests, DESIGN.md and every recorded profile use them, and the gaps are the
+// alternate tiles, timing-only ablations and cycle-stamp builds that were measured and dropped.
 // MODE 0: LDS-DMA of the next K-step right after the barrier, fragments read per sub-step; MODE 6: fragment reads
-// software-pipelined under the MFMAs; MODE 3/4/7/8: timing-only ablations (wrong results); TAG 2: cycle-stamp tracing
-// build (tdn_debug_trace, scripts/trace_gemm.py).
+// software-pipelined under the MFMAs.
 #define TDN_GEMM_CFGS(X) \
-  X(0, 64, 64, 64, 2, 2, 2, 0, 0, 1, P)             /* 32 KB, 256 thr: Cout = 64 layers, tiny grids */                                    \
-  X(1, 64, 128, 64, 2, 2, 2, 6, 0, 1, P)            /* 48 KB, 256 thr: mid-size layers */                                                 \
-  X(2, 128, 128, 64, 2, 2, 2, 6, 0, 1, P)           /* 64 KB, 256 thr: large-M, Cout = 128 */                                             \
-  X(3, 192, 256, 64, 2, 4, 2, 6, 0, 1, P)           /* 112 KB, 512 thr: large-M, Cout % 256 == 0 (fewest L2->LDS bytes per flop) */       \
-  X(4, 64, 128, 64, 2, 2, 2, 0, 0, 1, T)            /* alternates kept for scripts/conv_bench.py sweeps */                                \
-  X(5, 64, 128, 64, 2, 2, 3, 0, 0, 1, T)                                                                                                  \
-  X(6, 64, 64, 64, 2, 2, 4, 0, 0, 1, T)                                                                                                   \
-  X(7, 128, 128, 64, 2, 2, 2, 0, 0, 1, T)                                                                                                 \
-  X(8, 128, 64, 64, 2, 2, 2, 0, 0, 1, T)                                                                                                  \
-  X(9, 64, 256, 64, 2, 2, 2, 0, 0, 1, T)                                                                                                  \
-  X(10, 128, 256, 64, 2, 4, 2, 0, 0, 1, T)                                                                                                \
-  X(11, 256, 128, 64, 4, 2, 3, 6, 0, 1, T)                                                                                                \
-  X(12, 192, 256, 64, 2, 4, 2, 3, 0, 1, T)          /* ablation: no loads in the K loop */                                                \
-  X(13, 192, 256, 64, 2, 4, 2, 4, 0, 1, T)          /* ablation: loads only */                                                            \
-  X(14, 192, 256, 64, 2, 4, 2, 7, 0, 1, T)          /* ablation: MFMA only */                                                             \
-  X(15, 192, 256, 64, 2, 4, 2, 8, 0, 1, T)          /* ablation: LDS fragment reads only */                                               \
-  X(16, 64, 64, 64, 2, 2, 2, 0, 2, 1, T)            /* trace builds of 0, 1, 6, 3 */                                                      \
-  X(17, 64, 128, 64, 2, 2, 2, 6, 2, 1, T)                                                                                                 \
-  X(18, 64, 64, 64, 2, 2, 4, 0, 2, 1, T)                                                                                                  \
-  X(19, 192, 256, 64, 2, 4, 2, 6, 2, 1, T)                                                                                                \
-  X(20, 64, 64, 64, 2, 2, 2, 4, 2, 1, T)            /* traced ablations of the small tile: loads only (2- and 4-deep ring) */             \
-  X(21, 64, 64, 64, 2, 2, 4, 4, 2, 1, T)                                                                                                  \
-  X(22, 64, 64, 64, 2, 2, 2, 3, 2, 1, T)            /* no loads in the K loop */                                                          \
-  X(23, 64, 64, 64, 2, 2, 4, 3, 2, 1, T)                                                                                                  \
-  X(24, 64, 64, 64, 2, 2, 2, 0, 0, 4, T)            /* in-workgroup split-K: 4 groups x 4 waves, 128 KB */                                \
-  X(25, 64, 64, 64, 2, 2, 2, 0, 0, 2, P)            /* 2 groups x 4 waves, 64 KB */                                                       \
-  X(26, 64, 128, 64, 2, 2, 2, 6, 0, 2, T)           /* 2 groups x 4 waves, 96 KB */                                                       \
-  X(27, 64, 128, 64, 2, 2, 2, 0, 0, 2, T)                                                                                                 \
-  X(28, 128, 128, 64, 2, 2, 2, 6, 0, 2, T)          /* 2 groups x 4 waves, 128 KB */                                                      \
-  X(29, 64, 64, 64, 2, 2, 2, 0, 2, 4, T)            /* trace build of 24 */                                                               \
-  X(30, 64, 64, 64, 2, 2, 2, 6, 0, 4, T)                                                                                                  \
-  X(31, 192, 256, 64, 2, 4, 2, 4, 2, 1, T)          /* traced loads-only: 8 waves */                                                      \
-  X(32, 256, 256, 64, 4, 4, 2, 4, 2, 1, T)          /* traced loads-only: 16 waves */                                                     \
-  X(33, 256, 256, 64, 4, 4, 2, 0, 2, 1, T)          /* traced full kernel, 16 waves, MODE 0 */                                            \
-  X(34, 256, 256, 64, 4, 4, 2, 6, 2, 1, T)          /* traced full kernel, 16 waves, MODE 6 */                                            \
-  X(35, 128, 256, 64, 2, 8, 2, 4, 2, 1, T)          /* traced loads-only: 16 waves, 96 KB */                                              \
-  X(36, 128, 256, 64, 2, 8, 2, 6, 2, 1, T)          /* traced full, 16 waves */                                                           \
-  X(37, 64, 64, 64, 2, 2, 2, 9, 2, 1, T)            /* traced loads-only through registers (vs 20: LDS-DMA) */                            \
-  X(38, 64, 128, 64, 2, 2, 2, 9, 2, 1, T)                                                                                                 \
-  X(39, 64, 128, 64, 2, 2, 2, 4, 2, 1, T)           /* traced loads-only LDS-DMA, 64x128 */                                               \
-  X(40, 192, 256, 64, 2, 4, 2, 9, 2, 1, T)          /* traced loads-only through registers, big tile (vs 31) */                           \
-  X(41, 64, 128, 64, 2, 4, 2, 6, 2, 1, T)           /* traced 8-wave small tiles */                                                       \
-  X(42, 64, 64, 64, 2, 4, 2, 0, 2, 1, T)                                                                                                  \
-  X(43, 128, 128, 64, 2, 4, 2, 6, 2, 1, T)                                                                                                \
-  X(44, 64, 128, 64, 2, 4, 2, 6, 0, 1, T)           /* the same, untraced */                                                              \
-  X(45, 64, 64, 64, 2, 4, 2, 0, 0, 1, T)                                                                                                  \
-  X(46, 128, 128, 64, 2, 4, 2, 6, 0, 1, P)          /* production: 8 waves, 64 KB — mid-size layers with >= 128 such tiles */             \
-  X(47, 64, 64, 64, 2, 2, 2, 10, 2, 1, T)           /* traced loads-only, buffer_load ... lds (vs 20) */                                  \
-  X(48, 64, 64, 64, 2, 2, 4, 10, 2, 1, T)           /* (vs 21) */                                                                         \
-  X(49, 192, 256, 64, 2, 4, 2, 10, 2, 1, T)         /* (vs 31) */                                                                         \
-  X(50, 64, 64, 128, 2, 2, 2, 0, 0, 1, P)           /* BK = 128: twice the work per ~1300-cycle K-step */                                 \
-  X(51, 64, 128, 128, 2, 2, 2, 0, 0, 1, T)                                                                                                \
-  X(52, 128, 128, 128, 2, 4, 2, 0, 0, 1, T)                                                                                               \
-  X(53, 64, 64, 128, 2, 2, 2, 0, 2, 1, T)           /* traced 50 */                                                                       \
-  X(54, 64, 128, 128, 2, 4, 2, 0, 0, 1, T)          /* 8 waves */                                                                         \
-  X(55, 192, 256, 64, 2, 4, 2, 11, 0, 1, T)         /* staggered DMA issue (vs 3): K-step 2700 -> 2430 cycles traced, no gain in-step */  \
-  X(56, 192, 256, 64, 2, 4, 2, 11, 2, 1, T)         /* traced */                                                                          \
-  X(57, 128, 128, 64, 2, 4, 2, 11, 0, 1, T)         /* (vs 46) */                                                                         \
-  X(58, 256, 64, 64, 4, 2, 2, 6, 0, 1, T)           /* tall tiles for Cout = 64 layers: the 8 KB weight tile shared by 256 pixels */      \
-  X(59, 192, 64, 64, 2, 2, 2, 6, 0, 1, T)                                                                                                 \
-  X(60, 128, 64, 64, 2, 2, 2, 6, 0, 1, T)                                                                                                 \
-  X(61, 256, 64, 64, 4, 2, 3, 6, 0, 1, T)                                                                                                 \
-  X(62, 128, 64, 64, 2, 2, 3, 6, 0, 1, T)           
-struct GemmCfg { int bm, bn, bk, wm, wn, nstage, mode, tag, kg; bool prod; };
-#define TDN_CFG_PROD_P true
-#define TDN_CFG_PROD_T false
-#define TDN_CFG_ROW(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg, set) {bm, bn, bk, wm, wn, nstage, mode, tag, kg, TDN_CFG_PROD_##set},
+  X(0, 64, 64, 64, 2, 2, 2, 0, 0, 1)     /* 32 KB, 256 thr: Cout = 64 layers, tiny grids */                                \
+  X(1, 64, 128, 64, 2, 2, 2, 6, 0, 1)    /* 48 KB, 256 thr: mid-size layers */                                             \
+  X(2, 128, 128, 64, 2, 2, 2, 6, 0, 1)   /* 64 KB, 256 thr: large-M, Cout = 128 */                                         \
+  X(3, 192, 256, 64, 2, 4, 2, 6, 0, 1)   /* 112 KB, 512 thr: large-M, Cout % 256 == 0 (fewest L2->LDS bytes per flop) */   \
+  X(25, 64, 64, 64, 2, 2, 2, 0, 0, 2)    /* in-workgroup split-K: 2 groups x 4 waves, 64 KB */                             \
+  X(46, 128, 128, 64, 2, 4, 2, 6, 0, 1)  /* 8 waves, 64 KB: mid-size layers with >= 128 such tiles */                      \
+  X(50, 64, 64, 128, 2, 2, 2, 0, 0, 1)   /* BK = 128: twice the work per ~1300-cycle K-step */
+struct GemmCfg { int id, bm, bn, bk, wm, wn, nstage, mode, tag, kg; };
+#define TDN_CFG_ROW(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg) {id, bm, bn, bk, wm, wn, nstage, mode, tag, kg},
 static const GemmCfg kCfgs[] = {TDN_GEMM_CFGS(TDN_CFG_ROW)};
-#define TDN_CFG_ID(id, ...) id,
-static constexpr int kCfgIds[] = {TDN_GEMM_CFGS(TDN_CFG_ID)};
-static const int kNumCfgs = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
-constexpr bool cfg_ids_are_row_numbers() {
-  for (int i = 0; i < (int)(sizeof(kCfgIds) / sizeof(kCfgIds[0])); ++i)
-    if (kCfgIds[i] != i) return false;
-  return true;
+
+// the row named `id`, or nullptr
+static const GemmCfg* find_cfg(int id) {
+  for (const GemmCfg& t : kCfgs)
+    if (t.id == id) return &t;
+  return nullptr;
 }
-static_assert(cfg_ids_are_row_numbers(), "TDN_GEMM_CFGS: the id column must count 0, 1, 2, ...");
-#ifdef TDN_TRACE_BUILD
-static const bool kTraceBuild = true;
-#else
-static const bool kTraceBuild = false;
-#endif
 
 // a forced generic tile (tests, sweeps) is in effect: it also keeps the conv away from the halo kernel.  An empty
 // value counts and reads as config 0.
@@ -819,25 +578,9 @@ static bool gemm_cfg_forced() { return tdn_knob_present("TDN_GEMM_CFG") != nullp
 static int choose_cfg(int maxM, int ngemm, int kgemm, int grouped = 0, int ktap = 64) {
   if (grouped) return 0;   // block-diagonal grouped conv: one 64-channel block per N tile
   if (gemm_cfg_forced()) {
-    const int id = tdn_knob_int("TDN_GEMM_CFG", 0);
-    if (id >= 0 && id < kNumCfgs && (kTraceBuild || kCfgs[id].prod) && ngemm % kCfgs[id].bn == 0 &&
-        ktap % kCfgs[id].bk == 0)
-      return id;
+    const GemmCfg* t = find_cfg(tdn_knob_int("TDN_GEMM_CFG", 0));
+    if (t && ngemm % t->bn == 0 && ktap % t->bk == 0) return t->id;
   }
-#ifdef TDN_TRACE_BUILD
-  // experiments (libtdn_trace.so): TDN_CFG_RULE="M:N:K:cfg,M:N:K:cfg,..." picks a configuration for exactly that GEMM
-  if (const char* rule = tdn_knob_present("TDN_CFG_RULE")) {
-    const char* q = rule;
-    while (*q) {
-      int m_ = 0, n_ = 0, k_ = 0, id = -1;
-      if (sscanf(q, "%d:%d:%d:%d", &m_, &n_, &k_, &id) == 4 && m_ == maxM && n_ == ngemm && k_ == kgemm && id >= 0 &&
-          id < kNumCfgs && ngemm % kCfgs[id].bn == 0 && ktap % kCfgs[id].bk == 0)
-        return id;
-      while (*q && *q != ',') ++q;
-      if (*q == ',') ++q;
-    }
-  }
-#endif
   // sweep-only overrides of the thresholds below; a set but empty value reads as 0
   auto sweep = [](const char* name, int dflt) { return tdn_knob_present(name) ? tdn_knob_int(name, 0) : dflt; };
   // Measured on MI355X over the R50-FPN shapes (scripts/conv_bench.py; profiles/convbench_*.log): several small
@@ -861,7 +604,7 @@ static int choose_cfg(int maxM, int ngemm, int kgemm, int grouped = 0, int ktap 
   if (kgemm == ktap && (long)ceil_div(maxM, 64) * (ngemm / 64) <= bk128_tiles && kgemm >= 1024 && ktap % 128 == 0)
     return 50;
   if (ngemm % 128 == 0) {
-    // A K-step costs ~1300-1500 cycles of load latency whatever the tile (scripts/trace_gemm.py), so the 128x128
+    // A K-step costs ~1300-1500 cycles of load latency whatever the tile (cycle stamps), so the 128x128
     // tile does 2-4x the work per step of the 64-wide ones; with 8 waves (wave tile 64x32) two of them fit a CU.
     // Alone on the GPU it wins from ~128 tiles up, but inside the step (side-stream wgrad kernels beside the dgrad
     // chain) the 132-tile layers of layer3 (M = 8400, N = 256) run faster as 528 64x64 workgroups: whole-step A/B on
@@ -876,21 +619,10 @@ static int choose_cfg(int maxM, int ngemm, int kgemm, int grouped = 0, int ktap 
   return 0;
 }
 
-static unsigned long long* g_trace_buf = nullptr;
-static long long g_trace_bytes = 0;
-
-// Diagnostics: TAG-2 kernel instantiations (TDN_GEMM_CFG >= 80) write 32 x 8-byte cycle stamps per workgroup here.
-extern "C" int tdn_debug_trace(void* buf, long long bytes) {
-  g_trace_buf = (unsigned long long*)buf;
-  g_trace_bytes = bytes;
-  return 0;
-}
-
 template <int BM, int BN, int BK, int WM, int WN, int NSTAGE, int MODE = 0, int TAG = 0, int KG = 1, bool F16 = false>
 static int launch_gemm(GemmParams& p, int maxM, hipStream_t stream) {
   p.tiles_n = p.Cout / BN;
   fast_div_init((unsigned)p.tiles_n, &p.tn_mul, &p.tn_shr);
-  p.trace = nullptr;
   const int ntiles = ceil_div(maxM, BM) * p.tiles_n;
   p.nwg_pad = (ntiles + 7) & ~7;
   constexpr size_t lds = (size_t)KG * NSTAGE * (BM + BN) * BK * 2;
@@ -903,11 +635,6 @@ static int launch_gemm(GemmParams& p, int maxM, hipStream_t stream) {
         &nb, (const void*)conv_gemm_kernel<BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, F16>, WM * WN * KG * 64, lds);
     fprintf(stderr, "[tdn] conv_gemm<%d,%d,%d,%d,%d,%d,%d,%d,%d,%s>: %d B LDS, %d workgroups/CU\n", BM, BN, BK, WM,
             WN, NSTAGE, MODE, TAG, KG, F16 ? "f16" : "bf16", (int)lds, nb);
-  }
-  if (TAG == 2) {
-    TDN_CHECK(g_trace_buf && (long long)p.nwg_pad * p.ncls * 256 <= g_trace_bytes,
-              "trace config selected but tdn_debug_trace() buffer is missing or too small");
-    p.trace = g_trace_buf;
   }
   dim3 grid(p.nwg_pad, p.ncls, 1), block(WM * WN * KG * 64, 1, 1);
   TDN_LAUNCH((conv_gemm_kernel<BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, F16>), grid, block, lds, stream, p);
@@ -927,38 +654,24 @@ static int launch_cfg(GemmParams& p, int maxM, hipStream_t stream) {
   return launch_gemm<BM, BN, BK, WM, WN, NSTAGE, MODE, TAG, KG, F16>(p, maxM, stream);
 }
 
-// switch cases from TDN_GEMM_CFGS: set P rows (both element types, both libraries), then set T rows (bf16, and only
-// in the trace build: alternates, ablations and cycle-stamp builds).  P before T keeps the kernels in the order the
-// compiler has always emitted them, so the code object can be compared with an older build section by section.
-#define TDN_CFG_IF_P_P(...) __VA_ARGS__
-#define TDN_CFG_IF_P_T(...)
-#define TDN_CFG_IF_T_P(...)
-#ifdef TDN_TRACE_BUILD
-#define TDN_CFG_IF_T_T(...) __VA_ARGS__
-#else
-#define TDN_CFG_IF_T_T(...)
-#endif
+// switch cases from TDN_GEMM_CFGS, in table order: it is the order in which the compiler emits the kernels, so the
+// code object can be compared with an older build section by section
 #define TDN_CFG_CASE(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg) \
   case id: return launch_cfg<id, bm, bn, bk, wm, wn, nstage, mode, tag, kg, F16>(p, maxM, stream);
-#define TDN_CFG_CASE_P(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg, set) \
-  TDN_CFG_IF_P_##set(TDN_CFG_CASE(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg))
-#define TDN_CFG_CASE_T(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg, set) \
-  TDN_CFG_IF_T_##set(TDN_CFG_CASE(id, bm, bn, bk, wm, wn, nstage, mode, tag, kg))
 
 static int dispatch_gemm(GemmParams& p, int maxM, hipStream_t stream, int dtype) {
   if (maxM <= 0) return 0;
   const int id = choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap);
-  if (dtype == TDN_F16) {   // fp16 operands: the production tile set only
+  if (dtype == TDN_F16) {
     constexpr bool F16 = true;
     switch (id) {
-      TDN_GEMM_CFGS(TDN_CFG_CASE_P)
-      default: TDN_CHECK(false, "GEMM config %d (TDN_GEMM_CFG) has no TDN_F16 build", id); return -1;
+      TDN_GEMM_CFGS(TDN_CFG_CASE)
+      default: TDN_CHECK(false, "bad GEMM config id"); return -1;
     }
   }
   constexpr bool F16 = false;
   switch (id) {
-    TDN_GEMM_CFGS(TDN_CFG_CASE_P)
-    TDN_GEMM_CFGS(TDN_CFG_CASE_T)
+    TDN_GEMM_CFGS(TDN_CFG_CASE)
     default: TDN_CHECK(false, "bad GEMM config id"); return -1;
   }
 }
@@ -1119,7 +832,7 @@ extern "C" int tdn_conv2d_plan(int kind, int N, int H, int W, int Cin, int Cout,
   int maxM;
   if (kind == 0) { build_fwd(p, N, H, W, Cin, Cout, k, stride, pad); maxM = p.cls[0].M; }
   else maxM = build_dgrad(p, N, H, W, Cin, Cout, k, stride, pad);
-  const GemmCfg& t = kCfgs[choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap)];
+  const GemmCfg& t = *find_cfg(choose_cfg(maxM, p.Cout, p.cls[0].ntaps * p.Ktap, p.grouped, p.Ktap));
   int Mtot = 0, taps_tot = 0;
   for (int i = 0; i < p.ncls; ++i) { Mtot += p.cls[i].M; taps_tot += p.cls[i].ntaps; }
   o[0] = Mtot; o[1] = p.Cout; o[2] = p.cls[0].ntaps * p.Ktap; o[3] = t.bm; o[4] = t.bn; o[5] = t.bk;
