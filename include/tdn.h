@@ -827,6 +827,49 @@ int tdn_linear_dgrad(const void* g, int64_t ldg, const void* w_dgrad, const void
 int tdn_linear_wgrad(const void* x, int64_t ldx, const void* g, int64_t ldg, float* dw, float* dbias, float beta, int M,
                      int O, int K, int C, int splits, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- 2x2 stride-2 transposed convolution ------------------------------------------------------------------
+ * nn.ConvTranspose2d(Cin, Cout, 2, stride=2) as the mask head's upsampling layer uses it: 16-bit operands, fp32
+ * accumulation on the matrix cores, one rounding of the result.  The taps do not overlap:
+ *     y[r][2i+a][2j+b][o] = act(bias[o] + sum_c x[r][i][j][c] * W[c][o][a][b])
+ * i.e. one GEMM with M = R*H*W input pixels, K = Cin and N = 4*Cout columns n = (a*2+b)*Cout + o whose rows are
+ * scattered into (forward) or gathered from (dgrad, wgrad) the 2H x 2W map.  x is NHWC memory (R, H, W, Cin); y and its
+ * cotangent g are NHWC memory (R, 2H, 2W, Cout); all of them dense and 16-byte aligned.  weight (Cin, Cout, 2, 2) and
+ * bias (Cout) stay fp32.  Limits, checked on the host: Cin and Cout multiples of 64 in 64..65536, H >= 1, W >= 1,
+ * R >= 0 (R == 0 is legal: nothing is launched but wgrad's finalize), R*H*W < 2^29, R*2H*2W*Cout < 2^31 and
+ * R*H*W*Cin < 2^31.  kind: 0 forward, 1 dgrad, 2 wgrad.
+ *
+ * tdn_pack_deconv2x2_weight: w fp32 (Cin, Cout, 2, 2) with element strides (s_c, s_o, s_a, s_b) -> w_fwd [4*Cout][Cin],
+ *   row (a*2+b)*Cout + o, and, unless NULL, w_dgrad [Cin][4*Cout]; each value rounded once to `dtype`.  One launch.
+ * tdn_deconv2x2_fwd: y = act(x . w_fwd^T + bias) with the scatter in the epilogue; bias fp32 or NULL, act = ReLU if relu.
+ *   Every element of y is written exactly once, nothing else is written.  One launch.
+ * tdn_deconv2x2_dgrad: dx[r][i][j][c] = sum_{a,b,o} g[r][2i+a][2j+b][o] * W[c][o][a][b], rounded once to `dtype`.  The
+ *   reduction runs over 4*Cout in 64-element chunks, each read from the output pixel of its tap.  g is taken as it is: a
+ *   layer with a ReLU masks its cotangent first (tdn_linear_relu_bwd on the (R*2H*2W, Cout) matrix that y is in memory,
+ *   or the mask_src of the next layer's tdn_linear_dgrad).  One launch.
+ * tdn_deconv2x2_wgrad: dw[c][o][a][b] = beta * dw + sum_m x[m][c] * g[pix(m,a,b)][o] and dbias[o] = beta * dbias[o] + the
+ *   sum of g[.][o] over all R*2H*2W pixels, in fp32; dw contiguous in the parameter's own (Cin, Cout, 2, 2) layout;
+ *   dbias NULL: skipped.  beta == 0 never reads dw / dbias; R == 0 leaves beta * old.  The reduction over the pixels is
+ *   cut into `slices` runs of whole 64-pixel chunks (splits: 0 lets the library choose — as tdn_linear_wgrad does: up to
+ *   256 workgroups, at least 4 chunks per slice —, 1..ceil(M/64) forces a count; forward and dgrad are never cut and
+ *   take splits 0 or 1 in the queries).  Every workgroup stores its fp32 partial slab into the workspace with plain
+ *   stores; a finalize launch adds the slabs in slice order, the four taps' column sums in tap order, and writes dw and
+ *   dbias: no atomics, no counters, no memset, the same bits on every run.  Two launches (one if R == 0).
+ * tdn_deconv2x2_workspace_bytes: the workspace of that kind (forward / dgrad: 0; wgrad: slices * (4*Cout*Cin + 4*Cout)
+ *   floats, each region from a 256-byte boundary), 256-byte aligned; -1 on a refused shape.
+ * tdn_deconv2x2_plan (host only): out[0..15] = {BM, BN, BK, row tiles, column tiles, tiles, slices, chunks per slice,
+ *   chunks, workgroups of the GEMM launch, launches, 0, slab bytes low 31 bits, slab bytes >> 31, workspace bytes low 31
+ *   bits, workspace bytes >> 31}.  Rows x columns: forward M x 4*Cout, dgrad M x Cin, wgrad 4*Cout x Cin. */
+int tdn_pack_deconv2x2_weight(const float* w, int64_t s_c, int64_t s_o, int64_t s_a, int64_t s_b, int Cin, int Cout,
+                              void* w_fwd, void* w_dgrad, int dtype, void* stream);
+int64_t tdn_deconv2x2_workspace_bytes(int kind, int R, int H, int W, int Cin, int Cout, int splits);
+int tdn_deconv2x2_plan(int kind, int R, int H, int W, int Cin, int Cout, int splits, int32_t* out16);
+int tdn_deconv2x2_fwd(const void* x, const void* w_fwd, const float* bias, void* y, int R, int H, int W, int Cin,
+                      int Cout, int relu, int dtype, void* stream);
+int tdn_deconv2x2_dgrad(const void* g, const void* w_dgrad, void* dx, int R, int H, int W, int Cin, int Cout, int dtype,
+                        void* stream);
+int tdn_deconv2x2_wgrad(const void* x, const void* g, float* dw, float* dbias, float beta, int R, int H, int W, int Cin,
+                        int Cout, int splits, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

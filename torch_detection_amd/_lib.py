@@ -318,6 +318,12 @@ SIGNATURES = {
                          [c_void_p, c_i64, c_int, c_void_p]),
     "tdn_linear_wgrad": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_float] + [c_int] * 5 +
                          [c_void_p, c_i64, c_int, c_void_p]),
+    "tdn_pack_deconv2x2_weight": (c_int, [c_void_p] + [c_i64] * 4 + [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "tdn_deconv2x2_workspace_bytes": (c_i64, [c_int] * 7),
+    "tdn_deconv2x2_plan": (c_int, [c_int] * 7 + [ctypes.POINTER(ctypes.c_int32)]),
+    "tdn_deconv2x2_fwd": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
+    "tdn_deconv2x2_dgrad": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p]),
+    "tdn_deconv2x2_wgrad": (c_int, [c_void_p] * 4 + [c_float] + [c_int] * 6 + [c_void_p, c_i64, c_int, c_void_p]),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),

@@ -252,12 +252,14 @@ def invalidate_packed(*modules):
     the tensors' version counters (``p.data.copy_()``, ``p.data.mul_()``, kernels writing through raw pointers);
     ordinary in-place updates under ``torch.no_grad()`` (what optimizers do) are picked up automatically."""
     from .linear import forget               # imported here: linear.py imports this module
+    from .deconv import forget as forget_deconv
     for m in modules:
         for sub in m.modules():
             for u in sub.__dict__.get('_hip_units', {}).values():
                 u.key = None
         for p in m.parameters():
             forget(p)                        # packed copies made by a bare linear() call on this parameter
+            forget_deconv(p)                 # ... or by a bare conv_transpose2x2() call
 
 
 class StagedImages(object):
