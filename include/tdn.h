@@ -870,6 +870,54 @@ int tdn_deconv2x2_dgrad(const void* g, const void* w_dgrad, void* dx, int R, int
 int tdn_deconv2x2_wgrad(const void* x, const void* g, float* dw, float* dbias, float beta, int R, int H, int W, int Cin,
                         int Cout, int splits, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- dense head predictors over a pyramid -----------------------------------------------------------------
+ * The two 1x1 predictors of the RPN head (rpn_cls: A channels, rpn_reg: 4A channels; mmdetection-v1 RPNHead) on the
+ * hidden maps of ALL pyramid levels in one launch per product: 16-bit operands, fp32 accumulation on the matrix cores,
+ * one rounding of each result.  The weights are shared by the levels.  levels: HOST array of 1..TDN_PRED_MAX_LEVELS
+ * entries.  h is the level's hidden map, NHWC memory seen as a dense (rows, C) matrix, 16-byte aligned; cls and reg are
+ * dense (rows, A) and (rows, 4A) matrices of their own (2-byte aligned, nothing more): the outputs of the forward, the
+ * cotangents of dgrad and wgrad; dh (dgrad only) is the dense (rows, C) gradient of h, 16-byte aligned.  rows in
+ * 0..2^31-1 (row offsets are 64-bit); a level with rows == 0 is skipped and its pointers are not looked at.  C is a
+ * multiple of 64 in 64..512, A is in 1..12.  The stacked weight has O = 5A rows, the A cls rows first; Op = O rounded up to
+ * 16, Kp = O rounded up to 32.  kind: 0 forward, 1 dgrad, 2 wgrad.  With every rows == 0 nothing is launched but wgrad's
+ * finalize, which writes zeros.
+ *
+ * tdn_pack_pred_weight: w_cls fp32 (A, C) and w_reg fp32 (4A, C) with element strides (s_o, s_c) each -> w_fwd [Op][C]
+ *   and, unless NULL, w_dgrad [C][Kp]; each value rounded once to `dtype`, pad rows / columns zero.  One launch.
+ * tdn_pred_fwd:   cls_l[m][a] = sum_c h_l[m][c] * w_cls[a][c] + bias_cls[a], reg_l[m][j] likewise with w_reg, bias_reg
+ *   (fp32, not NULL).  Every element of cls_l and reg_l is written exactly once, nothing else is written.  One launch.
+ * tdn_pred_dgrad: dh_l[m][c] = h_l[m][c] > 0 ? sum_a cls_l[m][a] * w_cls[a][c] + sum_j reg_l[m][j] * w_reg[j][c] : 0; both
+ *   products are added in the fp32 accumulator, in the order of the stacked rows, and rounded once.  One launch.
+ * tdn_pred_wgrad: dw_cls (A, C), dw_reg (4A, C), dbias_cls (A), dbias_reg (4A), contiguous fp32, none NULL:
+ *   dw[o][c] = sum over all levels and rows of g_l[m][o] * h_l[m][c], dbias[o] = sum of g_l[m][o].  The rows are cut into
+ *   slices of slice_rows rows — ceil(total rows / 64) rounded up to whole 128-row steps, a function of the shapes alone
+ *   —, each level on its own, the slice list being the levels' slices in level order.  Every workgroup (slice x
+ *   64-channel tile) stores an fp32 partial slab into the workspace with plain stores; the finalize launch adds the slabs
+ *   in slice order: no atomics, no counters, no memset, the same bits on every run and on every device.
+ * tdn_pred_workspace_bytes: forward / dgrad 0; wgrad slices * (Op * C + Op) floats, each region from a 256-byte boundary;
+ *   256-byte aligned; -1 on a refused shape.  rows: HOST array of num_levels row counts.
+ * tdn_pred_plan (host only): out[0..15] = {rows per workgroup (forward / dgrad) = rows per wgrad step, workgroups of the
+ *   main launch, slices, rows per slice, launches, Op, Kp, channel tiles, LDS bytes, 0, 0, 0, slab bytes low 31 bits,
+ *   slab bytes >> 31, workspace bytes low 31 bits, workspace bytes >> 31}. */
+#define TDN_PRED_MAX_LEVELS 8
+typedef struct tdn_pred_level {
+  const void* h;
+  void* cls;
+  void* reg;
+  void* dh;
+  int64_t rows;
+} tdn_pred_level;
+int tdn_pack_pred_weight(const float* w_cls, int64_t c_so, int64_t c_sc, const float* w_reg, int64_t r_so, int64_t r_sc,
+                         int A, int C, void* w_fwd, void* w_dgrad, int dtype, void* stream);
+int64_t tdn_pred_workspace_bytes(int kind, const int64_t* rows, int num_levels, int C, int A);
+int tdn_pred_plan(int kind, const int64_t* rows, int num_levels, int C, int A, int32_t* out16);
+int tdn_pred_fwd(const tdn_pred_level* levels, int num_levels, const void* w_fwd, const float* bias_cls,
+                 const float* bias_reg, int C, int A, int dtype, void* stream);
+int tdn_pred_dgrad(const tdn_pred_level* levels, int num_levels, const void* w_dgrad, int C, int A, int dtype,
+                   void* stream);
+int tdn_pred_wgrad(const tdn_pred_level* levels, int num_levels, float* dw_cls, float* dbias_cls, float* dw_reg,
+                   float* dbias_reg, int C, int A, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

@@ -10,7 +10,8 @@ Drop-in surface (same names as the reference's ``models`` package): ``BACKBONES`
 ``multiclass_nms``, and the mask branch ``pack_polygons`` / ``mask_target`` / ``mask_head_loss`` /
 ``rois_from_detections`` / ``mask_head_masks``, the fused optimizer step ``SGD``, and the
 fully connected layers ``linear`` / ``BBoxHead`` between ``roi_align`` and the box losses, and the 2x2 stride-2 transposed
-conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask loss).  Everything computes through libtdn.so
+conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask loss, and ``RPNHead`` between ``FPN`` and
+``rpn_loss`` / ``rpn_proposals``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -38,6 +39,6 @@ from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_t
 from .optim import SGD  # noqa: F401
 from .linear import LinearFunction, linear  # noqa: F401
 from .deconv import ConvTranspose2x2Function, conv_transpose2x2  # noqa: F401
-from .heads import BBoxHead, FCNMaskHead  # noqa: F401
+from .heads import BBoxHead, FCNMaskHead, RPNHead  # noqa: F401
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)

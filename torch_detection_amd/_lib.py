@@ -27,6 +27,7 @@ TARGET_MAX_GT = 256
 TARGET_MAX_BOXES = 1 << 20
 TARGET_MAX_NUM = 8192
 LOSS_MAX_LEVELS = 8
+PRED_MAX_LEVELS = 8
 LOSS_MAX_CLASSES = 1024
 LOSS_MAX_ROWS = 1 << 20
 LOSS_MAX_AVG = 64
@@ -212,6 +213,14 @@ class SgdItem(ctypes.Structure):
 _SI = ctypes.POINTER(SgdItem)
 _I64P = ctypes.POINTER(c_i64)
 
+
+class PredLevel(ctypes.Structure):
+    """Mirror of ``tdn_pred_level`` (include/tdn.h): one pyramid level of the dense head predictors."""
+    _fields_ = [("h", c_void_p), ("cls", c_void_p), ("reg", c_void_p), ("dh", c_void_p), ("rows", c_i64)]
+
+
+_PL = ctypes.POINTER(PredLevel)
+
 # name -> (restype, argtypes); must list every symbol of include/tdn.h (tests/test_abi.py checks this)
 SIGNATURES = {
     "tdn_last_error": (ctypes.c_char_p, []),
@@ -324,6 +333,13 @@ SIGNATURES = {
     "tdn_deconv2x2_fwd": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
     "tdn_deconv2x2_dgrad": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p]),
     "tdn_deconv2x2_wgrad": (c_int, [c_void_p] * 4 + [c_float] + [c_int] * 6 + [c_void_p, c_i64, c_int, c_void_p]),
+    "tdn_pack_pred_weight": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p,
+                                     c_int, c_void_p]),
+    "tdn_pred_workspace_bytes": (c_i64, [c_int, _I64P, c_int, c_int, c_int]),
+    "tdn_pred_plan": (c_int, [c_int, _I64P, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32)]),
+    "tdn_pred_fwd": (c_int, [_PL, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "tdn_pred_dgrad": (c_int, [_PL, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "tdn_pred_wgrad": (c_int, [_PL, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p, c_i64, c_int, c_void_p]),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),

@@ -7,19 +7,27 @@ Every product runs through csrc/linear.hip; the whole head is one autograd node.
 ``FCNMaskHead`` — mmdetection v1's mask head: ``num_convs`` 3x3 ``ConvModule``s, the 2x2 stride-2
 transposed conv + ReLU (csrc/deconv.hip) and the 1x1 ``conv_logits``, run as a linear layer over the pixels
 (csrc/linear.hip) — between ``roi_align`` and ``mask_head_loss`` / ``mask_head_masks``.  The convs are the existing conv
-modules; the tail (upsampling + logits) is one autograd node."""
+modules; the tail (upsampling + logits) is one autograd node.
+
+``RPNHead`` — mmdetection v1's ``RPNHead``: the shared 3x3 ``rpn_conv`` + ReLU (the existing conv path,
+level by level) and the two 1x1 predictors ``rpn_cls`` / ``rpn_reg`` over the whole pyramid in one launch per product
+(csrc/dense_head.hip) — between ``FPN`` and ``rpn_loss`` / ``rpn_proposals``.  The whole head is one autograd node."""
 import torch
 import torch.nn as nn
 
-from . import deconv_ops, linear_ops, ops
+from . import dense_ops, deconv_ops, linear_ops, ops
+from . import functional as HF
+from .box import AnchorGenerator, anchor_pyramid, rpn_proposals
 from .deconv import DeconvUnit
 from .deconv import check_params as check_deconv_params
 from .functional import pick_dtype
 from .layers import ConvModule
 from .linear import LinearUnit, check_params, flatten_input
+from .losses import rpn_loss
 from .registry import HEADS
+from .target import anchor_target
 
-__all__ = ["BBoxHead", "BBoxHeadFunction", "FCNMaskHead", "MaskTailFunction"]
+__all__ = ["BBoxHead", "BBoxHeadFunction", "FCNMaskHead", "MaskTailFunction", "RPNHead", "RPNHeadFunction", "PredUnit"]
 
 
 class BBoxHeadFunction(torch.autograd.Function):
@@ -273,3 +281,209 @@ class FCNMaskHead(nn.Module):
             x = conv(x)
         return MaskTailFunction.apply(self, x, self.upsample.weight, self.upsample.bias, self.conv_logits.weight,
                                       self.conv_logits.bias)
+
+
+# ---- the RPN head -------------------------------------------------------------------------------------------------------
+class PredUnit(object):
+    """Packed 16-bit operands of the stacked predictor weight (``rpn_cls`` rows, then ``rpn_reg`` rows) for one compute
+    dtype, cached like ``LinearUnit`` / ``DeconvUnit``: under a version key (data pointers, ``_version``s, device); an
+    in-place update re-packs into the same buffers, ``invalidate_packed`` drops the key, and inside a graph capture the
+    pack is enqueued again when ``functional.REPACK_IN_CAPTURE`` is set."""
+
+    def __init__(self, w_cls, w_reg, dtype):
+        self.sources = (w_cls, w_reg)
+        self.dtype = dtype
+        self.key = None
+        self.w_fwd = self.w_dgrad = None
+        self._layout = None
+
+    def _version_key(self):
+        return (self.dtype,) + tuple((w.data_ptr(), w._version, w.device) for w in self.sources)
+
+    def refresh(self):
+        wc, wr = self.sources
+        if not wc.is_cuda:
+            raise RuntimeError('torch_detection_amd modules run on the MI355X HIP path only: move the module to '
+                               'a CUDA/HIP device (no CPU fallback)')
+        key = self._version_key()
+        capturing = HF.REPACK_IN_CAPTURE and torch.cuda.is_current_stream_capturing()
+        if key == self.key and not capturing:
+            return self
+        layout = (wc.device, self.dtype, tuple(wc.shape), tuple(wr.shape))
+        reuse = self.w_fwd is not None and layout == self._layout
+        self._layout = layout
+        with torch.no_grad():
+            self.w_fwd, self.w_dgrad = dense_ops.pack_pred_weight(
+                wc.detach(), wr.detach(), True, self.dtype, out=(self.w_fwd, self.w_dgrad) if reuse else None)
+        self.key = key
+        return self
+
+
+class RPNHeadFunction(torch.autograd.Function):
+    """``apply(head, n, feat_0 .. feat_{n-1}, w_conv, b_conv, w_cls, b_cls, w_reg, b_reg)`` ->
+    (cls_0 .. cls_{n-1}, reg_0 .. reg_{n-1}).
+
+    Forward: ``rpn_conv`` + ReLU level by level through the conv unit, then ONE ``pred_fwd`` over the pyramid.
+    Backward: ``pred_wgrad`` (two launches), then ONE ``pred_dgrad`` whose mask source is the hidden maps themselves —
+    the ReLU mask costs no launch —, then ``rpn_conv``'s weight gradients level by level on one shared ``WgradQueue``
+    flushed once, then its input gradients where an input needs one.  The shared ``rpn_conv`` weight and bias gradients
+    are the float32 sum of the per-level gradients in level order, finest (first) level first:
+    ``((g_0 + g_1) + g_2) + ...``."""
+
+    @staticmethod
+    def forward(ctx, head, n, *args):
+        feats, (w_conv, b_conv, w_cls, b_cls, w_reg, b_reg) = args[:n], args[n:]
+        dtype = HF.pick_dtype(head, feats)
+        unit = HF.prepare_unit(head, 'rpn_conv', head.rpn_conv, None, True, dtype)
+        if unit.sink is not None:
+            raise NotImplementedError("RPNHead: rpn_conv's per-level gradients cannot be written into a gradient bucket")
+        pred = head._pred_unit(dtype)
+        xs = [ops.to_nhwc_bf16(f, dtype) for f in feats]                  # zero-copy for channels_last 16-bit maps
+        hs = [HF.unit_fwd(unit, x).permute(0, 3, 1, 2) for x in xs]       # ReLU fused
+        cls, reg = dense_ops.pred_fwd(hs, pred.w_fwd, b_cls.detach(), b_reg.detach())
+        ctx.save_for_backward(*xs, *hs)
+        # (dtype, plain NCHW-contiguous?) of every input: its gradient comes back in the same dtype and layout
+        ctx.meta = (unit, pred, n, [(f.dtype, f.is_contiguous() and not f.permute(0, 2, 3, 1).is_contiguous())
+                                    for f in feats])
+        return tuple(cls) + tuple(reg)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        unit, pred, n, layouts = ctx.meta
+        xs, hs = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        dtype = hs[0].dtype
+        B, C = hs[0].shape[:2]
+        A = pred.sources[0].shape[0]
+        sizes = [tuple(h.shape[2:]) for h in hs]
+        zero = lambda g, ch, hw: torch.zeros((B, hw[0], hw[1], ch), dtype=dtype, device=hs[0].device).permute(0, 3, 1, 2) \
+            if g is None else g
+        g_cls = dense_ops.cotangents([zero(g, A, s) for g, s in zip(gs[:n], sizes)], "g_cls", dtype, B, A, sizes)
+        g_reg = dense_ops.cotangents([zero(g, 4 * A, s) for g, s in zip(gs[n:], sizes)], "g_reg", dtype, B, 4 * A, sizes)
+        dwc, dbc, dwr, dbr = dense_ops.pred_wgrad(hs, g_cls, g_reg)
+        dhs = [d.permute(0, 2, 3, 1) for d in dense_ops.pred_dgrad(g_cls, g_reg, pred.w_dgrad, hs)]   # masked by h > 0
+        dev = dhs[0].device
+        wq = HF.WgradQueue(dev)
+        per_level = [HF.unit_wgrad(unit, x, dh, queue=wq) for x, dh in zip(xs, dhs)]
+        wq.flush()
+        dxs = []
+        for l, (x, dh) in enumerate(zip(xs, dhs)):
+            dx = None
+            if ctx.needs_input_grad[2 + l]:
+                dx = HF.unit_dgrad(unit, dh, (x.shape[1], x.shape[2])).permute(0, 3, 1, 2)
+                in_dtype, nchw = layouts[l]
+                if dx.dtype != in_dtype:
+                    dx = dx.to(in_dtype)
+                if nchw:                                                  # the input's own layout
+                    dx = dx.contiguous()
+            dxs.append(dx)
+        HF.join_side_stream(dev)
+        dw, db = per_level[0]
+        for gw, gb in per_level[1:]:                                      # level order, finest first
+            dw, db = dw + gw, db + gb
+        return (None, None) + tuple(dxs) + (dw, db, dwc, dbc, dwr, dbr)
+
+
+@HEADS.register_module
+class RPNHead(nn.Module):
+    """``RPNHead`` of mmdetection v1: the 3x3 ``rpn_conv`` (in_channels -> feat_channels, bias, ReLU), shared by all
+    pyramid levels, and the two 1x1 predictors ``rpn_cls`` (A channels, A = len(anchor_scales) * len(anchor_ratios)) and
+    ``rpn_reg`` (4A channels).  The parameters live in ``nn.Conv2d`` containers, so the state-dict keys and shapes are
+    mmdetection's (``rpn_conv.weight`` ... ``rpn_reg.bias``); the containers' own forward is never called.  What the HIP
+    path does not cover — ``use_sigmoid_cls=False``, 5A > 64, channel counts that are no multiples of 64 or above 512 —
+    is accepted by the constructor and raises ``NotImplementedError`` in ``forward``."""
+
+    def __init__(self, in_channels=256, feat_channels=256, anchor_scales=(8,), anchor_ratios=(0.5, 1.0, 2.0),
+                 anchor_strides=(4, 8, 16, 32, 64), anchor_base_sizes=None, target_means=(0, 0, 0, 0),
+                 target_stds=(1, 1, 1, 1), use_sigmoid_cls=True):
+        super().__init__()
+        if min(in_channels, feat_channels) < 1 or not len(anchor_scales) or not len(anchor_ratios) or \
+                not len(anchor_strides):
+            raise ValueError("RPNHead: sizes must be positive and the anchor lists non-empty")
+        self.in_channels = int(in_channels)
+        self.feat_channels = int(feat_channels)
+        self.anchor_scales = list(anchor_scales)
+        self.anchor_ratios = list(anchor_ratios)
+        self.anchor_strides = list(anchor_strides)
+        self.anchor_base_sizes = list(anchor_strides) if anchor_base_sizes is None else list(anchor_base_sizes)
+        if len(self.anchor_base_sizes) != len(self.anchor_strides):
+            raise ValueError("RPNHead: one anchor base size per stride")
+        self.target_means = tuple(target_means)
+        self.target_stds = tuple(target_stds)
+        self.use_sigmoid_cls = bool(use_sigmoid_cls)
+        self.anchor_generators = [AnchorGenerator(b, self.anchor_scales, self.anchor_ratios)
+                                  for b in self.anchor_base_sizes]
+        self.num_anchors = len(self.anchor_ratios) * len(self.anchor_scales)
+        self.rpn_conv = nn.Conv2d(self.in_channels, self.feat_channels, 3, padding=1)
+        if self.in_channels % 64 == 0:                   # the conv path's K-major layout (layers._channels_last_)
+            self.rpn_conv.weight.data = self.rpn_conv.weight.data.contiguous(memory_format=torch.channels_last)
+        self.rpn_cls = nn.Conv2d(self.feat_channels, self.num_anchors * (1 if self.use_sigmoid_cls else 2), 1)
+        self.rpn_reg = nn.Conv2d(self.feat_channels, self.num_anchors * 4, 1)
+        self.init_weights()
+
+    def init_weights(self):
+        for m in (self.rpn_conv, self.rpn_cls, self.rpn_reg):
+            nn.init.normal_(m.weight, 0, 0.01)
+            nn.init.constant_(m.bias, 0)
+
+    def _pred_unit(self, dtype):
+        cache = self.__dict__.setdefault('_hip_units', {})
+        u = cache.get(('pred', dtype))
+        wc, wr = self.rpn_cls.weight, self.rpn_reg.weight
+        if u is None or u.sources[0] is not wc or u.sources[1] is not wr:
+            u = cache[('pred', dtype)] = PredUnit(wc, wr, dtype)
+        return u.refresh()
+
+    def _check_supported(self):
+        if not self.use_sigmoid_cls:
+            raise NotImplementedError("RPNHead: use_sigmoid_cls=False (a softmax RPN) is not on the HIP path")
+        if 5 * self.num_anchors > 64 or self.num_anchors > dense_ops.MAX_A:
+            raise NotImplementedError("RPNHead: %d anchors per cell are not on the HIP path (at most %d)"
+                                      % (self.num_anchors, dense_ops.MAX_A))
+        for name, c in (("in_channels", self.in_channels), ("feat_channels", self.feat_channels)):
+            if c % 64 or c > dense_ops.MAX_C:
+                raise NotImplementedError("RPNHead: %s=%d must be a multiple of 64, at most %d, on the HIP path"
+                                          % (name, c, dense_ops.MAX_C))
+
+    def forward(self, feats):
+        """feats: a list of 1..8 (B, in_channels, H_l, W_l) maps (16-bit channels_last is read in place, float32 is
+        converted as in the other heads) -> (cls_scores, bbox_preds): lists of (B, A, H_l, W_l) and (B, 4A, H_l, W_l)
+        tensors in the compute dtype, channel order ``a`` and ``4a + j``, channels_last memory: what ``rpn_loss``,
+        ``anchor_head_loss`` and ``rpn_proposals`` take in place."""
+        self._check_supported()
+        feats = list(feats)
+        if not 1 <= len(feats) <= dense_ops.MAX_LEVELS:
+            raise ValueError("feats must be a list of 1..%d levels, got %d" % (dense_ops.MAX_LEVELS, len(feats)))
+        if torch.is_tensor(feats[0]) and feats[0].dtype == torch.float32:
+            dtype = pick_dtype(self, feats[0])
+            feats = [f.to(dtype) for f in feats]
+        n = len(feats)
+        out = RPNHeadFunction.apply(self, n, *feats, self.rpn_conv.weight, self.rpn_conv.bias, self.rpn_cls.weight,
+                                    self.rpn_cls.bias, self.rpn_reg.weight, self.rpn_reg.bias)
+        return list(out[:n]), list(out[n:])
+
+    def get_anchors(self, featmap_sizes, valid_sizes=None, device='cuda'):
+        """(anchors, valid_flags): per-level lists from one ``anchor_pyramid`` launch over the head's own generators."""
+        n = len(featmap_sizes)
+        return anchor_pyramid(self.anchor_generators[:n], featmap_sizes, self.anchor_strides[:n], device, valid_sizes)
+
+    def loss(self, cls_scores, bbox_preds, anchors, valid_flags, gt_bboxes, gt_counts, img_shapes, **target_cfg):
+        """``anchor_target`` with the head's means / stds, then ``rpn_loss`` averaged over the sampled anchors
+        (``avg_factor=(num_pos, num_neg)``): -> losses (2,) = [loss_cls, loss_bbox].  ``anchors`` / ``valid_flags``: what
+        ``get_anchors`` returned (per-level lists) or their concatenation."""
+        cat = lambda t: torch.cat(list(t)) if isinstance(t, (list, tuple)) else t
+        cfg = dict(target_means=self.target_means, target_stds=self.target_stds)
+        cfg.update(target_cfg)
+        labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg, _ = anchor_target(
+            cat(anchors), cat(valid_flags), gt_bboxes, gt_counts, img_shapes, **cfg)
+        return rpn_loss(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights,
+                        avg_factor=(num_pos, num_neg))
+
+    def get_proposals(self, cls_scores, bbox_preds, anchors, img_shapes, **proposal_cfg):
+        """``rpn_proposals`` with the head's means / stds on the head's outputs, in place.  ``rpn_proposals`` takes
+        float32 or bfloat16 only: float16 outputs are cast to float32 first (one copy per map)."""
+        if cls_scores[0].dtype == torch.float16:
+            cls_scores = [t.float() for t in cls_scores]
+            bbox_preds = [t.float() for t in bbox_preds]
+        cfg = dict(target_means=self.target_means, target_stds=self.target_stds)
+        cfg.update(proposal_cfg)
+        return rpn_proposals(cls_scores, bbox_preds, anchors, img_shapes, **cfg)
