@@ -670,6 +670,72 @@ int tdn_bbox_detections(const float* rois, const void* cls, const void* reg, int
                         float* dense_scores, float* dense_boxes, float* dets, int64_t* labels, int64_t* row_idx,
                         int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- single-stage (RetinaNet-style) dense anchor heads: test-time detections from sigmoid class logits, and unsampled
+ *      class-labelled anchor targets (the project's own spec in the mmdetection-v1 lineage of
+ *      AnchorHead.get_bboxes / anchor_target with sampling off; decode is tdn_delta2bbox's arithmetic, the sigmoid is
+ *      tdn_rpn_proposals', the selection is tdn_multiclass_nms itself, the assignment is tdn_anchor_target's) ----
+ * Level l of B images: cls (B, A*C, H, W) logits, class channel a*C + c, and reg (B, 4A, H, W) deltas, box channel
+ * 4a + j, both of cfg->dtype (TDN_F32 / TDN_BF16 / TDN_F16), read in place through their element strides (n, c, h, w);
+ * anchors fp32 [H*W*A][4] in (y, x, a) order.  levels: HOST array.  The key of anchor i = (h*W + w)*A + a of (image,
+ * level) is the maximum of its C logits (-0 == +0; NaN unsupported).  A level of n_l > nms_pre > 0 anchors keeps the
+ * nms_pre first by (key desc, anchor asc), any other level all n_l; k_l kept, K = sum k_l, off_l their prefix sum.
+ * (image b, level l) owns dense rows [b*K + off_l, b*K + off_l + k_l), its kept anchors there in ascending anchor order:
+ * dense_scores fp32 [B*K][C+1] (column 0 = 0, column 1+c = 1 / (1 + expf(-x))), dense_boxes fp32 [B*K][4] (the decode
+ * clipped to img_shapes[b] = (h, w), device int32 [B][2]; then divided by scale_factors[b] (device fp32 [B]) or, when
+ * that is NULL, by cfg->scale_factor (0: none)), batch_idx int32 [B*K], dense_anchor_idx int64 [B*K] (row of the
+ * concatenated pyramid).  Then tdn_multiclass_nms on those four, class-agnostic boxes: dets, labels, row_idx, counts as
+ * there, and anchor_idx int64 [B][max_num] = dense_anchor_idx[row_idx], -1 on unused rows.
+ * Limits: 1..TDN_DENSE_MAX_LEVELS levels, 1 <= B <= 64, 1 <= C <= TDN_DET_MAX_CLASSES - 1, A >= 1, 0 <= nms_pre <=
+ * TDN_NMS_SEG_MAX, B*K <= TDN_DET_MAX_ROWS, B*A*C*H*W < 2^31 per level, and tdn_multiclass_nms's.
+ * Launches, whatever B, the number of levels and C: 1 class maximum of every anchor of the levels that select (grid
+ * grows with the anchors; none if no level selects), 1 per (image, level) threshold, ordered compaction, sigmoid and
+ * decode, tdn_multiclass_nms's 4, 1 anchor_idx gather: 7 (6).  No host synchronisation, no allocation, no memset, no
+ * float atomics.  tdn_dense_detections_plan is host-only: out16 = {K, B*K, anchors per image, launches, workgroups of
+ * the class-maximum launch, levels that select, key words of the workspace, 0, k_0 .. k_7}.
+ * workspace: tdn_dense_detections_workspace_bytes() bytes, 256-aligned. */
+#define TDN_DENSE_MAX_LEVELS 8
+typedef struct tdn_dense_level {
+  const void* cls;             /* device, (B, A*C, H, W) */
+  const void* reg;             /* device, (B, 4A, H, W) */
+  const float* anchors;        /* device, fp32 [H*W*A][4] */
+  int64_t cls_strides[4];      /* elements: n, c, h, w */
+  int64_t reg_strides[4];
+  int32_t H, W;
+} tdn_dense_level;
+typedef struct tdn_dense_config {
+  double wh_ratio_clip;        /* in (0, 1) */
+  int32_t dtype;               /* TDN_F32 / TDN_BF16 / TDN_F16, every head output */
+  int32_t num_anchors;         /* A */
+  int32_t num_classes;         /* C */
+  int32_t nms_pre;             /* > 0: anchors kept per level; 0: all */
+  int32_t max_num;             /* 1..TDN_RPN_MAX_NUM detections per image */
+  float score_thr, nms_thr;
+  float scale_factor;          /* used when scale_factors == NULL; 0: no rescale */
+  float means[4], stds[4];     /* target_means / target_stds of the deltas */
+} tdn_dense_config;
+int tdn_dense_detections_plan(const tdn_dense_level* levels, int nlevels, int B, const tdn_dense_config* cfg,
+                              int32_t* out16);
+int64_t tdn_dense_detections_workspace_bytes(const tdn_dense_level* levels, int nlevels, int B,
+                                             const tdn_dense_config* cfg);
+int tdn_dense_detections(const tdn_dense_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                         const float* scale_factors, const tdn_dense_config* cfg, float* dense_scores,
+                         float* dense_boxes, int32_t* batch_idx, int64_t* dense_anchor_idx, float* dets,
+                         int64_t* labels, int64_t* row_idx, int64_t* anchor_idx, int32_t* counts, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+/* Unsampled anchor targets: tdn_anchor_target's assignment (valid flags, allowed_border, the six steps), then every
+ * anchor is used.  labels int64 [B][N] = gt_labels[b][assigned - 1] where assigned > 0 (gt_labels int64 [B][G]; NULL:
+ * 1), else 0; label_weights fp32 [B][N] = 1 where assigned >= 0; bbox_targets / bbox_weights fp32 [B][N][4] = the
+ * encode / 1 where assigned > 0, else 0; num_pos / num_neg int32 [B] = anchors with assigned > 0 / == 0; assigned int32
+ * [B][N].  N >= 1.  cfg: the thresholds, gt_max_assign_all, allowed_border, means, stds; the sampling fields are not
+ * read.  The assignment's three launches (four with gt_max_assign_all = 0) plus one that writes every output element
+ * and, from one integer atomic add per workgroup on a word the first launch cleared, the counts. */
+int64_t tdn_anchor_target_all_workspace_bytes(int B, int N, int G);
+int tdn_anchor_target_all(const float* anchors, int64_t box_stride, const uint8_t* valid, int64_t valid_stride,
+                          const float* gt, const int64_t* gt_labels, const int32_t* gt_counts,
+                          const int32_t* img_shapes, int B, int N, int G, const tdn_target_config* cfg, int64_t* labels,
+                          float* label_weights, float* bbox_targets, float* bbox_weights, int32_t* num_pos,
+                          int32_t* num_neg, int32_t* assigned, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- the mask branch of Mask R-CNN: polygon mask targets, mask loss, mask paste (the project's own
  *      spec in the mmdetection-v1 lineage of mask_target / FCNMaskHead.loss / get_seg_masks) ----
  * Polygons: poly_xy fp32 [P][2] vertices in the network-input frame; poly_offsets int32 [Q + 1]: polygon q owns vertices

@@ -11,7 +11,8 @@ Drop-in surface (same names as the reference's ``models`` package): ``BACKBONES`
 ``rois_from_detections`` / ``mask_head_masks``, the fused optimizer step ``SGD``, and the
 fully connected layers ``linear`` / ``BBoxHead`` between ``roi_align`` and the box losses, and the 2x2 stride-2 transposed
 conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask loss, and ``RPNHead`` between ``FPN`` and
-``rpn_loss`` / ``rpn_proposals``).  Everything computes through libtdn.so
+``rpn_loss`` / ``rpn_proposals``, and the single-stage path ``anchor_target_all`` / ``anchor_head_detections`` either side
+of ``anchor_head_loss``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -34,6 +35,8 @@ from .target import anchor_target, assign_max_iou, sample_assigned, sample_rois 
 from .losses import (AnchorHeadLossFunction, BBoxHeadLossFunction, anchor_head_loss,  # noqa: F401
                      bbox_head_loss, rpn_loss)
 from .detect import bbox_head_detections, multiclass_nms  # noqa: F401
+from .dense_detect import (anchor_head_detections, anchor_head_detections_plan,  # noqa: F401
+                           anchor_target_all)
 from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_target,  # noqa: F401
                    pack_polygons, rois_from_detections)
 from .optim import SGD  # noqa: F401

@@ -33,6 +33,7 @@ LOSS_MAX_ROWS = 1 << 20
 LOSS_MAX_AVG = 64
 DET_MAX_CLASSES = 1024
 DET_MAX_ROWS = 1 << 18
+DENSE_MAX_LEVELS = 8
 MASK_MAX_SIZE = 56
 SGD_MAX_ITEMS = 1 << 20
 SGD_MAX_GROUPS = 1024
@@ -221,6 +222,24 @@ class PredLevel(ctypes.Structure):
 
 _PL = ctypes.POINTER(PredLevel)
 
+
+class DenseLevel(ctypes.Structure):
+    """Mirror of ``tdn_dense_level`` (include/tdn.h): one pyramid level of a single-stage head's outputs."""
+    _fields_ = [("cls", c_void_p), ("reg", c_void_p), ("anchors", c_void_p),
+                ("cls_strides", c_i64 * 4), ("reg_strides", c_i64 * 4), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
+class DenseConfig(ctypes.Structure):
+    """Mirror of ``tdn_dense_config`` (include/tdn.h)."""
+    _fields_ = [("wh_ratio_clip", ctypes.c_double), ("dtype", ctypes.c_int32), ("num_anchors", ctypes.c_int32),
+                ("num_classes", ctypes.c_int32), ("nms_pre", ctypes.c_int32), ("max_num", ctypes.c_int32),
+                ("score_thr", c_float), ("nms_thr", c_float), ("scale_factor", c_float),
+                ("means", c_float * 4), ("stds", c_float * 4)]
+
+
+_DL = ctypes.POINTER(DenseLevel)
+_DC = ctypes.POINTER(DenseConfig)
+
 # name -> (restype, argtypes); must list every symbol of include/tdn.h (tests/test_abi.py checks this)
 SIGNATURES = {
     "tdn_last_error": (ctypes.c_char_p, []),
@@ -304,6 +323,12 @@ SIGNATURES = {
     "tdn_bbox_detections": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_float,
                                     ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.c_double, c_float, c_float,
                                     c_int] + [c_void_p] * 7 + [c_i64, c_void_p]),
+    "tdn_dense_detections_plan": (c_int, [_DL, c_int, c_int, _DC, ctypes.POINTER(ctypes.c_int32)]),
+    "tdn_dense_detections_workspace_bytes": (c_i64, [_DL, c_int, c_int, _DC]),
+    "tdn_dense_detections": (c_int, [_DL, c_int, c_int, c_void_p, c_void_p, _DC] + [c_void_p] * 10 + [c_i64, c_void_p]),
+    "tdn_anchor_target_all_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "tdn_anchor_target_all": (c_int, [c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 4 + [c_int, c_int, c_int, _TC] +
+                              [c_void_p] * 8 + [c_i64, c_void_p]),
     "tdn_mask_target": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p]),
     "tdn_mask_loss_workspace_bytes": (c_i64, [c_int]),

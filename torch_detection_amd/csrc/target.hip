@@ -618,3 +618,33 @@ extern "C" int tdn_sample_rois(const float* proposals, const int32_t* counts, co
   TDN_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- hooks for dense_detect.hip (target_host.h): the assignment of tdn_anchor_target on its own -------------------
+#include "target_host.h"
+
+// the assignment words padded to an even count, then `extra` more: the first launch clears all of them
+static AssignWs assign_layout_extra(int B, int G, int64_t extra, void* base) {
+  const int64_t words = (((int64_t)B * (G > 0 ? G : 1) + 1) & ~1ll) + extra;
+  tdn_carver c{(char*)base, 0};
+  return {words, c.take<uint32_t>(words), c.take<int>(words), c.off};
+}
+
+int64_t tdn_target_anchor_assign_bytes(int B, int G, int64_t extra_words) {
+  return assign_layout_extra(B, G, extra_words, nullptr).bytes;
+}
+
+int tdn_target_anchor_assign(const char* who, const float* anchors, int64_t box_stride, const uint8_t* valid,
+                             int64_t valid_stride, const float* gt, const int32_t* gt_counts, const int32_t* img_shapes,
+                             int B, int N, int G, const tdn_target_config* cfg, int32_t* assigned, void* workspace,
+                             int64_t extra_words, uint32_t** extra, void* stream) {
+  if (check_common(who, B, N, G, cfg) != 0) return -1;
+  TDN_CHECK(N >= 1, "%s: no anchors", who);
+  TDN_CHECK(box_stride == 0 || box_stride >= (int64_t)N * 4, "%s: bad box_stride", who);
+  TDN_CHECK(valid_stride == 0 || valid_stride >= N, "%s: bad valid_stride", who);
+  TDN_CHECK(anchors && gt_counts && assigned && workspace && (G == 0 || gt), "%s: NULL pointer", who);
+  TDN_CHECK(cfg->allowed_border < 0 || img_shapes, "%s: allowed_border >= 0 needs img_shapes", who);
+  const AssignWs w = assign_layout_extra(B, G, extra_words, workspace);
+  *extra = w.colmax + (w.words - extra_words);
+  const BoxSrc S = anchor_src(anchors, box_stride, valid, valid_stride, gt, G, img_shapes, cfg->allowed_border);
+  return run_assign(S, gt_counts, B, N, G, cfg, assigned, nullptr, w, (hipStream_t)stream);
+}
