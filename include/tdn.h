@@ -984,6 +984,65 @@ int tdn_pred_dgrad(const tdn_pred_level* levels, int num_levels, const void* w_d
 int tdn_pred_wgrad(const tdn_pred_level* levels, int num_levels, float* dw_cls, float* dbias_cls, float* dw_reg,
                    float* dbias_reg, int C, int A, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- 3x3 conv with shared weights over a pyramid, ragged Cout ---------------------------------------------
+ * The tower layers and the two predictors of a single-stage head (mmdetection-v1 RetinaHead: retina_cls has A * C, retina_reg
+ * 4A output channels) on ALL pyramid levels in one launch per product: 3x3, stride 1, pad 1, 16-bit operands, fp32
+ * accumulation on the matrix cores, one rounding of each result.  levels: HOST array of 1..TDN_PYR_MAX_LEVELS entries of
+ * one batch size B (>= 0) and a map size (H, W) each.  x is the level's input, dense NHWC (B, H, W, Cin), 16-byte aligned;
+ * y is the dense NHWC (B, H, W, Cout) map — the output of the forward, the cotangent of dgrad and wgrad — whose rows are
+ * 2 * Cout bytes: 2-byte aligned, nothing more; dx (dgrad only) is the dense (B, H, W, Cin) gradient of x, mask_src and
+ * addend (dgrad only, each may be NULL) have dx's shape; the three are 16-byte aligned.  Cin is a multiple of 64 in
+ * 64..512, Cout is ANY integer in 1..1024, B * H * W < 2^31 per level (pixel offsets are 64-bit).  A level with
+ * B * H * W == 0 is skipped and its pointers are not looked at.  A tap outside the map contributes zero and is not read:
+ * no launch reads a neighbouring image, a neighbouring level or memory outside a map.  kind: 0 forward, 1 dgrad, 2 wgrad.
+ * Cp = Cout rounded up to 64, the column granularity of the kernels.
+ *
+ * tdn_pack_pyr_weight: w fp32 (Cout, Cin, 3, 3) with element strides (s_o, s_c, s_h, s_w) ->
+ *   w_fwd [Cp][9][Cin], w_fwd[o][3 kh + kw][c] = w[o][c][kh][kw], and, unless NULL,
+ *   w_dgrad [Cin][9][Cp], w_dgrad[c][3 th + tw][o] = w[o][c][2 - th][2 - tw];
+ *   each value rounded once to `dtype`, rows / columns o >= Cout zero.  One launch.
+ * tdn_pyr_conv_fwd: y_l[b][h][w][o] = relu?(sum_{kh,kw,c} x_l[b][h + kh - 1][w + kw - 1][c] * w[o][c][kh][kw] + bias[o]);
+ *   bias fp32 (Cout) or NULL, added to the fp32 sum before the rounding.  Every element of y_l is written exactly once,
+ *   with 16-, 8- or 2-byte stores as its address allows; nothing else is written.  One launch.
+ * tdn_pyr_conv_dgrad: dx_l = sum_{kh,kw,o} y_l[b][h - kh + 1][w - kw + 1][o] * w[o][c][kh][kw] (+ addend_l, in fp32 before
+ *   the rounding), then exactly 0 where mask_src_l <= 0.  The cotangent is read where it lies; the reduction over Cout is
+ *   padded to Cp with zero weight columns and zero operand registers.  One launch.
+ * tdn_pyr_conv_wgrad: dw fp32 written through the element strides (s_o, s_c, s_h, s_w) — the parameter's own layout —,
+ *   dbias fp32 (Cout), neither NULL: dw[o][c][kh][kw] = sum over levels and pixels of y_l[b][h][w][o] *
+ *   x_l[b][h + kh - 1][w + kw - 1][c], dbias[o] = sum of y_l[b][h][w][o].  The pixels are cut into slices of slice_rows
+ *   pixels, each level on its own, the slice list being the levels' slices in level order; slice_rows =
+ *   ceil(total pixels / S) rounded up to whole 128-pixel steps, S = min(64, ceil(1024 / units)), units = (Cp / 64) * 9 *
+ *   (Cin / 64): a function of the shapes alone.  Every workgroup (slice x unit) stores an fp32 partial slab into the
+ *   workspace with plain stores; the finalize launch adds the slabs in slice order: no atomics, no counters, no memset,
+ *   the same bits on every run and on every device.  With no pixels at all only the finalize runs and writes zeros.
+ * tdn_pyr_workspace_bytes: forward / dgrad 0; wgrad slices * (Cp * 9 * Cin + Cp) floats, each of the two regions from a
+ *   256-byte boundary; the workspace is 256-byte aligned; -1 on a refused shape.  hw: HOST int32 [num_levels][2] = (H, W).
+ * tdn_pyr_plan (host only): out[0..15] = {pixels per workgroup (forward / dgrad) = pixels per wgrad step, workgroups of the
+ *   main launch, slices, pixels per slice, launches, columns per workgroup (64), Cp, padded reduction length per tap,
+ *   LDS bytes, column tiles (forward / dgrad) or units per slice (wgrad), pixel tiles, 0, slab bytes low 31 bits, slab
+ *   bytes >> 31, workspace bytes low 31 bits, workspace bytes >> 31}. */
+#define TDN_PYR_MAX_LEVELS 8
+typedef struct tdn_pyr_level {
+  const void* x;
+  void* y;
+  void* dx;
+  const void* mask_src;
+  const void* addend;
+  int32_t H;
+  int32_t W;
+} tdn_pyr_level;
+int tdn_pack_pyr_weight(const float* w, int64_t s_o, int64_t s_c, int64_t s_h, int64_t s_w, int Cout, int Cin,
+                        void* w_fwd, void* w_dgrad, int dtype, void* stream);
+int64_t tdn_pyr_workspace_bytes(int kind, int B, const int32_t* hw, int num_levels, int Cin, int Cout);
+int tdn_pyr_plan(int kind, int B, const int32_t* hw, int num_levels, int Cin, int Cout, int32_t* out16);
+int tdn_pyr_conv_fwd(const tdn_pyr_level* levels, int num_levels, int B, const void* w_fwd, const float* bias, int Cin,
+                     int Cout, int relu, int dtype, void* stream);
+int tdn_pyr_conv_dgrad(const tdn_pyr_level* levels, int num_levels, int B, const void* w_dgrad, int Cin, int Cout,
+                       int dtype, void* stream);
+int tdn_pyr_conv_wgrad(const tdn_pyr_level* levels, int num_levels, int B, float* dw, int64_t s_o, int64_t s_c,
+                       int64_t s_h, int64_t s_w, float* dbias, int Cin, int Cout, void* workspace,
+                       int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

@@ -11,8 +11,8 @@ Drop-in surface (same names as the reference's ``models`` package): ``BACKBONES`
 ``rois_from_detections`` / ``mask_head_masks``, the fused optimizer step ``SGD``, and the
 fully connected layers ``linear`` / ``BBoxHead`` between ``roi_align`` and the box losses, and the 2x2 stride-2 transposed
 conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask loss, and ``RPNHead`` between ``FPN`` and
-``rpn_loss`` / ``rpn_proposals``, and the single-stage path ``anchor_target_all`` / ``anchor_head_detections`` either side
-of ``anchor_head_loss``).  Everything computes through libtdn.so
+``rpn_loss`` / ``rpn_proposals``, and the single-stage path ``RetinaHead`` between ``FPN`` and ``anchor_target_all`` /
+``anchor_head_loss`` / ``anchor_head_detections``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -42,6 +42,6 @@ from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_t
 from .optim import SGD  # noqa: F401
 from .linear import LinearFunction, linear  # noqa: F401
 from .deconv import ConvTranspose2x2Function, conv_transpose2x2  # noqa: F401
-from .heads import BBoxHead, FCNMaskHead, RPNHead  # noqa: F401
+from .heads import BBoxHead, FCNMaskHead, RetinaHead, RPNHead  # noqa: F401
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)

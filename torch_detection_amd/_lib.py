@@ -28,6 +28,7 @@ TARGET_MAX_BOXES = 1 << 20
 TARGET_MAX_NUM = 8192
 LOSS_MAX_LEVELS = 8
 PRED_MAX_LEVELS = 8
+PYR_MAX_LEVELS = 8
 LOSS_MAX_CLASSES = 1024
 LOSS_MAX_ROWS = 1 << 20
 LOSS_MAX_AVG = 64
@@ -223,6 +224,16 @@ class PredLevel(ctypes.Structure):
 _PL = ctypes.POINTER(PredLevel)
 
 
+class PyrLevel(ctypes.Structure):
+    """Mirror of ``tdn_pyr_level`` (include/tdn.h): one pyramid level of the shared-weight 3x3 conv."""
+    _fields_ = [("x", c_void_p), ("y", c_void_p), ("dx", c_void_p), ("mask_src", c_void_p), ("addend", c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
+_PyL = ctypes.POINTER(PyrLevel)
+_I32P = ctypes.POINTER(ctypes.c_int32)
+
+
 class DenseLevel(ctypes.Structure):
     """Mirror of ``tdn_dense_level`` (include/tdn.h): one pyramid level of a single-stage head's outputs."""
     _fields_ = [("cls", c_void_p), ("reg", c_void_p), ("anchors", c_void_p),
@@ -365,6 +376,14 @@ SIGNATURES = {
     "tdn_pred_fwd": (c_int, [_PL, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "tdn_pred_dgrad": (c_int, [_PL, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "tdn_pred_wgrad": (c_int, [_PL, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p, c_i64, c_int, c_void_p]),
+    "tdn_pack_pyr_weight": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_int,
+                                    c_void_p]),
+    "tdn_pyr_workspace_bytes": (c_i64, [c_int, c_int, _I32P, c_int, c_int, c_int]),
+    "tdn_pyr_plan": (c_int, [c_int, c_int, _I32P, c_int, c_int, c_int, _I32P]),
+    "tdn_pyr_conv_fwd": (c_int, [_PyL, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "tdn_pyr_conv_dgrad": (c_int, [_PyL, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "tdn_pyr_conv_wgrad": (c_int, [_PyL, c_int, c_int, c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p, c_int, c_int,
+                                   c_void_p, c_i64, c_int, c_void_p]),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),

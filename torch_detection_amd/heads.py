@@ -11,23 +11,32 @@ modules; the tail (upsampling + logits) is one autograd node.
 
 ``RPNHead`` — mmdetection v1's ``RPNHead``: the shared 3x3 ``rpn_conv`` + ReLU (the existing conv path,
 level by level) and the two 1x1 predictors ``rpn_cls`` / ``rpn_reg`` over the whole pyramid in one launch per product
-(csrc/dense_head.hip) — between ``FPN`` and ``rpn_loss`` / ``rpn_proposals``.  The whole head is one autograd node."""
+(csrc/dense_head.hip) — between ``FPN`` and ``rpn_loss`` / ``rpn_proposals``.  The whole head is one autograd node.
+
+``RetinaHead`` — mmdetection v1's ``RetinaHead``: two towers of 3x3 ``ConvModule``s and the 3x3
+predictors ``retina_cls`` / ``retina_reg``, weights shared by the levels, every layer one launch over the whole pyramid
+(csrc/pyramid_conv.hip) or the existing conv path level by level, product by product as measured — between ``FPN`` and
+``anchor_target_all`` / ``anchor_head_loss`` / ``anchor_head_detections``.  The whole head is one autograd node."""
+import math
+
 import torch
 import torch.nn as nn
 
-from . import dense_ops, deconv_ops, linear_ops, ops
+from . import dense_ops, deconv_ops, linear_ops, ops, pyramid_ops
 from . import functional as HF
 from .box import AnchorGenerator, anchor_pyramid, rpn_proposals
+from .dense_detect import anchor_head_detections, anchor_target_all
 from .deconv import DeconvUnit
 from .deconv import check_params as check_deconv_params
 from .functional import pick_dtype
 from .layers import ConvModule
 from .linear import LinearUnit, check_params, flatten_input
-from .losses import rpn_loss
+from .losses import anchor_head_loss, rpn_loss
 from .registry import HEADS
 from .target import anchor_target
 
-__all__ = ["BBoxHead", "BBoxHeadFunction", "FCNMaskHead", "MaskTailFunction", "RPNHead", "RPNHeadFunction", "PredUnit"]
+__all__ = ["BBoxHead", "BBoxHeadFunction", "FCNMaskHead", "MaskTailFunction", "RPNHead", "RPNHeadFunction", "PredUnit",
+           "RetinaHead", "RetinaHeadFunction", "PyrUnit"]
 
 
 class BBoxHeadFunction(torch.autograd.Function):
@@ -487,3 +496,390 @@ class RPNHead(nn.Module):
         cfg = dict(target_means=self.target_means, target_stds=self.target_stds)
         cfg.update(proposal_cfg)
         return rpn_proposals(cls_scores, bbox_preds, anchors, img_shapes, **cfg)
+
+
+# ---- the RetinaNet head -------------------------------------------------------------------------------------------------
+PYRAMID, COMPOSED, SPLIT = 'pyramid', 'composed', 'split'
+# Route of every product of every Cout class, decided by measurement (profiles/pyramid_conv_bench.jsonl)
+# with §4k's rule: a product stays on the pyramid kernel where its slowest repeat is below the composed form's fastest.
+# 'split': the levels of at least SPLIT_PIXELS pixels (B * H * W) level by level on the tuned conv path, the tail levels in
+# one pyramid launch — taken where it measured below both.
+RETINA_ROUTES = {
+    'tower': {'fwd': SPLIT, 'dgrad': SPLIT, 'wgrad': COMPOSED},
+    'cls': {'fwd': SPLIT, 'dgrad': SPLIT, 'wgrad': COMPOSED},
+    'reg': {'fwd': PYRAMID, 'dgrad': SPLIT, 'wgrad': COMPOSED},
+}
+RETINA_COMPOSED = {k: {p: COMPOSED for p in ('fwd', 'dgrad', 'wgrad')} for k in ('tower', 'cls', 'reg')}
+# between the second and the third level of the measured pyramid (8 400 and 2 100 pixels): the split that was timed
+SPLIT_PIXELS = 4096
+
+
+def split_levels(maps):
+    """(indices of the levels the split route runs level by level, indices of its pyramid launch)"""
+    big = [l for l, t in enumerate(maps) if t.shape[0] * t.shape[2] * t.shape[3] >= SPLIT_PIXELS]
+    return big, [l for l in range(len(maps)) if l not in big]
+
+
+class PyrUnit(object):
+    """Packed 16-bit operands of one shared 3x3 weight (``pyramid_ops.pack_pyramid_weight``) for one compute dtype,
+    cached under ``PredUnit``'s rules: a version key (data pointer, ``_version``, device); an in-place update re-packs
+    into the same buffers, ``invalidate_packed`` drops the key, and inside a graph capture the pack is enqueued again
+    when ``functional.REPACK_IN_CAPTURE`` is set."""
+
+    def __init__(self, weight, dtype):
+        self.sources = (weight,)
+        self.dtype = dtype
+        self.key = None
+        self.w_fwd = self.w_dgrad = None
+        self._layout = None
+
+    def refresh(self):
+        w = self.sources[0]
+        if not w.is_cuda:
+            raise RuntimeError('torch_detection_amd modules run on the MI355X HIP path only: move the module to '
+                               'a CUDA/HIP device (no CPU fallback)')
+        key = (self.dtype, w.data_ptr(), w._version, w.device)
+        capturing = HF.REPACK_IN_CAPTURE and torch.cuda.is_current_stream_capturing()
+        if key == self.key and not capturing:
+            return self
+        layout = (w.device, self.dtype, tuple(w.shape))
+        reuse = self.w_fwd is not None and layout == self._layout
+        self._layout = layout
+        with torch.no_grad():
+            self.w_fwd, self.w_dgrad = pyramid_ops.pack_pyramid_weight(
+                w.detach(), True, self.dtype, out=(self.w_fwd, self.w_dgrad) if reuse else None)
+        self.key = key
+        return self
+
+
+class _Layer(object):
+    """One shared 3x3 conv of the head during one forward / backward: its parameters, its Cout class (the routing key),
+    and the operands of the routes in use — the ``PyrUnit`` and / or the ``ConvUnit`` of the composition (for a
+    predictor: of a hidden conv whose weight and bias are the parameter zero padded to the next multiple of 64)."""
+
+    def __init__(self, head, name, conv, kind, relu, dtype):
+        self.name, self.kind, self.relu = name, kind, relu
+        self.weight, self.bias = conv.weight, conv.bias
+        self.Cout, self.Cin = conv.weight.shape[:2]
+        self.Cp = -(-self.Cout // 64) * 64
+        routes = head._routes[kind]
+        self.routes = routes
+        self.pyr = self.unit = None
+        self._pads = {}
+        if PYRAMID in routes.values() or SPLIT in routes.values():
+            self.pyr = head._pyr_unit(name, conv.weight, dtype)
+        if COMPOSED in routes.values() or SPLIT in routes.values():
+            if self.Cp != self.Cout:
+                conv = head._padded_conv(name, conv, self.Cp)
+            self.unit = HF.prepare_unit(head, name + '.composed', conv, None, relu, dtype)
+            if self.unit.sink is not None:
+                raise NotImplementedError("RetinaHead: %s's per-level gradients cannot be written into a gradient "
+                                          "bucket" % name)
+
+    @staticmethod
+    def _pick(ts, idx):
+        return None if ts is None else [ts[l] for l in idx]
+
+    def _routed(self, route, maps, pyramid, composed):
+        """The levels of ``maps`` through ``pyramid(indices)`` / ``composed(indices)`` as the route says, in level order"""
+        every = list(range(len(maps)))
+        big, tail = (every, []) if route == COMPOSED else ([], every) if route == PYRAMID else split_levels(maps)
+        out = [None] * len(maps)
+        for idx, fn in ((big, composed), (tail, pyramid)):
+            if idx:
+                for l, t in zip(idx, fn(idx)):
+                    out[l] = t
+        return out
+
+    # every map below is a logical (B, C, H, W) tensor in channels_last memory
+    def fwd(self, xs):
+        def composed(idx):
+            ys = [HF.unit_fwd(self.unit, xs[l].permute(0, 2, 3, 1)).permute(0, 3, 1, 2) for l in idx]
+            return [_dense_channels(y, self.Cout) for y in ys] if self.Cp != self.Cout else ys   # the slicing copies
+        return self._routed(self.routes['fwd'], xs, lambda idx: pyramid_ops.pyramid_conv_fwd(
+            self._pick(xs, idx), self.pyr.w_fwd, self.bias.detach(), self.Cout, self.relu), composed)
+
+    def _padded(self, g):
+        """A cotangent as the composition reads it: (B, H, W, Cp) with zero pad channels — one copy, shared by the input
+        and the weight gradient."""
+        if self.Cp == self.Cout:
+            return g.permute(0, 2, 3, 1)
+        hit = self._pads.get(id(g))
+        if hit is None or hit[0] is not g:
+            B, _, H, W = g.shape
+            p = torch.zeros((B, H, W, self.Cp), dtype=g.dtype, device=g.device)
+            p[..., :self.Cout].copy_(g.permute(0, 2, 3, 1))
+            hit = self._pads[id(g)] = (g, p)
+        return hit[1]
+
+    def dgrad(self, gs, mask_src=None, addend=None):
+        def composed(idx):
+            out = []
+            for l in idx:
+                g = self._padded(gs[l])
+                a = addend[l].permute(0, 2, 3, 1) if addend is not None else None
+                m = mask_src[l].permute(0, 2, 3, 1) if mask_src is not None else None
+                out.append(HF.unit_dgrad(self.unit, g, (g.shape[1], g.shape[2]), a, HF.ADD_SAME if a is not None else
+                                         HF.ADD_NONE, m).permute(0, 3, 1, 2))
+            return out
+        return self._routed(self.routes['dgrad'], gs, lambda idx: pyramid_ops.pyramid_conv_dgrad(
+            self._pick(gs, idx), self.pyr.w_dgrad, self._pick(mask_src, idx), self._pick(addend, idx)), composed)
+
+    def wgrad(self, xs, gs, queue):
+        """-> a thunk giving (dw, dbias) once the queue has been flushed and the side streams joined."""
+        if self.routes['wgrad'] == PYRAMID:
+            grads = pyramid_ops.pyramid_conv_wgrad(xs, gs, self.weight.permute(0, 2, 3, 1).is_contiguous())
+            return lambda: grads
+        if self.routes['wgrad'] != COMPOSED:
+            raise ValueError("RetinaHead: the weight gradient has the routes 'pyramid' and 'composed', got %r"
+                             % (self.routes['wgrad'],))
+        per_level = [HF.unit_wgrad(self.unit, x.permute(0, 2, 3, 1), self._padded(g), queue=queue)
+                     for x, g in zip(xs, gs)]
+
+        def total():
+            dw, db = per_level[0]
+            for gw, gb in per_level[1:]:                              # level order, finest first
+                dw, db = dw + gw, db + gb
+            return (dw[:self.Cout], db[:self.Cout]) if self.Cp != self.Cout else (dw, db)
+        return total
+
+
+def _dense_channels(y, C):
+    """The first C channels of a channels_last map as a dense channels_last map of its own."""
+    B, _, H, W = y.shape
+    out = torch.empty((B, H, W, C), dtype=y.dtype, device=y.device).permute(0, 3, 1, 2)
+    out.copy_(y[:, :C])
+    return out
+
+
+class RetinaHeadFunction(torch.autograd.Function):
+    """``apply(head, n, feat_0 .. feat_{n-1}, *parameters)`` -> (cls_0 .. cls_{n-1}, reg_0 .. reg_{n-1}); the parameters
+    in ``head.parameters()`` order (cls tower, reg tower, ``retina_cls``, ``retina_reg``; weight, bias each).
+
+    Forward: the two towers layer by layer (bias and ReLU fused), then the two predictors; every layer is ONE launch
+    over the pyramid on the pyramid route, one launch per level on the composed route (``head._routes``).  Backward: the
+    predictors' weight gradients, their input gradients masked by the last hidden maps, then down each tower — a
+    layer's weight gradient from the map below and the gradient above, its input gradient masked by the map below —;
+    the two first layers' input gradients meet in ``dfeats[l]``: the cls chain's is the addend of the reg chain's launch,
+    summed in fp32 and rounded once."""
+
+    @staticmethod
+    def forward(ctx, head, n, *args):
+        feats = args[:n]
+        dtype = HF.pick_dtype(head, feats)
+        chains = head._chains(dtype)
+        xs = [ops.to_nhwc_bf16(f, dtype).permute(0, 3, 1, 2) for f in feats]   # zero-copy for channels_last 16-bit maps
+        acts = []
+        for chain in chains:
+            maps = [xs]
+            for layer in chain:
+                maps.append(layer.fwd(maps[-1]))
+            acts.append(maps)
+        ctx.save_for_backward(*[t for maps in acts for level in maps[:-1] for t in level])
+        ctx.meta = (chains, n, [(f.dtype, f.is_contiguous() and not f.permute(0, 2, 3, 1).is_contiguous())
+                                for f in feats])
+        return tuple(acts[0][-1]) + tuple(acts[1][-1])
+
+    @staticmethod
+    def backward(ctx, *gs):
+        chains, n, layouts = ctx.meta
+        saved = list(ctx.saved_tensors)
+        acts = []
+        for chain in chains:
+            acts.append([saved[i * n:(i + 1) * n] for i in range(len(chain))])
+            saved = saved[len(chain) * n:]
+        dtype, dev = acts[0][0][0].dtype, acts[0][0][0].device
+        B = acts[0][0][0].shape[0]
+        sizes = [tuple(x.shape[2:]) for x in acts[0][0]]
+        need_dx = any(ctx.needs_input_grad[2:2 + n])
+        wq = HF.WgradQueue(dev)
+        thunks, first_dx = [], None
+        for ci, (chain, maps, g) in enumerate(zip(chains, acts, (gs[:n], gs[n:]))):
+            ch = chain[-1].Cout
+            g = [torch.zeros((B, H, W, ch), dtype=dtype, device=dev).permute(0, 3, 1, 2) if t is None else t
+                 for t, (H, W) in zip(g, sizes)]
+            g = dense_ops.cotangents(g, "g_cls" if ci == 0 else "g_reg", dtype, B, ch, sizes)
+            mine = []
+            for i in reversed(range(len(chain))):
+                mine.append(chain[i].wgrad(maps[i], g, wq))
+                if i:
+                    g = chain[i].dgrad(g, mask_src=maps[i])
+                elif need_dx:
+                    g = chain[i].dgrad(g, addend=first_dx)
+                    first_dx = g
+            thunks.append(mine[::-1])
+        wq.flush()
+        dxs = []
+        for l in range(n):
+            dx = None
+            if ctx.needs_input_grad[2 + l]:
+                dx = first_dx[l]
+                in_dtype, nchw = layouts[l]
+                if dx.dtype != in_dtype:
+                    dx = dx.to(in_dtype)
+                if nchw:                                                  # the input's own layout
+                    dx = dx.contiguous()
+            dxs.append(dx)
+        HF.join_side_stream(dev)
+        grads = []
+        for mine in (thunks[0][:-1], thunks[1][:-1], thunks[0][-1:], thunks[1][-1:]):
+            for t in mine:
+                grads += list(t())
+        return (None, None) + tuple(dxs) + tuple(grads)
+
+
+@HEADS.register_module
+class RetinaHead(nn.Module):
+    """``RetinaHead`` of mmdetection v1: two towers of ``stacked_convs`` 3x3 ``ConvModule``s (bias, ReLU), shared by all
+    pyramid levels, and the two 3x3 predictors ``retina_cls`` (A * (num_classes - 1) channels, A = ``scales_per_octave``
+    * len(anchor_ratios)) and ``retina_reg`` (4A channels).  The state-dict keys and shapes are mmdetection's
+    (``cls_convs.0.conv.weight`` ... ``retina_reg.bias``); the predictors live in ``nn.Conv2d`` containers whose own
+    forward is never called.  The whole head is one autograd node.  What the HIP path does not cover —
+    ``norm_cfg`` / ``conv_cfg``, channel counts that are no multiples of 64 or above 512, more than 1024 predictor
+    channels, more than 8 levels — is accepted by the constructor and raises ``NotImplementedError`` in ``forward``."""
+
+    def __init__(self, num_classes, in_channels, feat_channels=256, stacked_convs=4, octave_base_scale=4,
+                 scales_per_octave=3, anchor_ratios=(0.5, 1.0, 2.0), anchor_strides=(8, 16, 32, 64, 128),
+                 anchor_base_sizes=None, target_means=(.0, .0, .0, .0), target_stds=(1.0, 1.0, 1.0, 1.0), conv_cfg=None,
+                 norm_cfg=None):
+        super().__init__()
+        if num_classes < 2 or min(in_channels, feat_channels, scales_per_octave) < 1 or stacked_convs < 0 or \
+                not len(anchor_ratios) or not len(anchor_strides):
+            raise ValueError("RetinaHead: num_classes >= 2 (background included), positive sizes and non-empty anchor "
+                             "lists are required")
+        self.num_classes = int(num_classes)
+        self.cls_out_channels = self.num_classes - 1
+        self.in_channels = int(in_channels)
+        self.feat_channels = int(feat_channels)
+        self.stacked_convs = int(stacked_convs)
+        self.octave_base_scale = octave_base_scale
+        self.scales_per_octave = int(scales_per_octave)
+        self.anchor_scales = [octave_base_scale * 2 ** (i / self.scales_per_octave)
+                              for i in range(self.scales_per_octave)]
+        self.anchor_ratios = list(anchor_ratios)
+        self.anchor_strides = list(anchor_strides)
+        self.anchor_base_sizes = list(anchor_strides) if anchor_base_sizes is None else list(anchor_base_sizes)
+        if len(self.anchor_base_sizes) != len(self.anchor_strides):
+            raise ValueError("RetinaHead: one anchor base size per stride")
+        self.target_means = tuple(target_means)
+        self.target_stds = tuple(target_stds)
+        self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
+        self.anchor_generators = [AnchorGenerator(b, self.anchor_scales, self.anchor_ratios)
+                                  for b in self.anchor_base_sizes]
+        self.num_anchors = len(self.anchor_ratios) * len(self.anchor_scales)
+        self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
+        for convs in (self.cls_convs, self.reg_convs):
+            for i in range(self.stacked_convs):
+                convs.append(ConvModule(self.in_channels if i == 0 else self.feat_channels, self.feat_channels, 3,
+                                        padding=1, bias=True, activation='relu'))
+        last = self.feat_channels if self.stacked_convs else self.in_channels
+        self.retina_cls = nn.Conv2d(last, self.num_anchors * self.cls_out_channels, 3, padding=1)
+        self.retina_reg = nn.Conv2d(last, self.num_anchors * 4, 3, padding=1)
+        for m in (self.retina_cls, self.retina_reg):     # K-major, like the conv modules' weights (layers._channels_last_)
+            m.weight.data = m.weight.data.contiguous(memory_format=torch.channels_last)
+        self._routes = RETINA_ROUTES
+        self.init_weights()
+
+    def init_weights(self):
+        for m in list(self.cls_convs) + list(self.reg_convs):
+            nn.init.normal_(m.conv.weight, 0, 0.01)
+            nn.init.constant_(m.conv.bias, 0)
+        for m in (self.retina_cls, self.retina_reg):
+            nn.init.normal_(m.weight, 0, 0.01)
+            nn.init.constant_(m.bias, 0)
+        nn.init.constant_(self.retina_cls.bias, -math.log((1 - 0.01) / 0.01))
+
+    def _pyr_unit(self, name, weight, dtype):
+        cache = self.__dict__.setdefault('_hip_units', {})
+        u = cache.get((name, dtype))
+        if not isinstance(u, PyrUnit) or u.sources[0] is not weight:
+            u = cache[(name, dtype)] = PyrUnit(weight, dtype)
+        return u.refresh()
+
+    def _padded_conv(self, name, conv, Cp):
+        """The composed route's stand-in for a predictor: a conv of Cp output channels, not a submodule, whose weight and
+        bias are overwritten with the zero-padded parameter on every call (two copies, graph nodes inside a capture)."""
+        cache = self.__dict__.setdefault('_padded_convs', {})
+        pc = cache.get(name)
+        w = conv.weight
+        if pc is None or pc.weight.device != w.device or pc.weight.shape[1] != w.shape[1] or pc.weight.shape[0] != Cp:
+            pc = nn.Conv2d(w.shape[1], Cp, 3, padding=1).to(w.device)
+            pc.weight.data = torch.zeros_like(pc.weight.data).contiguous(memory_format=torch.channels_last)
+            pc.bias.data.zero_()
+            pc.requires_grad_(False)
+            cache[name] = pc
+        with torch.no_grad():
+            pc.weight[:w.shape[0]].copy_(w)
+            pc.bias[:w.shape[0]].copy_(conv.bias)
+        return pc
+
+    def _chains(self, dtype):
+        """[[the cls tower's layers ..., retina_cls], [the reg tower's layers ..., retina_reg]] with refreshed operands"""
+        for m in list(self.cls_convs) + list(self.reg_convs):
+            for u in m.__dict__.get('_hip_units', {}).values():
+                if getattr(u, 'sink', None) is not None:
+                    raise NotImplementedError("RetinaHead: a shared tower weight's per-level gradients cannot be written "
+                                              "into a gradient bucket")
+        chains = []
+        for tower, tname, pred, pname, kind in ((self.cls_convs, 'cls_convs', self.retina_cls, 'retina_cls', 'cls'),
+                                                (self.reg_convs, 'reg_convs', self.retina_reg, 'retina_reg', 'reg')):
+            chain = [_Layer(self, '%s.%d' % (tname, i), m.conv, 'tower', True, dtype) for i, m in enumerate(tower)]
+            chain.append(_Layer(self, pname, pred, kind, False, dtype))
+            chains.append(chain)
+        return chains
+
+    def _check_supported(self):
+        if self.norm_cfg is not None or self.conv_cfg is not None:
+            raise NotImplementedError("RetinaHead: norm_cfg / conv_cfg other than None are not on the HIP path")
+        for name, c in (("in_channels", self.in_channels), ("feat_channels", self.feat_channels)):
+            if c % 64 or c > pyramid_ops.MAX_CIN:
+                raise NotImplementedError("RetinaHead: %s=%d must be a multiple of 64, at most %d, on the HIP path"
+                                          % (name, c, pyramid_ops.MAX_CIN))
+        for name, c in (("A * cls_out_channels", self.num_anchors * self.cls_out_channels), ("4A", 4 * self.num_anchors)):
+            if c > pyramid_ops.MAX_COUT:
+                raise NotImplementedError("RetinaHead: %s = %d output channels are not on the HIP path (at most %d)"
+                                          % (name, c, pyramid_ops.MAX_COUT))
+
+    def forward(self, feats):
+        """feats: a list of 1..8 (B, in_channels, H_l, W_l) maps (16-bit channels_last is read in place, float32 is
+        converted as in the other heads) -> (cls_scores, bbox_preds): lists of (B, A*C, H_l, W_l) and (B, 4A, H_l, W_l)
+        tensors in the compute dtype, channel order ``a*C + c`` and ``4a + j``, channels_last memory: what
+        ``anchor_head_loss`` and ``anchor_head_detections`` take in place."""
+        self._check_supported()
+        feats = list(feats)
+        if not 1 <= len(feats) <= pyramid_ops.MAX_LEVELS:
+            raise NotImplementedError("RetinaHead: feats must be a list of 1..%d levels on the HIP path, got %d"
+                                      % (pyramid_ops.MAX_LEVELS, len(feats)))
+        if torch.is_tensor(feats[0]) and feats[0].dtype == torch.float32:
+            dtype = pick_dtype(self, feats[0])
+            feats = [f.to(dtype) for f in feats]
+        n = len(feats)
+        out = RetinaHeadFunction.apply(self, n, *feats, *self.parameters())
+        return list(out[:n]), list(out[n:])
+
+    def get_anchors(self, featmap_sizes, valid_sizes=None, device='cuda'):
+        """(anchors, valid_flags): per-level lists from one ``anchor_pyramid`` launch over the head's own generators."""
+        n = len(featmap_sizes)
+        return anchor_pyramid(self.anchor_generators[:n], featmap_sizes, self.anchor_strides[:n], device, valid_sizes)
+
+    def loss(self, cls_scores, bbox_preds, anchors, valid_flags, gt_bboxes, gt_labels, gt_counts, img_shapes, beta=1.0 / 9.0,
+             **target_cfg):
+        """``anchor_target_all`` (pos_iou_thr 0.5, neg_iou_thr 0.4, min_pos_iou 0, the head's means / stds), then the focal
+        ``anchor_head_loss`` (gamma 2, alpha 0.25, smooth-L1 ``beta``) averaged over the positives: -> losses (2,) =
+        [loss_cls, loss_bbox].  ``anchors`` / ``valid_flags``: what ``get_anchors`` returned or their concatenation."""
+        cat = lambda t: torch.cat(list(t)) if isinstance(t, (list, tuple)) else t
+        cfg = dict(pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, target_means=self.target_means,
+                   target_stds=self.target_stds)
+        cfg.update(target_cfg)
+        labels, label_weights, bbox_targets, bbox_weights, num_pos, _, _ = anchor_target_all(
+            cat(anchors), cat(valid_flags), gt_bboxes, gt_labels, gt_counts, img_shapes, **cfg)
+        return anchor_head_loss(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights,
+                                avg_factor=num_pos, num_classes=self.cls_out_channels, beta=beta, gamma=2.0, alpha=0.25)
+
+    def get_bboxes(self, cls_scores, bbox_preds, anchors, img_shapes, scale_factors=None, **test_cfg):
+        """``anchor_head_detections`` with the head's means / stds on the head's outputs, in place; defaults nms_pre 1000,
+        score_thr 0.05, nms_thr 0.5, max_per_img 100."""
+        cfg = dict(nms_pre=1000, score_thr=0.05, nms_thr=0.5, max_per_img=100, target_means=self.target_means,
+                   target_stds=self.target_stds)
+        cfg.update(test_cfg)
+        return anchor_head_detections(cls_scores, bbox_preds, anchors, img_shapes, scale_factors, **cfg)

@@ -3,7 +3,7 @@
 ``Registry(name)`` keeps a ``module_dict`` name -> class; ``register_module`` is a class decorator that
 returns the class, raises ``TypeError`` for non-``nn.Module`` classes (registry.py:25-28) and ``KeyError``
 for a duplicate name (registry.py:30-32).  ``BACKBONES`` / ``NECKS`` are the two registries of the hot path
-(registry.py:40-41); ``HEADS`` holds the box head, the mask head and the RPN head (heads.py).
+(registry.py:40-41); ``HEADS`` holds the box head, the mask head, the RPN head and the RetinaNet head (heads.py).
 """
 import torch.nn as nn
 
