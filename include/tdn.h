@@ -736,6 +736,105 @@ int tdn_anchor_target_all(const float* anchors, int64_t box_stride, const uint8_
                           float* label_weights, float* bbox_targets, float* bbox_weights, int32_t* num_pos,
                           int32_t* num_neg, int32_t* assigned, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- FCOS: points, point targets, focal + IoU + centre-ness loss, detections (the project's own spec in
+ *      the mmdetection-v1 lineage of FCOSHead; '+1' boxes, strict fp32 in the spec's operation order) ----
+ * The pyramid has L levels (HOST array) of H x W points and an integer stride s; point i = h*W + w of a level sits at
+ * (x, y) = (w*s + s/2, h*s + s/2) (integer division, exact in fp32: W*s, H*s < 2^24), points are level-major,
+ * N = sum H*W <= TDN_TARGET_MAX_BOXES.  Head outputs (loss, detections): cls (B, C, H, W), reg (B, 4, H, W), ctr
+ * (B, 1, H, W) of one dtype (TDN_F32 / TDN_BF16 / TDN_F16), each NCHW-contiguous (nhwc flag 0) or channels_last (1)
+ * memory, read in place; one level tensor holds fewer than 2^31 elements.  scales: device fp32 [L] or NULL (all 1): the
+ * distance of a point in direction j is expf(scales[l] * reg_j), one fp32 product. */
+#define TDN_FCOS_MAX_LEVELS 8
+typedef struct tdn_fcos_level {
+  const void* cls;             /* device; loss and detections only */
+  const void* reg;
+  const void* ctr;
+  void* dcls;                  /* backward only: gradients, laid out as cls / reg / ctr */
+  void* dreg;
+  void* dctr;
+  int32_t H, W;
+  int32_t stride;              /* 1..2^15 */
+  int32_t cls_nhwc, reg_nhwc;  /* 0: NCHW-contiguous memory, 1: channels_last memory */
+  int32_t reserved;
+  float lo, hi;                /* targets only: the level's regress range, lo <= hi, hi may be +inf */
+} tdn_fcos_level;
+/* points fp32 [N][4] = (x, y, stride, level).  One launch. */
+int tdn_fcos_points(const tdn_fcos_level* levels, int nlevels, float* points, void* stream);
+/* Point targets.  gt fp32 [B][G][4] xyxy, gt_labels int64 [B][G] (NULL: 1), gt_counts int32 [B] (clamped to 0..G),
+ * G <= TDN_TARGET_MAX_GT.  For point (x, y) of level l and ground truth j < gt_counts[b], ascending j:
+ * l = x - x1, t = y - y1, r = x2 - x, b = y2 - y; inside: min(l, t, r, b) > 0, or with radius > 0 the same test against
+ * (max(cx - radius*s, x1), max(cy - radius*s, y1), min(cx + radius*s, x2), min(cy + radius*s, y2)), cx = (x1 + x2)*0.5,
+ * cy = (y1 + y2)*0.5; range: lo <= max(l, t, r, b) <= hi; the smallest area (x2 - x1 + 1)*(y2 - y1 + 1) among those that
+ * pass both wins, ties to the lowest j.  labels int64 [B][N] (0: none), bbox_targets fp32 [B][N][4] = the winner's
+ * (l, t, r, b) or 0, assigned int32 [B][N] = j + 1 or 0, num_pos int32 [B].  radius 0: no centre sampling.  Two launches
+ * (targets with one integer count per workgroup; the counts' sum): no atomics at all. */
+int64_t tdn_fcos_target_workspace_bytes(const tdn_fcos_level* levels, int nlevels, int B, int G);
+int tdn_fcos_target(const tdn_fcos_level* levels, int nlevels, int B, const float* gt, const int64_t* gt_labels,
+                    const int32_t* gt_counts, int G, float radius, int64_t* labels, float* bbox_targets,
+                    int32_t* assigned, int32_t* num_pos, void* workspace, int64_t workspace_bytes, void* stream);
+/* The FCOS loss over all B*N points.  labels int64 [B][N] (0: background, k in 1..C: class channel k-1; > 0: positive),
+ * bbox_targets fp32 [B][N][4] = (l*, t*, r*, b*) as tdn_fcos_target writes them.
+ *   loss_cls: the focal term of tdn_loss_dense_fwd (A = 1, every weight 1), sum / (positives + B).
+ *   positives only, d_j = expf(scale_l * reg_j):  c* = sqrtf((min(l*,r*)/max(l*,r*)) * (min(t*,b*)/max(t*,b*)));
+ *     areas (l+r+1)*(t+b+1), intersection (min(l,l*)+min(r,r*)+1)*(min(t,t*)+min(b,b*)+1), iou = inter/(area+area*-inter);
+ *     giou 0: -logf(max(iou, eps)) (gradient 0 where iou < eps); giou 1: 1 - (iou - (enc - union)/enc), enc the same
+ *     product with max in place of min.  loss_bbox = sum c* loss / sum c* (0 without positives); loss_centerness =
+ *     sum (softplus(z) - c* z) / max(positives, 1), z the centre-ness logit.  min selects the prediction where
+ *     d <= d*, max where d >= d*: these masks carry the gradient.
+ * A point that is not positive has its reg / ctr elements never read and gets gradient exactly 0.
+ * Forward (two launches): losses fp32 [3] = (loss_cls, loss_bbox, loss_centerness); norm fp32 [3] = the three divisors;
+ * scale_sums fp64 [L] (NULL iff scales is NULL) = per level sum over positives and j of c* (dloss/dd_j) d_j reg_j.
+ * Backward (one launch) takes the cotangent g fp32 [3], norm and scale_sums back, writes every element of dcls / dreg /
+ * dctr in the head dtype and dscales fp32 [L] = (g[1] / norm[1]) * scale_sums[l] (NULL iff scales is NULL).
+ * Sums are fp64 in an order fixed by the shapes; no float atomics, no memset, no host synchronisation.
+ * Limits: B 1..64, C 1..TDN_LOSS_MAX_CLASSES, gamma >= 0, alpha in [0, 1], eps in (0, 1). */
+typedef struct tdn_fcos_loss_config {
+  int32_t dtype;               /* TDN_BF16 / TDN_F16 / TDN_F32, of every head output and gradient */
+  int32_t num_classes;         /* C */
+  int32_t giou;                /* 0: -log(iou), 1: GIoU */
+  int32_t reserved;
+  float gamma, alpha, eps;
+  int32_t reserved2;
+} tdn_fcos_loss_config;
+int64_t tdn_fcos_loss_workspace_bytes(const tdn_fcos_level* levels, int nlevels, int B, const tdn_fcos_loss_config* cfg);
+int tdn_fcos_loss_fwd(const tdn_fcos_level* levels, int nlevels, int B, const tdn_fcos_loss_config* cfg,
+                      const int64_t* labels, const float* bbox_targets, const float* scales, float* losses,
+                      float* norm, double* scale_sums, void* workspace, int64_t workspace_bytes, void* stream);
+int tdn_fcos_loss_bwd(const tdn_fcos_level* levels, int nlevels, int B, const tdn_fcos_loss_config* cfg,
+                      const int64_t* labels, const float* bbox_targets, const float* scales, const float* g,
+                      const float* norm, const double* scale_sums, float* dscales, void* stream);
+/* FCOS test-time detections: tdn_dense_detections' architecture and limits with A = 1 and points in place of anchors.
+ * sg(v) = 1 / (1 + expf(-v)).  The key of point i of (image, level) is sg(max_c cls_c) * sg(ctr), one fp32 product; a
+ * level of n_l > nms_pre > 0 points keeps the nms_pre first by (key desc, point asc), any other level all n_l; k_l kept,
+ * K = sum k_l.  (image b, level l) owns dense rows [b*K + off_l, b*K + off_l + k_l), its kept points there in ascending
+ * point order: dense_scores fp32 [B*K][C+1] (column 0 = 0, column 1+c = sg(cls_c) * sg(ctr)), dense_boxes fp32 [B*K][4]
+ * = (x - d_l, y - d_t, x + d_r, y + d_b), d_j = expf(scales[l] * reg_j), clipped to [0, w-1] / [0, h-1] of img_shapes[b]
+ * = (h, w) (device int32 [B][2]), then divided by scale_factors[b] (device fp32 [B]) or, when that is NULL, by
+ * cfg->scale_factor (0: none); batch_idx int32 [B*K]; dense_point_idx int64 [B*K] (row of the pyramid).  Then
+ * tdn_multiclass_nms on those four: dets, labels, row_idx, counts as there, and point_idx int64 [B][max_num] =
+ * dense_point_idx[row_idx], -1 on unused rows.  Launches: 1 key (none if no level selects), 1 select + decode,
+ * tdn_multiclass_nms's 4, 1 gather: 7 (6).  tdn_fcos_detections_plan is host-only: out16 = {K, B*K, points per image,
+ * launches, workgroups of the key launch, levels that select, key words of the workspace, 0, k_0 .. k_7}.
+ * workspace: tdn_fcos_detections_workspace_bytes() bytes, 256-aligned.  NaN logits are unsupported. */
+typedef struct tdn_fcos_det_config {
+  int32_t dtype;               /* TDN_F32 / TDN_BF16 / TDN_F16, every head output */
+  int32_t num_classes;         /* C, 1..TDN_DET_MAX_CLASSES - 1 */
+  int32_t nms_pre;             /* > 0: points kept per level; 0: all */
+  int32_t max_num;             /* 1..TDN_RPN_MAX_NUM detections per image */
+  float score_thr, nms_thr;
+  float scale_factor;          /* used when scale_factors == NULL; 0: no rescale */
+  int32_t reserved;
+} tdn_fcos_det_config;
+int tdn_fcos_detections_plan(const tdn_fcos_level* levels, int nlevels, int B, const tdn_fcos_det_config* cfg,
+                             int32_t* out16);
+int64_t tdn_fcos_detections_workspace_bytes(const tdn_fcos_level* levels, int nlevels, int B,
+                                            const tdn_fcos_det_config* cfg);
+int tdn_fcos_detections(const tdn_fcos_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                        const float* scale_factors, const float* scales, const tdn_fcos_det_config* cfg,
+                        float* dense_scores, float* dense_boxes, int32_t* batch_idx, int64_t* dense_point_idx,
+                        float* dets, int64_t* labels, int64_t* row_idx, int64_t* point_idx, int32_t* counts,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- the mask branch of Mask R-CNN: polygon mask targets, mask loss, mask paste (the project's own
  *      spec in the mmdetection-v1 lineage of mask_target / FCNMaskHead.loss / get_seg_masks) ----
  * Polygons: poly_xy fp32 [P][2] vertices in the network-input frame; poly_offsets int32 [Q + 1]: polygon q owns vertices

@@ -12,7 +12,8 @@ Drop-in surface (same names as the reference's ``models`` package): ``BACKBONES`
 fully connected layers ``linear`` / ``BBoxHead`` between ``roi_align`` and the box losses, and the 2x2 stride-2 transposed
 conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask loss, and ``RPNHead`` between ``FPN`` and
 ``rpn_loss`` / ``rpn_proposals``, and the single-stage path ``RetinaHead`` between ``FPN`` and ``anchor_target_all`` /
-``anchor_head_loss`` / ``anchor_head_detections``).  Everything computes through libtdn.so
+``anchor_head_loss`` / ``anchor_head_detections``, and the operations around an FCOS head: ``fcos_points`` /
+``fcos_target`` / ``fcos_loss`` / ``fcos_detections``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -37,6 +38,8 @@ from .losses import (AnchorHeadLossFunction, BBoxHeadLossFunction, anchor_head_l
 from .detect import bbox_head_detections, multiclass_nms  # noqa: F401
 from .dense_detect import (anchor_head_detections, anchor_head_detections_plan,  # noqa: F401
                            anchor_target_all)
+from .fcos import (FcosLossFunction, fcos_detections, fcos_detections_plan, fcos_loss,  # noqa: F401
+                   fcos_points, fcos_target)
 from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_target,  # noqa: F401
                    pack_polygons, rois_from_detections)
 from .optim import SGD  # noqa: F401

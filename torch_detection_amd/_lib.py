@@ -35,6 +35,7 @@ LOSS_MAX_AVG = 64
 DET_MAX_CLASSES = 1024
 DET_MAX_ROWS = 1 << 18
 DENSE_MAX_LEVELS = 8
+FCOS_MAX_LEVELS = 8
 MASK_MAX_SIZE = 56
 SGD_MAX_ITEMS = 1 << 20
 SGD_MAX_GROUPS = 1024
@@ -251,6 +252,34 @@ class DenseConfig(ctypes.Structure):
 _DL = ctypes.POINTER(DenseLevel)
 _DC = ctypes.POINTER(DenseConfig)
 
+
+class FcosLevel(ctypes.Structure):
+    """Mirror of ``tdn_fcos_level`` (include/tdn.h): one pyramid level of an FCOS head."""
+    _fields_ = [("cls", c_void_p), ("reg", c_void_p), ("ctr", c_void_p),
+                ("dcls", c_void_p), ("dreg", c_void_p), ("dctr", c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("cls_nhwc", ctypes.c_int32), ("reg_nhwc", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("lo", c_float), ("hi", c_float)]
+
+
+class FcosLossConfig(ctypes.Structure):
+    """Mirror of ``tdn_fcos_loss_config`` (include/tdn.h)."""
+    _fields_ = [("dtype", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("giou", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("gamma", c_float), ("alpha", c_float), ("eps", c_float),
+                ("reserved2", ctypes.c_int32)]
+
+
+class FcosDetConfig(ctypes.Structure):
+    """Mirror of ``tdn_fcos_det_config`` (include/tdn.h)."""
+    _fields_ = [("dtype", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("nms_pre", ctypes.c_int32),
+                ("max_num", ctypes.c_int32), ("score_thr", c_float), ("nms_thr", c_float), ("scale_factor", c_float),
+                ("reserved", ctypes.c_int32)]
+
+
+_FL = ctypes.POINTER(FcosLevel)
+_FLC = ctypes.POINTER(FcosLossConfig)
+_FDC = ctypes.POINTER(FcosDetConfig)
+
 # name -> (restype, argtypes); must list every symbol of include/tdn.h (tests/test_abi.py checks this)
 SIGNATURES = {
     "tdn_last_error": (ctypes.c_char_p, []),
@@ -340,6 +369,17 @@ SIGNATURES = {
     "tdn_anchor_target_all_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
     "tdn_anchor_target_all": (c_int, [c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 4 + [c_int, c_int, c_int, _TC] +
                               [c_void_p] * 8 + [c_i64, c_void_p]),
+    "tdn_fcos_points": (c_int, [_FL, c_int, c_void_p, c_void_p]),
+    "tdn_fcos_target_workspace_bytes": (c_i64, [_FL, c_int, c_int, c_int]),
+    "tdn_fcos_target": (c_int, [_FL, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float] + [c_void_p] * 5 +
+                        [c_i64, c_void_p]),
+    "tdn_fcos_loss_workspace_bytes": (c_i64, [_FL, c_int, c_int, _FLC]),
+    "tdn_fcos_loss_fwd": (c_int, [_FL, c_int, c_int, _FLC] + [c_void_p] * 7 + [c_i64, c_void_p]),
+    "tdn_fcos_loss_bwd": (c_int, [_FL, c_int, c_int, _FLC] + [c_void_p] * 8),
+    "tdn_fcos_detections_plan": (c_int, [_FL, c_int, c_int, _FDC, ctypes.POINTER(ctypes.c_int32)]),
+    "tdn_fcos_detections_workspace_bytes": (c_i64, [_FL, c_int, c_int, _FDC]),
+    "tdn_fcos_detections": (c_int, [_FL, c_int, c_int, c_void_p, c_void_p, c_void_p, _FDC] + [c_void_p] * 10 +
+                            [c_i64, c_void_p]),
     "tdn_mask_target": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p]),
     "tdn_mask_loss_workspace_bytes": (c_i64, [c_int]),

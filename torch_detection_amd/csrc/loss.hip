@@ -6,7 +6,7 @@
 // the workspace with a plain store and the last launch adds the partials in index order, so two runs agree bit for
 // bit.  An element whose weight is exactly 0 is not evaluated.  No float atomics, no host synchronisation, no
 // allocation; every launch goes through TDN_LAUNCH.
-#include "common.h"
+#include "loss_core.h"
 #include <string.h>
 
 namespace {
@@ -17,39 +17,7 @@ constexpr int LMAX_BLOCKS = 256;  // one workgroup per CU at most: that many par
 constexpr int PART = 4;           // doubles per partial: loss_cls, loss_bbox, rows with weight > 0, unused
 constexpr int MAXSEG = 2 * TDN_LOSS_MAX_LEVELS;
 
-// ---- elementwise spec ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float e_neg_abs(float z) { return expf(-fabsf(z)); }
-__device__ __forceinline__ float softplus(float z) { return __fadd_rn(fmaxf(z, 0.f), log1pf(e_neg_abs(z))); }
-__device__ __forceinline__ float sigmoid(float z) {
-  const float e = e_neg_abs(z);
-  const float d = __fadd_rn(1.f, e);
-  return z >= 0.f ? __fdiv_rn(1.f, d) : __fdiv_rn(e, d);
-}
-
-struct ClsParams {
-  int focal;
-  float gamma, alpha, one_minus_alpha;
-};
-
-// GRAD: d loss / d logit, else the loss; t: the element's class is the anchor's label
-template <bool GRAD>
-__device__ __forceinline__ float cls_elem(float x, bool t, const ClsParams& P) {
-  if (!P.focal) {
-    if (GRAD) return t ? -sigmoid(-x) : sigmoid(x);
-    return t ? softplus(-x) : softplus(x);
-  }
-  if (t) {
-    const float mod = __fmul_rn(P.alpha, expf(-__fmul_rn(P.gamma, softplus(x))));
-    if (!GRAD) return __fmul_rn(mod, softplus(-x));
-    const float inner = __fadd_rn(__fmul_rn(__fmul_rn(P.gamma, sigmoid(x)), softplus(-x)), sigmoid(-x));
-    return -__fmul_rn(mod, inner);
-  }
-  const float mod = __fmul_rn(P.one_minus_alpha, expf(-__fmul_rn(P.gamma, softplus(-x))));
-  if (!GRAD) return __fmul_rn(mod, softplus(x));
-  const float inner = __fadd_rn(__fmul_rn(__fmul_rn(P.gamma, sigmoid(-x)), softplus(x)), sigmoid(x));
-  return __fmul_rn(mod, inner);
-}
-
+// ---- elementwise spec: the sigmoid classification terms are loss_core.h ----------------------------------------------
 template <bool GRAD>
 __device__ __forceinline__ float smooth_l1(float pred, float target, float beta) {
   const float d = __fsub_rn(pred, target);
@@ -59,39 +27,7 @@ __device__ __forceinline__ float smooth_l1(float pred, float target, float beta)
   return __fsub_rn(ad, __fmul_rn(0.5f, beta));
 }
 
-// ---- storage types ------------------------------------------------------------------------------------------------
-template <int DT> struct Elem;
-template <> struct Elem<TDN_F32> {
-  typedef float T;
-  static constexpr int V = 4;
-  static __device__ __forceinline__ float ld(T v) { return v; }
-  static __device__ __forceinline__ T st(float v) { return v; }
-};
-template <> struct Elem<TDN_BF16> {
-  typedef bf16_t T;
-  static constexpr int V = 8;
-  static __device__ __forceinline__ float ld(T v) { return (float)v; }
-  static __device__ __forceinline__ T st(float v) { return (bf16_t)v; }
-};
-template <> struct Elem<TDN_F16> {
-  typedef f16_t T;
-  static constexpr int V = 8;
-  static __device__ __forceinline__ float ld(T v) { return (float)v; }
-  static __device__ __forceinline__ T st(float v) { return (f16_t)v; }
-};
-
-template <typename T, int V>
-struct alignas(16) Vec {
-  T v[V];
-};
-
-// ---- block reduction of the fp64 accumulators -----------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
+// ---- block reduction of the fp64 accumulators (storage types and wave_sum: loss_core.h) -------------------------------
 // lanes -> xor tree, waves -> wave 0 .. 15 in order; thread 0 stores the workgroup's partial
 __device__ __forceinline__ void block_partial(double a0, double a1, double a2, double* __restrict__ partials) {
   __shared__ double red[LWAVES][3];
