@@ -1142,6 +1142,54 @@ int tdn_pyr_conv_wgrad(const tdn_pyr_level* levels, int num_levels, int B, float
                        int64_t s_h, int64_t s_w, float* dbias, int Cin, int Cout, void* workspace,
                        int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- GroupNorm (+ ReLU) with shared affine parameters over a pyramid ---------------------------------------
+ * The conv -> GroupNorm -> ReLU tower layers of a single-stage head with norm_cfg GN (mmdetection-v1 FCOSHead) on ALL
+ * pyramid levels: three launches forward and three backward for the whole pyramid.  levels: HOST array of
+ * 1..TDN_PYR_MAX_LEVELS entries of one batch size B (>= 0) and a map size (H, W) each, H, W >= 0.  All maps are dense NHWC
+ * (B, H, W, C), 16-bit, 16-byte aligned: z the raw conv output, y the output of the forward and the ReLU mask source of
+ * the backward (may be NULL there when relu == 0), g = dL/dy UNMASKED, dz = dL/dz.  A level with B * H * W == 0 is skipped
+ * and its pointers are not looked at.  C is 64, 128, 256 or 512, G divides C, at most 256 channels per group;
+ * B * H * W < 2^31 per level (offsets are 64-bit), B <= 8191.  gamma, beta fp32 (C), shared by every level.  Statistics are
+ * per (level, image, group), biased variance; they are formed as in tdn_gn_fwd: fp32 sums about the pivot K_c = the
+ * channel's value at pixel 0 of the (level, image), pivots put back in double, y = (z - K) a + b' with b' formed in double.
+ * relu is 0 or 1.  kind: 0 forward, 1 backward.
+ *
+ * tdn_pyr_gn_fwd: y_l = relu?((z_l - mu) rstd gamma + beta); stats fp32 [level][B][C][2] = (mu, rstd) of the channel's
+ *   group, kept for the backward; the rows of a skipped level are zero (with no pixels at all nothing is launched).
+ * tdn_pyr_gn_bwd: with g'_l = g_l where y_l > 0 (or everywhere when relu == 0) and exactly 0 elsewhere, and
+ *   xhat = (z - mu) rstd: dz_l = rstd (gamma g' - mean_group(gamma g') - xhat mean_group(gamma g' xhat)), rounded once;
+ *   dgamma[c] = sum over ALL levels, images and pixels of g' xhat, dbeta[c] = sum of g', fp32 (C), 16-byte alignment not
+ *   needed; acc = 0 overwrites them, else they become acc * old + sum.  stats must be 16-byte aligned.  With no pixels at
+ *   all one launch writes the (zero) sums.
+ * The pixels of a (level, image) are cut into chunks by tdn_gn_fwd's rule applied to that level alone — min(ceil(1024 / B),
+ * ceil(H W / (4 * pixel lanes))) chunks, pixel lanes = 2048 / C —, a function of (B, H W, C): a level gives the same bits
+ * alone and inside a pyramid.  Partials are plain stores into the workspace and every reduction runs in a fixed order (chunk
+ * order within an image; images within a level, levels finest first for dgamma / dbeta): no atomics, no counters, no
+ * memset, the same bits on every run.
+ * tdn_pyr_gn_workspace_bytes: part [workgroup][2][C] | coef [level][B][3][C] | backward: sums [level][B][2][C], fp32, each
+ *   region from a 256-byte boundary; the workspace is 256-byte aligned; 0 with no pixels; -1 on a refused shape.
+ *   hw: HOST int32 [num_levels][2] = (H, W).
+ * tdn_pyr_gn_plan (host only): out32[0..7] chunks per image of each level (0: skipped), out32[8..15] pixels per chunk,
+ *   out32[16..18] workgroups of the three launches, out32[19] launches, out32[20] 16-byte lanes per workgroup of the third
+ *   launch, out32[21] channels per block of the second, out32[22] workspace bytes low 31 bits, out32[23] workspace bytes
+ *   >> 31, the rest 0. */
+typedef struct tdn_pyr_gn_level {
+  const void* z;
+  void* y;
+  const void* g;
+  void* dz;
+  int32_t H;
+  int32_t W;
+} tdn_pyr_gn_level;
+int64_t tdn_pyr_gn_workspace_bytes(int kind, int B, const int32_t* hw, int num_levels, int C, int G);
+int tdn_pyr_gn_plan(int kind, int B, const int32_t* hw, int num_levels, int C, int G, int32_t* out32);
+int tdn_pyr_gn_fwd(const tdn_pyr_gn_level* levels, int num_levels, int B, const float* gamma, const float* beta, int C,
+                   int G, float eps, int relu, float* stats, void* workspace, int64_t workspace_bytes, int dtype,
+                   void* stream);
+int tdn_pyr_gn_bwd(const tdn_pyr_gn_level* levels, int num_levels, int B, const float* stats, const float* gamma, int C,
+                   int G, int relu, float* dgamma, float* dbeta, float acc, void* workspace, int64_t workspace_bytes,
+                   int dtype, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

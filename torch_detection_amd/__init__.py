@@ -12,14 +12,14 @@ Drop-in surface (same names as the reference's ``models`` package): ``BACKBONES`
 fully connected layers ``linear`` / ``BBoxHead`` between ``roi_align`` and the box losses, and the 2x2 stride-2 transposed
 conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask loss, and ``RPNHead`` between ``FPN`` and
 ``rpn_loss`` / ``rpn_proposals``, and the single-stage path ``RetinaHead`` between ``FPN`` and ``anchor_target_all`` /
-``anchor_head_loss`` / ``anchor_head_detections``, and the operations around an FCOS head: ``fcos_points`` /
+``anchor_head_loss`` / ``anchor_head_detections``, and ``FCOSHead`` with the operations around it: ``fcos_points`` /
 ``fcos_target`` / ``fcos_loss`` / ``fcos_detections``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
 
 from .registry import BACKBONES, HEADS, NECKS, Registry  # noqa: F401
-from .layers import (ConvModule, conv1x1_group, conv3x3_group, conv7x7_group, get_group_gn,  # noqa: F401
+from .layers import (ConvModule, Scale, conv1x1_group, conv3x3_group, conv7x7_group, get_group_gn,  # noqa: F401
                      norm_layer)
 from .inits import (bias_init_with_prob, constant_init, kaiming_init, normal_init, uniform_init,  # noqa: F401
                     xavier_init)
@@ -45,6 +45,6 @@ from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_t
 from .optim import SGD  # noqa: F401
 from .linear import LinearFunction, linear  # noqa: F401
 from .deconv import ConvTranspose2x2Function, conv_transpose2x2  # noqa: F401
-from .heads import BBoxHead, FCNMaskHead, RetinaHead, RPNHead  # noqa: F401
+from .heads import BBoxHead, FCNMaskHead, FCOSHead, RetinaHead, RPNHead  # noqa: F401
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)

@@ -232,6 +232,15 @@ class PyrLevel(ctypes.Structure):
 
 
 _PyL = ctypes.POINTER(PyrLevel)
+
+
+class PyrGnLevel(ctypes.Structure):
+    """Mirror of ``tdn_pyr_gn_level`` (include/tdn.h): one pyramid level of the shared-affine GroupNorm."""
+    _fields_ = [("z", c_void_p), ("y", c_void_p), ("g", c_void_p), ("dz", c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
+_PgL = ctypes.POINTER(PyrGnLevel)
 _I32P = ctypes.POINTER(ctypes.c_int32)
 
 
@@ -424,6 +433,12 @@ SIGNATURES = {
     "tdn_pyr_conv_dgrad": (c_int, [_PyL, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "tdn_pyr_conv_wgrad": (c_int, [_PyL, c_int, c_int, c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p, c_int, c_int,
                                    c_void_p, c_i64, c_int, c_void_p]),
+    "tdn_pyr_gn_workspace_bytes": (c_i64, [c_int, c_int, _I32P, c_int, c_int, c_int]),
+    "tdn_pyr_gn_plan": (c_int, [c_int, c_int, _I32P, c_int, c_int, c_int, _I32P]),
+    "tdn_pyr_gn_fwd": (c_int, [_PgL, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
+                               c_i64, c_int, c_void_p]),
+    "tdn_pyr_gn_bwd": (c_int, [_PgL, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
+                               c_void_p, c_i64, c_int, c_void_p]),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),

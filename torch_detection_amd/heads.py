@@ -16,7 +16,12 @@ level by level) and the two 1x1 predictors ``rpn_cls`` / ``rpn_reg`` over the wh
 ``RetinaHead`` — mmdetection v1's ``RetinaHead``: two towers of 3x3 ``ConvModule``s and the 3x3
 predictors ``retina_cls`` / ``retina_reg``, weights shared by the levels, every layer one launch over the whole pyramid
 (csrc/pyramid_conv.hip) or the existing conv path level by level, product by product as measured — between ``FPN`` and
-``anchor_target_all`` / ``anchor_head_loss`` / ``anchor_head_detections``.  The whole head is one autograd node."""
+``anchor_target_all`` / ``anchor_head_loss`` / ``anchor_head_detections``.  The whole head is one autograd node.
+
+``FCOSHead`` — mmdetection v1's ``FCOSHead``: two towers of 3x3 conv -> GroupNorm -> ReLU layers and the
+3x3 predictors ``fcos_cls`` / ``fcos_reg`` / ``fcos_centerness``, weights and affine parameters shared by the levels; the
+convs as in ``RetinaHead``, the GroupNorm of a layer in three launches over the whole pyramid each way
+(csrc/pyramid_gn.hip) — between ``FPN`` and ``fcos_target`` / ``fcos_loss`` / ``fcos_detections``.  One autograd node."""
 import math
 
 import torch
@@ -29,14 +34,15 @@ from .dense_detect import anchor_head_detections, anchor_target_all
 from .deconv import DeconvUnit
 from .deconv import check_params as check_deconv_params
 from .functional import pick_dtype
-from .layers import ConvModule
+from .fcos import fcos_detections, fcos_loss, fcos_points, fcos_target
+from .layers import ConvModule, Scale
 from .linear import LinearUnit, check_params, flatten_input
 from .losses import anchor_head_loss, rpn_loss
 from .registry import HEADS
 from .target import anchor_target
 
 __all__ = ["BBoxHead", "BBoxHeadFunction", "FCNMaskHead", "MaskTailFunction", "RPNHead", "RPNHeadFunction", "PredUnit",
-           "RetinaHead", "RetinaHeadFunction", "PyrUnit"]
+           "RetinaHead", "RetinaHeadFunction", "PyrUnit", "FCOSHead", "FCOSHeadFunction"]
 
 
 class BBoxHeadFunction(torch.autograd.Function):
@@ -883,3 +889,390 @@ class RetinaHead(nn.Module):
                    target_stds=self.target_stds)
         cfg.update(test_cfg)
         return anchor_head_detections(cls_scores, bbox_preds, anchors, img_shapes, scale_factors, **cfg)
+
+
+# ---- the FCOS head ------------------------------------------------------------------------------------------------------
+INF = 1e8
+# Routes of the FCOS head's products, set by §4k's rule from profiles/pyramid_gn_bench.jsonl: a product
+# is on the form whose slowest repeat is below the others' fastest, else composed.  'cls' (80 columns), 'reg' (4) and 'ctr'
+# (1) are the predictors: the pyramid kernel measured below both other forms for every product but the 80-column weight
+# gradient.  'gn' is the GroupNorm (+ ReLU) of a tower layer, forward and backward ('pyramid' or 'composed').  The tower
+# convs are §4m's 256 -> 256 product without its epilogue and keep that section's routes (not timed again).
+FCOS_ROUTES = {
+    'tower': {'fwd': SPLIT, 'dgrad': SPLIT, 'wgrad': COMPOSED},
+    'cls': {'fwd': PYRAMID, 'dgrad': PYRAMID, 'wgrad': COMPOSED},
+    'reg': {'fwd': PYRAMID, 'dgrad': PYRAMID, 'wgrad': PYRAMID},
+    'ctr': {'fwd': PYRAMID, 'dgrad': PYRAMID, 'wgrad': PYRAMID},
+    'gn': {'fwd': PYRAMID, 'bwd': PYRAMID},
+}
+FCOS_COMPOSED = {k: {p: COMPOSED for p in v} for k, v in FCOS_ROUTES.items()}
+
+
+class _RawLayer(_Layer):
+    """A bias-free shared 3x3 conv whose raw product feeds a GroupNorm: ``_Layer`` without the bias and its gradient."""
+
+    def fwd(self, xs):
+        def composed(idx):
+            return [HF.unit_fwd(self.unit, xs[l].permute(0, 2, 3, 1)).permute(0, 3, 1, 2) for l in idx]
+        return self._routed(self.routes['fwd'], xs, lambda idx: pyramid_ops.pyramid_conv_fwd(
+            self._pick(xs, idx), self.pyr.w_fwd, None, self.Cout, False), composed)
+
+    def wgrad(self, xs, gs, queue):
+        if self.routes['wgrad'] == PYRAMID:
+            dw, _ = pyramid_ops.pyramid_conv_wgrad(xs, gs, self.weight.permute(0, 2, 3, 1).is_contiguous())
+            return lambda: (dw,)
+        if self.routes['wgrad'] != COMPOSED:
+            raise ValueError("FCOSHead: the weight gradient has the routes 'pyramid' and 'composed', got %r"
+                             % (self.routes['wgrad'],))
+        per_level = [HF.unit_wgrad(self.unit, x.permute(0, 2, 3, 1), g.permute(0, 2, 3, 1), queue=queue)[0]
+                     for x, g in zip(xs, gs)]
+
+        def total():
+            dw = per_level[0]
+            for gw in per_level[1:]:                                  # level order, finest first
+                dw = dw + gw
+            return (dw,)
+        return total
+
+
+class _GnLayer(object):
+    """The GroupNorm + ReLU of one tower layer during one forward / backward: shared (gamma, beta) over the pyramid."""
+
+    def __init__(self, head, norm, frozen):
+        self.norm, self.frozen = norm, frozen
+        self.routes = head._routes['gn']
+        for p in ('fwd', 'bwd'):
+            if self.routes[p] not in (PYRAMID, COMPOSED):
+                raise ValueError("FCOSHead: the GroupNorm has the routes 'pyramid' and 'composed', got %r"
+                                 % (self.routes[p],))
+        if self.routes['fwd'] != self.routes['bwd']:
+            raise ValueError("FCOSHead: the GroupNorm's backward reads its forward's statistics table: one route for both")
+
+    def fwd(self, zs):
+        """-> (ys, [statistics tensors])"""
+        nm = self.norm
+        if self.routes['fwd'] == PYRAMID:
+            ys, stats = pyramid_ops.pyramid_gn_fwd(zs, nm.weight.detach(), nm.bias.detach(), nm.num_groups, nm.eps, True)
+            return ys, [stats]
+        ys, stats = [], []
+        for z in zs:
+            y, st = ops.gn_fwd(z.permute(0, 2, 3, 1), nm.weight.detach(), nm.bias.detach(), nm.num_groups, nm.eps, None,
+                               True)
+            ys.append(y.permute(0, 3, 1, 2))
+            stats.append(st)
+        return ys, stats
+
+    def bwd(self, gs, ys, zs, stats):
+        """-> (dzs, dgamma, dbeta) from the unmasked cotangents"""
+        nm = self.norm
+        if self.routes['bwd'] == PYRAMID:
+            return pyramid_ops.pyramid_gn_bwd(gs, ys, zs, stats[0], nm.weight.detach(), nm.num_groups, True)
+        dzs, dg, db = [], None, None
+        for g, y, z, st in zip(gs, ys, zs, stats):                    # level order, finest first
+            gm = ops.act_mask(g.permute(0, 2, 3, 1), y.permute(0, 2, 3, 1))
+            dz, dg, db = ops.gn_bwd(gm, z.permute(0, 2, 3, 1), st, nm.weight.detach(), nm.num_groups, dg, db,
+                                    dg is not None)
+            dzs.append(dz.permute(0, 3, 1, 2))
+        return dzs, dg, db
+
+
+class FCOSHeadFunction(torch.autograd.Function):
+    """``apply(head, n, feat_0 .. feat_{n-1}, *parameters)`` -> (cls_0 .. cls_{n-1}, reg_0 .., ctr_0 ..); the parameters
+    in the order of ``head._chains``: per tower layer the conv weight (and bias without GroupNorm, or gamma, beta with
+    it), cls tower first, then ``fcos_cls``, ``fcos_reg``, ``fcos_centerness`` (weight, bias each).
+
+    Forward: per tower layer the raw conv product over the pyramid and the GroupNorm + ReLU product (three launches over
+    the pyramid); then the three predictors, centre-ness off the cls tower.  Saved per GroupNorm layer and level: the raw
+    map z and the output y.  Backward per chain: the predictor's weight gradient, its UNMASKED input gradient (the cls
+    tower receives ``fcos_cls``'s as the addend of ``fcos_centerness``'s), then per layer ``pyramid_gn_bwd`` — which
+    masks by y and gives dz, dgamma, dbeta —, the conv's weight gradient from the map below and dz, and its input
+    gradient; the two first layers' input gradients meet in ``dfeats[l]`` through the addend, as in ``RetinaHead``."""
+
+    @staticmethod
+    def forward(ctx, head, n, *args):
+        feats = args[:n]
+        dtype = HF.pick_dtype(head, feats)
+        towers, preds = head._chains(dtype)
+        xs = [ops.to_nhwc_bf16(f, dtype).permute(0, 3, 1, 2) for f in feats]
+        saved, counts, tops = list(xs), [], []
+        for tower in towers:
+            cur, cnt = xs, []
+            for conv, gn in tower:
+                if gn is None:
+                    cur = conv.fwd(cur)
+                    saved += cur
+                    cnt.append(0)
+                else:
+                    zs = conv.fwd(cur)
+                    cur, stats = gn.fwd(zs)
+                    saved += zs + cur + stats
+                    cnt.append(len(stats))
+            counts.append(cnt)
+            tops.append(cur)
+        outs = [preds[0].fwd(tops[0]), preds[1].fwd(tops[1]), preds[2].fwd(tops[0])]
+        ctx.save_for_backward(*saved)
+        ctx.meta = (towers, preds, counts, n, [(f.dtype, f.is_contiguous() and not f.permute(0, 2, 3, 1).is_contiguous())
+                                               for f in feats])
+        return tuple(outs[0]) + tuple(outs[1]) + tuple(outs[2])
+
+    @staticmethod
+    def backward(ctx, *gs):
+        towers, preds, counts, n, layouts = ctx.meta
+        saved = list(ctx.saved_tensors)
+        xs, saved = saved[:n], saved[n:]
+        acts = []                      # per tower, per layer: (zs or None, ys, stats or None)
+        for tower, cnt in zip(towers, counts):
+            rows = []
+            for (conv, gn), k in zip(tower, cnt):
+                if gn is None:
+                    rows.append((None, saved[:n], None))
+                    saved = saved[n:]
+                else:
+                    rows.append((saved[:n], saved[n:2 * n], saved[2 * n:2 * n + k]))
+                    saved = saved[2 * n + k:]
+            acts.append(rows)
+        dtype, dev, B = xs[0].dtype, xs[0].device, xs[0].shape[0]
+        sizes = [tuple(x.shape[2:]) for x in xs]
+        need_dx = any(ctx.needs_input_grad[2:2 + n])
+        wq = HF.WgradQueue(dev)
+
+        def cot(g, ch, name):
+            g = [torch.zeros((B, H, W, ch), dtype=dtype, device=dev).permute(0, 3, 1, 2) if t is None else t
+                 for t, (H, W) in zip(g, sizes)]
+            return dense_ops.cotangents(g, name, dtype, B, ch, sizes)
+
+        g_cls, g_reg, g_ctr = (cot(gs[i * n:(i + 1) * n], preds[i].Cout, nm)
+                               for i, nm in enumerate(("g_cls", "g_reg", "g_ctr")))
+        tower_thunks, pred_thunks, first_dx = [], [None] * 3, None
+        for ti, (tower, rows) in enumerate(zip(towers, acts)):
+            top = rows[-1][1] if rows else xs
+            # the map a predictor reads is masked by the GroupNorm's backward when there is one, else here
+            mask = top if rows and tower[-1][1] is None else None
+            below = bool(rows) or need_dx
+            if ti == 0:
+                pred_thunks[0] = preds[0].wgrad(top, g_cls, wq)
+                pred_thunks[2] = preds[2].wgrad(top, g_ctr, wq)
+                g = None
+                if below:
+                    last = not rows
+                    g = preds[0].dgrad(g_cls, mask_src=mask, addend=first_dx if last else None)
+                    g = preds[2].dgrad(g_ctr, mask_src=mask, addend=g)
+            else:
+                pred_thunks[1] = preds[1].wgrad(top, g_reg, wq)
+                g = preds[1].dgrad(g_reg, mask_src=mask, addend=first_dx if not rows else None) if below else None
+            mine = []
+            for i in reversed(range(len(tower))):
+                conv, gn = tower[i]
+                zs, ys, stats = rows[i]
+                x_in = rows[i - 1][1] if i else xs
+                if gn is not None:
+                    g, dgam, dbet = gn.bwd(g, ys, zs, stats)
+                    aff = (None, None) if gn.frozen else (dgam, dbet)
+                else:
+                    aff = ()
+                t = conv.wgrad(x_in, g, wq)
+                mine.append((t, aff))
+                if i:
+                    g = conv.dgrad(g, mask_src=x_in if tower[i - 1][1] is None else None)
+                elif need_dx:
+                    g = conv.dgrad(g, addend=first_dx)
+            if need_dx:
+                first_dx = g
+            tower_thunks.append(mine[::-1])
+        wq.flush()
+        dxs = []
+        for l in range(n):
+            dx = None
+            if ctx.needs_input_grad[2 + l]:
+                dx = first_dx[l]
+                in_dtype, nchw = layouts[l]
+                if dx.dtype != in_dtype:
+                    dx = dx.to(in_dtype)
+                if nchw:                                                  # the input's own layout
+                    dx = dx.contiguous()
+            dxs.append(dx)
+        HF.join_side_stream(dev)
+        grads = []
+        for mine in tower_thunks:
+            for t, aff in mine:
+                grads += list(t()) + list(aff)
+        for t in pred_thunks:
+            grads += list(t())
+        return (None, None) + tuple(dxs) + tuple(grads)
+
+
+@HEADS.register_module
+class FCOSHead(nn.Module):
+    """``FCOSHead`` of mmdetection v1: two towers of ``stacked_convs`` 3x3 ``ConvModule``s shared by all pyramid levels —
+    bias-free conv, GroupNorm(``norm_cfg['num_groups']``), ReLU with the default ``norm_cfg``; conv with bias, ReLU with
+    ``norm_cfg=None`` —, the 3x3 predictors ``fcos_cls`` (num_classes - 1 channels), ``fcos_reg`` (4) and
+    ``fcos_centerness`` (1, off the cls tower) and one ``Scale`` per stride.  The state-dict keys are those of the modules
+    (``cls_convs.0.conv.weight``, ``cls_convs.0.norm.weight`` ... ``scales.4.scale``); mmdetection's ``.gn.`` spelling of
+    the norm keys is accepted on loading.  The predictors live in ``nn.Conv2d`` containers whose own forward is never
+    called.  ``forward`` returns the RAW ``fcos_reg`` outputs: ``fcos_loss`` and ``fcos_detections`` take the ``Scale``
+    parameters (``scale_vector()``) and apply ``exp(scale * x)`` themselves.  The whole head is one autograd node
+    (DESIGN.md §4o).  What the HIP path does not cover is accepted by the constructor and raises ``NotImplementedError``
+    in ``forward``."""
+
+    def __init__(self, num_classes, in_channels, feat_channels=256, stacked_convs=4, strides=(8, 16, 32, 64, 128),
+                 regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, INF)), conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True)):
+        super().__init__()
+        if num_classes < 2 or min(in_channels, feat_channels) < 1 or stacked_convs < 0 or not len(strides):
+            raise ValueError("FCOSHead: num_classes >= 2 (background included), positive sizes and a non-empty stride "
+                             "list are required")
+        if len(regress_ranges) != len(strides):
+            raise ValueError("FCOSHead: one regress range per stride")
+        self.num_classes = int(num_classes)
+        self.cls_out_channels = self.num_classes - 1
+        self.in_channels = int(in_channels)
+        self.feat_channels = int(feat_channels)
+        self.stacked_convs = int(stacked_convs)
+        self.strides = list(strides)
+        self.regress_ranges = [tuple(r) for r in regress_ranges]
+        self.conv_cfg = conv_cfg
+        self.norm_cfg = None if norm_cfg is None else dict(norm_cfg)
+        gn = self.norm_cfg is not None and self.norm_cfg.get('type') == 'GN'
+        self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
+        for convs in (self.cls_convs, self.reg_convs):
+            for i in range(self.stacked_convs):
+                m = ConvModule(self.in_channels if i == 0 else self.feat_channels, self.feat_channels, 3, padding=1,
+                               bias=not gn, normalize=True if gn else None, use_gn=gn, activation='relu')
+                if gn:
+                    m.norm = nn.GroupNorm(int(self.norm_cfg.get('num_groups', 32)), self.feat_channels)
+                    if not self.norm_cfg.get('requires_grad', True):
+                        m.norm.requires_grad_(False)
+                convs.append(m)
+        last = self.feat_channels if self.stacked_convs else self.in_channels
+        self.fcos_cls = nn.Conv2d(last, self.cls_out_channels, 3, padding=1)
+        self.fcos_reg = nn.Conv2d(last, 4, 3, padding=1)
+        self.fcos_centerness = nn.Conv2d(last, 1, 3, padding=1)
+        for m in (self.fcos_cls, self.fcos_reg, self.fcos_centerness):   # K-major, like the conv modules' weights
+            m.weight.data = m.weight.data.contiguous(memory_format=torch.channels_last)
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
+        self._routes = FCOS_ROUTES
+        self.init_weights()
+
+    def init_weights(self):
+        for m in list(self.cls_convs) + list(self.reg_convs):
+            nn.init.normal_(m.conv.weight, 0, 0.01)
+            if m.conv.bias is not None:
+                nn.init.constant_(m.conv.bias, 0)
+        for m in (self.fcos_cls, self.fcos_reg, self.fcos_centerness):
+            nn.init.normal_(m.weight, 0, 0.01)
+            nn.init.constant_(m.bias, 0)
+        nn.init.constant_(self.fcos_cls.bias, -math.log((1 - 0.01) / 0.01))    # bias_init_with_prob(0.01)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # mmdetection names a ConvModule's norm layer after its type: cls_convs.0.gn.weight
+        for k in [k for k in state_dict if k.startswith(prefix)]:
+            parts = k[len(prefix):].split('.')
+            if len(parts) == 4 and parts[0] in ('cls_convs', 'reg_convs') and parts[2] == 'gn':
+                parts[2] = 'norm'
+                state_dict[prefix + '.'.join(parts)] = state_dict.pop(k)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    _pyr_unit = RetinaHead._pyr_unit
+    _padded_conv = RetinaHead._padded_conv
+
+    def _chains(self, dtype):
+        """([cls tower, reg tower], [fcos_cls, fcos_reg, fcos_centerness]) with refreshed operands; a tower is a list of
+        (conv layer, GroupNorm layer or None)."""
+        for u in self.__dict__.get('_hip_units', {}).values():
+            if getattr(u, 'sink', None) is not None:
+                raise NotImplementedError("FCOSHead: a shared weight's per-level gradients cannot be written into a "
+                                          "gradient bucket")
+        frozen = self.norm_cfg is not None and not self.norm_cfg.get('requires_grad', True)
+        towers = []
+        for convs, tname in ((self.cls_convs, 'cls_convs'), (self.reg_convs, 'reg_convs')):
+            tower = []
+            for i, m in enumerate(convs):
+                name = '%s.%d' % (tname, i)
+                if m.with_norm:
+                    layer = (_RawLayer(self, name, m.conv, 'tower', False, dtype), _GnLayer(self, m.norm, frozen))
+                else:
+                    layer = (_Layer(self, name, m.conv, 'tower', True, dtype), None)
+                tower.append(layer)
+            towers.append(tower)
+        preds = [_Layer(self, name, conv, kind, False, dtype) for name, conv, kind in (
+            ('fcos_cls', self.fcos_cls, 'cls'), ('fcos_reg', self.fcos_reg, 'reg'),
+            ('fcos_centerness', self.fcos_centerness, 'ctr'))]
+        return towers, preds
+
+    def _params(self):
+        """The parameters in the order ``FCOSHeadFunction`` returns their gradients"""
+        out = []
+        for convs in (self.cls_convs, self.reg_convs):
+            for m in convs:
+                out.append(m.conv.weight)
+                if m.conv.bias is not None:
+                    out.append(m.conv.bias)
+                if m.with_norm:
+                    out += [m.norm.weight, m.norm.bias]
+        for m in (self.fcos_cls, self.fcos_reg, self.fcos_centerness):
+            out += [m.weight, m.bias]
+        return out
+
+    def _check_supported(self):
+        if self.conv_cfg is not None:
+            raise NotImplementedError("FCOSHead: conv_cfg other than None is not on the HIP path")
+        if self.norm_cfg is not None and self.norm_cfg.get('type') != 'GN':
+            raise NotImplementedError("FCOSHead: norm type %r is not on the HIP path (GN or no norm_cfg)"
+                                      % (self.norm_cfg.get('type'),))
+        for name, c in (("in_channels", self.in_channels), ("feat_channels", self.feat_channels)):
+            if c % 64 or c > pyramid_ops.MAX_CIN:
+                raise NotImplementedError("FCOSHead: %s=%d must be a multiple of 64, at most %d, on the HIP path"
+                                          % (name, c, pyramid_ops.MAX_CIN))
+        if self.cls_out_channels > pyramid_ops.MAX_COUT:
+            raise NotImplementedError("FCOSHead: %d class channels are not on the HIP path (at most %d)"
+                                      % (self.cls_out_channels, pyramid_ops.MAX_COUT))
+        if self.norm_cfg is not None and self.stacked_convs:
+            C, G = self.feat_channels, int(self.norm_cfg.get('num_groups', 32))
+            if C not in pyramid_ops.GN_CHANNELS or C % G or C // G > pyramid_ops.GN_MAX_CPG:
+                raise NotImplementedError("FCOSHead: GroupNorm(%d groups, feat_channels=%d) is not on the HIP path "
+                                          "(feat_channels one of %s, at most %d channels per group)"
+                                          % (G, C, ", ".join(map(str, pyramid_ops.GN_CHANNELS)), pyramid_ops.GN_MAX_CPG))
+
+    def forward(self, feats):
+        """feats: a list of 1..8 (B, in_channels, H_l, W_l) maps (16-bit channels_last is read in place, float32 is
+        converted as in the other heads) -> (cls_scores, bbox_preds, centernesses): lists of (B, num_classes - 1, H_l,
+        W_l), (B, 4, H_l, W_l) and (B, 1, H_l, W_l) tensors in the compute dtype, channels_last memory: what ``fcos_loss``
+        and ``fcos_detections`` take in place.  ``bbox_preds`` are the raw ``fcos_reg`` outputs."""
+        self._check_supported()
+        feats = list(feats)
+        if not 1 <= len(feats) <= pyramid_ops.MAX_LEVELS:
+            raise NotImplementedError("FCOSHead: feats must be a list of 1..%d levels on the HIP path, got %d"
+                                      % (pyramid_ops.MAX_LEVELS, len(feats)))
+        if torch.is_tensor(feats[0]) and feats[0].dtype == torch.float32:
+            dtype = pick_dtype(self, feats[0])
+            feats = [f.to(dtype) for f in feats]
+        n = len(feats)
+        out = FCOSHeadFunction.apply(self, n, *feats, *self._params())
+        return list(out[:n]), list(out[n:2 * n]), list(out[2 * n:])
+
+    def scale_vector(self):
+        """The ``Scale`` parameters as one (L,) float32 tensor (differentiable): ``fcos_loss`` / ``fcos_detections``'
+        ``scales``."""
+        return torch.stack([s.scale for s in self.scales])
+
+    def get_points(self, featmap_sizes, device=None):
+        return fcos_points(featmap_sizes, self.strides[:len(featmap_sizes)], device)
+
+    def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, gt_counts, center_sample_radius=None,
+             **cfg):
+        """``fcos_target`` with the head's strides and regress ranges, then ``fcos_loss`` with the head's ``Scale``s:
+        -> what ``fcos_loss`` returns.  ``cfg``: ``fcos_loss``'s loss_type / gamma / alpha / eps."""
+        n = len(cls_scores)
+        sizes = [tuple(t.shape[2:]) for t in cls_scores]
+        labels, bbox_targets, _, _ = fcos_target(sizes, self.strides[:n], self.regress_ranges[:n], gt_bboxes, gt_labels,
+                                                 gt_counts, center_sample_radius)
+        return fcos_loss(cls_scores, bbox_preds, centernesses, labels, bbox_targets, self.scale_vector()[:n], **cfg)
+
+    def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_shapes, scale_factors=None, **test_cfg):
+        """``fcos_detections`` with the head's strides and ``Scale``s on the head's outputs, in place; defaults nms_pre
+        1000, score_thr 0.05, nms_thr 0.5, max_per_img 100."""
+        n = len(cls_scores)
+        cfg = dict(nms_pre=1000, score_thr=0.05, nms_thr=0.5, max_per_img=100)
+        cfg.update(test_cfg)
+        return fcos_detections(cls_scores, bbox_preds, centernesses, self.strides[:n], img_shapes,
+                               self.scale_vector().detach()[:n], scale_factors, **cfg)

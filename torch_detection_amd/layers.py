@@ -119,3 +119,14 @@ class ConvModule(nn.Module):
         if isinstance(unit, HF.PreActUnit):
             return HF.PreActConvFunction.apply(unit, x, *unit.params())
         return HF.ConvUnitFunction.apply(unit, x, *unit.params())
+
+
+class Scale(nn.Module):
+    """A learnable scalar factor (mmdetection v1's ``Scale``): parameter ``scale``, float32, shape ()."""
+
+    def __init__(self, scale=1.0):
+        super(Scale, self).__init__()
+        self.scale = nn.Parameter(torch.tensor(scale, dtype=torch.float))
+
+    def forward(self, x):
+        return x * self.scale

@@ -18,7 +18,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._args import integer, on_device, tensor
+from ._args import integer, number, on_device, tensor
 from .deconv_ops import _nhwc
 from .dense_ops import _levels, _same_count, cotangents
 from .ops import BF16, F16, _aligned_ws, _ptr, _workspace, dtype_code  # noqa: F401  (_workspace: swapped by the guard)
@@ -230,3 +230,148 @@ def pyramid_conv_wgrad(xs, gs, channels_last=True):
     _lib.check(_lib.load().tdn_pyr_conv_wgrad(arr, len(xs), B, _ptr(dw), s[0], s[1], s[2], s[3], _ptr(db), Cin, Cout, wp,
                                               nbytes, dtype_code(dtype), _lib.stream_ptr()), "tdn_pyr_conv_wgrad")
     return dw, db
+
+
+# ---- GroupNorm (+ ReLU) with shared affine parameters over a pyramid (csrc/pyramid_gn.hip) --------------
+GN_FWD, GN_BWD = 0, 1
+GN_CHANNELS = (64, 128, 256, 512)
+GN_MAX_CPG = 256
+
+
+def _gn_channels(C, G):
+    C = integer(C, "C", 1)
+    if C not in GN_CHANNELS:
+        raise ValueError("C must be one of %s, got %d" % (", ".join(map(str, GN_CHANNELS)), C))
+    G = integer(G, "groups", 1)
+    if C % G or C // G > GN_MAX_CPG:
+        raise ValueError("groups must divide C = %d into at most %d channels per group, got %d" % (C, GN_MAX_CPG, G))
+    return C, G
+
+
+def _gn_geometry(B, sizes):
+    """As ``_geometry``, but a level may be empty (H or W zero)."""
+    B = integer(B, "B", 0, 65535 // MAX_LEVELS)
+    if not isinstance(sizes, (list, tuple)) or not 1 <= len(sizes) <= MAX_LEVELS:
+        raise ValueError("sizes must be a list of 1..%d (H, W) pairs, got %s" % (
+            MAX_LEVELS, len(sizes) if isinstance(sizes, (list, tuple)) else type(sizes).__name__))
+    out = []
+    for l, hw in enumerate(sizes):
+        H, W = integer(hw[0], "sizes[%d][0]" % l, 0), integer(hw[1], "sizes[%d][1]" % l, 0)
+        integer(H * W, "sizes[%d]: H*W" % l, 0, MAX_ROWS)
+        integer(B * H * W, "sizes[%d]: B*H*W" % l, 0, MAX_ROWS)
+        out.append((H, W))
+    return B, out
+
+
+def _gn_maps(zs, name="zs"):
+    """The raw conv outputs: -> (list, dtype, B, C, [(H, W)]).  One dtype, one batch size, one channel count."""
+    zs = _levels(zs, name)
+    B, C, H, W = _nhwc(zs[0], "%s[0]" % name, _16, ("B", "C", "H", "W"))
+    dtype = zs[0].dtype
+    sizes = []
+    for l, z in enumerate(zs):
+        _, _, H, W = _nhwc(z, "%s[%d]" % (name, l), dtype, (B, C, "H", "W"))
+        sizes.append((H, W))
+    B, sizes = _gn_geometry(B, sizes)
+    return zs, dtype, B, C, sizes
+
+
+def _gn_same(ts, name, dtype, B, C, sizes):
+    ts = _same_count(ts, name, len(sizes))
+    for l, (t, (H, W)) in enumerate(zip(ts, sizes)):
+        _nhwc(t, "%s[%d]" % (name, l), dtype, (B, C, H, W))
+    return ts
+
+
+def _gn_table(sizes, z, y=None, g=None, dz=None):
+    arr = (_lib.PyrGnLevel * len(sizes))()
+    ptr = lambda ts, l: ts[l].data_ptr() if ts is not None and ts[l].numel() else None
+    for l, (H, W) in enumerate(sizes):
+        arr[l].z, arr[l].y, arr[l].g, arr[l].dz = ptr(z, l), ptr(y, l), ptr(g, l), ptr(dz, l)
+        arr[l].H, arr[l].W = H, W
+    return arr
+
+
+class PyramidGnPlan(object):
+    """What ``tdn_pyr_gn_plan`` answered (host side).  ``chunks[l]``: pixel chunks per image of level l (0: the level is
+    skipped), ``chunk_pixels[l]``: pixels per chunk, ``workgroups``: of the three launches."""
+    __slots__ = ("chunks", "chunk_pixels", "workgroups", "launches", "lanes_per_workgroup", "channels_per_block",
+                 "workspace_bytes")
+
+
+def pyramid_gn_plan(kind, B, sizes, C, groups):
+    """Host only: how one GroupNorm product (kind GN_FWD / GN_BWD) over levels of ``sizes[l]`` = (H_l, W_l) and batch
+    size B is cut.  Refusals are ValueErrors."""
+    if kind not in (GN_FWD, GN_BWD):
+        raise ValueError("kind must be GN_FWD (0) or GN_BWD (1), got %r" % (kind,))
+    B, sizes = _gn_geometry(B, sizes)
+    C, G = _gn_channels(C, groups)
+    out = (ctypes.c_int32 * 32)()
+    if _lib.load().tdn_pyr_gn_plan(int(kind), B, _hw(sizes), len(sizes), C, G, out) != 0:
+        _lib.ws_bytes(-1, "pyramid_gn_plan")
+    pl = PyramidGnPlan()
+    n = len(sizes)
+    pl.chunks, pl.chunk_pixels = list(out)[:n], list(out)[MAX_LEVELS:MAX_LEVELS + n]
+    pl.workgroups, pl.launches = tuple(out[16:19]), out[19]
+    pl.lanes_per_workgroup, pl.channels_per_block = out[20], out[21]
+    pl.workspace_bytes = out[22] + (out[23] << 31)
+    return pl
+
+
+def _gn_ws(kind, B, sizes, C, G, dev):
+    nbytes = _lib.ws_bytes(_lib.load().tdn_pyr_gn_workspace_bytes(kind, B, _hw(sizes), len(sizes), C, G),
+                           "pyramid GroupNorm workspace")
+    return (_aligned_ws(nbytes, dev) if nbytes else (None, None)) + (nbytes,)
+
+
+def pyramid_gn_fwd(zs, gamma, beta, groups, eps=1e-5, relu=True):
+    """-> (ys, stats): ``y_l = [relu](GroupNorm(z_l) * gamma + beta)`` for all levels in three launches, the statistics per
+    (level, image, group); ``ys[l]`` like ``zs[l]`` (logical (B, C, H_l, W_l), channels_last memory), ``stats``
+    (L, B, C, 2) float32 = (mean, rstd) of the channel's group, kept for ``pyramid_gn_bwd``.  ``gamma``, ``beta``: (C,)
+    float32, shared by the levels.  A level may be empty."""
+    zs, dtype, B, C, sizes = _gn_maps(zs)
+    C, G = _gn_channels(C, groups)
+    tensor(gamma, "gamma", F32, (C,))
+    tensor(beta, "beta", F32, (C,))
+    eps = number(eps, "eps", positive=True)
+    on_device([("zs[%d]" % l, z) for l, z in enumerate(zs)] + [("gamma", gamma), ("beta", beta)])
+    dev = zs[0].device
+    ys = [torch.empty((B, H, W, C), dtype=dtype, device=dev) for H, W in sizes]
+    stats = torch.empty((len(sizes), B, C, 2), dtype=F32, device=dev)
+    ws, wp, nbytes = _gn_ws(GN_FWD, B, sizes, C, G, dev)
+    arr = _gn_table(sizes, zs, y=ys)
+    _lib.check(_lib.load().tdn_pyr_gn_fwd(arr, len(zs), B, _ptr(gamma), _ptr(beta), C, G, eps, 1 if relu else 0,
+                                          _ptr(stats), wp, nbytes, dtype_code(dtype), _lib.stream_ptr()),
+               "tdn_pyr_gn_fwd")
+    return [t.permute(0, 3, 1, 2) for t in ys], stats
+
+
+def pyramid_gn_bwd(gs, ys, zs, stats, gamma, groups, relu=True, dgamma=None, dbeta=None, accumulate=False):
+    """-> (dzs, dgamma, dbeta) from the UNMASKED cotangents ``gs[l]`` = dL/dy_l: where ``ys[l] <= 0`` (``relu``) the
+    cotangent counts as exactly 0, in the sums and in ``dz``; ``ys`` may be None without ``relu``.  ``dgamma`` / ``dbeta``
+    (C,) float32 are the sums over all levels and images, added in level order, finest first; given buffers are
+    overwritten, or added to with ``accumulate``.  Three launches; the same bits on every run."""
+    zs, dtype, B, C, sizes = _gn_maps(zs)
+    C, G = _gn_channels(C, groups)
+    gs = cotangents(gs, "gs", dtype, B, C, sizes)
+    if relu or ys is not None:
+        ys = _gn_same(ys, "ys", dtype, B, C, sizes)
+    tensor(stats, "stats", F32, (len(sizes), B, C, 2))
+    tensor(gamma, "gamma", F32, (C,))
+    dev = zs[0].device
+    if dgamma is None:
+        dgamma = torch.empty((C,), dtype=F32, device=dev)
+    if dbeta is None:
+        dbeta = torch.empty((C,), dtype=F32, device=dev)
+    tensor(dgamma, "dgamma", F32, (C,))
+    tensor(dbeta, "dbeta", F32, (C,))
+    on_device([("zs[%d]" % l, z) for l, z in enumerate(zs)] + [("gs[%d]" % l, g) for l, g in enumerate(gs)] +
+              [("ys[%d]" % l, y) for l, y in enumerate(ys or [])] +
+              [("stats", stats), ("gamma", gamma), ("dgamma", dgamma), ("dbeta", dbeta)])
+    dzs = [torch.empty((B, H, W, C), dtype=dtype, device=dev) for H, W in sizes]
+    ws, wp, nbytes = _gn_ws(GN_BWD, B, sizes, C, G, dev)
+    arr = _gn_table(sizes, zs, y=ys, g=gs, dz=dzs)
+    _lib.check(_lib.load().tdn_pyr_gn_bwd(arr, len(zs), B, _ptr(stats), _ptr(gamma), C, G, 1 if relu else 0,
+                                          _ptr(dgamma), _ptr(dbeta), 1.0 if accumulate else 0.0, wp, nbytes,
+                                          dtype_code(dtype), _lib.stream_ptr()), "tdn_pyr_gn_bwd")
+    return [t.permute(0, 3, 1, 2) for t in dzs], dgamma, dbeta
