@@ -1190,6 +1190,50 @@ int tdn_pyr_gn_bwd(const tdn_pyr_gn_level* levels, int num_levels, int B, const 
                    int G, int relu, float* dgamma, float* dbeta, float acc, void* workspace, int64_t workspace_bytes,
                    int dtype, void* stream);
 
+/* ---- deformable convolution, DCN v1 / v2 (csrc/deform.hip) ---------------------------------------------
+ * y = conv1x1(cols, W) with cols[n, ho, wo, k, c] the bilinear sample of x (N, H, W, C NHWC, 16-bit) at
+ * (ho stride - pad + i pad + dy, wo stride - pad + j pad + dx), tap k = 3 i + j of a 3x3 kernel with dilation == pad,
+ * (dy, dx) = offset channels 2 (g 9 + k), 2 (g 9 + k) + 1 of deformable group g = c / (C / deformable_groups), times the
+ * mask channel g 9 + k when mask != NULL (mask_is_logit: times 1 / (1 + exp(-mask)), fp32).  offset (N, Ho, Wo, >= 18 dg)
+ * and mask (N, Ho, Wo, >= 9 dg) are NHWC with offset_pitch / mask_pitch ELEMENTS between pixels, fp32 (TDN_F32) or the
+ * compute dtype.  A sample is valid iff -1 < py < H and -1 < px < W, tested on the floats (NaN, inf: invalid); an invalid
+ * sample is 0 and has zero gradients; a corner outside the map contributes exactly 0.  fp32 arithmetic in the order of
+ * DESIGN.md §4p, one rounding to the compute dtype.  C a multiple of 64, (C / dg) a multiple of 8, stride 1 or 2, pad 1..32,
+ * H, W <= 32766, N Ho Wo 9 dg < 2^30.
+ *   tdn_deform_sample:      cols (N Ho Wo, 9 C) compute dtype, K index k C + c; 16-byte aligned.
+ *   tdn_pack_deform_weight: fp32 (Cout, C, 3, 3) of any element strides -> w_fwd [Cout][9 C] (the 1x1 forward operand over
+ *                           cols) and w_dgrad [9 C][Cout] (its tdn_conv2d_dgrad operand; may be NULL), one launch.
+ *   tdn_deform_coord_grad:  doffset / dmask in the offset's / mask's own dtype and pitch from dcol (N Ho Wo, 9 C):
+ *                           d dy = m sum_c dcol ((v3 - v1) hx + (v4 - v2) lx), d dx = m sum_c dcol ((v2 - v1) hy + (v4 - v3) ly),
+ *                           d m = sum_c dcol val (times s (1 - s) = t / (1 + t)^2, t = exp(-|m|), for a logit), sums over the group's channels in fp32: each
+ *                           of L = min(64, 2^ceil(log2(C / dg / 8))) lanes its 8-channel groups in order, then a fixed xor
+ *                           tree.  Channels of a pixel past 18 dg / 9 dg are not written.
+ *   tdn_deform_input_grad:  dx (N, H, W, C) compute dtype, every pixel written once: the fp32 sum of dcol m w_corner over
+ *                           the valid samples' corners landing on it, in sample order ((ho, wo), g, k), rounded once.  Two
+ *                           launches, no atomics: the same bits on every run.  x of the descriptor is not read.
+ *   tdn_deform_workspace_bytes (host only): bytes of tdn_deform_input_grad's workspace (256-byte aligned): records
+ *                           [N][chunks][256] of 16 bytes | boxes [N][chunks] of 16 bytes, chunks = ceil(Ho Wo dg 9 / 256),
+ *                           each region from a 256-byte boundary; -1 on a refused shape. */
+typedef struct tdn_deform_desc {
+  const void* x;
+  const void* offset;
+  const void* mask;            /* NULL: DCN v1 */
+  int64_t offset_pitch;
+  int64_t mask_pitch;
+  int32_t N, H, W, C;
+  int32_t stride, pad, deformable_groups;
+  int32_t dtype, offset_dtype, mask_dtype;
+  int32_t mask_is_logit;
+  int32_t reserved;
+} tdn_deform_desc;
+int64_t tdn_deform_workspace_bytes(int N, int H, int W, int stride, int pad, int deformable_groups);
+int tdn_deform_sample(const tdn_deform_desc* d, void* cols, void* stream);
+int tdn_pack_deform_weight(const float* w, int64_t s_o, int64_t s_i, int64_t s_h, int64_t s_w, int Cout, int C,
+                           void* w_fwd, void* w_dgrad, int dtype, void* stream);
+int tdn_deform_coord_grad(const tdn_deform_desc* d, const void* dcol, void* doffset, void* dmask, void* stream);
+int tdn_deform_input_grad(const tdn_deform_desc* d, const void* dcol, void* dx, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

@@ -13,7 +13,8 @@ fully connected layers ``linear`` / ``BBoxHead`` between ``roi_align`` and the b
 conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask loss, and ``RPNHead`` between ``FPN`` and
 ``rpn_loss`` / ``rpn_proposals``, and the single-stage path ``RetinaHead`` between ``FPN`` and ``anchor_target_all`` /
 ``anchor_head_loss`` / ``anchor_head_detections``, and ``FCOSHead`` with the operations around it: ``fcos_points`` /
-``fcos_target`` / ``fcos_loss`` / ``fcos_detections``).  Everything computes through libtdn.so
+``fcos_target`` / ``fcos_loss`` / ``fcos_detections``, and deformable convolution ``deform_conv2d`` with the modules
+``DeformConv`` / ``ModulatedDeformConv`` / ``DeformConvPack`` / ``ModulatedDeformConvPack``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -45,6 +46,8 @@ from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_t
 from .optim import SGD  # noqa: F401
 from .linear import LinearFunction, linear  # noqa: F401
 from .deconv import ConvTranspose2x2Function, conv_transpose2x2  # noqa: F401
+from .deform import (DeformConv, DeformConvFunction, DeformConvPack, ModulatedDeformConv,  # noqa: F401
+                     ModulatedDeformConvPack, deform_conv2d)
 from .heads import BBoxHead, FCNMaskHead, FCOSHead, RetinaHead, RPNHead  # noqa: F401
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)

@@ -179,6 +179,16 @@ class RoiConfig(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("scales", c_float * 8)]
 
 
+class DeformDesc(ctypes.Structure):
+    """Mirror of ``tdn_deform_desc`` (include/tdn.h)."""
+    _fields_ = [("x", c_void_p), ("offset", c_void_p), ("mask", c_void_p), ("offset_pitch", c_i64),
+                ("mask_pitch", c_i64), ("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("C", ctypes.c_int32), ("stride", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("deformable_groups", ctypes.c_int32), ("dtype", ctypes.c_int32), ("offset_dtype", ctypes.c_int32),
+                ("mask_dtype", ctypes.c_int32), ("mask_is_logit", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+_DfD = ctypes.POINTER(DeformDesc)
 _RoL = ctypes.POINTER(RoiLevel)
 _RoC = ctypes.POINTER(RoiConfig)
 
@@ -445,6 +455,12 @@ SIGNATURES = {
     "tdn_roi_align_bwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p, c_i64,
                                   c_void_p]),
     "tdn_rois_from_proposals": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "tdn_deform_workspace_bytes": (c_i64, [c_int] * 6),
+    "tdn_deform_sample": (c_int, [_DfD, c_void_p, c_void_p]),
+    "tdn_pack_deform_weight": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_int,
+                                       c_void_p]),
+    "tdn_deform_coord_grad": (c_int, [_DfD, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tdn_deform_input_grad": (c_int, [_DfD, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "tdn_pack_gconv_weight": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p, c_void_p, c_int, c_void_p]),
     "tdn_bottleneck_supported": (c_int, [c_int] * 5),

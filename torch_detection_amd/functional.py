@@ -253,6 +253,7 @@ def invalidate_packed(*modules):
     ordinary in-place updates under ``torch.no_grad()`` (what optimizers do) are picked up automatically."""
     from .linear import forget               # imported here: linear.py imports this module
     from .deconv import forget as forget_deconv
+    from .deform import forget as forget_deform
     for m in modules:
         for sub in m.modules():
             for u in sub.__dict__.get('_hip_units', {}).values():
@@ -260,6 +261,7 @@ def invalidate_packed(*modules):
         for p in m.parameters():
             forget(p)                        # packed copies made by a bare linear() call on this parameter
             forget_deconv(p)                 # ... or by a bare conv_transpose2x2() call
+            forget_deform(p)                 # ... or by deform_conv2d() / the deformable modules
 
 
 class StagedImages(object):
