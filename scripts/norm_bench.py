@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Median device-event time of gn_fwd / bn_train_fwd (+ residual add, ReLU) at (2, 256, 200, 336) bf16: 30 warm-up
-calls, then 300 timed replays each; prints one JSON line (median, 10th and 90th percentile in microseconds).
+"""Median device-event time of gn_fwd / bn_train_fwd (+ residual add, ReLU) and of gn_bwd / bn_train_bwd at
+(2, 256, 200, 336) bf16: 30 warm-up calls, then 300 timed replays each; prints one JSON line (median, 10th and 90th
+percentile in microseconds).
 TDN_LIB=<another build in the package directory> times that build instead, for an A/B run in alternation."""
 import json
 import os
@@ -18,6 +19,9 @@ beta = torch.rand(C, device="cuda", generator=g) - 0.5
 rm, rv = torch.zeros(C, device="cuda"), torch.ones(C, device="cuda")
 fns = {"gn_fwd": lambda: ops.gn_fwd(z, gamma, beta, 32, 1e-5, res, True),
        "bn_train_fwd": lambda: ops.bn_train_fwd(z, gamma, beta, rm, rv, 0.1, 1e-5, res, True)}
+gn_stats, bn_stats = fns["gn_fwd"]()[1], fns["bn_train_fwd"]()[1]
+fns["gn_bwd"] = lambda: ops.gn_bwd(res, z, gn_stats, gamma, 32)
+fns["bn_train_bwd"] = lambda: ops.bn_train_bwd(res, z, bn_stats, gamma)
 out = {"lib": os.path.basename(_lib.LIB_PATH)}
 for name, fn in fns.items():
     for _ in range(30):

@@ -256,6 +256,26 @@ def test_one_launch_over_the_pyramid_equals_level_by_level(P, name, cg):
 
 
 @pytest.mark.parametrize("dt", [BF, FP], ids=_id)
+@pytest.mark.parametrize("shape", [(2, 6, 10, 64, 32), (1, 37, 41, 64, 32), (2, 3, 2, 512, 2)],
+                         ids=lambda s: "B%d-%dx%d-C%d-G%d" % s)
+def test_a_single_level_equals_the_single_map_kernels_bit_for_bit(P, shape, dt):
+    """One level through pyramid_gn_fwd and the same map through ops.gn_fwd (no addend): the same bits of y and of the
+    statistics.  The shapes: one chunk; several chunks with a ragged last one; 256 channels per group."""
+    from torch_detection_amd import ops
+    B, H, W, C, Gr = shape
+    gamma, beta = GN._affine(C)
+    zs, _ = inputs(B, [(H, W)], C, dt)
+    zd = dev(zs[0], dt)
+    gam, bet = GN._vec(gamma), GN._vec(beta)
+    for relu in (False, True):
+        ys, stats = P.pyramid_gn_fwd([zd], gam, bet, Gr, EPS, relu)
+        y1, stats1 = ops.gn_fwd(zd.permute(0, 2, 3, 1), gam, bet, Gr, EPS, None, relu)
+        assert tuple(stats.shape) == (1, B, C, 2) and tuple(stats1.shape) == (B, C, 2)
+        assert same_bits(ys[0].permute(0, 2, 3, 1), y1), "y, relu=%d" % relu
+        assert same_bits(stats[0], stats1), "stats, relu=%d" % relu
+
+
+@pytest.mark.parametrize("dt", [BF, FP], ids=_id)
 def test_twice_and_graph_replay_are_bit_identical(P, dt):
     B, sizes = PYRAMIDS["chunks"]
     C, Gr = 256, 32

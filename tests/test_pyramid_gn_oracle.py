@@ -107,6 +107,18 @@ def test_the_cut_is_a_function_of_the_shapes_and_of_each_level_alone():
     assert big[0] == 2
 
 
+def test_a_single_level_is_cut_like_the_single_map_kernels():
+    """A one-level plan reports the `chunks` that tdn_gn_workspace(B, H, W, C, G) implies: its size is
+    256 + 4 * (B * chunks * 2 * C + 3 * B * C) bytes (the layout restated in tests/test_norm_oracle.py), solved for chunks."""
+    lib = _lib()
+    for B, H, W, C, G in ((2, 6, 10, 64, 32), (1, 37, 41, 64, 32), (2, 3, 2, 512, 2), (512, 9, 8, 64, 32),
+                          (1, 1, 1, 256, 32)):
+        size = lib.tdn_gn_workspace(B, H, W, C, G)
+        assert size > 0 and (size - 256 - B * C * 12) % (B * 2 * C * 4) == 0, (B, H, W, C, G)
+        rc, plan = _plan(0, B, [(H, W)], C, G)
+        assert rc == 0 and plan[0] == (size - 256 - B * C * 12) // (B * 2 * C * 4), (B, H, W, C, G)
+
+
 def test_an_empty_level_contributes_no_chunks():
     full = [(9, 8), (5, 4), (3, 2)]
     hole = [(9, 8), (0, 4), (3, 2)]

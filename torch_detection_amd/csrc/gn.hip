@@ -16,17 +16,15 @@
 //             per-(sample, channel) coefficients of dz = g*A + z*B + C  ->  [3'] dz, which then feeds the ordinary
 //             conv dgrad / wgrad kernels.
 // All three passes are HBM-bound streams, 16 bytes (8 channels) per lane; reductions are fixed-order (deterministic).
-#include "common.h"
+#include "norm_core.h"
 
 namespace {
-
-constexpr int kThreads = 256;
 
 struct GnGeom {
   int N, HW, C, G, cpg;      // cpg = C / G channels per group
   int C8;                    // C / 8 lanes per pixel
   int ppp;                   // pixels per pass of one 256-thread block
-  int chunks, chunk_px;      // pixel chunks per sample, pixels per chunk
+  int chunks, chunk_px;      // pixel chunks per sample, pixels per chunk: norm_core.h's cut_of
 };
 
 // [1] / [1']: partial per-channel sums over one pixel chunk of one sample.
@@ -97,41 +95,9 @@ __global__ __launch_bounds__(kThreads) void gn_partial_kernel(const bf16_t* __re
   }
 }
 
-// the pivot of channel c of sample n as the partial kernel read it
-__device__ __forceinline__ double pivot_of(const bf16_t* __restrict__ z, int64_t idx, int f16) {
-  return (double)(f16 ? elem_to_f32<true>(z[idx]) : elem_to_f32<false>(z[idx]));
-}
-
-// Sum of the per-chunk partials of channel c of sample n, both planes, by the KL chunk-lanes of a block (thread
-// (cl, kl) takes chunks kl, kl+KL, ...; lanes combined through LDS in lane order -> deterministic).  CB channels per
-// block, CB * KL = kThreads.  Returns the totals to every thread with kl == 0.
-__device__ __forceinline__ void chunk_totals(const float* __restrict__ part, const GnGeom& ge, int n, int c, int cl,
-                                             int kl, int CB, int KL, bool live, double* red /*[2][kThreads]*/,
-                                             double& s, double& ss) {
-  double a = 0.0, b = 0.0;
-  if (live) {
-    for (int k = kl; k < ge.chunks; k += KL) {
-      const float* q = part + (((int64_t)n * ge.chunks + k) * 2) * ge.C + c;
-      a += (double)q[0];
-      b += (double)q[ge.C];
-    }
-  }
-  red[kl * CB + cl] = a;
-  red[kThreads + kl * CB + cl] = b;
-  __syncthreads();
-  s = 0.0; ss = 0.0;
-  if (kl == 0) {
-    for (int j = 0; j < KL; ++j) { s += red[j * CB + cl]; ss += red[kThreads + j * CB + cl]; }
-  }
-  __syncthreads();
-}
-
 // [2]: block (sample n, channel block of CB = max(32, cpg) channels — whole groups); chunk sums -> group mean / rstd
-// (double), then per-channel stats[n][c] = (mu, rstd) and the three planes coef[3][n][c] = a, b, K of y = (z - K)*a + b
-// (planes, so that a lane's 8 channels are 32 contiguous bytes of each: fewer cache lines per load than [n][c][3]).
-// With s_c = sum (z - K_c), q_c = sum (z - K_c)^2 over the HW pixels of channel c:
-//   mu = sum_c (s_c + HW K_c) / cnt,   cnt var = sum_c (q_c + 2 (K_c - mu) s_c + HW (K_c - mu)^2)
-// (the second moment about the group mean, cross terms between the channels' pivots included), in channel order.
+// (norm_core.h's group_moments), then per-channel stats[n][c] = (mu, rstd) and the three planes coef[3][n][c] = a, b, K of
+// y = (z - K)*a + b (planes: a lane's 8 channels are 32 contiguous bytes of each, fewer cache lines than [n][c][3]).
 __global__ __launch_bounds__(kThreads) void gn_stats_kernel(const float* __restrict__ part, GnGeom ge, int CB,
                                                             const bf16_t* __restrict__ z, int f16,
                                                             const float* __restrict__ gamma,
@@ -142,34 +108,23 @@ __global__ __launch_bounds__(kThreads) void gn_stats_kernel(const float* __restr
   const int n = blockIdx.y;
   const int KL = kThreads / CB;
   const int cl = threadIdx.x % CB, kl = threadIdx.x / CB;
-  const int c = blockIdx.x * CB + cl;
-  // asked for ahead of the chunk sums, so that its latency hides behind theirs
-  const double K = (kl == 0 && c < ge.C) ? pivot_of(z, (int64_t)n * ge.HW * ge.C + c, f16) : 0.0;
+  const int c = blockIdx.x * CB + cl;               // < C: CB divides C
+  const bf16_t* zc = z + (int64_t)n * ge.HW * ge.C + c;
+  const double K = kl == 0 ? pivot_of(zc, f16) : 0.0;     // asked for ahead of the chunk sums: its latency hides
   double s, ss;
-  chunk_totals(part, ge, n, c, cl, kl, CB, KL, c < ge.C, red, s, ss);
+  row_totals(part + (int64_t)n * ge.chunks * 2 * ge.C, ge.chunks, ge.C, c, cl, kl, CB, KL, red, s, ss);
   if (kl == 0) { tot[cl] = s; tot[kThreads + cl] = ss; tot[2 * kThreads + cl] = K; }
   __syncthreads();
-  if (kl == 0 && c < ge.C) {
-    const int g0 = (cl / ge.cpg) * ge.cpg;
-    const double hw = (double)ge.HW, cnt = hw * ge.cpg;
-    double gs = 0.0;
-    for (int j = 0; j < ge.cpg; ++j) gs += tot[g0 + j] + hw * tot[2 * kThreads + g0 + j];
-    const double mu = gs / cnt;
-    double m2 = 0.0;
-    for (int j = 0; j < ge.cpg; ++j) {
-      const double dk = tot[2 * kThreads + g0 + j] - mu;
-      m2 += tot[kThreads + g0 + j] + 2.0 * dk * tot[g0 + j] + hw * dk * dk;
-    }
-    double var = m2 / cnt;                  // biased variance, like nn.GroupNorm
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    stats[((int64_t)n * ge.C + c) * 2] = (float)mu;
-    stats[((int64_t)n * ge.C + c) * 2 + 1] = rstd;
-    const float a = rstd * gamma[c];
+  if (kl == 0) {
+    const Moments m = group_moments(tot, (cl / ge.cpg) * ge.cpg, ge.cpg, ge.HW, eps);
+    stats[((int64_t)n * ge.C + c) * 2] = (float)m.mu;
+    stats[((int64_t)n * ge.C + c) * 2 + 1] = m.rstd;
+    float a, b;
+    fwd_coef(m.rstd, gamma[c], beta[c], m.mu - K, a, b);
     float* o = coef + (int64_t)n * ge.C + c;
     const int64_t plane = (int64_t)ge.N * ge.C;
     o[0] = a;
-    o[plane] = (float)((double)beta[c] - (mu - K) * (double)a);
+    o[plane] = b;
     o[2 * plane] = (float)K;
   }
 }
@@ -230,14 +185,15 @@ __global__ __launch_bounds__(kThreads) void gn_bwd_coef_kernel(const float* __re
   __shared__ float t1[kThreads], t2[kThreads];
   const int KL = kThreads / CB;
   const int cl = threadIdx.x % CB, kl = threadIdx.x / CB;
-  const int c = blockIdx.x * CB + cl;
-  const bool live = c < ge.C;
-  const float gm = live ? gamma[c] : 0.f;
+  const int c = blockIdx.x * CB + cl;               // < C: CB divides C
+  const float gm = gamma[c];
   float dg = 0.f, db = 0.f;
   const float cnt = (float)ge.HW * (float)ge.cpg;
   for (int n = 0; n < ge.N; ++n) {
+    // `red` is written again here: its last read, inside row_totals of the previous sample, is followed by the two
+    // barriers below, and t1 / t2 are written only after the barrier inside row_totals, which follows their last read
     double d1, d2;
-    chunk_totals(part, ge, n, c, cl, kl, CB, KL, live, red, d1, d2);
+    row_totals(part + (int64_t)n * ge.chunks * 2 * ge.C, ge.chunks, ge.C, c, cl, kl, CB, KL, red, d1, d2);
     const float s1 = (float)d1, s2 = (float)d2;
     if (kl == 0) {
       dg += s2;
@@ -246,12 +202,9 @@ __global__ __launch_bounds__(kThreads) void gn_bwd_coef_kernel(const float* __re
       t2[cl] = gm * s2;
     }
     __syncthreads();
-    if (kl == 0 && live) {
-      const int l0 = (cl / ge.cpg) * ge.cpg;
-      float m1 = 0.f, m2 = 0.f;
-      for (int j = 0; j < ge.cpg; ++j) { m1 += t1[l0 + j]; m2 += t2[l0 + j]; }
-      m1 /= cnt;
-      m2 /= cnt;
+    if (kl == 0) {
+      float m1, m2;
+      group_means(t1, t2, (cl / ge.cpg) * ge.cpg, ge.cpg, cnt, m1, m2);
       const float mu = stats[((int64_t)n * ge.C + c) * 2], r = stats[((int64_t)n * ge.C + c) * 2 + 1];
       float* o = coef3 + ((int64_t)n * ge.C + c) * 3;
       o[0] = r * gm;                       // A
@@ -260,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void gn_bwd_coef_kernel(const float* __re
     }
     __syncthreads();
   }
-  if (kl == 0 && live) {
+  if (kl == 0) {
     dgamma[c] = (acc != 0.f) ? acc * dgamma[c] + dg : dg;
     dbeta[c] = (acc != 0.f) ? acc * dbeta[c] + db : db;
   }
@@ -289,26 +242,8 @@ __global__ void gn_bwd_apply_kernel(const bf16_t* __restrict__ g, const bf16_t* 
 // ---- training-mode BatchNorm2d (batch statistics): the same three passes with the statistics taken per channel over
 // the whole batch (N, H, W) instead of per (sample, group).  Only the two small middle kernels differ; stats / coef
 // are still written per (sample, channel) — identical for every sample — so the element-wise passes are shared. ----
-// totals over ALL samples and chunks of channel c, by the KL lanes of a block of CB = 32 channels
-__device__ __forceinline__ void batch_totals(const float* __restrict__ part, const GnGeom& ge, int c, int cl, int kl,
-                                             int CB, int KL, bool live, double* red, double& s, double& ss) {
-  double a = 0.0, b = 0.0;
-  if (live) {
-    for (int k = kl; k < ge.N * ge.chunks; k += KL) {   // [n][chunk] is one flat index of the partials
-      const float* q = part + ((int64_t)k * 2) * ge.C + c;
-      a += (double)q[0];
-      b += (double)q[ge.C];
-    }
-  }
-  red[kl * CB + cl] = a;
-  red[kThreads + kl * CB + cl] = b;
-  __syncthreads();
-  s = 0.0; ss = 0.0;
-  if (kl == 0) {
-    for (int j = 0; j < KL; ++j) { s += red[j * CB + cl]; ss += red[kThreads + j * CB + cl]; }
-  }
-}
-
+// A block is CB = 32 channels (32 divides C); its totals run over ALL samples and chunks of a channel: [n][chunk] is
+// one flat index of the rows of the partials.
 // The pivot K_c is common to all samples (sample 0's pixel 0): mu = K_c + s / cnt, var = q / cnt - (s / cnt)^2 with
 // s, q the sums of z - K_c and its square over the batch, both of the size of the spread.
 __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const float* __restrict__ part, GnGeom ge,
@@ -321,18 +256,18 @@ __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const float* __restr
   constexpr int CB = 32, KL = kThreads / CB;
   const int cl = threadIdx.x % CB, kl = threadIdx.x / CB;
   const int c = blockIdx.x * CB + cl;
-  const double K = (kl == 0 && c < ge.C) ? pivot_of(z, c, f16) : 0.0;   // ahead of the sums: its latency hides
+  const double K = kl == 0 ? pivot_of(z + c, f16) : 0.0;   // ahead of the sums: its latency hides
   double s, ss;
-  batch_totals(part, ge, c, cl, kl, CB, KL, c < ge.C, red, s, ss);
-  if (kl != 0 || c >= ge.C) return;
+  row_totals(part, ge.N * ge.chunks, ge.C, c, cl, kl, CB, KL, red, s, ss);
+  if (kl != 0) return;
   const double cnt = (double)ge.N * ge.HW;
   const double dm = s / cnt;
   const double mu = K + dm;
   double var = ss / cnt - dm * dm;             // biased variance normalises (nn.BatchNorm2d, training)
-  if (var < 0.0) var = 0.0;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+  const float rstd = rstd_of(var, eps);
   const float muf = (float)mu;
-  const float a = rstd * gamma[c], b = (float)((double)beta[c] - dm * (double)a);
+  float a, b;
+  fwd_coef(rstd, gamma[c], beta[c], dm, a, b);
   for (int n = 0; n < ge.N; ++n) {
     stats[((int64_t)n * ge.C + c) * 2] = muf;
     stats[((int64_t)n * ge.C + c) * 2 + 1] = rstd;
@@ -346,6 +281,27 @@ __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const float* __restr
     const double unb = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
     running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * muf;
     running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
+  }
+}
+
+// bn_bwd_coef_kernel's own copy of row_totals(part, N * chunks, ...), dead `live` predicate included: with the shared
+// one this kernel is allocated more registers (profiles/norm_core_refactor_checks.md §2), so it keeps its old text.
+__device__ __forceinline__ void batch_totals(const float* __restrict__ part, const GnGeom& ge, int c, int cl, int kl,
+                                             int CB, int KL, bool live, double* red, double& s, double& ss) {
+  double a = 0.0, b = 0.0;
+  if (live) {
+    for (int k = kl; k < ge.N * ge.chunks; k += KL) {
+      const float* q = part + ((int64_t)k * 2) * ge.C + c;
+      a += (double)q[0];
+      b += (double)q[ge.C];
+    }
+  }
+  red[kl * CB + cl] = a;
+  red[kThreads + kl * CB + cl] = b;
+  __syncthreads();
+  s = 0.0; ss = 0.0;
+  if (kl == 0) {
+    for (int j = 0; j < KL; ++j) { s += red[j * CB + cl]; ss += red[kThreads + j * CB + cl]; }
   }
 }
 
@@ -383,60 +339,84 @@ int make_geom(GnGeom& ge, int N, int H, int W, int C, int G) {
   ge.N = N; ge.HW = H * W; ge.C = C; ge.G = G; ge.cpg = C / G;
   TDN_CHECK((ge.cpg & (ge.cpg - 1)) == 0 && ge.cpg <= 256, "GroupNorm: %d channels per group not supported", ge.cpg);
   ge.C8 = C / 8;
-  ge.ppp = kThreads / ge.C8;
-  int chunks = ceil_div(1024, N);                       // ~1024 blocks in flight
-  const int max_chunks = ceil_div(ge.HW, ge.ppp * 4);   // at least 4 passes per block
-  if (chunks > max_chunks) chunks = max_chunks;
-  if (chunks < 1) chunks = 1;
-  ge.chunk_px = ceil_div(ge.HW, chunks);
-  ge.chunks = ceil_div(ge.HW, ge.chunk_px);
+  const Cut cut = cut_of(N, ge.HW, ge.C8);
+  ge.ppp = cut.ppp; ge.chunks = cut.chunks; ge.chunk_px = cut.chunk_px;
   return 0;
 }
 
 // workspace: part [N][chunks][2][C] floats | coef: 3 N C floats (forward: planes [3][N][C], backward: [N][C][3])
-int64_t ws_floats(const GnGeom& ge) { return (int64_t)ge.N * ge.chunks * 2 * ge.C + (int64_t)ge.N * ge.C * 3; }
+struct GnWs { float* part; float* coef; int64_t bytes; };
+GnWs ws_layout(const GnGeom& ge, void* base) {
+  const int64_t part_floats = (int64_t)ge.N * ge.chunks * 2 * ge.C, coef_floats = (int64_t)ge.N * ge.C * 3;
+  return GnWs{(float*)base, base ? (float*)base + part_floats : nullptr, (part_floats + coef_floats) * 4};
+}
+
+// the geometry of a call and its workspace, checked
+int prepare(const char* who, int N, int H, int W, int C, int G, void* workspace, int64_t workspace_bytes, GnGeom& ge,
+            GnWs& ws) {
+  if (make_geom(ge, N, H, W, C, G)) return -1;
+  ws = ws_layout(ge, workspace);
+  TDN_CHECK(workspace_bytes >= ws.bytes && ((uintptr_t)workspace & 15) == 0, "%s: workspace too small or misaligned",
+            who);
+  return 0;
+}
+
+// the addend of a forward -> up_w: W / 2 if it is the coarser level read with 2x upsampling, else 0; -1: refused
+int addend_up_w(const char* who, const void* addend, int addend_mode, int H, int W) {
+  TDN_CHECK(!addend || addend_mode == TDN_ADD_SAME || addend_mode == TDN_ADD_UP2X,
+            "%s: addend_mode %d (TDN_ADD_SAME or TDN_ADD_UP2X)", who, addend_mode);
+  TDN_CHECK(!(addend && addend_mode == TDN_ADD_UP2X) || (H % 2 == 0 && W % 2 == 0),
+            "%s: UP2X addend needs even H, W (got %dx%d)", who, H, W);
+  return (addend && addend_mode == TDN_ADD_UP2X) ? W / 2 : 0;
+}
+
+// [1] (mode 0; g and stats are not read) or [1'] (mode 1; pivot_stride is not read)
+void launch_partial(int mode, int dtype, const GnGeom& ge, const void* z, const void* g, const float* stats,
+                    int64_t pivot_stride, float* part, hipStream_t st) {
+  using Kernel = void (*)(const bf16_t*, const bf16_t*, const float*, GnGeom, int64_t, float*);
+  static const Kernel kernels[2][2] = {{gn_partial_kernel<0, false>, gn_partial_kernel<0, true>},
+                                       {gn_partial_kernel<1, false>, gn_partial_kernel<1, true>}};
+  const Kernel kernel = kernels[mode][dtype == TDN_F16 ? 1 : 0];
+  TDN_LAUNCH(kernel, dim3(ge.chunks, ge.N), dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge,
+             pivot_stride, part);
+}
+
+// grid of the grid-stride apply kernels [3] / [3']
+dim3 apply_grid(const GnGeom& ge) {
+  const int64_t total = (int64_t)ge.N * ge.HW * ge.C8;
+  int grid = (int)((total + kThreads - 1) / kThreads);
+  if (grid > 8192) grid = 8192;
+  return dim3(grid);
+}
+
+int stats_block(const GnGeom& ge) { return ge.cpg > 32 ? ge.cpg : 32; }   // channels per block of [2] / [2']: divides C
 
 }  // namespace
 
 extern "C" int64_t tdn_gn_workspace(int N, int H, int W, int C, int G) {
   GnGeom ge;
   if (make_geom(ge, N, H, W, C, G)) return -1;
-  return ws_floats(ge) * 4 + 256;
+  return ws_layout(ge, nullptr).bytes + 256;
 }
 
 extern "C" int tdn_gn_fwd(const void* z, const float* gamma, const float* beta, int N, int H, int W, int C, int G,
                           float eps, const void* addend, int addend_mode, int relu, void* y, float* stats,
-                          void* workspace,
-                          int64_t workspace_bytes, int dtype, void* stream) {
+                          void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
+  const char* who = "tdn_gn_fwd";
   TDN_CHECK_DTYPE(dtype);
-  TDN_CHECK(z && gamma && beta && y && stats && workspace, "tdn_gn_fwd: NULL pointer");
-  TDN_CHECK(!addend || addend_mode == TDN_ADD_SAME || addend_mode == TDN_ADD_UP2X,
-            "tdn_gn_fwd: addend_mode %d (TDN_ADD_SAME or TDN_ADD_UP2X)", addend_mode);
-  TDN_CHECK(!(addend && addend_mode == TDN_ADD_UP2X) || (H % 2 == 0 && W % 2 == 0),
-            "tdn_gn_fwd: UP2X addend needs even H, W (got %dx%d)", H, W);
-  const int up_w = (addend && addend_mode == TDN_ADD_UP2X) ? W / 2 : 0;
+  TDN_CHECK(z && gamma && beta && y && stats && workspace, "%s: NULL pointer", who);
   GnGeom ge;
-  if (make_geom(ge, N, H, W, C, G)) return -1;
-  TDN_CHECK(workspace_bytes >= ws_floats(ge) * 4 && ((uintptr_t)workspace & 15) == 0,
-            "tdn_gn_fwd: workspace too small or misaligned");
-  float* part = (float*)workspace;
-  float* coef = part + (int64_t)ge.N * ge.chunks * 2 * ge.C;
+  GnWs ws;
+  const int up_w = addend_up_w(who, addend, addend_mode, H, W);
+  if (up_w < 0) return -1;
+  if (prepare(who, N, H, W, C, G, workspace, workspace_bytes, ge, ws)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 gp(ge.chunks, N);
-  if (dtype == TDN_F16)
-    TDN_LAUNCH((gn_partial_kernel<0, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge,
-               (int64_t)ge.HW * ge.C, part);
-  else
-    TDN_LAUNCH((gn_partial_kernel<0, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge,
-               (int64_t)ge.HW * ge.C, part);
-  const int CB = ge.cpg > 32 ? ge.cpg : 32;
-  TDN_LAUNCH(gn_stats_kernel, dim3(ceil_div(C, CB), N), dim3(kThreads), 0, st, part, ge, CB, (const bf16_t*)z,
-             dtype == TDN_F16 ? 1 : 0, gamma, beta, eps, stats, coef);
-  const int64_t total = (int64_t)N * ge.HW * ge.C8;
-  int grid = (int)((total + kThreads - 1) / kThreads);
-  if (grid > 8192) grid = 8192;
-  TDN_LAUNCH_T(gn_apply_kernel, dtype, dim3(grid), dim3(kThreads), st, (const bf16_t*)z, coef, (const bf16_t*)addend,
-               relu, up_w, ge, (bf16_t*)y);
+  launch_partial(0, dtype, ge, z, nullptr, nullptr, (int64_t)ge.HW * ge.C, ws.part, st);
+  const int CB = stats_block(ge);
+  TDN_LAUNCH(gn_stats_kernel, dim3(C / CB, N), dim3(kThreads), 0, st, (const float*)ws.part, ge, CB, (const bf16_t*)z,
+             dtype == TDN_F16 ? 1 : 0, gamma, beta, eps, stats, ws.coef);
+  TDN_LAUNCH_T(gn_apply_kernel, dtype, apply_grid(ge), dim3(kThreads), st, (const bf16_t*)z, (const float*)ws.coef,
+               (const bf16_t*)addend, relu, up_w, ge, (bf16_t*)y);
   TDN_LAUNCH_CHECK();
   return 0;
 }
@@ -444,30 +424,19 @@ extern "C" int tdn_gn_fwd(const void* z, const float* gamma, const float* beta, 
 extern "C" int tdn_gn_bwd(const void* g, const void* z, const float* stats, const float* gamma, int N, int H, int W,
                           int C, int G, void* dz, float* dgamma, float* dbeta, float acc, void* workspace,
                           int64_t workspace_bytes, int dtype, void* stream) {
+  const char* who = "tdn_gn_bwd";
   TDN_CHECK_DTYPE(dtype);
-  TDN_CHECK(g && z && stats && gamma && dz && dgamma && dbeta && workspace, "tdn_gn_bwd: NULL pointer");
+  TDN_CHECK(g && z && stats && gamma && dz && dgamma && dbeta && workspace, "%s: NULL pointer", who);
   GnGeom ge;
-  if (make_geom(ge, N, H, W, C, G)) return -1;
-  TDN_CHECK(workspace_bytes >= ws_floats(ge) * 4 && ((uintptr_t)workspace & 15) == 0,
-            "tdn_gn_bwd: workspace too small or misaligned");
-  float* part = (float*)workspace;
-  float* coef3 = part + (int64_t)ge.N * ge.chunks * 2 * ge.C;
+  GnWs ws;
+  if (prepare(who, N, H, W, C, G, workspace, workspace_bytes, ge, ws)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 gp(ge.chunks, N);
-  if (dtype == TDN_F16)
-    TDN_LAUNCH((gn_partial_kernel<1, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge,
-               (int64_t)0, part);
-  else
-    TDN_LAUNCH((gn_partial_kernel<1, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge,
-               (int64_t)0, part);
-  const int CB = ge.cpg > 32 ? ge.cpg : 32;
-  TDN_LAUNCH(gn_bwd_coef_kernel, dim3(ceil_div(C, CB)), dim3(kThreads), 0, st, part, ge, CB, gamma, stats,
-                     coef3, dgamma, dbeta, acc);
-  const int64_t total = (int64_t)N * ge.HW * ge.C8;
-  int grid = (int)((total + kThreads - 1) / kThreads);
-  if (grid > 8192) grid = 8192;
-  TDN_LAUNCH_T(gn_bwd_apply_kernel, dtype, dim3(grid), dim3(kThreads), st, (const bf16_t*)g, (const bf16_t*)z, coef3,
-               ge, (bf16_t*)dz);
+  launch_partial(1, dtype, ge, z, g, stats, 0, ws.part, st);
+  const int CB = stats_block(ge);
+  TDN_LAUNCH(gn_bwd_coef_kernel, dim3(C / CB), dim3(kThreads), 0, st, (const float*)ws.part, ge, CB, gamma, stats,
+             ws.coef, dgamma, dbeta, acc);
+  TDN_LAUNCH_T(gn_bwd_apply_kernel, dtype, apply_grid(ge), dim3(kThreads), st, (const bf16_t*)g, (const bf16_t*)z,
+               (const float*)ws.coef, ge, (bf16_t*)dz);
   TDN_LAUNCH_CHECK();
   return 0;
 }
@@ -479,35 +448,21 @@ extern "C" int tdn_bn_train_fwd(const void* z, const float* gamma, const float* 
                                 float* running_var, float momentum, int N, int H, int W, int C, float eps,
                                 const void* addend, int addend_mode, int relu, void* y, float* stats, void* workspace,
                                 int64_t workspace_bytes, int dtype, void* stream) {
+  const char* who = "tdn_bn_train_fwd";
   TDN_CHECK_DTYPE(dtype);
-  TDN_CHECK(z && gamma && beta && y && stats && workspace, "tdn_bn_train_fwd: NULL pointer");
-  TDN_CHECK((running_mean == nullptr) == (running_var == nullptr), "tdn_bn_train_fwd: give both running stats or none");
-  TDN_CHECK(!addend || addend_mode == TDN_ADD_SAME || addend_mode == TDN_ADD_UP2X,
-            "tdn_bn_train_fwd: addend_mode %d (TDN_ADD_SAME or TDN_ADD_UP2X)", addend_mode);
-  TDN_CHECK(!(addend && addend_mode == TDN_ADD_UP2X) || (H % 2 == 0 && W % 2 == 0),
-            "tdn_bn_train_fwd: UP2X addend needs even H, W (got %dx%d)", H, W);
-  const int up_w = (addend && addend_mode == TDN_ADD_UP2X) ? W / 2 : 0;
+  TDN_CHECK(z && gamma && beta && y && stats && workspace, "%s: NULL pointer", who);
+  TDN_CHECK((running_mean == nullptr) == (running_var == nullptr), "%s: give both running stats or none", who);
   GnGeom ge;
-  if (make_geom(ge, N, H, W, C, C)) return -1;
-  TDN_CHECK(workspace_bytes >= ws_floats(ge) * 4 && ((uintptr_t)workspace & 15) == 0,
-            "tdn_bn_train_fwd: workspace too small or misaligned");
-  float* part = (float*)workspace;
-  float* coef = part + (int64_t)ge.N * ge.chunks * 2 * ge.C;
+  GnWs ws;
+  const int up_w = addend_up_w(who, addend, addend_mode, H, W);
+  if (up_w < 0) return -1;
+  if (prepare(who, N, H, W, C, C, workspace, workspace_bytes, ge, ws)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 gp(ge.chunks, N);
-  if (dtype == TDN_F16)
-    TDN_LAUNCH((gn_partial_kernel<0, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge,
-               (int64_t)0, part);
-  else
-    TDN_LAUNCH((gn_partial_kernel<0, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, nullptr, nullptr, ge,
-               (int64_t)0, part);
-  TDN_LAUNCH(bn_stats_kernel, dim3(ceil_div(C, 32)), dim3(kThreads), 0, st, part, ge, (const bf16_t*)z,
-             dtype == TDN_F16 ? 1 : 0, gamma, beta, eps, momentum, running_mean, running_var, stats, coef);
-  const int64_t total = (int64_t)N * ge.HW * ge.C8;
-  int grid = (int)((total + kThreads - 1) / kThreads);
-  if (grid > 8192) grid = 8192;
-  TDN_LAUNCH_T(gn_apply_kernel, dtype, dim3(grid), dim3(kThreads), st, (const bf16_t*)z, coef, (const bf16_t*)addend,
-               relu, up_w, ge, (bf16_t*)y);
+  launch_partial(0, dtype, ge, z, nullptr, nullptr, 0, ws.part, st);
+  TDN_LAUNCH(bn_stats_kernel, dim3(C / 32), dim3(kThreads), 0, st, (const float*)ws.part, ge, (const bf16_t*)z,
+             dtype == TDN_F16 ? 1 : 0, gamma, beta, eps, momentum, running_mean, running_var, stats, ws.coef);
+  TDN_LAUNCH_T(gn_apply_kernel, dtype, apply_grid(ge), dim3(kThreads), st, (const bf16_t*)z, (const float*)ws.coef,
+               (const bf16_t*)addend, relu, up_w, ge, (bf16_t*)y);
   TDN_LAUNCH_CHECK();
   return 0;
 }
@@ -515,29 +470,18 @@ extern "C" int tdn_bn_train_fwd(const void* z, const float* gamma, const float* 
 extern "C" int tdn_bn_train_bwd(const void* g, const void* z, const float* stats, const float* gamma, int N, int H,
                                 int W, int C, void* dz, float* dgamma, float* dbeta, float acc, void* workspace,
                                 int64_t workspace_bytes, int dtype, void* stream) {
+  const char* who = "tdn_bn_train_bwd";
   TDN_CHECK_DTYPE(dtype);
-  TDN_CHECK(g && z && stats && gamma && dz && dgamma && dbeta && workspace, "tdn_bn_train_bwd: NULL pointer");
+  TDN_CHECK(g && z && stats && gamma && dz && dgamma && dbeta && workspace, "%s: NULL pointer", who);
   GnGeom ge;
-  if (make_geom(ge, N, H, W, C, C)) return -1;
-  TDN_CHECK(workspace_bytes >= ws_floats(ge) * 4 && ((uintptr_t)workspace & 15) == 0,
-            "tdn_bn_train_bwd: workspace too small or misaligned");
-  float* part = (float*)workspace;
-  float* coef3 = part + (int64_t)ge.N * ge.chunks * 2 * ge.C;
+  GnWs ws;
+  if (prepare(who, N, H, W, C, C, workspace, workspace_bytes, ge, ws)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 gp(ge.chunks, N);
-  if (dtype == TDN_F16)
-    TDN_LAUNCH((gn_partial_kernel<1, true>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge,
-               (int64_t)0, part);
-  else
-    TDN_LAUNCH((gn_partial_kernel<1, false>), gp, dim3(kThreads), 0, st, (const bf16_t*)z, (const bf16_t*)g, stats, ge,
-               (int64_t)0, part);
-  TDN_LAUNCH(bn_bwd_coef_kernel, dim3(ceil_div(C, 32)), dim3(kThreads), 0, st, part, ge, gamma, stats,
-                     coef3, dgamma, dbeta, acc);
-  const int64_t total = (int64_t)N * ge.HW * ge.C8;
-  int grid = (int)((total + kThreads - 1) / kThreads);
-  if (grid > 8192) grid = 8192;
-  TDN_LAUNCH_T(gn_bwd_apply_kernel, dtype, dim3(grid), dim3(kThreads), st, (const bf16_t*)g, (const bf16_t*)z, coef3,
-               ge, (bf16_t*)dz);
+  launch_partial(1, dtype, ge, z, g, stats, 0, ws.part, st);
+  TDN_LAUNCH(bn_bwd_coef_kernel, dim3(C / 32), dim3(kThreads), 0, st, (const float*)ws.part, ge, gamma, stats, ws.coef,
+             dgamma, dbeta, acc);
+  TDN_LAUNCH_T(gn_bwd_apply_kernel, dtype, apply_grid(ge), dim3(kThreads), st, (const bf16_t*)g, (const bf16_t*)z,
+               (const float*)ws.coef, ge, (bf16_t*)dz);
   TDN_LAUNCH_CHECK();
   return 0;
 }

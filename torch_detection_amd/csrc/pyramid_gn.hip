@@ -11,16 +11,15 @@
 //             [2'] per (level, image): the channel sums (s1, s2) and the coefficients of dz
 //             [3'] dz = g * A - xhat * Bq - Cq;  its block 0 also adds the (s1, s2) of all levels and images, level order
 //                  finest first, image order within a level, into dgamma / dbeta
-// The statistics are gn.hip's ("Numerics of the statistics"): sums about the pivot K_c = the channel's value
-// at pixel 0 of the (level, image), pivots put back in double, output formed about the pivot.  The chunk cut of a
-// (level, image) is gn.hip's rule applied to that level alone, so it is a function of (B, H_l W_l, C) only: a level gives
-// the same bits whether it is launched alone or inside a pyramid.  Partials are plain stores; every reduction runs in a
-// fixed order; no atomics, no counters, no memset.  All passes are HBM-bound streams, 16 bytes (8 channels) per lane.
-#include "common.h"
+// The statistics are norm_core.h's, shared with gn.hip ("Numerics of the statistics"): sums about the pivot
+// K_c = the channel's value at pixel 0 of the (level, image), pivots put back in double, output formed about the pivot.
+// The chunk cut of a (level, image) is that header's cut_of for the level alone, a function of (B, H_l W_l, C) only: a
+// level gives the same bits launched alone, inside a pyramid, or through gn.hip.  Partials are plain stores; every
+// reduction runs in a fixed order; no atomics, no counters, no memset.  All passes are HBM-bound, 16 bytes per lane.
+#include "norm_core.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int MAXL = TDN_PYR_MAX_LEVELS;
 constexpr int TILE = 4 * kThreads;      // 16-byte lanes per workgroup of the apply launches
 constexpr int64_t MAX_ROWS = (int64_t)1 << 31;
@@ -116,31 +115,9 @@ __global__ __launch_bounds__(kThreads) void pgn_partial_kernel(const PgnArgs p, 
   }
 }
 
-// Sum of the per-chunk partials of channel c of one (level, image), both planes, by the KL chunk-lanes of a block:
-// thread (cl, kl) takes chunks kl, kl + KL, ...; the lanes are combined through LDS in lane order.  rows: the image's
-// first row of `part`.  Returns the totals to every thread with kl == 0.
-__device__ __forceinline__ void chunk_totals(const float* __restrict__ rows, int chunks, int C, int c, int cl, int kl,
-                                             int CB, int KL, double* red /*[2][kThreads]*/, double& s, double& ss) {
-  double a = 0.0, b = 0.0;
-  for (int k = kl; k < chunks; k += KL) {
-    const float* q = rows + (int64_t)k * 2 * C + c;
-    a += (double)q[0];
-    b += (double)q[C];
-  }
-  red[kl * CB + cl] = a;
-  red[kThreads + kl * CB + cl] = b;
-  __syncthreads();
-  s = 0.0; ss = 0.0;
-  if (kl == 0) {
-    for (int j = 0; j < KL; ++j) { s += red[j * CB + cl]; ss += red[kThreads + j * CB + cl]; }
-  }
-}
-
-// [2]: block (channel block of CB = max(32, cpg) channels — whole groups —, level * B + image).  With s_c = sum (z - K_c),
-// q_c = sum (z - K_c)^2 over the HW pixels of channel c:
-//   mu = sum_c (s_c + HW K_c) / cnt,   cnt var = sum_c (q_c + 2 (K_c - mu) s_c + HW (K_c - mu)^2)
-// in channel order, in double.  stats[level][image][c] = (mu, rstd); coef[level][image][3][C] = a, b', K of
-// y = (z - K) * a + b', b' = beta - (mu - K) a formed in double.
+// [2]: block (channel block of CB = max(32, cpg) channels — whole groups —, level * B + image): norm_core.h's
+// group_moments of the channels' (s_c, q_c, K_c).  stats[level][image][c] = (mu, rstd); coef[level][image][3][C] =
+// a, b', K of y = (z - K) * a + b' (fwd_coef).
 __global__ __launch_bounds__(kThreads) void pgn_stats_kernel(const PgnArgs p, int CB, int f16,
                                                              const float* __restrict__ part,
                                                              const float* __restrict__ gamma,
@@ -161,34 +138,23 @@ __global__ __launch_bounds__(kThreads) void pgn_stats_kernel(const PgnArgs p, in
     }
     return;
   }
-  const bf16_t* z = p.z[l] + (int64_t)n * HW * C + c;    // asked for ahead of the chunk sums: its latency hides
-  const double K = kl == 0 ? (double)(f16 ? elem_to_f32<true>(*z) : elem_to_f32<false>(*z)) : 0.0;
+  const bf16_t* z = p.z[l] + (int64_t)n * HW * C + c;
+  const double K = kl == 0 ? pivot_of(z, f16) : 0.0;     // asked for ahead of the chunk sums: its latency hides
   double s, ss;
-  chunk_totals(part + ((int64_t)p.first_wg[l] + (int64_t)n * p.chunks[l]) * 2 * C, p.chunks[l], C, c, cl, kl, CB, KL,
-               red, s, ss);
+  row_totals(part + ((int64_t)p.first_wg[l] + (int64_t)n * p.chunks[l]) * 2 * C, p.chunks[l], C, c, cl, kl, CB, KL, red,
+             s, ss);
   if (kl == 0) { tot[cl] = s; tot[kThreads + cl] = ss; tot[2 * kThreads + cl] = K; }
   __syncthreads();
   if (kl == 0) {
-    const int cpg = p.cpg, g0 = (cl / cpg) * cpg;
-    const double hw = (double)HW, cnt = hw * cpg;
-    double gs = 0.0;
-    for (int j = 0; j < cpg; ++j) gs += tot[g0 + j] + hw * tot[2 * kThreads + g0 + j];
-    const double mu = gs / cnt;
-    double m2 = 0.0;
-    for (int j = 0; j < cpg; ++j) {
-      const double dk = tot[2 * kThreads + g0 + j] - mu;
-      m2 += tot[kThreads + g0 + j] + 2.0 * dk * tot[g0 + j] + hw * dk * dk;
-    }
-    double var = m2 / cnt;                               // biased variance, like nn.GroupNorm
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    const Moments m = group_moments(tot, (cl / p.cpg) * p.cpg, p.cpg, HW, eps);
     const int64_t row = (int64_t)l * p.B + n;
-    stats[(row * C + c) * 2] = (float)mu;
-    stats[(row * C + c) * 2 + 1] = rstd;
-    const float a = rstd * gamma[c];
+    stats[(row * C + c) * 2] = (float)m.mu;
+    stats[(row * C + c) * 2 + 1] = m.rstd;
+    float a, b;
+    fwd_coef(m.rstd, gamma[c], beta[c], m.mu - K, a, b);
     float* o = coef + row * 3 * C + c;
     o[0] = a;
-    o[C] = (float)((double)beta[c] - (mu - K) * (double)a);
+    o[C] = b;
     o[2 * C] = (float)K;
   }
 }
@@ -260,18 +226,14 @@ __global__ __launch_bounds__(kThreads) void pgn_bwd_coef_kernel(const PgnArgs p,
   const int c = blockIdx.x * CB + cl;
   const float gm = gamma[c];
   double d1, d2;
-  chunk_totals(part + ((int64_t)p.first_wg[l] + (int64_t)n * p.chunks[l]) * 2 * C, p.chunks[l], C, c, cl, kl, CB, KL,
-               red, d1, d2);
+  row_totals(part + ((int64_t)p.first_wg[l] + (int64_t)n * p.chunks[l]) * 2 * C, p.chunks[l], C, c, cl, kl, CB, KL, red,
+             d1, d2);
   const float s1 = (float)d1, s2 = (float)d2;
   if (kl == 0) { t1[cl] = gm * s1; t2[cl] = gm * s2; }
   __syncthreads();
   if (kl == 0) {
-    const int cpg = p.cpg, l0 = (cl / cpg) * cpg;
-    const float cnt = (float)HW * (float)cpg;
-    float m1 = 0.f, m2 = 0.f;
-    for (int j = 0; j < cpg; ++j) { m1 += t1[l0 + j]; m2 += t2[l0 + j]; }
-    m1 /= cnt;
-    m2 /= cnt;
+    float m1, m2;
+    group_means(t1, t2, (cl / p.cpg) * p.cpg, p.cpg, (float)HW * (float)p.cpg, m1, m2);
     const int64_t row = (int64_t)l * p.B + n;
     const float r = stats[(row * C + c) * 2 + 1];
     float* o = coef + row * 3 * C + c;
@@ -384,12 +346,11 @@ int check_shape(const char* who, int kind, int B, const int32_t* hw, int n, int 
   return 0;
 }
 
-// The cut of level l is gn.hip's for a map of its size alone: about 1024 workgroups per level, at least four passes of
-// the block's pixel lanes per chunk.  A function of (B, H_l * W_l, C).
+// The cut of level l is norm_core.h's cut_of for a map of its size alone: a function of (B, H_l * W_l, C).
 void make_plan(int B, const int32_t* hw, int n, int C, int G, PgnPlan& pl) {
   pl.C8 = C / 8;
   pl.cpg = C / G;
-  pl.ppp = kThreads / pl.C8;
+  pl.ppp = pixel_lanes(pl.C8);
   pl.CB = pl.cpg > 32 ? pl.cpg : 32;
   int wg = 0, tl = 0;
   pl.live = 0;
@@ -400,13 +361,10 @@ void make_plan(int B, const int32_t* hw, int n, int C, int G, PgnPlan& pl) {
     if (l >= n) continue;
     const int HW = B > 0 ? hw[2 * l] * hw[2 * l + 1] : 0;
     if (HW == 0) continue;
-    int chunks = ceil_div(1024, B);
-    const int max_chunks = ceil_div(HW, pl.ppp * 4);
-    if (chunks > max_chunks) chunks = max_chunks;
-    if (chunks < 1) chunks = 1;
+    const Cut cut = cut_of(B, HW, pl.C8);
     pl.HW[l] = HW;
-    pl.chunk_px[l] = ceil_div(HW, chunks);
-    pl.chunks[l] = ceil_div(HW, pl.chunk_px[l]);
+    pl.chunk_px[l] = cut.chunk_px;
+    pl.chunks[l] = cut.chunks;
     wg += B * pl.chunks[l];
     tl += (int)(((int64_t)B * HW * pl.C8 + TILE - 1) / TILE);
     ++pl.live;
@@ -467,6 +425,15 @@ int sizes_of(const char* who, const tdn_pyr_gn_level* levels, int n, int32_t* hw
   return 0;
 }
 
+// [1] (mode 0; stats is not read) or [1'] (mode 1)
+void launch_partial(int mode, int dtype, const PgnArgs& p, int wgs, const float* stats, float* part, void* stream) {
+  using Kernel = void (*)(const PgnArgs, const float*, float*);
+  static const Kernel kernels[2][2] = {{pgn_partial_kernel<0, false>, pgn_partial_kernel<0, true>},
+                                       {pgn_partial_kernel<1, false>, pgn_partial_kernel<1, true>}};
+  const Kernel kernel = kernels[mode][dtype == TDN_F16 ? 1 : 0];
+  TDN_LAUNCH(kernel, dim3(wgs), dim3(kThreads), 0, stream, p, stats, part);
+}
+
 }  // namespace
 
 extern "C" int64_t tdn_pyr_gn_workspace_bytes(int kind, int B, const int32_t* hw, int num_levels, int C, int G) {
@@ -517,10 +484,7 @@ extern "C" int tdn_pyr_gn_fwd(const tdn_pyr_gn_level* levels, int num_levels, in
   if (tdn_check_ws(who, workspace, workspace_bytes, ws.bytes) != 0) return -1;
   PgnArgs p;
   if (fill_args(who, 0, levels, num_levels, B, C, relu, pl, p) != 0) return -1;
-  if (dtype == TDN_F16)
-    TDN_LAUNCH((pgn_partial_kernel<0, true>), dim3(pl.wgs), dim3(kThreads), 0, stream, p, (const float*)nullptr, ws.part);
-  else
-    TDN_LAUNCH((pgn_partial_kernel<0, false>), dim3(pl.wgs), dim3(kThreads), 0, stream, p, (const float*)nullptr, ws.part);
+  launch_partial(0, dtype, p, pl.wgs, nullptr, ws.part, stream);
   TDN_LAUNCH(pgn_stats_kernel, dim3(C / pl.CB, num_levels * B), dim3(kThreads), 0, stream, p, pl.CB,
              dtype == TDN_F16 ? 1 : 0, (const float*)ws.part, gamma, beta, eps, stats, ws.coef);
   TDN_LAUNCH_T(pgn_apply_kernel, dtype, dim3(pl.tiles), dim3(kThreads), stream, p, (const float*)ws.coef);
@@ -546,10 +510,7 @@ extern "C" int tdn_pyr_gn_bwd(const tdn_pyr_gn_level* levels, int num_levels, in
   PgnArgs p;
   if (fill_args(who, 1, levels, num_levels, B, C, relu, pl, p) != 0) return -1;
   if (pl.wgs > 0) {
-    if (dtype == TDN_F16)
-      TDN_LAUNCH((pgn_partial_kernel<1, true>), dim3(pl.wgs), dim3(kThreads), 0, stream, p, stats, ws.part);
-    else
-      TDN_LAUNCH((pgn_partial_kernel<1, false>), dim3(pl.wgs), dim3(kThreads), 0, stream, p, stats, ws.part);
+    launch_partial(1, dtype, p, pl.wgs, stats, ws.part, stream);
     TDN_LAUNCH(pgn_bwd_coef_kernel, dim3(C / pl.CB, num_levels * B), dim3(kThreads), 0, stream, p, pl.CB,
                (const float*)ws.part, gamma, stats, ws.coef, ws.sums);
   }

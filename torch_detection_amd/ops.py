@@ -1145,9 +1145,8 @@ def _gn_ws(N, H, W, C, G, device):
     return _workspace(nbytes, device)
 
 
-def gn_fwd(z, gamma, beta, groups, eps=1e-5, addend=None, relu=False, addend_mode=ADD_SAME):
-    """y = relu?(GroupNorm(z) (+ addend)) on an NHWC raw conv output; returns (y, stats) with stats (N, C, 2) float32
-    = per-channel (mean, rstd) for the backward."""
+def _norm_fwd_args(name, z, gamma, beta, addend, addend_mode):
+    """The checked operands of gn_fwd / bn_train_fwd -> (N, H, W, C, y, stats), y and stats new."""
     _chk_act(z, "z")
     N, H, W, C = z.shape
     _chk_vec(gamma.detach(), "gamma", C)
@@ -1155,29 +1154,23 @@ def gn_fwd(z, gamma, beta, groups, eps=1e-5, addend=None, relu=False, addend_mod
     if addend is not None:
         _chk_act(addend, "addend", C, z.dtype)
         if addend_mode not in (ADD_SAME, ADD_UP2X):
-            raise ValueError("gn_fwd: addend_mode must be ADD_SAME or ADD_UP2X")
+            raise ValueError("%s: addend_mode must be ADD_SAME or ADD_UP2X" % name)
         exp = (N, H, W, C) if addend_mode == ADD_SAME else (N, H // 2, W // 2, C)
         if tuple(addend.shape) != exp or (addend_mode == ADD_UP2X and (H % 2 or W % 2)):
             raise RuntimeError("epilogue addend of spatial size %s does not match output %s (mode %d)" %
                                (tuple(addend.shape[1:3]), (H, W), addend_mode))
-    y = torch.empty_like(z)
-    stats = torch.empty(N, C, 2, dtype=torch.float32, device=z.device)
-    ws = _gn_ws(N, H, W, C, groups, z.device)
-    _lib.check(_lib.load().tdn_gn_fwd(_ptr(z), _ptr(gamma), _ptr(beta), N, H, W, C, int(groups), float(eps),
-                                      _ptr(addend), int(addend_mode), _relu_code(relu), _ptr(y), _ptr(stats), _ptr(ws),
-                                      ws.numel(),
-                                      dtype_code(z.dtype), _lib.stream_ptr()), "tdn_gn_fwd")
-    return y, stats
+    return N, H, W, C, torch.empty_like(z), torch.empty(N, C, 2, dtype=torch.float32, device=z.device)
 
 
-def gn_bwd(g, z, stats, gamma, groups, dgamma=None, dbeta=None, accumulate=False):
-    """(dz, dgamma, dbeta) from g = dL/dy (ReLU mask already applied)."""
+def _norm_bwd_args(name, g, z, stats, gamma, dgamma, dbeta):
+    """The checked operands of gn_bwd / bn_train_bwd -> (N, H, W, C, dz, dgamma, dbeta); dz is new, dgamma / dbeta are
+    the caller's or new."""
     _chk_act(z, "z")
     _chk_act(g, "g", z.shape[3], z.dtype)
     N, H, W, C = z.shape
     if g.shape != z.shape or tuple(stats.shape) != (N, C, 2) or stats.dtype != torch.float32:
-        raise RuntimeError("gn_bwd: inconsistent shapes g=%s z=%s stats=%s" %
-                           (tuple(g.shape), tuple(z.shape), tuple(stats.shape)))
+        raise RuntimeError("%s: inconsistent shapes g=%s z=%s stats=%s" %
+                           (name, tuple(g.shape), tuple(z.shape), tuple(stats.shape)))
     _chk_vec(gamma.detach(), "gamma", C)
     if dgamma is None:
         dgamma = torch.empty(C, dtype=torch.float32, device=z.device)
@@ -1185,7 +1178,23 @@ def gn_bwd(g, z, stats, gamma, groups, dgamma=None, dbeta=None, accumulate=False
         dbeta = torch.empty(C, dtype=torch.float32, device=z.device)
     _chk_vec(dgamma, "dgamma", C)
     _chk_vec(dbeta, "dbeta", C)
-    dz = torch.empty_like(z)
+    return N, H, W, C, torch.empty_like(z), dgamma, dbeta
+
+
+def gn_fwd(z, gamma, beta, groups, eps=1e-5, addend=None, relu=False, addend_mode=ADD_SAME):
+    """y = relu?(GroupNorm(z) (+ addend)) on an NHWC raw conv output; returns (y, stats) with stats (N, C, 2) float32
+    = per-channel (mean, rstd) for the backward."""
+    N, H, W, C, y, stats = _norm_fwd_args("gn_fwd", z, gamma, beta, addend, addend_mode)
+    ws = _gn_ws(N, H, W, C, groups, z.device)
+    _lib.check(_lib.load().tdn_gn_fwd(_ptr(z), _ptr(gamma), _ptr(beta), N, H, W, C, int(groups), float(eps),
+                                      _ptr(addend), int(addend_mode), _relu_code(relu), _ptr(y), _ptr(stats), _ptr(ws),
+                                      ws.numel(), dtype_code(z.dtype), _lib.stream_ptr()), "tdn_gn_fwd")
+    return y, stats
+
+
+def gn_bwd(g, z, stats, gamma, groups, dgamma=None, dbeta=None, accumulate=False):
+    """(dz, dgamma, dbeta) from g = dL/dy (ReLU mask already applied)."""
+    N, H, W, C, dz, dgamma, dbeta = _norm_bwd_args("gn_bwd", g, z, stats, gamma, dgamma, dbeta)
     ws = _gn_ws(N, H, W, C, groups, z.device)
     _lib.check(_lib.load().tdn_gn_bwd(_ptr(g), _ptr(z), _ptr(stats), _ptr(gamma), N, H, W, C, int(groups), _ptr(dz),
                                       _ptr(dgamma), _ptr(dbeta), 1.0 if accumulate else 0.0, _ptr(ws), ws.numel(),
@@ -1292,22 +1301,11 @@ def bn_train_fwd(z, gamma, beta, running_mean=None, running_var=None, momentum=0
                  relu=False, addend_mode=ADD_SAME):
     """y = relu?(BatchNorm_train(z) (+ addend)); running statistics (if given) are updated in place like
     nn.BatchNorm2d does.  Returns (y, stats) with stats (N, C, 2) float32 for the backward."""
-    _chk_act(z, "z")
-    N, H, W, C = z.shape
-    _chk_vec(gamma.detach(), "gamma", C)
-    _chk_vec(beta.detach(), "beta", C)
+    N, H, W, C, y, stats = _norm_fwd_args("bn_train_fwd", z, gamma, beta, addend, addend_mode)
     _chk_vec(running_mean, "running_mean", C)
     _chk_vec(running_var, "running_var", C)
     if (running_mean is None) != (running_var is None):
         raise ValueError("bn_train_fwd: give both running statistics or none")
-    if addend is not None:
-        _chk_act(addend, "addend", C, z.dtype)
-        exp = (N, H, W, C) if addend_mode == ADD_SAME else (N, H // 2, W // 2, C)
-        if addend_mode not in (ADD_SAME, ADD_UP2X) or tuple(addend.shape) != exp:
-            raise RuntimeError("epilogue addend of spatial size %s does not match output %s (mode %d)" %
-                               (tuple(addend.shape[1:3]), (H, W), addend_mode))
-    y = torch.empty_like(z)
-    stats = torch.empty(N, C, 2, dtype=torch.float32, device=z.device)
     ws = _gn_ws(N, H, W, C, C, z.device)
     _lib.check(_lib.load().tdn_bn_train_fwd(_ptr(z), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
                                             float(momentum), N, H, W, C, float(eps), _ptr(addend), int(addend_mode),
@@ -1318,19 +1316,7 @@ def bn_train_fwd(z, gamma, beta, running_mean=None, running_var=None, momentum=0
 
 def bn_train_bwd(g, z, stats, gamma, dgamma=None, dbeta=None, accumulate=False):
     """(dz, dgamma, dbeta) of training-mode BatchNorm from g = dL/dy (ReLU mask already applied)."""
-    _chk_act(z, "z")
-    _chk_act(g, "g", z.shape[3], z.dtype)
-    N, H, W, C = z.shape
-    if g.shape != z.shape or tuple(stats.shape) != (N, C, 2) or stats.dtype != torch.float32:
-        raise RuntimeError("bn_train_bwd: inconsistent shapes")
-    _chk_vec(gamma.detach(), "gamma", C)
-    if dgamma is None:
-        dgamma = torch.empty(C, dtype=torch.float32, device=z.device)
-    if dbeta is None:
-        dbeta = torch.empty(C, dtype=torch.float32, device=z.device)
-    _chk_vec(dgamma, "dgamma", C)
-    _chk_vec(dbeta, "dbeta", C)
-    dz = torch.empty_like(z)
+    N, H, W, C, dz, dgamma, dbeta = _norm_bwd_args("bn_train_bwd", g, z, stats, gamma, dgamma, dbeta)
     ws = _gn_ws(N, H, W, C, C, z.device)
     _lib.check(_lib.load().tdn_bn_train_bwd(_ptr(g), _ptr(z), _ptr(stats), _ptr(gamma), N, H, W, C, _ptr(dz),
                                             _ptr(dgamma), _ptr(dbeta), 1.0 if accumulate else 0.0, _ptr(ws),
