@@ -670,6 +670,45 @@ int tdn_bbox_detections(const float* rois, const void* cls, const void* reg, int
                         float* dense_scores, float* dense_boxes, float* dets, int64_t* labels, int64_t* row_idx,
                         int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Cascade R-CNN: box refinement between the stages and detections from the stages' averaged scores (DESIGN.md
+ *      §4q: mmdetection v1's BBoxHead.refine_bboxes / regress_by_class and CascadeRCNN.simple_test; decode is
+ *      tdn_delta2bbox's arithmetic, everything after the averaged logit is tdn_bbox_detections itself) ----
+ * tdn_cascade_detections: tdn_bbox_detections with cls a HOST array of num_stages = 1..TDN_CASCADE_MAX_STAGES device
+ * matrices [R][C] of one dtype; the logit of (r, c) is (((x_0 + x_1) + ...) + x_{S-1}) / (float)S, fp32 additions in
+ * stage order and one fp32 division; reg is the last stage's.  Same five launches, outputs, limits and workspace
+ * (tdn_bbox_detections_workspace_bytes) as tdn_bbox_detections; with one stage the outputs are its outputs bit for bit. */
+#define TDN_CASCADE_MAX_STAGES 8
+int tdn_cascade_detections(const float* rois, const void* const* cls, int num_stages, const void* reg, int dtype, int R,
+                           int C, int reg_cols, int B, const int32_t* img_shapes, const float* scale_factors,
+                           float scale_factor, const float* means4, const float* stds4, double wh_ratio_clip,
+                           float score_thr, float nms_thr, int max_num, float* dense_scores, float* dense_boxes,
+                           float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+/* tdn_refine_bboxes: rois fp32 [R][5] = (batch_idx, x1, y1, x2, y2) (a row whose (int)batch_idx is not in [0, B) is
+ * padding); bbox_pred [R][reg_cols] of dtype TDN_F32 / TDN_BF16 / TDN_F16, reg_cols = 4C (row r reads columns
+ * 4*label .., label 0 the background's, as regress_by_class does) or 4.  Exactly one of labels (int64 [R], as
+ * tdn_sample_rois writes them) and cls_score ([R][C] of dtype: the label is the arg-max over all C columns, ties to the
+ * lowest column, as cls_score.argmax(dim=1)) is non-NULL; with reg_cols = 4C a given label outside [0, C) makes the row
+ * padding.  The new box is tdn_delta2bbox's decode of the row against img_shapes[b] (int32 [B][2] = (h, w)).
+ *   max_per_img = 0, row-aligned (test time): rois_out fp32 [R][5], row r = (b, box) of input row r, padding rows
+ *     (-1, 0, 0, 0, 0).  One launch, no workspace.
+ *   max_per_img = P in 1..TDN_RPN_MAX_NUM, compacted (training): proposals fp32 [B][P][5] = (x1, y1, x2, y2, 0) and
+ *     counts int32 [B], the form tdn_sample_rois reads: image b's kept rows in ascending input row, the first P of them,
+ *     counts[b] = min(kept, P), rows past it 0.  Padding rows are dropped, and with pos_gt_inds (int32 [R]) and
+ *     gt_bboxes (fp32 [B][G][4]) also every row with 0 <= pos_gt_inds[r] < G whose four coordinates are bitwise those
+ *     of gt_bboxes[b][pos_gt_inds[r]] (refine_bboxes' pos_is_gt).  Two launches; workspace: TDN_REFINE_WS_BYTES(R, B)
+ *     bytes, 256-aligned (none for R = 0).
+ * Limits: 1 <= B <= 64, R <= TDN_DET_MAX_ROWS, 1 <= C <= TDN_DET_MAX_CLASSES.  No host synchronisation, no memset, no
+ * float atomics; NaN logits are unsupported. */
+#define TDN_REFINE_CHUNK 1024           /* rows per workgroup */
+#define TDN_REFINE_WS_BYTES(R, B) \
+  (((((int64_t)(R) + TDN_REFINE_CHUNK - 1) / TDN_REFINE_CHUNK) * (int64_t)(B) * 4 + 255) & ~(int64_t)255)
+int tdn_refine_bboxes(const float* rois, const void* bbox_pred, int dtype, int R, int reg_cols, int B,
+                      const int32_t* img_shapes, const int64_t* labels, const void* cls_score, int C,
+                      const int32_t* pos_gt_inds, const float* gt_bboxes, int G, const float* means4,
+                      const float* stds4, double wh_ratio_clip, int max_per_img, float* rois_out, float* proposals,
+                      int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- single-stage (RetinaNet-style) dense anchor heads: test-time detections from sigmoid class logits, and unsampled
  *      class-labelled anchor targets (the project's own spec in the mmdetection-v1 lineage of
  *      AnchorHead.get_bboxes / anchor_target with sampling off; decode is tdn_delta2bbox's arithmetic, the sigmoid is

@@ -14,7 +14,8 @@ conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask 
 ``rpn_loss`` / ``rpn_proposals``, and the single-stage path ``RetinaHead`` between ``FPN`` and ``anchor_target_all`` /
 ``anchor_head_loss`` / ``anchor_head_detections``, and ``FCOSHead`` with the operations around it: ``fcos_points`` /
 ``fcos_target`` / ``fcos_loss`` / ``fcos_detections``, and deformable convolution ``deform_conv2d`` with the modules
-``DeformConv`` / ``ModulatedDeformConv`` / ``DeformConvPack`` / ``ModulatedDeformConvPack``).  Everything computes through libtdn.so
+``DeformConv`` / ``ModulatedDeformConv`` / ``DeformConvPack`` / ``ModulatedDeformConvPack``, and Cascade R-CNN's
+``refine_bboxes`` / ``cascade_detections`` / ``CascadeRoIHead``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -51,3 +52,4 @@ from .deform import (DeformConv, DeformConvFunction, DeformConvPack, ModulatedDe
 from .heads import BBoxHead, FCNMaskHead, FCOSHead, RetinaHead, RPNHead  # noqa: F401
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)
+from .cascade import CascadeRoIHead, cascade_detections, refine_bboxes  # noqa: F401

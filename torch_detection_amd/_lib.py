@@ -34,6 +34,8 @@ LOSS_MAX_ROWS = 1 << 20
 LOSS_MAX_AVG = 64
 DET_MAX_CLASSES = 1024
 DET_MAX_ROWS = 1 << 18
+CASCADE_MAX_STAGES = 8
+REFINE_CHUNK = 1024
 DENSE_MAX_LEVELS = 8
 FCOS_MAX_LEVELS = 8
 MASK_MAX_SIZE = 56
@@ -382,6 +384,12 @@ SIGNATURES = {
     "tdn_bbox_detections": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_float,
                                     ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.c_double, c_float, c_float,
                                     c_int] + [c_void_p] * 7 + [c_i64, c_void_p]),
+    "tdn_cascade_detections": (c_int, [c_void_p, ctypes.POINTER(c_void_p), c_int, c_void_p] + [c_int] * 5 +
+                               [c_void_p, c_void_p, c_float, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
+                                ctypes.c_double, c_float, c_float, c_int] + [c_void_p] * 7 + [c_i64, c_void_p]),
+    "tdn_refine_bboxes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
+                                  ctypes.c_double, c_int] + [c_void_p] * 4 + [c_i64, c_void_p]),
     "tdn_dense_detections_plan": (c_int, [_DL, c_int, c_int, _DC, ctypes.POINTER(ctypes.c_int32)]),
     "tdn_dense_detections_workspace_bytes": (c_i64, [_DL, c_int, c_int, _DC]),
     "tdn_dense_detections": (c_int, [_DL, c_int, c_int, c_void_p, c_void_p, _DC] + [c_void_p] * 10 + [c_i64, c_void_p]),

@@ -7,7 +7,8 @@
 // multiclass_nms is four launches for any B, C and N; bbox_head_detections puts one launch in front:
 //   0 det_softmax_decode_kernel  one wavefront per RoI row: the softmax row of loss_roi_kernel (fp64 sum in the fixed
 //                                lane -> column order) and the decode of every foreground class, written once as dense
-//                                fp32 (R, C) scores and (R, 4C') boxes; everything after reads those.
+//                                fp32 (R, C) scores and (R, 4C') boxes; everything after reads those.  The STAGES
+//                                instantiation (cascade_detections, §4q) reads the logit as the mean of S matrices.
 //   1 det_segment_kernel         one workgroup per (image, class): ordered compaction of the image's rows whose score
 //                                in the class's column is > score_thr, LDS bitonic sort of (key << 32 | ~row), box
 //                                gather into the segment's rows.  More than TDN_NMS_SEG_MAX candidates: count -1.
@@ -51,7 +52,8 @@ template <> struct DetElem<TDN_F16> { typedef f16_t T; };
 
 struct HeadArgs {
   const float* rois;          // (R, 5)
-  const void* cls;            // (R, C)
+  const void* cls[TDN_CASCADE_MAX_STAGES];            // S matrices (R, C); bbox_head_detections: one
+  int32_t S;
   const void* reg;            // (R, reg_cols)
   const int32_t* img_shapes;  // (B, 2)
   const float* scales;        // (B,) or null
@@ -61,7 +63,19 @@ struct HeadArgs {
   float max_ratio;
 };
 
-template <int DT>
+// the logit of (r, c) at element offset i = r * C + c.  STAGES: (((x_0 + x_1) + ...) + x_{S-1}) / float(S), fp32
+// additions in stage order and one fp32 division (S = 1 divides by 1: the value itself)
+template <class T, bool STAGES>
+__device__ __forceinline__ float head_logit(const HeadArgs& A, size_t i) {
+  float v = (float)((const T*)A.cls[0])[i];
+  if constexpr (STAGES) {
+    for (int s = 1; s < A.S; ++s) v = __fadd_rn(v, (float)((const T*)A.cls[s])[i]);
+    v = __fdiv_rn(v, (float)A.S);
+  }
+  return v;
+}
+
+template <int DT, bool STAGES>
 __global__ __launch_bounds__(BLK) void det_softmax_decode_kernel(const HeadArgs A, float* __restrict__ scores,
                                                                  float* __restrict__ boxes) {
   typedef typename DetElem<DT>::T T;
@@ -79,13 +93,12 @@ __global__ __launch_bounds__(BLK) void det_softmax_decode_kernel(const HeadArgs 
       continue;
     }
     // softmax: the row of loss_roi_kernel, operation for operation
-    const T* xr = (const T*)A.cls + (size_t)r * C;
     float x[DET_COLS];
     float m = -INFINITY;
 #pragma unroll
     for (int j = 0; j < DET_COLS; ++j) {
       const int c = lane + 64 * j;
-      x[j] = c < C ? (float)xr[c] : -INFINITY;
+      x[j] = c < C ? head_logit<T, STAGES>(A, (size_t)r * C + c) : -INFINITY;
       m = fmaxf(m, x[j]);
     }
 #pragma unroll
@@ -408,13 +421,22 @@ extern "C" int64_t tdn_bbox_detections_workspace_bytes(int R, int C, int B) {
   return det_layout(p, nullptr).bytes;
 }
 
-extern "C" int tdn_bbox_detections(const float* rois, const void* cls, const void* reg, int dtype, int R, int C,
-                                   int reg_cols, int B, const int32_t* img_shapes, const float* scale_factors,
-                                   float scale_factor, const float* means4, const float* stds4, double wh_ratio_clip,
-                                   float score_thr, float nms_thr, int max_num, float* dense_scores, float* dense_boxes,
-                                   float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
-                                   int64_t workspace_bytes, void* stream) {
-  const char* who = "tdn_bbox_detections";
+namespace {
+
+template <bool STAGES>
+void head_launch(int dtype, dim3 grid, void* stream, const HeadArgs& H, float* dense_scores, float* dense_boxes) {
+  const dim3 block(BLK);
+  if (dtype == TDN_F32) TDN_LAUNCH((det_softmax_decode_kernel<TDN_F32, STAGES>), grid, block, 0, stream, H, dense_scores, dense_boxes);
+  else if (dtype == TDN_BF16) TDN_LAUNCH((det_softmax_decode_kernel<TDN_BF16, STAGES>), grid, block, 0, stream, H, dense_scores, dense_boxes);
+  else TDN_LAUNCH((det_softmax_decode_kernel<TDN_F16, STAGES>), grid, block, 0, stream, H, dense_scores, dense_boxes);
+}
+
+// tdn_bbox_detections (stages = false: cls[0] read as it is) and tdn_cascade_detections (stages = true: the mean of S)
+int head_detections(const char* who, bool stages, const float* rois, const void* const* cls, int S, const void* reg,
+                    int dtype, int R, int C, int reg_cols, int B, const int32_t* img_shapes, const float* scale_factors,
+                    float scale_factor, const float* means4, const float* stds4, double wh_ratio_clip, float score_thr,
+                    float nms_thr, int max_num, float* dense_scores, float* dense_boxes, float* dets, int64_t* labels,
+                    int64_t* row_idx, int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
   DetPlan p;
   if (det_plan(who, R, C, B, &p) != 0) return -1;
   TDN_CHECK(dtype == TDN_F32 || dtype == TDN_BF16 || dtype == TDN_F16, "%s: dtype %d", who, dtype);
@@ -423,11 +445,15 @@ extern "C" int tdn_bbox_detections(const float* rois, const void* cls, const voi
   TDN_CHECK(wh_ratio_clip > 0.0 && wh_ratio_clip < 1.0, "%s: wh_ratio_clip must be in (0, 1)", who);
   TDN_CHECK(scale_factors || scale_factor == 0.f || (scale_factor > 0.f && scale_factor - scale_factor == 0.f),
             "%s: scale_factor must be positive and finite (0: none)", who);
-  TDN_CHECK(R == 0 || (rois && cls && reg && dense_scores && dense_boxes), "%s: NULL pointer", who);
+  TDN_CHECK(R == 0 || (rois && reg && dense_scores && dense_boxes), "%s: NULL pointer", who);
   HeadArgs H;
   memset(&H, 0, sizeof(H));
   H.rois = rois;
-  H.cls = cls;
+  for (int s = 0; s < S; ++s) {
+    TDN_CHECK(R == 0 || cls[s], "%s: NULL pointer", who);
+    H.cls[s] = cls[s];
+  }
+  H.S = S;
   H.reg = reg;
   H.img_shapes = img_shapes;
   H.scales = scale_factors;
@@ -440,10 +466,9 @@ extern "C" int tdn_bbox_detections(const float* rois, const void* cls, const voi
   H.stds = host_f4(stds4);
   H.max_ratio = (float)fabs(log(wh_ratio_clip));     // as tdn_delta2bbox: in double, rounded to fp32
   if (R > 0) {
-    const dim3 grid(tdn_grid_1d(R, DET_WAVES, 4096)), block(BLK);
-    if (dtype == TDN_F32) TDN_LAUNCH(det_softmax_decode_kernel<TDN_F32>, grid, block, 0, stream, H, dense_scores, dense_boxes);
-    else if (dtype == TDN_BF16) TDN_LAUNCH(det_softmax_decode_kernel<TDN_BF16>, grid, block, 0, stream, H, dense_scores, dense_boxes);
-    else TDN_LAUNCH(det_softmax_decode_kernel<TDN_F16>, grid, block, 0, stream, H, dense_scores, dense_boxes);
+    const dim3 grid(tdn_grid_1d(R, DET_WAVES, 4096));
+    if (stages) head_launch<true>(dtype, grid, stream, H, dense_scores, dense_boxes);
+    else head_launch<false>(dtype, grid, stream, H, dense_scores, dense_boxes);
     TDN_LAUNCH_CHECK();
   }
   p.A.boxes = dense_boxes;
@@ -453,3 +478,322 @@ extern "C" int tdn_bbox_detections(const float* rois, const void* cls, const voi
   p.A.box_cols = reg_cols == 4 ? 4 : 4 * (C - 1);
   return det_run(who, p, score_thr, nms_thr, max_num, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
 }
+
+}  // namespace
+
+extern "C" int tdn_bbox_detections(const float* rois, const void* cls, const void* reg, int dtype, int R, int C,
+                                   int reg_cols, int B, const int32_t* img_shapes, const float* scale_factors,
+                                   float scale_factor, const float* means4, const float* stds4, double wh_ratio_clip,
+                                   float score_thr, float nms_thr, int max_num, float* dense_scores, float* dense_boxes,
+                                   float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+  return head_detections("tdn_bbox_detections", false, rois, &cls, 1, reg, dtype, R, C, reg_cols, B, img_shapes,
+                         scale_factors, scale_factor, means4, stds4, wh_ratio_clip, score_thr, nms_thr, max_num,
+                         dense_scores, dense_boxes, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tdn_cascade_detections(const float* rois, const void* const* cls, int num_stages, const void* reg,
+                                      int dtype, int R, int C, int reg_cols, int B, const int32_t* img_shapes,
+                                      const float* scale_factors, float scale_factor, const float* means4,
+                                      const float* stds4, double wh_ratio_clip, float score_thr, float nms_thr,
+                                      int max_num, float* dense_scores, float* dense_boxes, float* dets,
+                                      int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
+                                      int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_cascade_detections";
+  TDN_CHECK(cls && num_stages >= 1 && num_stages <= TDN_CASCADE_MAX_STAGES, "%s: %d stages (1..%d)", who, num_stages,
+            TDN_CASCADE_MAX_STAGES);
+  return head_detections(who, true, rois, cls, num_stages, reg, dtype, R, C, reg_cols, B, img_shapes, scale_factors,
+                         scale_factor, means4, stds4, wh_ratio_clip, score_thr, nms_thr, max_num, dense_scores,
+                         dense_boxes, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
+}
+
+// ---- box refinement between the stages of a cascade ---------------------------------------------------
+// Row r of (R, 5) rois decodes against the deltas of ONE class: its label (given, or the arg-max of its class logits).
+//   row-aligned  one launch, one thread per row, 256 rows per workgroup: row r of the output is [image, box] or
+//                [-1, 0, 0, 0, 0].
+//   compacted    two launches over chunks of REFINE_CHUNK = 1024 rows, one workgroup each, one thread per row:
+//     0 refine_count_kernel  kept rows of every image in the chunk -> chunk_cnt[chunk][B] (the workspace)
+//     1 refine_kernel        every workgroup sums chunk_cnt over the chunks before it (its images' first output rows)
+//                            and over all chunks (the counts); a kept row's position is that base + the kept rows of
+//                            its image in the waves before it (LDS) + those in the lanes before it (ballot), so an
+//                            image's rows keep their input order; rows past the counts are zeroed by the same launch.
+// The integer LDS atomics of launch 0 only count, so every output is a pure function of the inputs.
+namespace {
+
+constexpr int REFINE_CHUNK = TDN_REFINE_CHUNK;
+static_assert(REFINE_CHUNK == BLK, "one row per thread");
+
+struct RefineArgs {
+  const float* rois;          // (R, 5)
+  const void* reg;            // (R, reg_cols)
+  const int64_t* labels;      // (R,) or null
+  const void* cls;            // (R, C) or null: the label is the arg-max, ties to the lowest column
+  const int32_t* img_shapes;  // (B, 2)
+  const int32_t* gt_inds;     // (R,) or null
+  const float* gt;            // (B, G, 4) or null
+  int32_t R, C, reg_cols, B, G, P;
+  f32x4_t means, stds;
+  float max_ratio;
+};
+
+// image of row r if the row is kept, else -1: padding, a class-specific label outside [0, C), or (compacted mode with
+// gt_inds) a row whose four coordinates are bitwise those of its own ground truth
+__device__ __forceinline__ int refine_image(const RefineArgs& A, int r, long long label) {
+  int b = row_image(A.rois, IDX_ROI, r, A.B);
+  if (A.reg_cols != 4 && (label < 0 || label >= A.C)) b = -1;
+  if (b >= 0 && A.gt_inds) {
+    const int gi = A.gt_inds[r];
+    if (gi >= 0 && gi < A.G) {
+      const uint32_t* p = (const uint32_t*)(A.rois + (size_t)r * 5 + 1);
+      const uint32_t* g = (const uint32_t*)(A.gt + ((size_t)b * A.G + gi) * 4);
+      if (p[0] == g[0] && p[1] == g[1] && p[2] == g[2] && p[3] == g[3]) b = -1;
+    }
+  }
+  return b;
+}
+
+__global__ __launch_bounds__(BLK) void refine_count_kernel(const RefineArgs A, int* __restrict__ chunk_cnt) {
+  __shared__ int cnt[64];
+  const int tid = threadIdx.x;
+  if (tid < 64) cnt[tid] = 0;
+  __syncthreads();
+  const int r = blockIdx.x * REFINE_CHUNK + tid;
+  if (r < A.R) {
+    // with class logits the arg-max is always inside [0, C): the label only matters when it is given
+    const int b = refine_image(A, r, A.labels ? (long long)A.labels[r] : 0ll);
+    if (b >= 0) atomicAdd(&cnt[b], 1);
+  }
+  __syncthreads();
+  if (tid < A.B) chunk_cnt[blockIdx.x * A.B + tid] = cnt[tid];
+}
+
+// label of row r0 + lane: the wavefront takes its 64 rows ARGMAX_ROWS at a time (their loads are in flight together:
+// one row after the other is a chain of 64 load latencies), lanes stride the columns
+constexpr int ARGMAX_ROWS = 16;
+
+template <class T>
+__device__ __forceinline__ int wave_argmax(const T* cls, int r0, int R, int C, int lane) {
+  int label = 0;
+  for (int i0 = 0; i0 < 64 && r0 + i0 < R; i0 += ARGMAX_ROWS) {       // wave-uniform bounds
+    // no branch around a load: a row past R reads row R - 1 (its label is never used), a lane past C column C - 1
+    float best[ARGMAX_ROWS];
+    int bi[ARGMAX_ROWS];
+    const T* x[ARGMAX_ROWS];
+#pragma unroll
+    for (int k = 0; k < ARGMAX_ROWS; ++k) x[k] = cls + (size_t)min(r0 + i0 + k, R - 1) * C;
+#pragma unroll
+    for (int k = 0; k < ARGMAX_ROWS; ++k) {
+      const float v = (float)x[k][min(lane, C - 1)];
+      best[k] = lane < C ? v : -INFINITY;
+      bi[k] = lane < C ? lane : 0x7fffffff;
+    }
+    for (int c = lane + 64; c < C; c += 64) {
+      float v[ARGMAX_ROWS];
+#pragma unroll
+      for (int k = 0; k < ARGMAX_ROWS; ++k) v[k] = (float)x[k][c];
+#pragma unroll
+      for (int k = 0; k < ARGMAX_ROWS; ++k)
+        if (v[k] > best[k]) {                         // ascending columns: the first of equals stays
+          best[k] = v[k];
+          bi[k] = c;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+#pragma unroll
+      for (int k = 0; k < ARGMAX_ROWS; ++k) {
+        const float ov = __shfl_xor(best[k], o);
+        const int oi = __shfl_xor(bi[k], o);
+        if (ov > best[k] || (ov == best[k] && oi < bi[k])) {
+          best[k] = ov;
+          bi[k] = oi;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < ARGMAX_ROWS; ++k)
+      if (lane == i0 + k) label = bi[k];
+  }
+  return label;
+}
+
+template <int DT>
+__device__ __forceinline__ f32x4_t refine_box(const RefineArgs& A, int r, int b, int label) {
+  typedef typename DetElem<DT>::T T;
+  const float* roi = A.rois + (size_t)r * 5;
+  const f32x4_t rb = {roi[1], roi[2], roi[3], roi[4]};
+  const T* dr = (const T*)A.reg + (size_t)r * A.reg_cols + (A.reg_cols == 4 ? 0 : 4 * label);
+  f32x4_t d;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) d[e] = (float)dr[e];
+  return decode_box(rb, d, A.means, A.stds, A.max_ratio, A.img_shapes[2 * b], A.img_shapes[2 * b + 1]);
+}
+
+template <int DT, bool COMPACT>
+__global__ __launch_bounds__(BLK) void refine_kernel(const RefineArgs A, const int* __restrict__ chunk_cnt, int nchunks,
+                                                     float* __restrict__ rois_out, float* __restrict__ props,
+                                                     int32_t* __restrict__ counts) {
+  typedef typename DetElem<DT>::T T;
+  constexpr int W = BLK / 64;
+  __shared__ int part[2][W][64];                      // [before this chunk | all chunks][slice][image]
+  __shared__ int wcnt[W][64];                         // kept rows of (wave, image) in this chunk
+  __shared__ int base[64], total[64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (COMPACT) {
+    int pre = 0, tot = 0;                             // thread (slice = wave, image = lane)
+    if (lane < A.B)
+      for (int c = wave; c < nchunks; c += W) {
+        const int v = chunk_cnt[c * A.B + lane];
+        tot += v;
+        pre += c < (int)blockIdx.x ? v : 0;
+      }
+    part[0][wave][lane] = pre;
+    part[1][wave][lane] = tot;
+    wcnt[wave][lane] = 0;
+    __syncthreads();
+    if (tid < 64) {
+      int p = 0, t = 0;
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        p += part[0][w][tid];
+        t += part[1][w][tid];
+      }
+      base[tid] = p;
+      total[tid] = t;
+    }
+    __syncthreads();
+  }
+  const int r = blockIdx.x * blockDim.x + tid;        // compacted: blockDim.x = REFINE_CHUNK
+  const int r0 = r - lane;                            // the wavefront's first row
+  long long label = 0;
+  if (A.cls) label = wave_argmax((const T*)A.cls, r0, A.R, A.C, lane);
+  else if (r < A.R) label = A.labels[r];
+  const int b = r < A.R ? refine_image(A, r, label) : -1;
+  const bool keep = b >= 0;
+  if constexpr (!COMPACT) {
+    if (r < A.R) {
+      float* o = rois_out + (size_t)r * 5;
+      f32x4_t bx = {0.f, 0.f, 0.f, 0.f};
+      if (keep) bx = refine_box<DT>(A, r, b, (int)label);
+      o[0] = keep ? (float)b : -1.f;
+      o[1] = bx[0];
+      o[2] = bx[1];
+      o[3] = bx[2];
+      o[4] = bx[3];
+    }
+  } else {
+    // rank among the wavefront's kept rows of the same image: one ballot per distinct image of the wavefront
+    const u64 below = (1ull << lane) - 1ull;
+    int rank = 0;
+    u64 todo = __ballot(keep);
+    while (todo) {                                    // wave-uniform
+      const int leader = __ffsll((long long)todo) - 1;
+      const int lb = __shfl(b, leader);
+      const u64 same = __ballot(keep && b == lb);
+      if (keep && b == lb) rank = __popcll(same & below);
+      if (lane == leader) wcnt[wave][lb] = __popcll(same);
+      todo &= ~same;
+    }
+    __syncthreads();
+    if (keep) {
+      int pos = base[b] + rank;
+      for (int w = 0; w < wave; ++w) pos += wcnt[w][b];
+      if (pos < A.P) {
+        const f32x4_t bx = refine_box<DT>(A, r, b, (int)label);
+        float* o = props + ((size_t)b * A.P + pos) * 5;
+        o[0] = bx[0];
+        o[1] = bx[1];
+        o[2] = bx[2];
+        o[3] = bx[3];
+        o[4] = 0.f;
+      }
+    }
+    // the rows past every image's count, shared out over the grid
+    for (int q = blockIdx.x * BLK + tid; q < A.B * A.P; q += gridDim.x * BLK) {
+      const int bq = q / A.P, p = q - bq * A.P;
+      if (p >= total[bq]) {
+        float* o = props + (size_t)q * 5;
+#pragma unroll
+        for (int e = 0; e < 5; ++e) o[e] = 0.f;
+      }
+    }
+    if (blockIdx.x == 0 && tid < A.B) counts[tid] = min(total[tid], A.P);
+  }
+}
+
+constexpr int REFINE_ROWS = 256;                      // rows per workgroup of the row-aligned launch (no LDS, no scan)
+
+template <bool COMPACT>
+void refine_launch(int dtype, dim3 grid, void* stream, const RefineArgs& A, const int* chunk_cnt, int nchunks,
+                   float* rois_out, float* props, int32_t* counts) {
+  const dim3 block(COMPACT ? BLK : REFINE_ROWS);
+  if (dtype == TDN_F32) TDN_LAUNCH((refine_kernel<TDN_F32, COMPACT>), grid, block, 0, stream, A, chunk_cnt, nchunks, rois_out, props, counts);
+  else if (dtype == TDN_BF16) TDN_LAUNCH((refine_kernel<TDN_BF16, COMPACT>), grid, block, 0, stream, A, chunk_cnt, nchunks, rois_out, props, counts);
+  else TDN_LAUNCH((refine_kernel<TDN_F16, COMPACT>), grid, block, 0, stream, A, chunk_cnt, nchunks, rois_out, props, counts);
+}
+
+}  // namespace
+
+extern "C" int tdn_refine_bboxes(const float* rois, const void* bbox_pred, int dtype, int R, int reg_cols, int B,
+                                 const int32_t* img_shapes, const int64_t* labels, const void* cls_score, int C,
+                                 const int32_t* pos_gt_inds, const float* gt_bboxes, int G, const float* means4,
+                                 const float* stds4, double wh_ratio_clip, int max_per_img, float* rois_out,
+                                 float* proposals, int32_t* counts, void* workspace, int64_t workspace_bytes,
+                                 void* stream) {
+  const char* who = "tdn_refine_bboxes";
+  if (tdn_check_batch(who, B) != 0) return -1;
+  TDN_CHECK(dtype == TDN_F32 || dtype == TDN_BF16 || dtype == TDN_F16, "%s: dtype %d", who, dtype);
+  TDN_CHECK(R >= 0 && R <= TDN_DET_MAX_ROWS, "%s: %d rows (max %d)", who, R, TDN_DET_MAX_ROWS);
+  TDN_CHECK(C >= 1 && C <= TDN_DET_MAX_CLASSES, "%s: C=%d out of 1..%d", who, C, TDN_DET_MAX_CLASSES);
+  TDN_CHECK(reg_cols == 4 || reg_cols == 4 * C, "%s: reg_cols=%d is neither 4 nor 4 * C", who, reg_cols);
+  TDN_CHECK(max_per_img >= 0 && max_per_img <= TDN_RPN_MAX_NUM, "%s: max_per_img=%d out of 0..%d (0: row-aligned)", who,
+            max_per_img, TDN_RPN_MAX_NUM);
+  TDN_CHECK(means4 && stds4 && img_shapes, "%s: NULL means / stds / img_shapes", who);
+  TDN_CHECK(wh_ratio_clip > 0.0 && wh_ratio_clip < 1.0, "%s: wh_ratio_clip must be in (0, 1)", who);
+  TDN_CHECK((labels != nullptr) != (cls_score != nullptr) || R == 0, "%s: exactly one of labels and cls_score", who);
+  TDN_CHECK(R == 0 || (rois && bbox_pred), "%s: NULL pointer", who);
+  const bool compact = max_per_img > 0;
+  TDN_CHECK(compact ? (proposals && counts) : (R == 0 || rois_out), "%s: NULL output", who);
+  if (R == 0) pos_gt_inds = nullptr, gt_bboxes = nullptr;      // no row reads them
+  TDN_CHECK((pos_gt_inds != nullptr) == (gt_bboxes != nullptr) && (!pos_gt_inds || (compact && G >= 1)),
+            "%s: pos_gt_inds and gt_bboxes (B, G >= 1, 4) go together, in compacted mode only", who);
+  RefineArgs A;
+  memset(&A, 0, sizeof(A));
+  A.rois = rois;
+  A.reg = bbox_pred;
+  A.labels = labels;
+  A.cls = cls_score;
+  A.img_shapes = img_shapes;
+  A.gt_inds = pos_gt_inds;
+  A.gt = gt_bboxes;
+  A.R = R;
+  A.C = C;
+  A.reg_cols = reg_cols;
+  A.B = B;
+  A.G = G;
+  A.P = max_per_img;
+  A.means = host_f4(means4);
+  A.stds = host_f4(stds4);
+  A.max_ratio = (float)fabs(log(wh_ratio_clip));     // as tdn_delta2bbox: in double, rounded to fp32
+  const int nchunks = (R + REFINE_CHUNK - 1) / REFINE_CHUNK;
+  if (!compact) {
+    if (R > 0) {
+      refine_launch<false>(dtype, dim3((R + REFINE_ROWS - 1) / REFINE_ROWS), stream, A, nullptr, 0, rois_out, nullptr,
+                           nullptr);
+      TDN_LAUNCH_CHECK();
+    }
+    return 0;
+  }
+  int* chunk_cnt = nullptr;
+  if (nchunks > 0) {
+    tdn_carver c{(char*)workspace, 0};
+    chunk_cnt = c.take<int>((int64_t)nchunks * B);
+    if (tdn_check_ws(who, workspace, workspace_bytes, TDN_REFINE_WS_BYTES(R, B)) != 0) return -1;
+    TDN_LAUNCH(refine_count_kernel, dim3(nchunks), dim3(BLK), 0, stream, A, chunk_cnt);
+    TDN_LAUNCH_CHECK();
+  }
+  refine_launch<true>(dtype, dim3(nchunks > 0 ? nchunks : 1), stream, A, chunk_cnt, nchunks, nullptr, proposals, counts);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
