@@ -574,6 +574,33 @@ int tdn_sample_rois(const float* proposals, const int32_t* counts, const float* 
                     float* rois, int64_t* labels, float* label_weights, float* bbox_targets, float* bbox_weights,
                     int32_t* pos_gt_inds, int32_t* num_pos, int32_t* num_neg, void* workspace,
                     int64_t workspace_bytes, void* stream);
+/* IoU-balanced negative sampling (Libra R-CNN): tdn_sample_assigned and tdn_sample_rois with ONLY the
+ * choice of negatives replaced; assignment, positives, row layout, labels, targets, weights and the launch counts are
+ * theirs.  "Choose k of a set at random" is "the k smallest (key, index) of the set" with tdn_sample_assigned's keys.
+ * Per image, o_i = max_overlaps of candidate i, n = the number of negatives tdn_sample_assigned would take at most:
+ *   at most n negatives: all of them.  Else among the negatives F = {o < floor_thr}, S = {o >= floor_thr}, t0 = floor_thr
+ *   (floor_thr > 0); F = {o == 0}, S = {o > 0}, t0 = 0 (floor_thr == 0); F empty, S all, t0 = 0 (floor_thr < 0).
+ *   n_S = (int)((double)n * (1.0 - (double)floor_fraction)).  |S| <= n_S: all of S.  Else, num_bins >= 2: m = the maximum
+ *   of o over ALL candidates of the image, w = (m - t0) / num_bins, per = n_S / num_bins (integers); from each bin
+ *   {i in S: t0 + k w <= o_i < t0 + (k + 1) w} (fp32, product and sum rounded separately), k = 0 .. num_bins - 1, its
+ *   per smallest (all if it has no more); then the n_S - taken smallest of the rest of S.  num_bins == 1: the n_S smallest
+ *   of S.  Then from F the n - taken smallest (all if it has no more), then from the remaining negatives up to n.
+ * num_bins 1..8, floor_fraction in [0, 1], floor_thr < 1.  max_overlaps fp32 [B][N] as tdn_assign_max_iou writes it. */
+typedef struct tdn_balanced_config {
+  float floor_thr;
+  float floor_fraction;
+  int32_t num_bins;
+  int32_t reserved;
+} tdn_balanced_config;
+int tdn_sample_assigned_balanced(const int32_t* assigned, const float* max_overlaps, int B, int N,
+                                 const tdn_target_config* cfg, const tdn_balanced_config* bal, const int32_t* keys,
+                                 uint8_t* pos_mask, uint8_t* neg_mask, int32_t* num_pos, int32_t* num_neg, void* stream);
+int64_t tdn_sample_rois_balanced_workspace_bytes(int B, int P, int G, int add_gt_as_proposals);
+int tdn_sample_rois_balanced(const float* proposals, const int32_t* counts, const float* gt, const int64_t* gt_labels,
+                             const int32_t* gt_counts, int B, int P, int G, const tdn_target_config* cfg,
+                             const tdn_balanced_config* bal, const int32_t* keys, float* rois, int64_t* labels,
+                             float* label_weights, float* bbox_targets, float* bbox_weights, int32_t* pos_gt_inds,
+                             int32_t* num_pos, int32_t* num_neg, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- losses of the dense anchor heads (RPN, RetinaNet) and of the RoI box head, with their gradients (DESIGN.md §4e:
  *      sigmoid BCE / focal + smooth L1 over the level-major anchors of tdn_anchor_target; softmax CE + smooth L1 over
@@ -634,6 +661,23 @@ int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int R, int C, 
 int tdn_loss_roi_bwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols, const int64_t* labels,
                      const float* label_weights, const float* bbox_targets, const float* bbox_weights, float beta,
                      const float* g, const float* avg_in, void* dcls, void* dreg, void* stream);
+/* The same two entry points with balanced L1 (Libra R-CNN) in place of smooth L1 as the box term; the
+ * classification term, the divisor, the weight-0 rule, the column rule, the reduction and the workspace
+ * (tdn_loss_roi_workspace_bytes) are the same.  Per element, fp32, in the order written, d = pred - target, a = |d|:
+ *   a <  beta:  t = log1pf((b a) / beta);  l = ((alpha / b) (b a + 1)) t - alpha a;
+ *               dl = sign(d) (alpha t + (alpha (1 - beta)) / (b a + beta))      (the second term is +0 at beta = 1)
+ *   a >= beta:  l = gamma a + (gamma / b - alpha beta);                              dl = sign(d) gamma
+ * b = e^(gamma / alpha) - 1, alpha / b, gamma / b - alpha beta and alpha (1 - beta) are formed on the host in double and
+ * rounded once to fp32.  alpha, gamma finite and > 0, b finite in fp32; beta is the knee.  a = 0: loss 0 and gradient 0
+ * exactly. */
+int tdn_loss_roi_balanced_fwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
+                              const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                              const float* bbox_weights, float beta, float alpha, float gamma, const tdn_loss_avg* avg,
+                              float* losses, float* avg_out, void* workspace, int64_t workspace_bytes, void* stream);
+int tdn_loss_roi_balanced_bwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
+                              const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                              const float* bbox_weights, float beta, float alpha, float gamma, const float* g,
+                              const float* avg_in, void* dcls, void* dreg, void* stream);
 
 /* ---- test-time detections of the RoI box head: softmax + decode, per-class NMS, per-image top-k (the
  *      project's own spec in the mmdetection-v0.x lineage of multiclass_nms / get_det_bboxes; NMS is tdn_batched_nms's
@@ -1228,6 +1272,41 @@ int tdn_pyr_gn_fwd(const tdn_pyr_gn_level* levels, int num_levels, int B, const 
 int tdn_pyr_gn_bwd(const tdn_pyr_gn_level* levels, int num_levels, int B, const float* stats, const float* gamma, int C,
                    int G, int relu, float* dgamma, float* dbeta, float acc, void* workspace, int64_t workspace_bytes,
                    int dtype, void* stream);
+
+/* ---- Balanced Feature Pyramid, Libra R-CNN's BFP neck (csrc/bfp.hip) ------------------------------------------
+ * levels: HOST array of 1..TDN_PYR_MAX_LEVELS entries of one batch size B (1..64), one channel count C (a multiple of 8 in
+ * 8..1024) and a map size (H, W) each, 1 <= H, W <= 32767 and B H W C < 2^31, in ANY relation to one another.  All maps
+ * are dense NHWC (B, H, W, C), 16-bit, 16-byte aligned, finite.  (Hg, Wg) is the size of level refine_level; bsf and dbsf
+ * are (B, Hg, Wg, C).  An axis map sends destination index d to a window [lo, hi) of n_src source indices:
+ *   pool     lo = floor(d n_src / n_dst), hi = ceil((d + 1) n_src / n_dst)   (adaptive_max_pool2d; windows may overlap)
+ *   nearest  lo = min((int)floorf((float)d * ((float)n_src / (float)n_dst)), n_src - 1), hi = lo + 1, fp32 (interpolate)
+ * and a destination element is the FIRST maximum of its 2-D window in row-major order.  M_l (level -> refine grid) is the
+ * pool for l < refine_level and nearest otherwise; N_l (refine grid -> level) is nearest for l < refine_level and the pool
+ * otherwise.  Sums are fp32, in the order written, starting from +0; every result is rounded once to the dtype.
+ *   tdn_bfp_gather_fwd:  reads x.   bsf[q] = (M_0(x_0)[q] + M_1(x_1)[q] + ...) / L, one fp32 division.
+ *   tdn_bfp_scatter_fwd: reads x, writes out.   out_l[p] = N_l(bsf)[p] + x_l[p]   (bsf: the refined map).
+ *   tdn_bfp_scatter_bwd: reads g.   dbsf[q] = s_0 + s_1 + ..., s_l = the sum, in row-major order of p, of g_l[p] over the
+ *                        p whose window under N_l contains q and has its first maximum, recomputed from bsf, at q.
+ *   tdn_bfp_gather_bwd:  reads x, g, writes dx.   dx_l[p] = g_l[p] + s / L, s = the sum, in row-major order of q, of
+ *                        dbsf[q] over the q whose window under M_l contains p and has its first maximum, recomputed from
+ *                        x_l, at p.
+ * One launch each, no workspace, no atomics: every element is written once by one lane; the same bits on every run. */
+typedef struct tdn_bfp_level {
+  const void* x;
+  void* out;
+  const void* g;
+  void* dx;
+  int32_t H;
+  int32_t W;
+} tdn_bfp_level;
+int tdn_bfp_gather_fwd(const tdn_bfp_level* levels, int num_levels, int refine_level, int B, int C, void* bsf, int dtype,
+                       void* stream);
+int tdn_bfp_scatter_fwd(const tdn_bfp_level* levels, int num_levels, int refine_level, int B, int C, const void* bsf,
+                        int dtype, void* stream);
+int tdn_bfp_scatter_bwd(const tdn_bfp_level* levels, int num_levels, int refine_level, int B, int C, const void* bsf,
+                        void* dbsf, int dtype, void* stream);
+int tdn_bfp_gather_bwd(const tdn_bfp_level* levels, int num_levels, int refine_level, int B, int C, const void* dbsf,
+                       int dtype, void* stream);
 
 /* ---- deformable convolution, DCN v1 / v2 (csrc/deform.hip) ---------------------------------------------
  * y = conv1x1(cols, W) with cols[n, ho, wo, k, c] the bilinear sample of x (N, H, W, C NHWC, 16-bit) at

@@ -15,7 +15,8 @@ conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask 
 ``anchor_head_loss`` / ``anchor_head_detections``, and ``FCOSHead`` with the operations around it: ``fcos_points`` /
 ``fcos_target`` / ``fcos_loss`` / ``fcos_detections``, and deformable convolution ``deform_conv2d`` with the modules
 ``DeformConv`` / ``ModulatedDeformConv`` / ``DeformConvPack`` / ``ModulatedDeformConvPack``, and Cascade R-CNN's
-``refine_bboxes`` / ``cascade_detections`` / ``CascadeRoIHead``).  Everything computes through libtdn.so
+``refine_bboxes`` / ``cascade_detections`` / ``CascadeRoIHead``, and Libra R-CNN's ``BFP`` neck,
+``sample_assigned_iou_balanced`` / ``sample_rois(neg_sampler='iou_balanced')`` and ``bbox_head_loss(reg_loss='balanced_l1')``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -28,15 +29,16 @@ from .inits import (bias_init_with_prob, constant_init, kaiming_init, normal_ini
 from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint  # noqa: F401
 from .backbone import (BasicBlock, Bottleneck, ResNet, ResNeXt, ResNeXtBasicBlock,  # noqa: F401
                        ResNeXtBottleneck)
-from .necks import FPN, PAFPN  # noqa: F401
+from .necks import BFP, FPN, PAFPN  # noqa: F401
 from .staging import ImageTransforms, StagedImages  # noqa: F401
 from .graph import GraphedStep, PreparedStep  # noqa: F401
 from .functional import invalidate_packed  # noqa: F401
 from .box import (AnchorGenerator, anchor_pyramid, batched_nms, bbox2delta, bbox_denormalize,  # noqa: F401
                   bbox_normalize, bbox_overlaps, delta2bbox, nms, nms_mask, rpn_proposals)
-from .target import anchor_target, assign_max_iou, sample_assigned, sample_rois  # noqa: F401
-from .losses import (AnchorHeadLossFunction, BBoxHeadLossFunction, anchor_head_loss,  # noqa: F401
-                     bbox_head_loss, rpn_loss)
+from .target import (anchor_target, assign_max_iou, sample_assigned, sample_assigned_iou_balanced,  # noqa: F401
+                     sample_rois)
+from .losses import (AnchorHeadLossFunction, BalancedBBoxHeadLossFunction, BBoxHeadLossFunction,  # noqa: F401
+                     anchor_head_loss, bbox_head_loss, rpn_loss)
 from .detect import bbox_head_detections, multiclass_nms  # noqa: F401
 from .dense_detect import (anchor_head_detections, anchor_head_detections_plan,  # noqa: F401
                            anchor_target_all)

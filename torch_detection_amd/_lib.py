@@ -144,6 +144,15 @@ class TargetConfig(ctypes.Structure):
 _TC = ctypes.POINTER(TargetConfig)
 
 
+class BalancedConfig(ctypes.Structure):
+    """Mirror of ``tdn_balanced_config`` (include/tdn.h)."""
+    _fields_ = [("floor_thr", c_float), ("floor_fraction", c_float), ("num_bins", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+_BC = ctypes.POINTER(BalancedConfig)
+
+
 class LossLevel(ctypes.Structure):
     """Mirror of ``tdn_loss_level`` (include/tdn.h)."""
     _fields_ = [("cls", c_void_p), ("reg", c_void_p), ("dcls", c_void_p), ("dreg", c_void_p),
@@ -253,6 +262,15 @@ class PyrGnLevel(ctypes.Structure):
 
 
 _PgL = ctypes.POINTER(PyrGnLevel)
+
+
+class BfpLevel(ctypes.Structure):
+    """Mirror of ``tdn_bfp_level`` (include/tdn.h): one pyramid level of the Balanced Feature Pyramid."""
+    _fields_ = [("x", c_void_p), ("out", c_void_p), ("g", c_void_p), ("dx", c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
+_BfL = ctypes.POINTER(BfpLevel)
 _I32P = ctypes.POINTER(ctypes.c_int32)
 
 
@@ -368,6 +386,10 @@ SIGNATURES = {
                           [c_i64, c_void_p]),
     "tdn_sample_rois_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "tdn_sample_rois": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, _TC] + [c_void_p] * 10 + [c_i64, c_void_p]),
+    "tdn_sample_assigned_balanced": (c_int, [c_void_p, c_void_p, c_int, c_int, _TC, _BC] + [c_void_p] * 6),
+    "tdn_sample_rois_balanced_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "tdn_sample_rois_balanced": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, _TC, _BC] + [c_void_p] * 10 +
+                                 [c_i64, c_void_p]),
     "tdn_loss_dense_workspace_bytes": (c_i64, [_LL, c_int, c_int, _LC]),
     "tdn_loss_dense_fwd": (c_int, [_LL, c_int, c_int, _LC] + [c_void_p] * 4 + [_LA, c_void_p, c_void_p, c_void_p, c_i64,
                                                                               c_void_p]),
@@ -377,6 +399,10 @@ SIGNATURES = {
                          [c_float, _LA, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "tdn_loss_roi_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4 +
                          [c_float] + [c_void_p] * 5),
+    "tdn_loss_roi_balanced_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4 +
+                                  [c_float, c_float, c_float, _LA, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "tdn_loss_roi_balanced_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4 +
+                                  [c_float, c_float, c_float] + [c_void_p] * 5),
     "tdn_multiclass_nms_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
     "tdn_multiclass_nms": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
                                    c_int] + [c_void_p] * 5 + [c_i64, c_void_p]),
@@ -457,6 +483,10 @@ SIGNATURES = {
                                c_i64, c_int, c_void_p]),
     "tdn_pyr_gn_bwd": (c_int, [_PgL, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                                c_void_p, c_i64, c_int, c_void_p]),
+    "tdn_bfp_gather_fwd": (c_int, [_BfL, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "tdn_bfp_scatter_fwd": (c_int, [_BfL, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "tdn_bfp_scatter_bwd": (c_int, [_BfL, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "tdn_bfp_gather_bwd": (c_int, [_BfL, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "tdn_roi_map_levels": (c_int, [c_void_p, c_i64, c_int, c_float, c_void_p, c_void_p]),
     "tdn_roi_align_fwd": (c_int, [_RoL, c_int, c_int, c_int, c_void_p, c_i64, _RoC, c_void_p, c_void_p]),
     "tdn_roi_align_bwd_workspace": (c_i64, [c_i64]),

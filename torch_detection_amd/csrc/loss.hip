@@ -260,9 +260,10 @@ struct RoiArgs {
   const float* bw;
   int32_t R, C, reg_cols;
   float beta;
+  BalancedL1 bal;                 // BALANCED instantiations only
 };
 
-template <int DT, bool GRAD>
+template <int DT, bool GRAD, bool BALANCED>
 __global__ __launch_bounds__(LT) void loss_roi_kernel(const RoiArgs A, const float* __restrict__ g,
                                                       const float* __restrict__ avg, double* __restrict__ partials) {
   typedef Elem<DT> E;
@@ -338,7 +339,8 @@ __global__ __launch_bounds__(LT) void loss_roi_kernel(const RoiArgs A, const flo
       float res = 0.f;
       if (bw != 0.f) {
         const float pred = E::ld(((const T*)A.reg)[(size_t)r * A.reg_cols + col0 + lane]);
-        const float v = smooth_l1<GRAD>(pred, A.bt[(size_t)r * 4 + lane], A.beta);
+        const float tgt = A.bt[(size_t)r * 4 + lane];
+        const float v = BALANCED ? balanced_l1<GRAD>(pred, tgt, A.bal) : smooth_l1<GRAD>(pred, tgt, A.beta);
         if (GRAD) res = __fmul_rn(__fmul_rn(bw, v), s_reg);
         else acc_reg += (double)__fmul_rn(bw, v);
       }
@@ -458,6 +460,23 @@ int check_roi(const char* who, int dtype, int R, int C, int reg_cols, float beta
   return 0;
 }
 
+// the knee, the two shape parameters and the host-formed constants of balanced L1
+int balanced_params(const char* who, float beta, float alpha, float gamma, BalancedL1* P) {
+  TDN_CHECK(alpha > 0.f && alpha < INFINITY && gamma > 0.f && gamma < INFINITY,
+            "%s: balanced L1 needs finite alpha > 0 and gamma > 0", who);
+  const double b = exp((double)gamma / (double)alpha) - 1.0;
+  P->alpha = alpha;
+  P->gamma = gamma;
+  P->beta = beta;
+  P->b = (float)b;
+  P->alpha_over_b = (float)((double)alpha / b);
+  P->outer_c = (float)((double)gamma / b - (double)alpha * (double)beta);
+  P->knee_c = (float)((double)alpha * (1.0 - (double)beta));
+  TDN_CHECK(P->b > 0.f && P->b < INFINITY && P->alpha_over_b > 0.f, "%s: gamma / alpha = %g leaves float range", who,
+            (double)gamma / (double)alpha);
+  return 0;
+}
+
 #define LOSS_LAUNCH_DT(kernel, GRAD, dtype, grid, st, ...)                                             \
   do {                                                                                                 \
     if ((dtype) == TDN_F32) TDN_LAUNCH((kernel<TDN_F32, GRAD>), grid, dim3(LT), 0, st, __VA_ARGS__);    \
@@ -523,13 +542,22 @@ extern "C" int64_t tdn_loss_roi_workspace_bytes(int R) {
   return partials_layout(roi_blocks(R), nullptr).bytes;
 }
 
-extern "C" int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
-                                const int64_t* labels, const float* label_weights, const float* bbox_targets,
-                                const float* bbox_weights, float beta, const tdn_loss_avg* avg, float* losses,
-                                float* avg_out, void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* who = "tdn_loss_roi_fwd";
+namespace {
+
+#define LOSS_LAUNCH_ROI(GRAD, BAL, dtype, grid, st, ...)                                                          \
+  do {                                                                                                            \
+    if ((dtype) == TDN_F32) TDN_LAUNCH((loss_roi_kernel<TDN_F32, GRAD, BAL>), grid, dim3(LT), 0, st, __VA_ARGS__); \
+    else if ((dtype) == TDN_F16) TDN_LAUNCH((loss_roi_kernel<TDN_F16, GRAD, BAL>), grid, dim3(LT), 0, st, __VA_ARGS__); \
+    else TDN_LAUNCH((loss_roi_kernel<TDN_BF16, GRAD, BAL>), grid, dim3(LT), 0, st, __VA_ARGS__);                   \
+  } while (0)
+
+// bal: nullptr for smooth L1
+int roi_fwd(const char* who, const BalancedL1* bal, const void* cls, const void* reg, int dtype, int R, int C,
+            int reg_cols, const int64_t* labels, const float* label_weights, const float* bbox_targets,
+            const float* bbox_weights, float beta, const tdn_loss_avg* avg, float* losses, float* avg_out,
+            void* workspace, int64_t workspace_bytes, void* stream) {
   AvgArgs V;
-  if (check_roi(who, dtype, R, C, reg_cols, beta) != 0 || check_avg(who, avg, true, &V) != 0) return -1;
+  if (check_avg(who, avg, true, &V) != 0) return -1;
   TDN_CHECK(losses && avg_out && workspace, "%s: NULL pointer", who);
   TDN_CHECK(R == 0 || (cls && reg && labels && label_weights && bbox_targets && bbox_weights), "%s: NULL pointer", who);
   const int blocks = roi_blocks(R);
@@ -547,8 +575,10 @@ extern "C" int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int
   A.C = C;
   A.reg_cols = reg_cols;
   A.beta = beta;
+  if (bal) A.bal = *bal;
   const float* none = nullptr;
-  LOSS_LAUNCH_DT(loss_roi_kernel, false, dtype, dim3(blocks), stream, A, none, none, w.partials);
+  if (bal) LOSS_LAUNCH_ROI(false, true, dtype, dim3(blocks), stream, A, none, none, w.partials);
+  else LOSS_LAUNCH_ROI(false, false, dtype, dim3(blocks), stream, A, none, none, w.partials);
   TDN_LAUNCH_CHECK();
   TDN_LAUNCH(loss_finalize_kernel, dim3(1), dim3(LMAX_BLOCKS), 0, stream, (const double*)w.partials, blocks, V, losses,
              avg_out);
@@ -556,12 +586,10 @@ extern "C" int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int
   return 0;
 }
 
-extern "C" int tdn_loss_roi_bwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
-                                const int64_t* labels, const float* label_weights, const float* bbox_targets,
-                                const float* bbox_weights, float beta, const float* g, const float* avg_in, void* dcls,
-                                void* dreg, void* stream) {
-  const char* who = "tdn_loss_roi_bwd";
-  if (check_roi(who, dtype, R, C, reg_cols, beta) != 0) return -1;
+int roi_bwd(const char* who, const BalancedL1* bal, const void* cls, const void* reg, int dtype, int R, int C,
+            int reg_cols, const int64_t* labels, const float* label_weights, const float* bbox_targets,
+            const float* bbox_weights, float beta, const float* g, const float* avg_in, void* dcls, void* dreg,
+            void* stream) {
   if (R == 0) return 0;
   TDN_CHECK(cls && reg && labels && label_weights && bbox_targets && bbox_weights && g && avg_in && dcls && dreg,
             "%s: NULL pointer", who);
@@ -579,8 +607,55 @@ extern "C" int tdn_loss_roi_bwd(const void* cls, const void* reg, int dtype, int
   A.C = C;
   A.reg_cols = reg_cols;
   A.beta = beta;
+  if (bal) A.bal = *bal;
   double* none = nullptr;
-  LOSS_LAUNCH_DT(loss_roi_kernel, true, dtype, dim3(roi_blocks(R)), stream, A, g, avg_in, none);
+  if (bal) LOSS_LAUNCH_ROI(true, true, dtype, dim3(roi_blocks(R)), stream, A, g, avg_in, none);
+  else LOSS_LAUNCH_ROI(true, false, dtype, dim3(roi_blocks(R)), stream, A, g, avg_in, none);
   TDN_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
+                                const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                                const float* bbox_weights, float beta, const tdn_loss_avg* avg, float* losses,
+                                float* avg_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_loss_roi_fwd";
+  if (check_roi(who, dtype, R, C, reg_cols, beta) != 0) return -1;
+  return roi_fwd(who, nullptr, cls, reg, dtype, R, C, reg_cols, labels, label_weights, bbox_targets, bbox_weights, beta,
+                 avg, losses, avg_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tdn_loss_roi_bwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
+                                const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                                const float* bbox_weights, float beta, const float* g, const float* avg_in, void* dcls,
+                                void* dreg, void* stream) {
+  const char* who = "tdn_loss_roi_bwd";
+  if (check_roi(who, dtype, R, C, reg_cols, beta) != 0) return -1;
+  return roi_bwd(who, nullptr, cls, reg, dtype, R, C, reg_cols, labels, label_weights, bbox_targets, bbox_weights, beta, g,
+                 avg_in, dcls, dreg, stream);
+}
+
+extern "C" int tdn_loss_roi_balanced_fwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
+                                         const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                                         const float* bbox_weights, float beta, float alpha, float gamma,
+                                         const tdn_loss_avg* avg, float* losses, float* avg_out, void* workspace,
+                                         int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_loss_roi_balanced_fwd";
+  BalancedL1 P;
+  if (check_roi(who, dtype, R, C, reg_cols, beta) != 0 || balanced_params(who, beta, alpha, gamma, &P) != 0) return -1;
+  return roi_fwd(who, &P, cls, reg, dtype, R, C, reg_cols, labels, label_weights, bbox_targets, bbox_weights, beta, avg,
+                 losses, avg_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tdn_loss_roi_balanced_bwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
+                                         const int64_t* labels, const float* label_weights, const float* bbox_targets,
+                                         const float* bbox_weights, float beta, float alpha, float gamma, const float* g,
+                                         const float* avg_in, void* dcls, void* dreg, void* stream) {
+  const char* who = "tdn_loss_roi_balanced_bwd";
+  BalancedL1 P;
+  if (check_roi(who, dtype, R, C, reg_cols, beta) != 0 || balanced_params(who, beta, alpha, gamma, &P) != 0) return -1;
+  return roi_bwd(who, &P, cls, reg, dtype, R, C, reg_cols, labels, label_weights, bbox_targets, bbox_weights, beta, g,
+                 avg_in, dcls, dreg, stream);
 }

@@ -36,6 +36,34 @@ __device__ __forceinline__ float cls_elem(float x, bool t, const ClsParams& P) {
   return __fmul_rn(mod, inner);
 }
 
+// Balanced L1 (Libra R-CNN) of one box coordinate, knee at beta:
+//   a <  beta:  t = log1pf((b a) / beta);  l = ((alpha / b) (b a + 1)) t - alpha a
+//               dl = sign(d) (alpha t + (alpha (1 - beta)) / (b a + beta))
+//   a >= beta:  l = gamma a + (gamma / b - alpha beta);                              dl = sign(d) gamma
+// d = pred - target, a = |d|; b = e^(gamma / alpha) - 1 and the constants alpha / b, gamma / b - alpha beta and
+// alpha (1 - beta) are formed on the host in double and rounded once.  The second term of dl is what the derivative of l
+// has beside alpha t when the knee is not at 1; at beta = 1 it is +0 and dl = sign(d) (alpha t) bit for bit.
+// a = 0 gives loss 0 and gradient 0 exactly (sign(0) = 0); a == beta is the outer branch.
+struct BalancedL1 {
+  float alpha, gamma, beta, b, alpha_over_b, outer_c, knee_c;
+};
+template <bool GRAD>
+__device__ __forceinline__ float balanced_l1(float pred, float target, const BalancedL1& P) {
+  const float d = __fsub_rn(pred, target);
+  const float a = fabsf(d);
+  if (a < P.beta) {
+    const float ba = __fmul_rn(P.b, a);
+    const float t = log1pf(__fdiv_rn(ba, P.beta));
+    if (GRAD) {
+      const float v = __fadd_rn(__fmul_rn(P.alpha, t), __fdiv_rn(P.knee_c, __fadd_rn(ba, P.beta)));
+      return d > 0.f ? v : (d < 0.f ? -v : d);
+    }
+    return __fsub_rn(__fmul_rn(__fmul_rn(P.alpha_over_b, __fadd_rn(ba, 1.f)), t), __fmul_rn(P.alpha, a));
+  }
+  if (GRAD) return d > 0.f ? P.gamma : (d < 0.f ? -P.gamma : d);      // NaN stays NaN
+  return __fadd_rn(__fmul_rn(P.gamma, a), P.outer_c);
+}
+
 // ---- storage types ------------------------------------------------------------------------------------------------
 template <int DT> struct Elem;
 template <> struct Elem<TDN_F32> {

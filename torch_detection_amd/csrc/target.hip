@@ -229,6 +229,52 @@ struct ClassFetch {
   }
 };
 
+// The marking pass of a selection: key > T is taken, key == T while fewer than `need` of them came before in index order.
+// CLEAR: a byte that is not taken becomes 0 (the row is this selection's alone); else it keeps what it holds (the row
+// collects several selections).
+template <bool CLEAR, class Fetch>
+__device__ __forceinline__ void mark_selected(const Fetch& F, int N, uint32_t T, int need, uint8_t* mrow, int* misc) {
+  const int tid = threadIdx.x;
+  int ties_done = 0;
+  for (int base = 0; base < N; base += TK_STEP) {
+    const int i0 = base + tid * TK_PER;
+    const int cnt = max(0, min(TK_PER, N - i0));
+    uint32_t kk[TK_PER];
+    if (cnt > 0) F(i0, cnt, kk);
+    int tpos = 0;
+    if (need > 0) {                            // workgroup-uniform
+      int nt = 0, tot;
+#pragma unroll
+      for (int e = 0; e < TK_PER; ++e)
+        if (e < cnt) nt += kk[e] == T ? 1 : 0;
+      tpos = ties_done + block_excl_scan(nt, misc, &tot);
+      ties_done += tot;
+    }
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e)
+      if (e < cnt) {
+        bool sel = kk[e] > T;
+        if (kk[e] == T) {
+          sel = tpos < need;
+          ++tpos;
+        }
+        if (CLEAR) mrow[i0 + e] = sel ? 1 : 0;
+        else if (sel) mrow[i0 + e] = 1;
+      }
+  }
+}
+
+// The k smallest (key, index) of the `members` of a class into mrow; k <= members.
+__device__ __forceinline__ void select_class(const ClassFetch& F, int N, int k, int members, uint8_t* mrow, int* hist,
+                                             int* misc) {
+  uint32_t T;
+  int need = 0;
+  if (k == members) T = 0x7FFFFFFFu;           // every member
+  else if (k == 0) T = 0xFFFFFFFFu;            // nothing
+  else T = block_radix_threshold(F, N, k, hist, misc, &need);
+  mark_selected<true>(F, N, T, need, mrow, misc);
+}
+
 struct SampleArgs {
   int N, num, num_pos_expected;
   double neg_pos_ub;
@@ -263,40 +309,143 @@ __global__ __launch_bounds__(1024) void sample_select_kernel(const SampleArgs A,
   const int neg = min(nneg, max(neg_exp, 0));
   const int k = cls ? neg : pos, members = cls ? nneg : npos;
   const ClassFetch F{arow, keys ? keys + (int64_t)b * N : nullptr, A.seed, (uint32_t)b, cls};
-  // key > T is taken, key == T while fewer than `need` of them came before in index order
-  uint32_t T;
-  int need = 0;
-  if (k == members) T = 0x7FFFFFFFu;           // every member
-  else if (k == 0) T = 0xFFFFFFFFu;            // nothing
-  else T = block_radix_threshold(F, N, k, hist, misc, &need);
-  uint8_t* mrow = (cls ? neg_mask : pos_mask) + (int64_t)b * N;
-  int ties_done = 0;
-  for (int base = 0; base < N; base += TK_STEP) {
-    const int i0 = base + tid * TK_PER;
-    const int cnt = max(0, min(TK_PER, N - i0));
-    uint32_t kk[TK_PER];
-    if (cnt > 0) F(i0, cnt, kk);
-    int tpos = 0;
-    if (need > 0) {                            // workgroup-uniform
-      int nt = 0, tot;
-#pragma unroll
-      for (int e = 0; e < TK_PER; ++e)
-        if (e < cnt) nt += kk[e] == T ? 1 : 0;
-      tpos = ties_done + block_excl_scan(nt, misc, &tot);
-      ties_done += tot;
-    }
+  select_class(F, N, k, members, (cls ? neg_mask : pos_mask) + (int64_t)b * N, hist, misc);
+  if (tid == 0) (cls ? num_neg : num_pos)[b] = k;
+}
+
+// ---- IoU-balanced negatives (Libra R-CNN) -------------------------------------------------------------
+// The positives are sample_select_kernel's.  The negatives of an image are chosen by a sequence of dependent keyed
+// selections — "the k smallest (key, index) of a set" with the set changing from one to the next — run one after the
+// other by the image's second workgroup; the byte row of neg_mask is the "taken" state between them.
+struct BalancedArgs {
+  float floor_thr, floor_fraction;
+  int num_bins;
+};
+
+// negatives not taken yet, of one category: 0 a bin [lo, hi) of S, 1 S, 2 F (the floor set), 3 any
+struct BalancedFetch {
+  const int32_t* assigned;
+  const float* ov;
+  const int32_t* keys;
+  const uint8_t* taken;
+  uint32_t seed, b;
+  int kind;
+  float lo, hi, floor_thr;
+  __device__ __forceinline__ bool in_s(float o) const {
+    return floor_thr > 0.f ? o >= floor_thr : (floor_thr == 0.f ? o > 0.f : true);
+  }
+  __device__ __forceinline__ bool member(int i) const {
+    if (assigned[i] != 0 || taken[i] != 0) return false;
+    const float o = ov[i];
+    if (kind == 0) return in_s(o) && o >= lo && o < hi;
+    if (kind == 1) return in_s(o);
+    if (kind == 2) return !in_s(o);          // the negatives outside S: 0 <= o < floor_thr, or o == 0 at floor_thr == 0
+    return true;
+  }
+  __device__ __forceinline__ void operator()(int i0, int cnt, uint32_t* kk) const {
 #pragma unroll
     for (int e = 0; e < TK_PER; ++e)
       if (e < cnt) {
-        bool sel = kk[e] > T;
-        if (kk[e] == T) {
-          sel = tpos < need;
-          ++tpos;
-        }
-        mrow[i0 + e] = sel ? 1 : 0;
+        const uint32_t key = keys ? ((uint32_t)keys[i0 + e] & 0x7FFFFFFFu) : target_key(seed, b, (uint32_t)(i0 + e));
+        kk[e] = member(i0 + e) ? (0x80000000u | (0x7FFFFFFFu - key)) : 0u;
       }
   }
-  if (tid == 0) (cls ? num_neg : num_pos)[b] = k;
+};
+
+__device__ __forceinline__ int balanced_count(const BalancedFetch& F, int N, int* misc) {
+  int c = 0, tot;
+  for (int i = threadIdx.x; i < N; i += BLK) c += F.member(i) ? 1 : 0;
+  block_excl_scan(c, misc, &tot);
+  return tot;
+}
+
+// marks the k smallest (key, index) of F's members in mrow (all of them when there are no more than k); returns how many
+__device__ __forceinline__ int balanced_take(const BalancedFetch& F, int N, int k, uint8_t* mrow, int* hist, int* misc) {
+  const int members = balanced_count(F, N, misc);
+  if (k <= 0 || members == 0) return 0;        // workgroup-uniform
+  uint32_t T;
+  int need = 0;
+  if (k >= members) T = 0x7FFFFFFFu;
+  else T = block_radix_threshold(F, N, k, hist, misc, &need);
+  mark_selected<false>(F, N, T, need, mrow, misc);
+  __syncthreads();                             // the marks are the next selection's "taken"
+  return k < members ? k : members;
+}
+
+__global__ __launch_bounds__(1024) void sample_select_balanced_kernel(const SampleArgs A, const BalancedArgs Q,
+                                                                      const int32_t* __restrict__ assigned,
+                                                                      const float* __restrict__ overlaps,
+                                                                      const int32_t* __restrict__ keys, uint8_t* pos_mask,
+                                                                      uint8_t* neg_mask, int32_t* num_pos,
+                                                                      int32_t* num_neg) {
+  __shared__ int hist[TK_BINS];
+  __shared__ int misc[TK_MISC];
+  const int tid = threadIdx.x, cls = blockIdx.x, b = blockIdx.y, N = A.N;
+  const int32_t* arow = assigned + (int64_t)b * N;
+  const float* orow = overlaps + (int64_t)b * N;
+  uint8_t* mrow = (cls ? neg_mask : pos_mask) + (int64_t)b * N;
+  if (tid < 3) misc[32 + tid] = 0;
+  __syncthreads();
+  int cp = 0, cn = 0, om = 0;
+  for (int i = tid; i < N; i += BLK) {
+    const int a = arow[i];
+    cp += a > 0 ? 1 : 0;
+    cn += a == 0 ? 1 : 0;
+    const float o = orow[i];
+    if (o > 0.f) om = max(om, __float_as_int(o));          // positive floats order as their bit patterns
+    if (cls) mrow[i] = 0;
+  }
+  if (cp) atomicAdd(&misc[32], cp);
+  if (cn) atomicAdd(&misc[33], cn);
+  if (om) atomicMax(&misc[34], om);
+  __syncthreads();
+  const int npos = misc[32], nneg = misc[33];
+  const float m = __int_as_float(misc[34]);
+  const int pos = min(npos, A.num_pos_expected);
+  int neg_exp = A.num - pos;
+  if (A.neg_pos_ub >= 0.0) {
+    const double ub = A.neg_pos_ub * (double)max(1, pos);
+    if (ub < (double)neg_exp) neg_exp = (int)ub;
+  }
+  const int n = max(neg_exp, 0);
+  const int32_t* krow = keys ? keys + (int64_t)b * N : nullptr;
+  if (cls == 0) {                              // the positives: sample_select_kernel's own code
+    select_class(ClassFetch{arow, krow, A.seed, (uint32_t)b, 0}, N, pos, npos, mrow, hist, misc);
+    if (tid == 0) num_pos[b] = pos;
+    return;
+  }
+  BalancedFetch F{arow, orow, krow, mrow, A.seed, (uint32_t)b, 3, 0.f, 0.f, Q.floor_thr};
+  if (nneg <= n) {                             // every negative
+    balanced_take(F, N, nneg, mrow, hist, misc);
+    if (tid == 0) num_neg[b] = nneg;
+    return;
+  }
+  F.kind = 1;
+  const int in_s = balanced_count(F, N, misc);
+  const int n_s = (int)((double)n * (1.0 - (double)Q.floor_fraction));
+  int got = 0;
+  if (in_s <= n_s) {
+    got = balanced_take(F, N, in_s, mrow, hist, misc);
+  } else if (Q.num_bins >= 2) {
+    const float t0 = Q.floor_thr > 0.f ? Q.floor_thr : 0.f;
+    const float w = __fdiv_rn(__fsub_rn(m, t0), (float)Q.num_bins);
+    const int per = n_s / Q.num_bins;
+    F.kind = 0;
+    for (int k = 0; k < Q.num_bins; ++k) {
+      F.lo = __fadd_rn(t0, __fmul_rn((float)k, w));
+      F.hi = __fadd_rn(t0, __fmul_rn((float)(k + 1), w));
+      got += balanced_take(F, N, per, mrow, hist, misc);
+    }
+    F.kind = 1;
+    if (got < n_s) got += balanced_take(F, N, n_s - got, mrow, hist, misc);
+  } else {
+    got = balanced_take(F, N, n_s, mrow, hist, misc);
+  }
+  F.kind = 2;
+  got += balanced_take(F, N, n - got, mrow, hist, misc);
+  F.kind = 3;
+  if (got < n) balanced_take(F, N, n - got, mrow, hist, misc);
+  if (tid == 0) num_neg[b] = n;
 }
 
 // ---- output fills -----------------------------------------------------------------------------------------------
@@ -615,6 +764,105 @@ extern "C" int tdn_sample_rois(const float* proposals, const int32_t* counts, co
   TDN_LAUNCH(sample_rois_fill_kernel, dim3(B), dim3(BLK), 0, st, F, (const int32_t*)w.assigned,
              (const uint8_t*)w.pos_mask, (const uint8_t*)w.neg_mask, gt_labels, rois, labels, label_weights, bbox_targets,
              bbox_weights, pos_gt_inds);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- IoU-balanced negative sampling -----------------------------------------------------------------
+static int check_balanced(const char* who, const tdn_balanced_config* bal) {
+  TDN_CHECK(bal != nullptr, "%s: NULL balanced config", who);
+  TDN_CHECK(bal->num_bins >= 1 && bal->num_bins <= 8, "%s: num_bins=%d out of 1..8", who, bal->num_bins);
+  TDN_CHECK(bal->floor_fraction >= 0.f && bal->floor_fraction <= 1.f, "%s: floor_fraction out of [0, 1]", who);
+  TDN_CHECK(bal->floor_thr < 1.f, "%s: floor_thr must be below 1", who);
+  return 0;
+}
+
+static int run_select_balanced(const int32_t* assigned, const float* overlaps, int B, int N, const tdn_target_config* cfg,
+                               const tdn_balanced_config* bal, const int32_t* keys, uint8_t* pos_mask, uint8_t* neg_mask,
+                               int32_t* num_pos, int32_t* num_neg, hipStream_t st) {
+  SampleArgs A;
+  A.N = N;
+  A.num = cfg->num;
+  A.num_pos_expected = cfg->num_pos_expected;
+  A.neg_pos_ub = cfg->neg_pos_ub;
+  A.seed = cfg->seed;
+  const BalancedArgs Q{bal->floor_thr, bal->floor_fraction, bal->num_bins};
+  TDN_LAUNCH(sample_select_balanced_kernel, dim3(2, B), dim3(BLK), 0, st, A, Q, assigned, overlaps, keys, pos_mask,
+             neg_mask, num_pos, num_neg);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tdn_sample_assigned_balanced(const int32_t* assigned, const float* max_overlaps, int B, int N,
+                                            const tdn_target_config* cfg, const tdn_balanced_config* bal,
+                                            const int32_t* keys, uint8_t* pos_mask, uint8_t* neg_mask, int32_t* num_pos,
+                                            int32_t* num_neg, void* stream) {
+  const char* who = "tdn_sample_assigned_balanced";
+  if (check_common(who, B, N, 0, cfg) != 0 || check_sampling(who, cfg) != 0 || check_balanced(who, bal) != 0) return -1;
+  TDN_CHECK(num_pos && num_neg && (N == 0 || (assigned && max_overlaps && pos_mask && neg_mask)), "%s: NULL pointer", who);
+  return run_select_balanced(assigned, max_overlaps, B, N, cfg, bal, keys, pos_mask, neg_mask, num_pos, num_neg,
+                             (hipStream_t)stream);
+}
+
+// tdn_sample_rois' workspace, then the candidates' max_overlaps
+struct BalancedWs { SampleWs s; float* overlaps; int64_t bytes; };
+static BalancedWs balanced_layout(int B, int64_t N, int G, void* base) {
+  const SampleWs s = sample_layout(B, N, G, true, base);
+  tdn_carver c{(char*)base, s.bytes};
+  return {s, c.take<float>((int64_t)B * (N > 0 ? N : 1)), c.off};
+}
+
+extern "C" int64_t tdn_sample_rois_balanced_workspace_bytes(int B, int P, int G, int add_gt_as_proposals) {
+  const char* who = "tdn_sample_rois_balanced_workspace_bytes";
+  if (check_props(who, P) != 0 || check_dims(who, B, P, G) != 0) return -1;
+  return balanced_layout(B, (int64_t)P + (add_gt_as_proposals ? G : 0), G, nullptr).bytes;
+}
+
+extern "C" int tdn_sample_rois_balanced(const float* proposals, const int32_t* counts, const float* gt,
+                                        const int64_t* gt_labels, const int32_t* gt_counts, int B, int P, int G,
+                                        const tdn_target_config* cfg, const tdn_balanced_config* bal, const int32_t* keys,
+                                        float* rois, int64_t* labels, float* label_weights, float* bbox_targets,
+                                        float* bbox_weights, int32_t* pos_gt_inds, int32_t* num_pos, int32_t* num_neg,
+                                        void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_sample_rois_balanced";
+  if (check_props(who, P) != 0 || check_common(who, B, P, G, cfg) != 0 || check_sampling(who, cfg) != 0 ||
+      check_balanced(who, bal) != 0)
+    return -1;
+  const int Nc = P + (cfg->add_gt_as_proposals ? G : 0);
+  TDN_CHECK(gt_counts && counts && num_pos && num_neg && workspace && (G == 0 || (gt && gt_labels)) &&
+                (P == 0 || proposals), "%s: NULL pointer", who);
+  TDN_CHECK(cfg->num == 0 || (rois && labels && label_weights && bbox_targets && bbox_weights && pos_gt_inds),
+            "%s: NULL output", who);
+  const BalancedWs w = balanced_layout(B, Nc, G, workspace);
+  if (tdn_check_ws(who, workspace, workspace_bytes, w.bytes) != 0) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  BoxSrc S;
+  memset(&S, 0, sizeof(S));
+  S.cand = 1;
+  S.props = proposals;
+  S.counts = counts;
+  S.P = P;
+  S.add_gt = cfg->add_gt_as_proposals != 0;
+  S.gt = gt;
+  S.G = G;
+  S.border = -1;
+  if (Nc > 0 && run_assign(S, gt_counts, B, Nc, G, cfg, w.s.assigned, w.overlaps, w.s.a, st) != 0) return -1;
+  if (run_select_balanced(w.s.assigned, w.overlaps, B, Nc, cfg, bal, keys, w.s.pos_mask, w.s.neg_mask, num_pos, num_neg,
+                          st) != 0)
+    return -1;
+  if (cfg->num == 0) return 0;
+  FillArgs F;
+  F.S = S;
+  F.gt_counts = gt_counts;
+  F.B = B;
+  F.N = Nc;
+  F.G = G;
+  F.num = cfg->num;
+  F.means = host_f4(cfg->means);
+  F.stds = host_f4(cfg->stds);
+  TDN_LAUNCH(sample_rois_fill_kernel, dim3(B), dim3(BLK), 0, st, F, (const int32_t*)w.s.assigned,
+             (const uint8_t*)w.s.pos_mask, (const uint8_t*)w.s.neg_mask, gt_labels, rois, labels, label_weights,
+             bbox_targets, bbox_weights, pos_gt_inds);
   TDN_LAUNCH_CHECK();
   return 0;
 }

@@ -1570,3 +1570,67 @@ class PAPathFunction(torch.autograd.Function):
             flat += unit_grads.get(u, [None] * len(u.params()))
         join_side_stream(dev)
         return (None,) + tuple(_as_nchw(t) if t is not None else None for t in dP) + tuple(flat)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Balanced Feature Pyramid (Libra R-CNN's BFP neck)
+# ---------------------------------------------------------------------------------------------------
+class BFPNet(object):
+    """``refine``: the prepared conv (+ norm) + ReLU unit of ``refine_type='conv'``, or None."""
+
+    def __init__(self, num_levels, refine_level, refine, dtype):
+        self.num_levels, self.refine_level, self.refine, self.dtype = num_levels, refine_level, refine, dtype
+
+    def units(self):
+        return [self.refine] if self.refine is not None else []
+
+    def params(self):
+        return self.refine.params() if self.refine is not None else []
+
+
+class BFPFunction(torch.autograd.Function):
+    """BFP.forward of mmdetection v1: gather every level at the refine level's size (max pool down, nearest up) and
+    average, refine, scatter back (nearest up, max pool down) and add the inputs — one launch each for the gather and the
+    scatter over all levels, and one each for their adjoints, around the refine conv's own launches."""
+
+    @staticmethod
+    def forward(ctx, net, *args):
+        ctx.gn_saved = {}
+        with gn_scope(ctx.gn_saved):
+            return BFPFunction._forward(ctx, net, *args)
+
+    @staticmethod
+    def _forward(ctx, net, *args):
+        from . import libra_ops
+        xs = [_as_nchw(ops.to_nhwc_bf16(t, net.dtype)) for t in args[:net.num_levels]]
+        bsf = libra_ops.bfp_gather_fwd(xs, net.refine_level)
+        u = net.refine
+        refined = _as_nchw(unit_fwd(u, bsf.permute(0, 2, 3, 1))) if u is not None else bsf
+        outs = libra_ops.bfp_scatter_fwd(xs, refined, net.refine_level)
+        ctx.net, ctx.xs, ctx.bsf, ctx.refined = net, xs, bsf, refined
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        with gn_scope(ctx.gn_saved):
+            return BFPFunction._backward(ctx, *douts)
+
+    @staticmethod
+    def _backward(ctx, *douts):
+        from . import libra_ops
+        net, xs, u = ctx.net, ctx.xs, ctx.net.refine
+        gs = [d if d is not None else torch.zeros_like(x) for d, x in zip(douts, xs)]
+        gs = libra_ops.cotangents(gs, "douts", net.dtype, xs[0].shape[0], xs[0].shape[1],
+                                  [(x.shape[2], x.shape[3]) for x in xs])
+        dbsf = libra_ops.bfp_scatter_bwd(gs, ctx.refined, net.refine_level)
+        grads = []
+        if u is not None:
+            y, x_in = ctx.refined.permute(0, 2, 3, 1), ctx.bsf.permute(0, 2, 3, 1)
+            g = dbsf.permute(0, 2, 3, 1)
+            if u.relu:
+                g = ops.act_mask(g, y, 6.0) if u.act6 else ops.add_relu_mask(g, None, y)
+            grads = unit_wgrad(u, x_in, g)
+            dbsf = _as_nchw(unit_dgrad(u, g, _hw(x_in)))
+            join_side_stream(g.device)         # (BFP builds its refine conv without a bias when it has a norm)
+        dxs = libra_ops.bfp_gather_bwd(xs, gs, dbsf, net.refine_level)
+        return (None,) + tuple(dxs) + tuple(grads)

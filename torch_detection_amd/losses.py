@@ -8,9 +8,11 @@ from a graph.  An element whose weight is exactly 0 is never evaluated (loss 0, 
 """
 import torch
 
+from . import libra_ops as _b
 from . import loss_ops as _l
 
-__all__ = ["AnchorHeadLossFunction", "BBoxHeadLossFunction", "anchor_head_loss", "rpn_loss", "bbox_head_loss"]
+__all__ = ["AnchorHeadLossFunction", "BBoxHeadLossFunction", "BalancedBBoxHeadLossFunction", "anchor_head_loss",
+           "rpn_loss", "bbox_head_loss"]
 
 
 def _avg_tensors(avg_factor):
@@ -67,6 +69,28 @@ class BBoxHeadLossFunction(torch.autograd.Function):
         return (None,) * (7 + ctx.n_avg) + (dcls, dreg)
 
 
+class BalancedBBoxHeadLossFunction(torch.autograd.Function):
+    """:class:`BBoxHeadLossFunction` with balanced L1 as the box term: ``apply((beta, alpha, gamma), avg_number, n_avg,
+    labels, label_weights, bbox_targets, bbox_weights, *avg_tensors, cls_score, bbox_pred)``."""
+
+    @staticmethod
+    def forward(ctx, meta, avg_number, n_avg, labels, label_weights, bbox_targets, bbox_weights, *rest):
+        avg_ts, (cls_score, bbox_pred) = rest[:n_avg], rest[n_avg:]
+        avg_factor = avg_number if n_avg == 0 else tuple(avg_ts)
+        targets = (labels, label_weights, bbox_targets, bbox_weights)
+        losses, avg = _b.bbox_head_loss_balanced_fwd(cls_score, bbox_pred, *targets, avg_factor, *meta)
+        ctx.save_for_backward(*targets, cls_score, bbox_pred)
+        ctx.meta, ctx.n_avg, ctx.avg = meta, n_avg, avg
+        return losses
+
+    @staticmethod
+    def backward(ctx, g):
+        targets, (cls_score, bbox_pred) = ctx.saved_tensors[:4], ctx.saved_tensors[4:]
+        g = g.to(torch.float32).contiguous()
+        dcls, dreg = _b.bbox_head_loss_balanced_bwd(cls_score, bbox_pred, *targets, g, ctx.avg, *ctx.meta)
+        return (None,) * (7 + ctx.n_avg) + (dcls, dreg)
+
+
 def anchor_head_loss(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factor,
                      num_classes=1, beta=1.0 / 9.0, gamma=None, alpha=0.25):
     """Sigmoid classification loss (binary cross entropy, or focal with ``gamma`` / ``alpha``) and smooth-L1 box loss of
@@ -92,11 +116,20 @@ def rpn_loss(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_w
                             num_classes=1, beta=beta, gamma=None)
 
 
-def bbox_head_loss(cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights, avg_factor=None, beta=1.0):
-    """Softmax cross entropy and smooth-L1 box loss of the RoI head on ``sample_rois``' rows.  ``cls_score``: (R, C),
+def bbox_head_loss(cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights, avg_factor=None, beta=1.0,
+                   reg_loss='smooth_l1', reg_alpha=0.5, reg_gamma=1.5):
+    """Softmax cross entropy and the box loss of the RoI head on ``sample_rois``' rows.  ``cls_score``: (R, C),
     class 0 background; ``bbox_pred``: (R, 4C) (row r regresses columns ``4*labels[r] ..``, every other column gets
     gradient 0) or (R, 4); targets stay (R, 4).  ``avg_factor``: as for :func:`anchor_head_loss`, or None for the number
-    of rows with ``label_weights > 0`` (counted on the device, at least 1).  Padding rows (weight 0) are never read."""
+    of rows with ``label_weights > 0`` (counted on the device, at least 1).  Padding rows (weight 0) are never read.
+    ``reg_loss``: ``'smooth_l1'`` with knee ``beta``, or ``'balanced_l1'`` (Libra R-CNN) with knee ``beta`` and the shape
+    parameters ``reg_alpha`` / ``reg_gamma``, which smooth L1 does not look at."""
     avg_ts, _ = _avg_tensors(avg_factor)
+    if reg_loss == 'balanced_l1':
+        return BalancedBBoxHeadLossFunction.apply((beta, reg_alpha, reg_gamma), avg_factor if not avg_ts else None,
+                                                  len(avg_ts), labels, label_weights, bbox_targets, bbox_weights, *avg_ts,
+                                                  cls_score, bbox_pred)
+    if reg_loss != 'smooth_l1':
+        raise ValueError("reg_loss must be 'smooth_l1' or 'balanced_l1', got %r" % (reg_loss,))
     return BBoxHeadLossFunction.apply(beta, avg_factor if not avg_ts else None, len(avg_ts), labels, label_weights,
                                       bbox_targets, bbox_weights, *avg_ts, cls_score, bbox_pred)

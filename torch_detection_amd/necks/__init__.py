@@ -1,4 +1,5 @@
+from .bfp import BFP
 from .fpn import FPN
 from .pafpn import PAFPN
 
-__all__ = ['FPN', 'PAFPN']
+__all__ = ['BFP', 'FPN', 'PAFPN']

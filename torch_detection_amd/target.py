@@ -7,6 +7,7 @@ xyxy boxes.  Ground truths come padded as the reference's ``bbox_pad`` (datasets
 ``gt_bboxes`` (B, G, 4) with zero rows past ``gt_counts`` (B,) int32.  ``boxes`` / ``anchors`` are (N, 4), shared by
 all images, or (B, N, 4).  Nothing here synchronises with the host: every call can be captured in a graph.
 """
+from . import libra_ops as _b
 from . import target_ops as _t
 
 
@@ -41,16 +42,37 @@ def anchor_target(anchors, valid_flags, gt_bboxes, gt_counts, img_shapes, pos_io
                             target_means, target_stds, keys, seed)
 
 
+def sample_assigned_iou_balanced(assigned_gt_inds, max_overlaps, num, pos_fraction, neg_pos_ub=-1, floor_thr=-1.0,
+                                 floor_fraction=0.0, num_bins=3, keys=None, seed=0):
+    """:func:`sample_assigned` with the negatives chosen by IoU-balanced sampling (Libra R-CNN, in the lineage of
+    mmdetection v1's ``IoUBalancedNegSampler``): when an image has more negatives than it may keep, they
+    are drawn evenly from ``num_bins`` bins of ``max_overlaps`` between ``floor_thr`` and the image's largest overlap,
+    "k at random from a set" being the k smallest (key, index) of the set; ``floor_fraction`` of them may come from below
+    ``floor_thr``.  ``max_overlaps``: (B, N) float32, as :func:`assign_max_iou` returns it.  The same four outputs."""
+    return _b.sample_assigned_iou_balanced(assigned_gt_inds, max_overlaps, num, pos_fraction, neg_pos_ub, floor_thr,
+                                           floor_fraction, num_bins, keys, seed)
+
+
 def sample_rois(proposals, counts, gt_bboxes, gt_labels, gt_counts, pos_iou_thr=0.5, neg_iou_thr=0.5, min_pos_iou=0.5,
                 num=512, pos_fraction=0.25, neg_pos_ub=-1, add_gt_as_proposals=True, target_means=(0, 0, 0, 0),
-                target_stds=(0.1, 0.1, 0.2, 0.2), keys=None, seed=0, gt_max_assign_all=True):
+                target_stds=(0.1, 0.1, 0.2, 0.2), keys=None, seed=0, gt_max_assign_all=True, neg_sampler='random',
+                floor_thr=-1.0, floor_fraction=0.0, num_bins=3):
     """RoI-head training samples and targets from ``rpn_proposals``' padded output (``proposals`` (B, P, 5), ``counts``
     (B,)), in five launches.  Candidates of an image: its ground truths first (``add_gt_as_proposals``), then its
     ``counts[b]`` proposals; ``gt_labels``: (B, G) int64.  Fixed shapes: image b owns rows ``[b * num, (b + 1) * num)``
     — sampled positives in ascending candidate index, then sampled negatives likewise, then padding (batch index -1,
     zeros, weight 0), which ``roi_align`` treats as invalid rows.  Returns ``rois`` (B*num, 5) = [b, x1, y1, x2, y2],
     ``labels`` (B*num,) int64, ``label_weights``, ``bbox_targets`` (B*num, 4) class-agnostic, ``bbox_weights``,
-    ``pos_assigned_gt_inds`` (B*num,) int32 (-1 off the positives), ``num_pos``, ``num_neg``."""
+    ``pos_assigned_gt_inds`` (B*num,) int32 (-1 off the positives), ``num_pos``, ``num_neg``.
+    ``neg_sampler``: ``'random'``, or ``'iou_balanced'`` with ``floor_thr`` / ``floor_fraction`` / ``num_bins``
+    (:func:`sample_assigned_iou_balanced`), which replaces only the choice of the negatives."""
+    if neg_sampler == 'iou_balanced':
+        return _b.sample_rois_iou_balanced(proposals, counts, gt_bboxes, gt_labels, gt_counts, pos_iou_thr, neg_iou_thr,
+                                           min_pos_iou, gt_max_assign_all, num, pos_fraction, neg_pos_ub,
+                                           add_gt_as_proposals, target_means, target_stds, keys, seed, floor_thr,
+                                           floor_fraction, num_bins)
+    if neg_sampler != 'random':
+        raise ValueError("neg_sampler must be 'random' or 'iou_balanced', got %r" % (neg_sampler,))
     return _t.sample_rois(proposals, counts, gt_bboxes, gt_labels, gt_counts, pos_iou_thr, neg_iou_thr, min_pos_iou,
                           gt_max_assign_all, num, pos_fraction, neg_pos_ub, add_gt_as_proposals, target_means,
                           target_stds, keys, seed)
