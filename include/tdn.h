@@ -959,6 +959,65 @@ int tdn_mask_paste(const void* pred, int dtype, int nhwc, int B, int max_num, in
                    const int64_t* labels, const int32_t* counts, const int32_t* img_shapes, int H, int W, float thr,
                    int packed, uint8_t* out, void* stream);
 
+/* ---- Mask Scoring R-CNN around the MaskIoUHead's layers (mmdetection v1's MaskIoUHead.get_target,
+ *      its MSELoss on the positive targets and get_mask_scores) ----
+ * tdn_mask_iou_target, one launch: rois, gt_inds and the polygon arrays are tdn_mask_target's and so is the validity of
+ * a row; pred / dtype / nhwc / C / labels are tdn_mask_loss_fwd's (row r reads channel labels[r]); targets uint8
+ * [R][M][M] are tdn_mask_target's; img_shapes int32 [B][2] = (h, w), each clamped to 0..TDN_MASK_IOU_MAX_CANVAS on the
+ * device.  The instance's bitmap has pixel (x, y) of the h x w canvas set iff (x + 0.5, y + 0.5) is inside any of its
+ * polygons by §4g's crossing test; full = its population count, in = the count over x in [max(x1, 0), min(x2, w - 1)],
+ * y alike (the truncated box; an empty range counts 0); pa = #{logit > thr}, ts = #{target == 1}, ov = #{both}.
+ *   ratio = in / (full + 1e-7f);  gf = ts / (ratio + 1e-7f);  den = (pa + gf) - ov;  iou = den > 0 ? ov / den : 0
+ * in fp32, one rounding per operation.  iou fp32 [R]; an invalid row or a label without a channel gives 0 and neither
+ * its logits nor its polygons are read. */
+#define TDN_MASK_IOU_MAX_CANVAS 8192
+int tdn_mask_iou_target(const float* rois, const int32_t* gt_inds, int R, const float* poly_xy, int P,
+                        const int32_t* poly_offsets, int Q, const int32_t* gt_poly_offsets, int B, int G,
+                        const void* pred, int dtype, int nhwc, int C, int M, const int64_t* labels,
+                        const uint8_t* targets, const int32_t* img_shapes, float thr, float* iou, void* stream);
+/* pred [R][C] TDN_F32 / TDN_BF16 / TDN_F16; row r is live iff targets[r] > 0 and labels[r] (int64) is in 1..C-1; a row
+ * that is not live is never read.  loss fp32 [1] = loss_weight sum_live (pred[r][labels[r]] - targets[r])^2 / D with
+ * D = max(#live, 1) counted on the device; avg_out fp32 [1] = D, which the backward takes as avg_in with the cotangent
+ * g fp32 [1]: dpred [R][C] = (pred - target) ((2 loss_weight g) / D) at [r][labels[r]] of a live row, 0 elsewhere,
+ * written in full in pred's dtype.  Forward two launches, backward one.  workspace:
+ * tdn_mask_iou_loss_workspace_bytes() bytes, 256-aligned. */
+int64_t tdn_mask_iou_loss_workspace_bytes(int R);
+int tdn_mask_iou_loss_fwd(const void* pred, int dtype, int R, int C, const int64_t* labels, const float* targets,
+                          float loss_weight, float* loss, float* avg_out, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+int tdn_mask_iou_loss_bwd(const void* pred, int dtype, int R, int C, const int64_t* labels, const float* targets,
+                          float loss_weight, const float* g, const float* avg_in, void* dpred, void* stream);
+/* scores fp32 [B][max_num] = (float)pred[b max_num + d][labels[b][d] + 1] * dets[b][d][4] (one fp32 product) for
+ * d < counts[b] and 0 <= labels[b][d] + 1 < C, 0 elsewhere (every row under the overflow marker counts[b] = -1).  One
+ * launch. */
+int tdn_mask_scores(const void* pred, int dtype, int B, int max_num, int C, const float* dets, const int64_t* labels,
+                    const int32_t* counts, float* scores, void* stream);
+
+/* The mask channel of the MaskIoUHead's first 3x3 conv over cat(feats, maxpool2x2(sigmoid(pred[r][ch_r]))): by
+ * linearity the layer is conv_Cf(feats) + conv_1(P), and these form the second term as the epilogue addend of the
+ * library's own conv launch.  pred [R][C][2S][2S] as tdn_mask_loss_fwd takes it; row r reads channel
+ * labels[r] + label_offset (1..C-1; C == 1: channel 0), a row without a channel has P = 0, is never read and gets no
+ * gradient.  weight fp32 [Cout][Cf + 1][3][3] contiguous (only its last input channel is read); Cf and Cout multiples
+ * of 64, Cout <= TDN_MASK_IOU_MAX_COUT, 1 <= S <= TDN_MASK_MAX_SIZE / 2, R >= 1.
+ * tdn_mask_iou_stem_fwd, one launch: P fp32 [R][S][S] = the FIRST maximum in row-major order of each 2x2 window of
+ * sigmoid(pred) (replaced on strict >), idx uint8 [R][S][S] = its place 2 dy + dx in the window (255: no channel),
+ * a [R][S][S][Cout] in out_dtype (TDN_BF16 / TDN_F16) = sum over the nine taps in (ky, kx) order of
+ * weight[co][Cf][ky][kx] P[i + ky - 1][j + kx - 1] (P = 0 outside the map), fp32 products and adds, rounded once.
+ * tdn_mask_iou_stem_bwd, two launches, from gz [R][S][S][Cout] (gz_dtype) = the layer's cotangent behind its ReLU:
+ * dP fp32 [R][S][S] = sum_taps sum_co weight[co][Cf][ky][kx] gz[i - ky + 1][j - kx + 1][co]; dpred (pred's layout and
+ * dtype, written in full) = dP sigmoid(x) sigmoid(-x) at each window's first maximum, 0 elsewhere; dw1 fp32
+ * [Cout][3][3] = sum_{r,i,j} gz[r][i][j][co] P[r][i + ky - 1][j + kx - 1] (fp32 products, fp64 sums in a fixed order).
+ * workspace: tdn_mask_iou_stem_bwd_workspace_bytes() bytes, 256-aligned. */
+#define TDN_MASK_IOU_MAX_COUT 512
+int tdn_mask_iou_stem_fwd(const void* pred, int dtype, int nhwc, int R, int C, int S, const int64_t* labels,
+                          int label_offset, const float* weight, int Cf, int Cout, void* a, int out_dtype, float* P,
+                          uint8_t* idx, void* stream);
+int64_t tdn_mask_iou_stem_bwd_workspace_bytes(int R, int S, int Cout);
+int tdn_mask_iou_stem_bwd(const void* gz, int gz_dtype, const float* P, const uint8_t* idx, const float* weight, int Cf,
+                          int Cout, const void* pred, int dtype, int nhwc, int R, int C, int S, const int64_t* labels,
+                          int label_offset, float* dP, void* dpred, float* dw1, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* ---- fused SGD step: gradient-norm clip, loss unscaling, momentum update (no reference counterpart:
  *      SURVEY row 25) ----
  * One item per parameter: p, g and buf are fp32 device pointers to the lowest address of a dense, non-overlapping

@@ -16,7 +16,8 @@ conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask 
 ``fcos_target`` / ``fcos_loss`` / ``fcos_detections``, and deformable convolution ``deform_conv2d`` with the modules
 ``DeformConv`` / ``ModulatedDeformConv`` / ``DeformConvPack`` / ``ModulatedDeformConvPack``, and Cascade R-CNN's
 ``refine_bboxes`` / ``cascade_detections`` / ``CascadeRoIHead``, and Libra R-CNN's ``BFP`` neck,
-``sample_assigned_iou_balanced`` / ``sample_rois(neg_sampler='iou_balanced')`` and ``bbox_head_loss(reg_loss='balanced_l1')``).  Everything computes through libtdn.so
+``sample_assigned_iou_balanced`` / ``sample_rois(neg_sampler='iou_balanced')`` and ``bbox_head_loss(reg_loss='balanced_l1')``,
+and Mask Scoring R-CNN's ``MaskIoUHead`` with ``mask_iou_stem`` / ``mask_iou_target`` / ``mask_iou_loss`` / ``mask_scores``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -46,12 +47,14 @@ from .fcos import (FcosLossFunction, fcos_detections, fcos_detections_plan, fcos
                    fcos_points, fcos_target)
 from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_target,  # noqa: F401
                    pack_polygons, rois_from_detections)
+from .mask_iou import (MaskIoULossFunction, MaskIoUStemFunction, mask_iou_loss, mask_iou_stem,  # noqa: F401
+                       mask_iou_target, mask_scores)
 from .optim import SGD  # noqa: F401
 from .linear import LinearFunction, linear  # noqa: F401
 from .deconv import ConvTranspose2x2Function, conv_transpose2x2  # noqa: F401
 from .deform import (DeformConv, DeformConvFunction, DeformConvPack, ModulatedDeformConv,  # noqa: F401
                      ModulatedDeformConvPack, deform_conv2d)
-from .heads import BBoxHead, FCNMaskHead, FCOSHead, RetinaHead, RPNHead  # noqa: F401
+from .heads import BBoxHead, FCNMaskHead, FCOSHead, MaskIoUHead, RetinaHead, RPNHead  # noqa: F401
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)
 from .cascade import CascadeRoIHead, cascade_detections, refine_bboxes  # noqa: F401

@@ -39,6 +39,8 @@ REFINE_CHUNK = 1024
 DENSE_MAX_LEVELS = 8
 FCOS_MAX_LEVELS = 8
 MASK_MAX_SIZE = 56
+MASK_IOU_MAX_CANVAS = 8192
+MASK_IOU_MAX_COUT = 512
 SGD_MAX_ITEMS = 1 << 20
 SGD_MAX_GROUPS = 1024
 SGD_PATH_LINEAR, SGD_PATH_TRANSPOSED, SGD_PATH_GENERAL = 0, 1, 2
@@ -442,6 +444,19 @@ SIGNATURES = {
     "tdn_rois_from_detections": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p]),
     "tdn_mask_paste": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 4 + [c_int, c_int, c_float, c_int, c_void_p,
                                                                           c_void_p]),
+    "tdn_mask_iou_target": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                    c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                    c_void_p]),
+    "tdn_mask_iou_loss_workspace_bytes": (c_i64, [c_int]),
+    "tdn_mask_iou_loss_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                      c_void_p, c_i64, c_void_p]),
+    "tdn_mask_iou_loss_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 4),
+    "tdn_mask_scores": (c_int, [c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 5),
+    "tdn_mask_iou_stem_fwd": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                                                                 c_void_p, c_void_p, c_void_p]),
+    "tdn_mask_iou_stem_bwd_workspace_bytes": (c_i64, [c_int] * 3),
+    "tdn_mask_iou_stem_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p] +
+                              [c_int] * 5 + [c_void_p, c_int] + [c_void_p] * 4 + [c_i64, c_void_p]),
     "tdn_sgd_plan": (c_int, [_SI, c_int, c_int, _I64P, c_void_p, c_i64, ctypes.POINTER(ctypes.c_int32)]),
     "tdn_sgd_step": (c_int, [c_void_p, _I64P, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, c_float,
                              c_float, c_int, c_void_p]),

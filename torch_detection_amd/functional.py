@@ -254,6 +254,7 @@ def invalidate_packed(*modules):
     from .linear import forget               # imported here: linear.py imports this module
     from .deconv import forget as forget_deconv
     from .deform import forget as forget_deform
+    from .mask_iou import forget as forget_mask_iou
     for m in modules:
         for sub in m.modules():
             for u in sub.__dict__.get('_hip_units', {}).values():
@@ -262,6 +263,7 @@ def invalidate_packed(*modules):
             forget(p)                        # packed copies made by a bare linear() call on this parameter
             forget_deconv(p)                 # ... or by a bare conv_transpose2x2() call
             forget_deform(p)                 # ... or by deform_conv2d() / the deformable modules
+            forget_mask_iou(p)               # ... or by mask_iou_stem() / MaskIoUHead's first layer
 
 
 class StagedImages(object):

@@ -21,7 +21,12 @@ predictors ``retina_cls`` / ``retina_reg``, weights shared by the levels, every 
 ``FCOSHead`` — mmdetection v1's ``FCOSHead``: two towers of 3x3 conv -> GroupNorm -> ReLU layers and the
 3x3 predictors ``fcos_cls`` / ``fcos_reg`` / ``fcos_centerness``, weights and affine parameters shared by the levels; the
 convs as in ``RetinaHead``, the GroupNorm of a layer in three launches over the whole pyramid each way
-(csrc/pyramid_gn.hip) — between ``FPN`` and ``fcos_target`` / ``fcos_loss`` / ``fcos_detections``.  One autograd node."""
+(csrc/pyramid_gn.hip) — between ``FPN`` and ``fcos_target`` / ``fcos_loss`` / ``fcos_detections``.  One autograd node.
+
+``MaskIoUHead`` — mmdetection v1's ``MaskIoUHead`` of Mask Scoring R-CNN: a 3x3 conv over the mask head's
+features and its pooled predicted mask (``mask_iou_stem``, csrc/mask_iou.hip), further 3x3 convs (the last of stride 2),
+fully connected layers and the ragged ``fc_mask_iou`` — beside ``FCNMaskHead``, between ``roi_align`` and
+``mask_iou_loss`` / ``mask_scores``."""
 import math
 
 import torch
@@ -37,11 +42,13 @@ from .functional import pick_dtype
 from .fcos import fcos_detections, fcos_loss, fcos_points, fcos_target
 from .layers import ConvModule, Scale
 from .linear import LinearUnit, check_params, flatten_input
+from .linear import linear as _linear
+from .mask_iou import MaskIoUStemFunction, MaskIoUStemUnit, mask_iou_loss, mask_iou_target, mask_scores
 from .losses import anchor_head_loss, rpn_loss
 from .registry import HEADS
 from .target import anchor_target
 
-__all__ = ["BBoxHead", "BBoxHeadFunction", "FCNMaskHead", "MaskTailFunction", "RPNHead", "RPNHeadFunction", "PredUnit",
+__all__ = ["BBoxHead", "BBoxHeadFunction", "FCNMaskHead", "MaskTailFunction", "MaskIoUHead", "RPNHead", "RPNHeadFunction", "PredUnit",
            "RetinaHead", "RetinaHeadFunction", "PyrUnit", "FCOSHead", "FCOSHeadFunction"]
 
 
@@ -296,6 +303,115 @@ class FCNMaskHead(nn.Module):
             x = conv(x)
         return MaskTailFunction.apply(self, x, self.upsample.weight, self.upsample.bias, self.conv_logits.weight,
                                       self.conv_logits.bias)
+
+
+# ---- the mask-IoU head (Mask Scoring R-CNN) --------------------------------------------------------------------------------
+@HEADS.register_module
+class MaskIoUHead(nn.Module):
+    """``MaskIoUHead`` of mmdetection v1 (Mask Scoring R-CNN): ``num_convs`` 3x3 convs + ReLU, the first over
+    ``cat(mask_feat, max_pool2x2(sigmoid(mask_pred[r, label_r])))`` (``in_channels + 1`` inputs), the LAST of stride 2;
+    ``num_fcs`` ``Linear + ReLU`` layers on the flattened map and ``fc_mask_iou`` to ``num_classes`` outputs.  The
+    parameters live in plain ``nn.Conv2d`` / ``nn.Linear`` containers, so the state-dict keys are mmdetection's
+    (``convs.0.weight`` ... ``fcs.1.bias``, ``fc_mask_iou.weight``); the containers' own forward is never called.
+    Anything the HIP path does not cover — channel counts that are no multiples of 64, fewer than two convs, an odd
+    ``roi_feat_size``, a ``loss_iou`` other than ``MSELoss`` — is accepted by the constructor and raises
+    ``NotImplementedError`` in ``forward``."""
+
+    def __init__(self, num_convs=4, num_fcs=2, roi_feat_size=14, in_channels=256, conv_out_channels=256,
+                 fc_out_channels=1024, num_classes=81, loss_iou=dict(type='MSELoss', loss_weight=0.5)):
+        super().__init__()
+        if num_convs < 1 or num_fcs < 0 or min(roi_feat_size, in_channels, conv_out_channels, fc_out_channels,
+                                               num_classes) < 1:
+            raise ValueError("MaskIoUHead: sizes must be positive")
+        self.num_convs = int(num_convs)
+        self.num_fcs = int(num_fcs)
+        self.roi_feat_size = int(roi_feat_size)
+        self.in_channels = int(in_channels)
+        self.conv_out_channels = int(conv_out_channels)
+        self.fc_out_channels = int(fc_out_channels)
+        self.num_classes = int(num_classes)
+        self.loss_iou = dict(loss_iou)
+        self.loss_weight = float(self.loss_iou.get('loss_weight', 1.0))
+        self.convs = nn.ModuleList()
+        for i in range(self.num_convs):
+            cin = self.in_channels + 1 if i == 0 else self.conv_out_channels
+            self.convs.append(nn.Conv2d(cin, self.conv_out_channels, 3, stride=2 if i == self.num_convs - 1 else 1,
+                                        padding=1))
+        pooled = self.roi_feat_size // 2
+        self.fcs = nn.ModuleList()
+        for i in range(self.num_fcs):
+            fin = self.conv_out_channels * pooled * pooled if i == 0 else self.fc_out_channels
+            self.fcs.append(nn.Linear(fin, self.fc_out_channels))
+        last = self.fc_out_channels if self.num_fcs else self.conv_out_channels * pooled * pooled
+        self.fc_mask_iou = nn.Linear(last, self.num_classes)
+        self.init_weights()
+
+    def init_weights(self):
+        for conv in self.convs:
+            nn.init.kaiming_normal_(conv.weight, mode='fan_out', nonlinearity='relu')
+            nn.init.constant_(conv.bias, 0)
+        for fc in self.fcs:
+            nn.init.kaiming_uniform_(fc.weight, a=1, mode='fan_in', nonlinearity='leaky_relu')
+            nn.init.constant_(fc.bias, 0)
+        nn.init.normal_(self.fc_mask_iou.weight, 0, 0.01)
+        nn.init.constant_(self.fc_mask_iou.bias, 0)
+
+    def _stem_unit(self, weight, dtype):
+        cache = self.__dict__.setdefault('_hip_units', {})
+        u = cache.get(('stem', dtype))
+        if u is None or u.weight is not weight:
+            u = cache[('stem', dtype)] = MaskIoUStemUnit(weight, dtype)
+        return u
+
+    def _check_supported(self):
+        if self.in_channels % 64 or self.conv_out_channels % 64:
+            raise NotImplementedError("MaskIoUHead: in_channels=%d and conv_out_channels=%d must be multiples of 64 on "
+                                      "the HIP path" % (self.in_channels, self.conv_out_channels))
+        if self.num_convs < 2:
+            raise NotImplementedError("MaskIoUHead: num_convs=%d is not on the HIP path (the first conv runs at stride "
+                                      "1: at least 2)" % self.num_convs)
+        if self.roi_feat_size % 2:
+            raise NotImplementedError("MaskIoUHead: an odd roi_feat_size (%d) is not on the HIP path" % self.roi_feat_size)
+        if self.loss_iou.get('type') != 'MSELoss':
+            raise NotImplementedError("MaskIoUHead: loss_iou type %r is not on the HIP path (only 'MSELoss')"
+                                      % (self.loss_iou.get('type'),))
+
+    def forward(self, mask_feat, mask_pred, labels=None, label_offset=0):
+        """mask_feat: (R, in_channels, S, S) RoI features of the mask branch (16-bit channels_last is read in place);
+        mask_pred: (R, C, 2S, 2S) logits of ``FCNMaskHead`` (read in place); labels (R,) int64: row r pools channel
+        ``labels[r] + label_offset`` (None: channel 0 of a class-agnostic ``mask_pred``) -> mask_iou_pred
+        (R, num_classes) float32."""
+        self._check_supported()
+        if torch.is_tensor(mask_feat) and mask_feat.dtype == torch.float32:
+            mask_feat = mask_feat.to(pick_dtype(self, mask_feat)).contiguous(memory_format=torch.channels_last)
+        dtype = mask_feat.dtype
+        if labels is None:
+            if mask_pred.dim() == 4 and mask_pred.shape[1] != 1:
+                raise ValueError("MaskIoUHead: labels are needed to pick a channel of a %d-channel mask_pred"
+                                 % mask_pred.shape[1])
+            labels = torch.zeros(mask_pred.shape[0], dtype=torch.int64, device=mask_pred.device)
+        c0 = self.convs[0]
+        x = MaskIoUStemFunction.apply(mask_feat, mask_pred, labels, c0.weight, c0.bias, int(label_offset), True,
+                                      self._stem_unit(c0.weight, dtype))
+        for i in range(1, self.num_convs):
+            unit = HF.prepare_unit(self, 'conv%d' % i, self.convs[i], None, True, dtype)
+            x = HF.ConvUnitFunction.apply(unit, x, *unit.params())
+        for fc in self.fcs:
+            x = _linear(x, fc.weight, fc.bias, relu=True)
+        return _linear(x, self.fc_mask_iou.weight, self.fc_mask_iou.bias, out_f32=True)
+
+    def get_target(self, rois, pos_assigned_gt_inds, poly_xy, poly_offsets, gt_poly_offsets, mask_pred, labels,
+                   mask_targets, img_shapes, thr=0.5):
+        """:func:`mask_iou_target` (mmdetection's ``get_target`` with ``rcnn_train_cfg.mask_thr_binary`` as ``thr``)."""
+        return mask_iou_target(rois, pos_assigned_gt_inds, poly_xy, poly_offsets, gt_poly_offsets, mask_pred, labels,
+                               mask_targets, img_shapes, thr)
+
+    def loss(self, mask_iou_pred, labels, mask_iou_targets):
+        return dict(loss_mask_iou=mask_iou_loss(mask_iou_pred, labels, mask_iou_targets, self.loss_weight))
+
+    def get_mask_scores(self, mask_iou_pred, dets, labels, counts):
+        """:func:`mask_scores`."""
+        return mask_scores(mask_iou_pred, dets, labels, counts)
 
 
 # ---- the RPN head -------------------------------------------------------------------------------------------------------
