@@ -37,6 +37,7 @@ import test_gpu_kernels as K
 import test_gpu_proposals as PR
 import test_gpu_roi_align as RA
 import test_gpu_staging as ST
+import test_gpu_wgrad_plans as WP
 from golden_util import det_tensor, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -294,6 +295,19 @@ def test_wgrad_group_many_members(ops, guard, monkeypatch):
             if u is not None:
                 assert not bool(torch.isnan(u).any()), (i, nm)
                 assert rel_l2(u.cpu(), v.cpu()) <= K.TOL, (i, GROUP_MEMBERS[i], nm)
+
+
+@pytest.mark.parametrize("case", WP.WC.CASES, ids=WP.WC.IDS)
+def test_wgrad_plan_case(ops, guard, case, monkeypatch):
+    """Every forced plan of tests/wgrad_cases.py (tile shapes, split layouts with idle workgroup slots, the 256-split
+    cap, stem / grouped / nine-tap members, one mixed group) with its own oracle checks, under poisoned, guard-banded
+    dw / dgamma / dbeta and a NaN-filled workspace of exactly tdn_wgrad_group_workspace() bytes: a finalize pass that
+    reads an idle slot's slab or colsum, or a split that writes past its region, is a NaN or a band hit."""
+    WP.run_case(ops, case, monkeypatch)
+    assert guard.ws_log, "no workspace was handed out"
+    for op, asked, given in guard.ws_log:
+        assert op == "wgrad_group" and asked > 0 and 0 <= given - asked < 16, guard.ws_log
+    guard.clean()
 
 
 @pytest.mark.parametrize("case", [(2, 12, 16, 128, 32, 3, 1), (1, 13, 21, 256, 32, 3, 2), (2, 9, 10, 512, 32, 3, 1),

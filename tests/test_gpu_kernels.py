@@ -171,7 +171,7 @@ T9_CASES = [(3, 13, 21, 128, 128, 3, 1), (2, 40, 48, 64, 256, 3, 1), (1, 7, 7, 1
 @pytest.mark.parametrize("bn", [True, False])
 def test_conv_wgrad(ops, case, bn, monkeypatch):
     if case in T9_CASES:
-        monkeypatch.setenv("TDN_WGRAD9", "1")   # the plan would pick the tap-per-tile kernel at these small sizes
+        monkeypatch.setenv("TDN_WGRAD9", "1")   # the default, pinned: these cases are about the nine-tap kernel
     N, H, W, Cin, Cout, k, s = case
     Ho, Wo = ops.conv_out_size(H, k, s, k // 2), ops.conv_out_size(W, k, s, k // 2)
     x = det_tensor((N, Cin, H, W), 31, -1, 1)
