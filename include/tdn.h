@@ -1411,6 +1411,39 @@ int tdn_deform_coord_grad(const tdn_deform_desc* d, const void* dcol, void* doff
 int tdn_deform_input_grad(const tdn_deform_desc* d, const void* dcol, void* dx, void* workspace, int64_t workspace_bytes,
                           void* stream);
 
+/* ---- CARAFE content-aware upsampling (csrc/carafe.hip) ------------------------------------------------
+ * out[n, c, ph, pw] = sum over taps t = i k + j, in that order, of w[n, gi k^2 + t, ph, pw] * x[n, c, h - r + i, w - r + j],
+ * h = ph / s, w = pw / s, gi = c / (C / g), r = (k - 1) / 2; a tap whose source pixel lies outside the map is skipped.
+ * x (N, H, W, C), out / gout / addend (N, out_h, out_w, C) and dx are NHWC in the compute dtype (16-byte aligned).
+ * `weights` is NHWC with weight_pitch ELEMENTS between pixels, fp32 (TDN_F32) or the compute dtype: the stored masks
+ * (N, sH, sW, >= g k^2), or with weights_are_logits the content encoder's output (N, H, W, >= g k^2 s^2) whose channel
+ * (gi k^2 + t) s^2 + dy s + dx is the logit of tap t at output pixel (s h + dy, s w + dx); the kernels then use
+ * p_t = exp(l_t - max) / sum_u exp(l_u - max) (fp32, the sum in tap order).  (out_h, out_w) in (sH - s + 1 .. sH,
+ * sW - s + 1 .. sW) crops the output top-left: only those pixels are computed, gout counts as zero outside.  fp32
+ * accumulation, one rounding per output.  C a multiple of 64, C / g a multiple of 8, k odd in 1..7, s in 1..4,
+ * g k^2 s^2 <= 1024, H, W <= 32766, N sH sW < 2^30.  No workspace, no atomics: the same bits on every run.
+ *   tdn_carafe_forward:       out = addend (when non-NULL) + the sum above, one launch.
+ *   tdn_carafe_feature_grad:  dx[n, c, h, w] = sum over the source pixels (h2, w2) of the window, row-major, and their s^2
+ *                             sub-pixels, row-major, of gout * w; one thread per element, one launch.  x is not read.
+ *   tdn_carafe_mask_grad:     dweights in the dtype, layout and pitch of `weights`: d mask[t] = sum over the group's
+ *                             channels of gout * x (0 for a tap outside the map; each of L lanes its 8-channel vectors in
+ *                             order, then a fixed xor tree); for logits p_t (dm_t - sum_u p_u dm_u).  Every channel of
+ *                             every pixel below g k^2 (s^2) is written; one launch. */
+typedef struct tdn_carafe_desc {
+  const void* x;
+  const void* weights;
+  const void* addend;          /* forward only; may be NULL */
+  int64_t weight_pitch;
+  int32_t N, H, W, C;
+  int32_t kernel_size, group_size, scale_factor;
+  int32_t out_h, out_w;
+  int32_t dtype, weight_dtype;
+  int32_t weights_are_logits;
+} tdn_carafe_desc;
+int tdn_carafe_forward(const tdn_carafe_desc* d, void* out, void* stream);
+int tdn_carafe_feature_grad(const tdn_carafe_desc* d, const void* gout, void* dx, void* stream);
+int tdn_carafe_mask_grad(const tdn_carafe_desc* d, const void* gout, void* dweights, void* stream);
+
 /* ---- GroupNorm ----------------------------------------------------
  * nn.GroupNorm(get_group_gn(planes), planes) — models/utils/layers.py:50-54,138-154 (32 groups, eps 1e-5, biased
  * variance) — after a conv of ResNet(use_gn=True) (models/backbone/resnet.py:42-59,97-119,254-257) or of a

@@ -17,7 +17,7 @@ conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask 
 ``DeformConv`` / ``ModulatedDeformConv`` / ``DeformConvPack`` / ``ModulatedDeformConvPack``, and Cascade R-CNN's
 ``refine_bboxes`` / ``cascade_detections`` / ``CascadeRoIHead``, and Libra R-CNN's ``BFP`` neck,
 ``sample_assigned_iou_balanced`` / ``sample_rois(neg_sampler='iou_balanced')`` and ``bbox_head_loss(reg_loss='balanced_l1')``,
-and Mask Scoring R-CNN's ``MaskIoUHead`` with ``mask_iou_stem`` / ``mask_iou_target`` / ``mask_iou_loss`` / ``mask_scores``).  Everything computes through libtdn.so
+and Mask Scoring R-CNN's ``MaskIoUHead`` with ``mask_iou_stem`` / ``mask_iou_target`` / ``mask_iou_loss`` / ``mask_scores``, and CARAFE upsampling: the ``carafe`` op, ``CARAFEPack`` and the ``FPN_CARAFE`` neck).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -30,7 +30,7 @@ from .inits import (bias_init_with_prob, constant_init, kaiming_init, normal_ini
 from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint  # noqa: F401
 from .backbone import (BasicBlock, Bottleneck, ResNet, ResNeXt, ResNeXtBasicBlock,  # noqa: F401
                        ResNeXtBottleneck)
-from .necks import BFP, FPN, PAFPN  # noqa: F401
+from .necks import BFP, FPN, FPN_CARAFE, PAFPN  # noqa: F401
 from .staging import ImageTransforms, StagedImages  # noqa: F401
 from .graph import GraphedStep, PreparedStep  # noqa: F401
 from .functional import invalidate_packed  # noqa: F401
@@ -54,6 +54,7 @@ from .linear import LinearFunction, linear  # noqa: F401
 from .deconv import ConvTranspose2x2Function, conv_transpose2x2  # noqa: F401
 from .deform import (DeformConv, DeformConvFunction, DeformConvPack, ModulatedDeformConv,  # noqa: F401
                      ModulatedDeformConvPack, deform_conv2d)
+from .carafe import CarafeFunction, CARAFEPack, CARAFEPackFunction, carafe  # noqa: F401
 from .heads import BBoxHead, FCNMaskHead, FCOSHead, MaskIoUHead, RetinaHead, RPNHead  # noqa: F401
 from .roi import (RoIAlignFunction, SingleRoIExtractor, map_roi_levels, roi_align,  # noqa: F401
                   rois_from_proposals)

@@ -201,6 +201,16 @@ class DeformDesc(ctypes.Structure):
                 ("mask_dtype", ctypes.c_int32), ("mask_is_logit", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class CarafeDesc(ctypes.Structure):
+    """Mirror of ``tdn_carafe_desc`` (include/tdn.h)."""
+    _fields_ = [("x", c_void_p), ("weights", c_void_p), ("addend", c_void_p), ("weight_pitch", c_i64),
+                ("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("kernel_size", ctypes.c_int32), ("group_size", ctypes.c_int32), ("scale_factor", ctypes.c_int32),
+                ("out_h", ctypes.c_int32), ("out_w", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("weight_dtype", ctypes.c_int32), ("weights_are_logits", ctypes.c_int32)]
+
+
+_CfD = ctypes.POINTER(CarafeDesc)
 _DfD = ctypes.POINTER(DeformDesc)
 _RoL = ctypes.POINTER(RoiLevel)
 _RoC = ctypes.POINTER(RoiConfig)
@@ -514,6 +524,9 @@ SIGNATURES = {
                                        c_void_p]),
     "tdn_deform_coord_grad": (c_int, [_DfD, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tdn_deform_input_grad": (c_int, [_DfD, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "tdn_carafe_forward": (c_int, [_CfD, c_void_p, c_void_p]),
+    "tdn_carafe_feature_grad": (c_int, [_CfD, c_void_p, c_void_p, c_void_p]),
+    "tdn_carafe_mask_grad": (c_int, [_CfD, c_void_p, c_void_p, c_void_p]),
     "tdn_pack_gconv_weight": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p, c_void_p, c_int, c_void_p]),
     "tdn_bottleneck_supported": (c_int, [c_int] * 5),

@@ -1,5 +1,6 @@
 from .bfp import BFP
 from .fpn import FPN
+from .fpn_carafe import FPN_CARAFE
 from .pafpn import PAFPN
 
-__all__ = ['BFP', 'FPN', 'PAFPN']
+__all__ = ['BFP', 'FPN', 'FPN_CARAFE', 'PAFPN']
