@@ -598,6 +598,23 @@ def ws_bytes(nbytes, what):
     return nbytes
 
 
+_GEMM128_PLAN = ("bm", "bn", "bk", "tiles_r", "tiles_c", "tiles", "slices", "chunks_per_slice", "chunks", "workgroups",
+                 "launches")
+
+
+def gemm128_plan(pl, query, args, what):
+    """Fill ``pl`` from the 16-word record that ``tdn_linear_plan`` / ``tdn_deconv2x2_plan`` (``query``) write for
+    ``args`` (csrc/gemm128_core.h, ``write_plan``) and return word 11, the file's own flags.  A refusal is a ValueError."""
+    out = (ctypes.c_int32 * 16)()
+    if query(*[int(a) for a in args], out) != 0:
+        ws_bytes(-1, what)
+    for name, v in zip(_GEMM128_PLAN, out):
+        setattr(pl, name, v)
+    pl.slab_bytes = out[12] + (out[13] << 31)
+    pl.workspace_bytes = out[14] + (out[15] << 31)
+    return out[11]
+
+
 _tls = threading.local()
 
 

@@ -1,5 +1,6 @@
-// 2x2 stride-2 transposed convolution: the mask head's upsampling layer as one MFMA GEMM family, a close
-// relative of csrc/linear.hip (same 128 x 128 x 64 tiles, the same two-slot LDS ring fed by LDS-DMA, the same XOR swizzles).
+// 2x2 stride-2 transposed convolution: the mask head's upsampling layer as one MFMA GEMM family on the
+// core it shares with csrc/linear.hip (csrc/gemm128_core.h: 128 x 128 x 64 tiles, the two-slot LDS ring fed by LDS-DMA,
+// the XOR swizzles, both MFMA loops, the split rule).  This file supplies the tap gather of its loaders and its epilogues.
 //
 // The four taps of a 2x2 stride-2 transposed conv do not overlap:
 //     y[r][2i+a][2j+b][o] = act(bias[o] + sum_c x[r][i][j][c] * W[c][o][a][b])
@@ -19,26 +20,12 @@
 // does: every workgroup stores an fp32 partial slab into the caller's workspace with plain stores and a finalize launch
 // adds the slabs in slice order, folds the four tap sums into dbias and writes dw in the parameter's own layout.  No
 // workgroup waits for another one, there are no counters, no atomics and no memset: the same bits on every run.
-#include "common.h"
+#include "gemm128_core.h"
 
 namespace {
 
-constexpr int NT = 256;                    // threads per workgroup: 4 waves as 2 x 2
-constexpr int BM = 128, BN = 128, BK = 64; // output tile and reduction step of every product
-constexpr int TILE_BYTES = BM * BK * 2;    // one operand, one step: 16 KB
-constexpr int STAGE = 2 * TILE_BYTES;
-constexpr int NST = 2;                     // ring slots, as in csrc/linear.hip (two workgroups per CU measured faster there)
-constexpr int LOADS = 8;                   // LDS-DMA instructions per wave and step (4 per operand)
-constexpr int LDS_BYTES = NST * STAGE;     // 64 KB
-constexpr int FILL_WGS = 256;              // the split rule aims at one workgroup per CU
 constexpr int64_t MAX_PIX = (int64_t)1 << 29, MAX_OUT = (int64_t)1 << 31;
 constexpr int MAX_C = 1 << 16;
-
-// Every wave issues exactly LOADS LDS-DMA instructions per step (rows or steps past the end read the zero page), so a
-// counted wait retires a step; the barrier makes every wave's share of it visible and frees the slot multiplied last.
-__device__ __forceinline__ void wait_step_and_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(LOADS * (NST - 2)) : "memory");
-}
 
 // output pixel of tap (0, 0) of input pixel m, in pixels of the (R, 2H, 2W) map
 __device__ __forceinline__ int64_t pix0(int m, int W) { return 4 * m - 2 * (m % W); }   // 4M < 2^31 (checked on the host)
@@ -66,15 +53,15 @@ __global__ __launch_bounds__(NT) void deconv_gemm_kernel(const DcArgs p) {
   const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
 
-  // ---- loader: one wave-instruction fills 8 rows x 128 bytes; LDS position c of row r holds source piece c ^ (r & 7)
+  // ---- loader: dgrad gathers a row of A from the output pixel of the chunk's tap; a row past its operand reads the zero page
   const int lrow = lane >> 3;
-  const int src_el = ((lane & 7) ^ lrow) * 8;
+  const int src_el = kc_src_el(lane, lrow);
   const bf16_t* const zero = (const bf16_t*)g_zero_page + src_el;
   const bf16_t* a_src[4];
   const bf16_t* b_src[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
-    const int row = (it * 4 + wave) * 8 + lrow;
+    const int row = kc_row(it, wave, lrow);
     const int m = m0 + row;
     if (m < p.M) a_src[it] = DGRAD ? p.A + pix0(m, p.W) * p.Cout + src_el : p.A + (int64_t)m * p.Cin + src_el;
     else a_src[it] = nullptr;
@@ -91,22 +78,21 @@ __global__ __launch_bounds__(NT) void deconv_gemm_kernel(const DcArgs p) {
       a_k = (int64_t)tap_off(t, p.W) * p.Cout + (k0 - t * p.Cout);
     }
 #pragma unroll
-    for (int it = 0; it < 4; ++it) glds16_async((in && a_src[it]) ? a_src[it] + a_k : zero, sA + (it * 4 + wave) * 1024);
+    for (int it = 0; it < 4; ++it) glds16_async((in && a_src[it]) ? a_src[it] + a_k : zero, sA + kc_dst(it, wave));
 #pragma unroll
-    for (int it = 0; it < 4; ++it) glds16_async((in && b_src[it]) ? b_src[it] + k0 : zero, sB + (it * 4 + wave) * 1024);
+    for (int it = 0; it < 4; ++it) glds16_async((in && b_src[it]) ? b_src[it] + k0 : zero, sB + kc_dst(it, wave));
   };
 
-  // ---- fragment reads: lane l takes row (l & 15), k pieces (l >> 4) and 4 + (l >> 4) of the step
   const int wm = wave >> 1, wn = wave & 1;
   const int fr = lane & 15, fq = lane >> 4;
   int a_off[4], b_off[4], k_off[2];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    a_off[i] = (wm * 64 + i * 16 + fr) * 128;
-    b_off[i] = TILE_BYTES + (wn * 64 + i * 16 + fr) * 128;
+    a_off[i] = kc_a_off(wm, i, fr);
+    b_off[i] = kc_b_off(wn, i, fr);
   }
 #pragma unroll
-  for (int kk = 0; kk < 2; ++kk) k_off[kk] = ((kk * 4 + fq) ^ (fr & 7)) * 16;
+  for (int kk = 0; kk < 2; ++kk) k_off[kk] = kc_k_off(kk, fq, fr);
 
   f32x4_t acc[4][4];
 #pragma unroll
@@ -114,30 +100,7 @@ __global__ __launch_bounds__(NT) void deconv_gemm_kernel(const DcArgs p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-#pragma unroll
-  for (int s = 0; s < NST - 1; ++s) stage_load(s, s);
-  int slot = 0, fill = NST - 1;
-  for (int c = 0; c < p.nchunks; ++c) {
-    wait_step_and_barrier();                      // step c has landed for every wave; the slot of step c - 1 is free
-    stage_load(c + NST - 1, fill);
-    const char* st = smem + slot * STAGE;
-    slot = (slot + 1 == NST) ? 0 : slot + 1;
-    fill = (fill + 1 == NST) ? 0 : fill + 1;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8_t af[4], bf[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = lds_read_b128(st + a_off[i] + k_off[kk]);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bf[j] = lds_read_b128(st + b_off[j] + k_off[kk]);
-      // D[row = n][col = m]: a lane ends up with 4 consecutive n of one m
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<F16>(bf[j], af[i], acc[i][j]);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the dummy tail loads still target the ring
+  kc_ring<F16>(smem, 0, p.nchunks, stage_load, a_off, b_off, k_off, acc);   // nchunks >= 1
 
   // ---- store: through LDS (the ring is free now).  Straight from the accumulators a wave instruction would write 32-byte
   // pieces of 16 different rows; staged, every lane stores 16 bytes and 16 lanes the 256 contiguous bytes of one row of
@@ -190,13 +153,9 @@ struct DcWgradArgs {
   float* slab; float* colsum;                 // slab[slice][4 Cout][Cin], colsum[slice][4 Cout]
 };
 
-// 32-byte-chunk XOR swizzle of a 256-byte row read with ds_read_b64_tr_b16
-__device__ __forceinline__ int tr_swz(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
-
 template <bool F16>
 __global__ __launch_bounds__(NT) void deconv_wgrad_kernel(const DcWgradArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int RB = 256;                       // row bytes of both tiles: 128 columns
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -207,10 +166,10 @@ __global__ __launch_bounds__(NT) void deconv_wgrad_kernel(const DcWgradArgs p) {
   const int m_begin = slice * p.cps * BK;
   const int m_end = min(p.M, m_begin + p.cps * BK);
 
-  // ---- loader: one wave-instruction fills 4 rows x 256 bytes; a lane's 16-byte piece of G lies inside one tap
+  // ---- loader: a lane's 16-byte piece of G lies inside one tap; x columns past Cin and rows >= m_end read the zero page
   const int lrow = lane >> 4, pc = lane & 15;
-  const int row0 = wave * 4 + lrow;             // + it * 16
-  const int src_el = ((((pc >> 1) ^ tr_swz(row0)) << 1) | (pc & 1)) * 8;
+  const int row0 = tr_row0(wave, lrow);         // + it * 16
+  const int src_el = tr_src_el(pc, row0);
   const bf16_t* const zero = (const bf16_t*)g_zero_page + (src_el & 63);
   const bool x_ok = k0 + src_el < p.Cin;
   const int gn = o0 + src_el, gt = gn / p.Cout;
@@ -222,16 +181,15 @@ __global__ __launch_bounds__(NT) void deconv_wgrad_kernel(const DcWgradArgs p) {
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int m = mt + it * 16 + row0;
-      glds16_async(m < m_end ? gsrc + pix0(m, p.W) * p.Cout : zero, sG + (it * 16 + wave * 4) * RB);
+      glds16_async(m < m_end ? gsrc + pix0(m, p.W) * p.Cout : zero, sG + tr_dst(it, wave));
     }
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int m = mt + it * 16 + row0;
-      glds16_async((x_ok && m < m_end) ? xsrc + (int64_t)m * p.Cin : zero, sX + (it * 16 + wave * 4) * RB);
+      glds16_async((x_ok && m < m_end) ? xsrc + (int64_t)m * p.Cin : zero, sX + tr_dst(it, wave));
     }
   };
 
-  // ---- fragment reads (ds_read_b64_tr_b16): lane group q4 takes rows 8 * q4 .. + 7 of a 32-row half step
   const int wm = wave >> 1, wn = wave & 1;
   const int grp4 = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
   const int rrow = 8 * grp4 + q;                // + kk * 32 + 4 * half
@@ -239,8 +197,8 @@ __global__ __launch_bounds__(NT) void deconv_wgrad_kernel(const DcWgradArgs p) {
   int g_off[4], x_off[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    g_off[i] = rrow * RB + ((((wm * 64 + i * 16) >> 4) ^ f) << 5) + pp * 8;
-    x_off[i] = TILE_BYTES + rrow * RB + ((((wn * 64 + i * 16) >> 4) ^ f) << 5) + pp * 8;
+    g_off[i] = tr_off(rrow, (wm * 64 + i * 16) >> 4, f, pp);
+    x_off[i] = TILE_BYTES + tr_off(rrow, (wn * 64 + i * 16) >> 4, f, pp);
   }
 
   f32x4_t acc[4][4], acc1[4];
@@ -255,45 +213,8 @@ __global__ __launch_bounds__(NT) void deconv_wgrad_kernel(const DcWgradArgs p) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) ones[e] = f32_to_elem<F16>(1.0f);
 
-  if (m_end > m_begin) {
-    const int T = ceil_div(m_end - m_begin, BK);
-#pragma unroll
-    for (int s = 0; s < NST - 1; ++s) stage_load(m_begin + s * BK, s);   // rows >= m_end read the zero page
-    int slot = 0, fill = NST - 1;
-    for (int t = 0; t < T; ++t) {
-      wait_step_and_barrier();
-      stage_load(m_begin + (t + NST - 1) * BK, fill);
-      const char* st = smem + slot * STAGE;
-      slot = (slot + 1 == NST) ? 0 : slot + 1;
-      fill = (fill + 1 == NST) ? 0 : fill + 1;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        bf16x8_t gf[4], xf[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const s16x4_t lo = lds_read_tr16(st + g_off[i] + kk * 32 * RB);
-          const s16x4_t hi = lds_read_tr16(st + g_off[i] + (kk * 32 + 4) * RB);
-          gf[i] = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const s16x4_t lo = lds_read_tr16(st + x_off[j] + kk * 32 * RB);
-          const s16x4_t hi = lds_read_tr16(st + x_off[j] + (kk * 32 + 4) * RB);
-          xf[j] = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
-        // D[row = channel of x][col = n] += sum_m x[m][c] * G[m][n]
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<F16>(xf[j], gf[i], acc[i][j]);
-        if (do_colsum) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc1[i] = mfma16<F16>(ones, gf[i], acc1[i]);
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the dummy tail loads still target the ring
-  }
+  if (m_end > m_begin)
+    tr_ring<F16>(smem, m_begin, ceil_div(m_end - m_begin, BK), stage_load, g_off, x_off, do_colsum, ones, acc, acc1);
 
   // ---- store: a lane holds input channels c .. c + 3 of GEMM column n ----
   const int fr = lane & 15;
@@ -395,9 +316,9 @@ int check_shape(const char* who, int kind, int R, int H, int W, int Cin, int Cou
   return 0;
 }
 
-// Forward and dgrad are never cut.  The weight gradient is cut as csrc/linear.hip cuts its own: a product whose tiles
-// already give every CU a workgroup runs as one slice, otherwise the slice count aims at FILL_WGS workgroups with at
-// least 4 chunks of 64 pixels per slice.
+// Forward and dgrad are never cut.  The weight gradient is cut by split_rule as csrc/linear.hip's is: a product whose
+// tiles already give every CU a workgroup runs as one slice, otherwise the slice count aims at FILL_WGS workgroups with
+// at least 4 chunks of 64 pixels per slice.
 void make_plan(int kind, int64_t M, int Cin, int Cout, int splits, DcPlan& pl) {
   const int N = 4 * Cout;
   if (kind == 0) { pl.tiles_r = (int)((M + BM - 1) / BM); pl.tiles_c = N / BN; pl.chunks = Cin / BK; }
@@ -410,16 +331,9 @@ void make_plan(int kind, int64_t M, int Cin, int Cout, int splits, DcPlan& pl) {
     pl.launches = M > 0 ? 1 : 0;
     return;
   }
-  int want = 1;
-  if (splits > 0) want = splits;
-  else if (pl.tiles < FILL_WGS) {
-    want = FILL_WGS / pl.tiles;
-    if (want > pl.chunks / 4) want = pl.chunks / 4;
-  }
-  if (want > pl.chunks) want = pl.chunks;
-  if (want < 1) want = 1;
-  pl.cps = pl.chunks > 0 ? (pl.chunks + want - 1) / want : 0;
-  pl.slices = pl.chunks > 0 ? (pl.chunks + pl.cps - 1) / pl.cps : 0;
+  const Split sp = split_rule(pl.tiles, pl.chunks, splits, FILL_WGS, 4);
+  pl.cps = sp.cps;
+  pl.slices = sp.slices;                                 // 0 for an empty product: the finalize alone writes beta * old
   pl.launches = (M > 0 ? 1 : 0) + 1;                     // the partial products, the finalize
   pl.slab_bytes = (int64_t)pl.slices * N * Cin * 4;
 }
@@ -435,8 +349,6 @@ DcWs ws_layout(int kind, int Cout, const DcPlan& pl, void* base) {
   w.bytes = c.off;
   return w;
 }
-
-bool aligned(const void* p, int a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 template <bool F16, bool DGRAD>
 int launch_gemm(DcArgs& p, const DcPlan& pl, hipStream_t stream) {
@@ -476,14 +388,8 @@ extern "C" int tdn_deconv2x2_plan(int kind, int R, int H, int W, int Cin, int Co
   DcPlan pl;
   make_plan(kind, (int64_t)R * H * W, Cin, Cout, splits, pl);
   const int64_t ws = ws_layout(kind, Cout, pl, nullptr).bytes;
-  out[0] = BM; out[1] = BN; out[2] = BK;
-  out[3] = pl.tiles_r; out[4] = pl.tiles_c; out[5] = pl.tiles;
-  out[6] = pl.slices; out[7] = pl.cps; out[8] = pl.chunks;
-  out[9] = kind == 2 ? pl.tiles * pl.slices : pl.tiles;
-  out[10] = pl.launches;
-  out[11] = 0;
-  out[12] = (int32_t)(pl.slab_bytes & 0x7fffffff); out[13] = (int32_t)(pl.slab_bytes >> 31);
-  out[14] = (int32_t)(ws & 0x7fffffff); out[15] = (int32_t)(ws >> 31);
+  write_plan(out, pl.tiles_r, pl.tiles_c, pl.slices, pl.cps, pl.chunks, kind == 2 ? pl.tiles * pl.slices : pl.tiles,
+             pl.launches, 0, pl.slab_bytes, ws);
   return 0;
 }
 
@@ -551,18 +457,7 @@ extern "C" int tdn_deconv2x2_wgrad(const void* x, const void* g, float* dw, floa
   p.cps = pl.cps; p.tiles_o = pl.tiles_r; p.ntiles = pl.tiles;
   p.dw = dw; p.dbias = dbias; p.beta = beta;
   p.slab = w.slab; p.colsum = w.colsum;
-  if (M > 0) {
-    const bool f16 = dtype == TDN_F16;
-    if ((f16 ? tdn_allow_lds<deconv_wgrad_kernel<true>>(LDS_BYTES, "deconv_wgrad_kernel")
-             : tdn_allow_lds<deconv_wgrad_kernel<false>>(LDS_BYTES, "deconv_wgrad_kernel")) < 0) return -1;
-    const dim3 grid((unsigned)(pl.tiles * pl.slices));
-    if (f16) TDN_LAUNCH(deconv_wgrad_kernel<true>, grid, dim3(NT), LDS_BYTES, stream, p);
-    else TDN_LAUNCH(deconv_wgrad_kernel<false>, grid, dim3(NT), LDS_BYTES, stream, p);
-    TDN_LAUNCH_CHECK();
-  }
-  const int fgrid = tdn_grid_1d((int64_t)Cout * Cin, NT, 4096);
-  const int slices = pl.slices;
-  TDN_LAUNCH(deconv_wgrad_finalize_kernel, dim3(fgrid), dim3(NT), 0, stream, p, slices);
-  TDN_LAUNCH_CHECK();
-  return 0;
+  return launch_wgrad<deconv_wgrad_kernel<true>, deconv_wgrad_kernel<false>, deconv_wgrad_finalize_kernel>(
+      "deconv_wgrad_kernel", dtype == TDN_F16, pl.tiles * pl.slices, p, (int64_t)Cout * Cin, pl.slices,
+      (hipStream_t)stream);
 }

@@ -22,29 +22,12 @@
 //
 // A cotangent whose rows are not 16-byte aligned (the predictors' 81 / 324 / 405 columns) is first copied, zero padded
 // to Op = O rounded up to 64 columns, into the workspace by one pad launch (linear_pad_kernel).
-#include "common.h"
+// Tiles, ring, swizzles, MFMA loops, split rule and plan record: csrc/gemm128_core.h, shared with csrc/deconv.hip.
+#include "gemm128_core.h"
 
 namespace {
 
-constexpr int NT = 256;                    // threads per workgroup: 4 waves as 2 x 2
-constexpr int BM = 128, BN = 128, BK = 64; // output tile and reduction step of every product
-constexpr int TILE_BYTES = BM * BK * 2;    // one operand, one step: 16 KB
-constexpr int STAGE = 2 * TILE_BYTES;
-constexpr int NST = 2;                     // ring slots: the loads of NST - 1 steps are in flight while one is multiplied.
-                                           // Measured: a CU cannot pull the 32 KB a 128 x 128 x 64 step needs
-                                           // faster than it multiplies it, so 4 slots (one workgroup per CU) were slower on
-                                           // every many-tile product than 2 slots (two workgroups per CU)
-constexpr int LOADS = 8;                   // LDS-DMA instructions per wave and step (4 per operand)
-constexpr int LDS_BYTES = NST * STAGE;     // 64 KB: two workgroups per CU
-constexpr int FILL_WGS = 256;              // the split rule aims at one workgroup per CU
 constexpr int MAX_M = 1 << 18, MAX_O = 65536, MAX_K = 1 << 20;
-
-// Every wave issues exactly LOADS LDS-DMA instructions per step (rows or steps past the end read the zero page), so a
-// counted wait retires a step: with the NST - 2 youngest steps left in flight, the oldest one has landed; the barrier
-// then makes every wave's share of it visible and frees the slot that was multiplied last.
-__device__ __forceinline__ void wait_step_and_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(LOADS * (NST - 2)) : "memory");
-}
 
 // ---- forward / dgrad: C[m][n] = sum_k A[m][k] * B[n][k] -----------------------------------------------------------------
 struct GemmArgs {
@@ -79,15 +62,15 @@ __global__ __launch_bounds__(NT) void linear_gemm_kernel(const GemmArgs p) {
   const int m0 = tm * BM, n0 = tn * BN;
   const int c_begin = slice * p.cps, c_end = min(p.nchunks, c_begin + p.cps);
 
-  // ---- loader: one wave-instruction fills 8 rows x 128 bytes; LDS position c of row r holds source piece c ^ (r & 7)
+  // ---- loader: plain rows; a row past its operand reads the zero page
   const int lrow = lane >> 3;
-  const int src_el = ((lane & 7) ^ lrow) * 8;
+  const int src_el = kc_src_el(lane, lrow);
   const bf16_t* const zero = (const bf16_t*)g_zero_page + src_el;
   const bf16_t* a_src[4];
   const bf16_t* b_src[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
-    const int row = (it * 4 + wave) * 8 + lrow;
+    const int row = kc_row(it, wave, lrow);
     a_src[it] = (m0 + row < p.a_rows) ? p.A + (int64_t)(m0 + row) * p.lda + src_el : nullptr;
     b_src[it] = (n0 + row < p.b_rows) ? p.B + (int64_t)(n0 + row) * p.ldb + src_el : nullptr;
   }
@@ -97,29 +80,29 @@ __global__ __launch_bounds__(NT) void linear_gemm_kernel(const GemmArgs p) {
     const int k0 = chunk * BK;
     const bool in = chunk < c_end;                  // past the slice: the zero page (keeps the vmcnt bookkeeping uniform)
 #pragma unroll
-    for (int it = 0; it < 4; ++it) glds16_async((in && a_src[it]) ? a_src[it] + k0 : zero, sA + (it * 4 + wave) * 1024);
+    for (int it = 0; it < 4; ++it) glds16_async((in && a_src[it]) ? a_src[it] + k0 : zero, sA + kc_dst(it, wave));
 #pragma unroll
-    for (int it = 0; it < 4; ++it) glds16_async((in && b_src[it]) ? b_src[it] + k0 : zero, sB + (it * 4 + wave) * 1024);
+    for (int it = 0; it < 4; ++it) glds16_async((in && b_src[it]) ? b_src[it] + k0 : zero, sB + kc_dst(it, wave));
   };
 
-  // ---- fragment reads: lane l takes row (l & 15), k pieces (l >> 4) and 4 + (l >> 4) of the step
   const int wm = wave >> 1, wn = wave & 1;
   const int fr = lane & 15, fq = lane >> 4;
   int a_off[4], b_off[4], k_off[2];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    a_off[i] = (wm * 64 + i * 16 + fr) * 128;
-    b_off[i] = TILE_BYTES + (wn * 64 + i * 16 + fr) * 128;
+    a_off[i] = kc_a_off(wm, i, fr);
+    b_off[i] = kc_b_off(wn, i, fr);
   }
 #pragma unroll
-  for (int kk = 0; kk < 2; ++kk) k_off[kk] = ((kk * 4 + fq) ^ (fr & 7)) * 16;
+  for (int kk = 0; kk < 2; ++kk) k_off[kk] = kc_k_off(kk, fq, fr);
 
   f32x4_t acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
+  // kc_ring's loop, kept as this kernel's own text: through kc_ring the same instructions come out in another order,
+  // which measured 4 % (split fc6) to 14 % (unsplit fc6) slower (profiles/gemm128_core_refactor_checks.md §4)
   if (c_end > c_begin) {
 #pragma unroll
     for (int s = 0; s < NST - 1; ++s) stage_load(c_begin + s, s);
@@ -137,7 +120,6 @@ __global__ __launch_bounds__(NT) void linear_gemm_kernel(const GemmArgs p) {
         for (int i = 0; i < 4; ++i) af[i] = lds_read_b128(st + a_off[i] + k_off[kk]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) bf[j] = lds_read_b128(st + b_off[j] + k_off[kk]);
-        // D[row = n][col = m]: a lane ends up with 4 consecutive n of one m
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -232,13 +214,9 @@ struct WgradArgs {
   float* slab; float* colsum;                 // more than one slice: slab[slice][O][K] in PACKED column order
 };
 
-// 32-byte-chunk XOR swizzle of a 256-byte row read with ds_read_b64_tr_b16
-__device__ __forceinline__ int tr_swz(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
-
 template <bool F16>
 __global__ __launch_bounds__(NT) void linear_wgrad_kernel(const WgradArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int RB = 256;                       // row bytes of both tiles: 128 columns
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -248,10 +226,10 @@ __global__ __launch_bounds__(NT) void linear_wgrad_kernel(const WgradArgs p) {
   const int m_begin = slice * p.cps * BK;
   const int m_end = min(p.M, m_begin + p.cps * BK);
 
-  // ---- loader: one wave-instruction fills 4 rows x 256 bytes
+  // ---- loader: plain rows; a piece at a column past its operand and a row >= m_end read the zero page
   const int lrow = lane >> 4, pc = lane & 15;
-  const int row0 = wave * 4 + lrow;             // + it * 16
-  const int src_el = ((((pc >> 1) ^ tr_swz(row0)) << 1) | (pc & 1)) * 8;
+  const int row0 = tr_row0(wave, lrow);         // + it * 16
+  const int src_el = tr_src_el(pc, row0);
   const bf16_t* const zero = (const bf16_t*)g_zero_page + (src_el & 63);
   const bool g_ok = o0 + src_el < p.g_cols, x_ok = k0 + src_el < p.K;
   const bf16_t* const gsrc = p.g + o0 + src_el;
@@ -262,16 +240,15 @@ __global__ __launch_bounds__(NT) void linear_wgrad_kernel(const WgradArgs p) {
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int m = mt + it * 16 + row0;
-      glds16_async((g_ok && m < m_end) ? gsrc + (int64_t)m * p.ldg : zero, sG + (it * 16 + wave * 4) * RB);
+      glds16_async((g_ok && m < m_end) ? gsrc + (int64_t)m * p.ldg : zero, sG + tr_dst(it, wave));
     }
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int m = mt + it * 16 + row0;
-      glds16_async((x_ok && m < m_end) ? xsrc + (int64_t)m * p.ldx : zero, sX + (it * 16 + wave * 4) * RB);
+      glds16_async((x_ok && m < m_end) ? xsrc + (int64_t)m * p.ldx : zero, sX + tr_dst(it, wave));
     }
   };
 
-  // ---- fragment reads (ds_read_b64_tr_b16): lane group q4 takes rows 8 * q4 .. + 7 of a 32-row half step
   const int wm = wave >> 1, wn = wave & 1;
   const int grp4 = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
   const int rrow = 8 * grp4 + q;                // + kk * 32 + 4 * half
@@ -279,8 +256,8 @@ __global__ __launch_bounds__(NT) void linear_wgrad_kernel(const WgradArgs p) {
   int g_off[4], x_off[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    g_off[i] = rrow * RB + ((((wm * 64 + i * 16) >> 4) ^ f) << 5) + pp * 8;
-    x_off[i] = TILE_BYTES + rrow * RB + ((((wn * 64 + i * 16) >> 4) ^ f) << 5) + pp * 8;
+    g_off[i] = tr_off(rrow, (wm * 64 + i * 16) >> 4, f, pp);
+    x_off[i] = TILE_BYTES + tr_off(rrow, (wn * 64 + i * 16) >> 4, f, pp);
   }
 
   f32x4_t acc[4][4], acc1[4];
@@ -295,45 +272,8 @@ __global__ __launch_bounds__(NT) void linear_wgrad_kernel(const WgradArgs p) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) ones[e] = f32_to_elem<F16>(1.0f);
 
-  if (m_end > m_begin) {
-    const int T = ceil_div(m_end - m_begin, BK);
-#pragma unroll
-    for (int s = 0; s < NST - 1; ++s) stage_load(m_begin + s * BK, s);   // rows >= m_end read the zero page
-    int slot = 0, fill = NST - 1;
-    for (int t = 0; t < T; ++t) {
-      wait_step_and_barrier();
-      stage_load(m_begin + (t + NST - 1) * BK, fill);
-      const char* st = smem + slot * STAGE;
-      slot = (slot + 1 == NST) ? 0 : slot + 1;
-      fill = (fill + 1 == NST) ? 0 : fill + 1;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        bf16x8_t gf[4], xf[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const s16x4_t lo = lds_read_tr16(st + g_off[i] + kk * 32 * RB);
-          const s16x4_t hi = lds_read_tr16(st + g_off[i] + (kk * 32 + 4) * RB);
-          gf[i] = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const s16x4_t lo = lds_read_tr16(st + x_off[j] + kk * 32 * RB);
-          const s16x4_t hi = lds_read_tr16(st + x_off[j] + (kk * 32 + 4) * RB);
-          xf[j] = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
-        // D[row = column of x][col = o] += sum_m x[m][k] * g[m][o]
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<F16>(xf[j], gf[i], acc[i][j]);
-        if (do_colsum) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc1[i] = mfma16<F16>(ones, gf[i], acc1[i]);
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the dummy tail loads still target the ring
-  }
+  if (m_end > m_begin)
+    tr_ring<F16>(smem, m_begin, ceil_div(m_end - m_begin, BK), stage_load, g_off, x_off, do_colsum, ones, acc, acc1);
 
   // ---- store: a lane holds packed columns kp .. kp + 3 of row o ----
   const int fr = lane & 15;
@@ -423,8 +363,6 @@ __global__ __launch_bounds__(NT) void linear_pack_kernel(const float* __restrict
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-inline int round64(int v) { return (v + 63) & ~63; }
-
 struct LinPlan {
   int rows, cols;          // extent of the product's output (wgrad: O x K)
   int tiles_r, tiles_c, tiles, chunks, slices, cps, launches, pad;
@@ -456,17 +394,10 @@ void make_plan(int kind, int M, int O, int K, int splits, LinPlan& pl) {
   pl.tiles_r = (pl.rows + BM - 1) / BM;
   pl.tiles_c = (pl.cols + BN - 1) / BN;
   pl.tiles = pl.tiles_r * pl.tiles_c;
-  int want = 1;
-  if (splits > 0) want = splits;
-  else if (pl.tiles > 0 && pl.tiles < ((kind != 2 && O % 64 == 0) ? FILL_WGS / 2 : FILL_WGS)) {
-    const int min_cps = (kind != 2 && O % 64 == 0) ? 16 : 4;
-    want = FILL_WGS / pl.tiles;
-    if (want > pl.chunks / min_cps) want = pl.chunks / min_cps;
-  }
-  if (want > pl.chunks) want = pl.chunks;
-  if (want < 1) want = 1;
-  pl.cps = pl.chunks > 0 ? (pl.chunks + want - 1) / want : 0;
-  pl.slices = pl.chunks > 0 ? (pl.chunks + pl.cps - 1) / pl.cps : 1;
+  const bool strict = kind != 2 && O % 64 == 0;
+  const Split sp = split_rule(pl.tiles, pl.chunks, splits, strict ? FILL_WGS / 2 : FILL_WGS, strict ? 16 : 4);
+  pl.cps = sp.cps;
+  pl.slices = sp.slices > 0 ? sp.slices : 1;              // an empty product still counts as one slice
   pl.pad = (kind != 0 && (O % 64) != 0 && M > 0) ? 1 : 0;
   pl.conv = (splits == 0 && kind != 2 && O % 64 == 0 && pl.slices == 1 && M > 0) ? 1 : 0;
   const bool empty = kind != 2 && M == 0;
@@ -519,8 +450,6 @@ int launch_pad(const void* g, int64_t ldg, bf16_t* gp, int M, int O, hipStream_t
   return 0;
 }
 
-bool aligned(const void* p, int a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int tdn_pack_linear_weight(const float* w, int64_t s_o, int64_t s_k, int O, int K, int C, void* w_fwd,
@@ -568,14 +497,8 @@ extern "C" int tdn_linear_plan(int kind, int M, int O, int K, int splits, int32_
   LinPlan pl;
   make_plan(kind, M, O, K, splits, pl);
   const int64_t ws = ws_layout(kind, M, O, K, pl, nullptr).bytes;
-  out[0] = BM; out[1] = BN; out[2] = BK;
-  out[3] = pl.tiles_r; out[4] = pl.tiles_c; out[5] = pl.tiles;
-  out[6] = pl.slices; out[7] = pl.cps; out[8] = pl.chunks;
-  out[9] = pl.tiles * pl.slices;
-  out[10] = pl.launches;
-  out[11] = pl.pad + 2 * pl.conv;
-  out[12] = (int32_t)(pl.slab_bytes & 0x7fffffff); out[13] = (int32_t)(pl.slab_bytes >> 31);
-  out[14] = (int32_t)(ws & 0x7fffffff); out[15] = (int32_t)(ws >> 31);
+  write_plan(out, pl.tiles_r, pl.tiles_c, pl.slices, pl.cps, pl.chunks, pl.tiles * pl.slices, pl.launches,
+             pl.pad + 2 * pl.conv, pl.slab_bytes, ws);
   return 0;
 }
 
@@ -684,18 +607,7 @@ extern "C" int tdn_linear_wgrad(const void* x, int64_t ldx, const void* g, int64
   p.mchunks = pl.chunks; p.cps = pl.cps; p.tiles_o = pl.tiles_r; p.ntiles = pl.tiles;
   p.dw = dw; p.dbias = dbias; p.beta = beta;
   p.slab = w.slab; p.colsum = w.colsum;
-  const bool f16 = dtype == TDN_F16;
-  if ((f16 ? tdn_allow_lds<linear_wgrad_kernel<true>>(LDS_BYTES, "linear_wgrad_kernel")
-           : tdn_allow_lds<linear_wgrad_kernel<false>>(LDS_BYTES, "linear_wgrad_kernel")) < 0) return -1;
-  const dim3 grid((unsigned)(pl.tiles * pl.slices));
-  if (f16) TDN_LAUNCH(linear_wgrad_kernel<true>, grid, dim3(NT), LDS_BYTES, stream, p);
-  else TDN_LAUNCH(linear_wgrad_kernel<false>, grid, dim3(NT), LDS_BYTES, stream, p);
-  TDN_LAUNCH_CHECK();
-  if (pl.slices > 1) {
-    const int fgrid = tdn_grid_1d((int64_t)O * K, NT, 4096);
-    const int slices = pl.slices;
-    TDN_LAUNCH(linear_wgrad_finalize_kernel, dim3(fgrid), dim3(NT), 0, stream, p, slices);
-    TDN_LAUNCH_CHECK();
-  }
-  return 0;
+  return launch_wgrad<linear_wgrad_kernel<true>, linear_wgrad_kernel<false>, linear_wgrad_finalize_kernel>(
+      "linear_wgrad_kernel", dtype == TDN_F16, pl.tiles * pl.slices, p, pl.slices > 1 ? (int64_t)O * K : 0, pl.slices,
+      (hipStream_t)stream);
 }

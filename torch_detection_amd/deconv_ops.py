@@ -10,7 +10,6 @@ hand on — i.e. ``t.permute(0, 2, 3, 1)`` is contiguous: ``x`` (R, Cin, H, W), 
 Like the other ``*_ops`` modules this lives beside ``ops.py`` rather than in it; ``tests/test_gpu_deconv.py`` puts THIS
 module under the guard of ``tests/guard_util.py``.
 """
-import ctypes
 
 import torch
 
@@ -70,14 +69,8 @@ class DeconvPlan(object):
 
 def deconv2x2_plan(kind, R, H, W, Cin, Cout, splits=0):
     """Host only: the decomposition of one product (kind FWD / DGRAD / WGRAD).  Refusals of the library are ValueErrors."""
-    out = (ctypes.c_int32 * 16)()
-    if _lib.load().tdn_deconv2x2_plan(int(kind), int(R), int(H), int(W), int(Cin), int(Cout), int(splits), out) != 0:
-        _lib.ws_bytes(-1, "deconv2x2_plan")
     pl = DeconvPlan()
-    (pl.bm, pl.bn, pl.bk, pl.tiles_r, pl.tiles_c, pl.tiles, pl.slices, pl.chunks_per_slice, pl.chunks, pl.workgroups,
-     pl.launches) = list(out)[:11]
-    pl.slab_bytes = out[12] + (out[13] << 31)
-    pl.workspace_bytes = out[14] + (out[15] << 31)
+    _lib.gemm128_plan(pl, _lib.load().tdn_deconv2x2_plan, (kind, R, H, W, Cin, Cout, splits), "deconv2x2_plan")
     return pl
 
 

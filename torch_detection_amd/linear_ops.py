@@ -9,7 +9,6 @@ float32.  A channels_last RoI feature buffer is such an ``x`` through the pack's
 Like the other ``*_ops`` modules this lives beside ``ops.py`` rather than in it; ``tests/test_gpu_linear.py`` puts THIS
 module under the guard of ``tests/guard_util.py``.
 """
-import ctypes
 
 import torch
 
@@ -56,15 +55,9 @@ class LinearPlan(object):
 
 def linear_plan(kind, M, O, K, splits=0):
     """Host only: the decomposition of one product (kind FWD / DGRAD / WGRAD).  Refusals of the library are ValueErrors."""
-    out = (ctypes.c_int32 * 16)()
-    if _lib.load().tdn_linear_plan(int(kind), int(M), int(O), int(K), int(splits), out) != 0:
-        _lib.ws_bytes(-1, "linear_plan")
     pl = LinearPlan()
-    (pl.bm, pl.bn, pl.bk, pl.tiles_r, pl.tiles_c, pl.tiles, pl.slices, pl.chunks_per_slice, pl.chunks, pl.workgroups,
-     pl.launches, pl.pad) = list(out)[:12]
-    pl.pad, pl.conv = pl.pad & 1, pl.pad >> 1
-    pl.slab_bytes = out[12] + (out[13] << 31)
-    pl.workspace_bytes = out[14] + (out[15] << 31)
+    flags = _lib.gemm128_plan(pl, _lib.load().tdn_linear_plan, (kind, M, O, K, splits), "linear_plan")
+    pl.pad, pl.conv = flags & 1, flags >> 1
     return pl
 
 
