@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Every workspace size query of the detection-head files over a fixed grid of arguments (host arithmetic: no device
-is touched).  For comparing two builds of the library:
+"""Every workspace size query of the detection-head files, and the plan and workspace queries of the pyramid-wide heads
+(csrc/pyramid_core.h), over a fixed grid of arguments (host arithmetic: no device is touched).  For comparing two builds of the library:
 
     python scripts/workspace_query_grid.py OTHER/libtdn.so [THIS/libtdn.so]
 
@@ -69,6 +69,32 @@ def points(_lib):
         cfg = _lib.LossConfig(dtype=dt, num_anchors=A, num_classes=C, focal=0, beta=1.0 / 9.0)
         yield "tdn_loss_dense_workspace_bytes", (lv, L, B, ctypes.byref(cfg)), (L, H, W, dt, A, C, B)
     yield "tdn_loss_dense_workspace_bytes", (None, 1, 1, None), "NULL"
+    # the pyramid-wide heads (csrc/pyramid_core.h): level counts 0..9, an empty level, row totals on both sides of the
+    # wgrad slice threshold (64 slices x 128 rows for the predictors), refused kinds, channels and sizes
+    pbases = ((1, 1), (3, 5), (13, 21), (50, 84), (64, 127), (64, 128), (64, 129), (100, 168), (200, 336), (1 << 15, 1 << 15))
+    for kind, L, (H, W), B, empty in itertools.product((-1, 0, 1, 2, 3), (0, 1, 2, 5, 8, 9), pbases, (0, 1, 2), (None, 1)):
+        if (empty is not None and L < 2) or (kind in (-1, 3) and (L, B) != (5, 2)):
+            continue
+        maps = pyramid(H, W, max(L, 1), empty)
+        hw = (ctypes.c_int32 * (2 * len(maps)))(*[v for m in maps for v in m])
+        rows = (ctypes.c_int64 * len(maps))(*[B * h * w for h, w in maps])
+        for A, C in ((1, 64), (3, 256), (12, 512), (0, 64), (13, 64), (3, 0), (3, 96), (3, 576)):
+            yield "tdn_pred_workspace_bytes", (kind, rows, L, C, A), (kind, L, H, W, B, empty, C, A)
+            yield "tdn_pred_plan", (kind, rows, L, C, A), (kind, L, H, W, B, empty, C, A, "plan")
+        for Cin, Cout in ((64, 1), (64, 9), (64, 65), (256, 36), (512, 720), (64, 1024), (64, 0), (64, 1025), (96, 9), (576, 9)):
+            yield "tdn_pyr_workspace_bytes", (kind, B, hw, L, Cin, Cout), (kind, L, H, W, B, empty, Cin, Cout)
+            yield "tdn_pyr_plan", (kind, B, hw, L, Cin, Cout), (kind, L, H, W, B, empty, Cin, Cout, "plan")
+        if kind < 2:
+            for C, G in ((64, 32), (128, 32), (256, 32), (512, 2), (512, 1), (96, 32), (256, 3), (256, 0)):
+                yield "tdn_pyr_gn_workspace_bytes", (kind, B, hw, L, C, G), (kind, L, H, W, B, empty, C, G)
+                yield "tdn_pyr_gn_plan", (kind, B, hw, L, C, G), (kind, L, H, W, B, empty, C, G, "plan")
+    for B in (-1, 8191, 8192):
+        hw = (ctypes.c_int32 * 2)(3, 5)
+        yield "tdn_pyr_gn_workspace_bytes", (0, B, hw, 1, 64, 32), (B, "B")
+        yield "tdn_pyr_workspace_bytes", (2, B, hw, 1, 64, 9), (B, "B")
+    yield "tdn_pred_plan", (2, None, 1, 64, 3), ("NULL", "plan")
+    yield "tdn_pyr_plan", (2, 1, None, 1, 64, 9), ("NULL", "plan")
+    yield "tdn_pyr_gn_plan", (0, 1, None, 1, 64, 32), ("NULL", "plan")
 
 
 def one(lib_path):
@@ -76,7 +102,12 @@ def one(lib_path):
     _lib.LIB_PATH = os.path.abspath(lib_path)
     lib = _lib.load()
     for name, args, key in points(_lib):
-        print(name, key, "->", getattr(lib, name)(*args))
+        if name.endswith("_plan"):                       # a plan query: the record it wrote, or the refusal's text
+            out = (ctypes.c_int32 * 32)(*([-7] * 32))
+            rc = getattr(lib, name)(*(args + (out,)))
+            print(name, key, "->", rc, list(out) if rc == 0 else lib.tdn_last_error().decode())
+        else:
+            print(name, key, "->", getattr(lib, name)(*args))
 
 
 def main(argv):
@@ -92,7 +123,7 @@ def main(argv):
         n, d, h, r = per.setdefault(q, [0, 0, hashlib.sha256(), 0])
         per[q][0] += 1
         per[q][1] += a != b
-        per[q][3] += a.endswith("-> -1")
+        per[q][3] += a.endswith("-> -1") or "-> -1 " in a
         h.update(a.encode())
     assert len(outs[0]) == len(outs[1])
     for q, (n, d, h, r) in per.items():

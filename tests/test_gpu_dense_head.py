@@ -59,17 +59,19 @@ def row_tile():
 
 
 # (B, [(H, W)]): odd sizes over several workgroups, a single row, eight levels several of them 1x1, row counts one
-# below, at and one above the kernel's row tile (filled in from pred_plan), an empty batch
+# below, at and one above the kernel's row tile (filled in from pred_plan), an empty batch; "long": 16,412 rows, more than
+# the wgrad planner's 64 slices x 128 rows, so that a slice is three 128-row steps (the last slice's third holds 16 rows)
 PYRAMIDS = {
     "four": (2, [(9, 8), (5, 4), (3, 2), (1, 1)]),
     "one": (1, [(1, 1)]),
     "eight": (1, [(5, 5), (1, 1), (3, 3), (1, 1), (2, 2), (1, 1), (1, 2), (1, 1)]),
     "tile": None,
     "empty": (0, [(4, 4), (2, 2)]),
+    "long": (2, [(82, 100), (3, 2)]),
 }
 CASES = [("four", 3, 64), ("four", 1, 256), ("four", 4, 64), ("four", 9, 64), ("four", 12, 512), ("one", 3, 256),
          ("one", 12, 64), ("eight", 3, 64), ("eight", 9, 256), ("tile", 3, 256), ("tile", 4, 512), ("tile", 12, 64),
-         ("empty", 3, 64)]
+         ("empty", 3, 64), ("long", 3, 64), ("long", 12, 64)]
 
 
 def pyramid(name):
@@ -161,6 +163,7 @@ def test_products_against_the_bound_under_the_guard(T, guard, name, A, C, dtype)
         ratios["dbias"] = R.within(torch.cat([dbc, dbr]), R.dbias_bound(gc, gr), torch.float32, "pred_wgrad dbias")["ratio"]
         pl = D.pred_plan(WGRAD, [B * H * Wd for H, Wd in sizes], C, A)
         assert pl.slices == sum(-(-B * H * Wd // pl.rows_per_slice) for H, Wd in sizes)
+        assert name != "long" or pl.rows_per_slice > pl.rows_per_workgroup     # several steps per wgrad workgroup
     else:
         assert all(not t.abs().sum().item() for t in (dwc, dbc, dwr, dbr))      # zeros, not poison
         assert all(t.numel() == 0 for t in cls + reg + dhs)

@@ -64,7 +64,8 @@ def tiles():
 # (B, [(H, W)]): odd sizes over several workgroups; a single pixel; maps one pixel wide or high, where every off-centre tap
 # of a row or column is padding; eight levels, several of them 1x1; per-image pixel counts one below, at and one above the
 # kernel's pixel tile (from the plan) with two images, so that a tile straddles rows and images, the widths 127 and 43 not
-# dividing the tile; an empty batch
+# dividing the tile; an empty batch; "long": 16,412 pixels, more than the wgrad planner's slice count x 128, so that a slice
+# is three 128-pixel steps (the last slice's third holds 16 pixels)
 PYRAMIDS = {
     "four": (2, [(9, 8), (5, 4), (3, 2), (1, 1)]),
     "one": (1, [(1, 1)]),
@@ -72,13 +73,14 @@ PYRAMIDS = {
     "eight": (1, [(5, 5), (1, 1), (3, 3), (1, 1), (2, 2), (1, 1), (1, 2), (1, 1)]),
     "tile": None,
     "empty": (0, [(4, 4), (2, 2)]),
+    "long": (2, [(82, 100), (3, 2)]),
 }
 # (pyramid, Cout, Cin): Cout 1, 9 (odd: 18-byte rows), 36, 80, one below / at / one above the column tile (64, asserted
 # against the plan), 720 and 1024 once with Cin = 64; Cin 64, 256, 512
 CASES = [("four", 1, 64), ("four", 9, 64), ("four", 36, 256), ("four", 80, 64), ("four", 63, 64), ("four", 64, 64),
          ("four", 65, 64), ("four", 9, 512), ("four", 720, 64), ("four", 1024, 64), ("one", 36, 256), ("one", 9, 64),
          ("thin", 9, 64), ("thin", 65, 256), ("eight", 36, 64), ("eight", 80, 512), ("tile", 9, 64), ("tile", 64, 256),
-         ("tile", 65, 64), ("empty", 36, 64)]
+         ("tile", 65, 64), ("empty", 36, 64), ("long", 9, 64), ("long", 65, 64)]
 
 
 def pyramid(name):
@@ -185,6 +187,7 @@ def test_products_against_the_bound_under_the_guard(T, guard, name, Cout, Cin, d
         ratios["dbias"] = R.within(db, R.dbias_bound(gs), torch.float32, "pyramid_conv_wgrad dbias")["ratio"]
         pl = P.pyramid_conv_plan(WGRAD, B, sizes, Cin, Cout)
         assert pl.slices == sum(-(-B * H * Wd // pl.pixels_per_slice) for H, Wd in sizes)
+        assert name != "long" or pl.pixels_per_slice > pl.pixels_per_workgroup   # several steps per wgrad workgroup
     else:
         assert not dw.abs().sum().item() and not db.abs().sum().item()         # zeros, not poison
         assert all(t.numel() == 0 for t in ys + dxs)

@@ -598,6 +598,11 @@ def ws_bytes(nbytes, what):
     return nbytes
 
 
+def size_word(out, i):
+    """A 64-bit size of a plan record: its low 31 bits in word ``i``, the rest in word ``i + 1``."""
+    return out[i] + (out[i + 1] << 31)
+
+
 _GEMM128_PLAN = ("bm", "bn", "bk", "tiles_r", "tiles_c", "tiles", "slices", "chunks_per_slice", "chunks", "workgroups",
                  "launches")
 
@@ -610,8 +615,7 @@ def gemm128_plan(pl, query, args, what):
         ws_bytes(-1, what)
     for name, v in zip(_GEMM128_PLAN, out):
         setattr(pl, name, v)
-    pl.slab_bytes = out[12] + (out[13] << 31)
-    pl.workspace_bytes = out[14] + (out[15] << 31)
+    pl.slab_bytes, pl.workspace_bytes = size_word(out, 12), size_word(out, 14)
     return out[11]
 
 

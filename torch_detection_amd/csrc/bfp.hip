@@ -18,7 +18,7 @@
 // smaller and no later one is larger — so the forward stores no indices.  Every output element is written by exactly one
 // lane, with plain stores: no atomics, no workspace, the same bits on every run.
 // All four kernels are memory-bound: a lane owns 8 channels (16 bytes) of one pixel, channels run across the wavefront.
-#include "common.h"
+#include "pyramid_core.h"
 
 namespace {
 
@@ -40,13 +40,6 @@ struct BfpArgs {
   int n, B, C8, Hg, Wg;
   float num_levels;           // the divisor L, as the float it is divided by
 };
-
-__device__ __forceinline__ int find_level(const int* first, int n, int b) {
-  int l = 0;
-  for (int i = 1; i < n; ++i)
-    if (b >= first[i]) l = i;
-  return __builtin_amdgcn_readfirstlane(l);
-}
 
 __device__ __forceinline__ int win_lo(const Axis& a, int d) {
   if (a.mode == POOL) return (int)(((int64_t)d * a.n_src) / a.n_dst);
@@ -242,8 +235,6 @@ __global__ __launch_bounds__(kThreads) void bfp_gather_bwd_kernel(const BfpArgs 
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 Axis axis_of(int mode, int n_src, int n_dst) {
   return Axis{n_src, n_dst, mode, mode == NEAREST ? (float)n_src / (float)n_dst : 0.f};
 }
@@ -251,31 +242,30 @@ Axis axis_of(int mode, int n_src, int n_dst) {
 // what: bit 0 x, bit 1 out, bit 2 g, bit 3 dx are needed
 int fill_args(const char* who, const tdn_bfp_level* levels, int n, int refine, int B, int C, int what, BfpArgs& p) {
   TDN_CHECK(levels, "%s: NULL levels", who);
-  TDN_CHECK(n >= 1 && n <= MAXL, "%s: num_levels=%d out of 1..%d", who, n, MAXL);
+  if (check_levels(who, n, MAXL) != 0) return -1;
   TDN_CHECK(refine >= 0 && refine < n, "%s: refine_level=%d out of 0..%d", who, refine, n - 1);
   if (tdn_check_batch(who, B) != 0) return -1;
   TDN_CHECK(C >= 8 && C <= 1024 && C % 8 == 0, "%s: C=%d is not a multiple of 8 in 8..1024", who, C);
   p = BfpArgs{};
-  int64_t wg = 0;
+  int64_t lanes[MAXL];
   for (int l = 0; l < n; ++l) {
     const tdn_bfp_level& L = levels[l];
     TDN_CHECK(L.H >= 1 && L.W >= 1 && L.H <= 32767 && L.W <= 32767, "%s: level %d: H=%d, W=%d out of 1..32767", who, l,
               L.H, L.W);
     TDN_CHECK((int64_t)B * L.H * L.W * C < ((int64_t)1 << 31), "%s: level %d holds 2^31 elements or more", who, l);
-    TDN_CHECK(!(what & 1) || (L.x && aligned16(L.x)), "%s: level %d: x must be a 16-byte aligned pointer", who, l);
-    TDN_CHECK(!(what & 2) || (L.out && aligned16(L.out)), "%s: level %d: out must be a 16-byte aligned pointer", who, l);
-    TDN_CHECK(!(what & 4) || (L.g && aligned16(L.g)), "%s: level %d: g must be a 16-byte aligned pointer", who, l);
-    TDN_CHECK(!(what & 8) || (L.dx && aligned16(L.dx)), "%s: level %d: dx must be a 16-byte aligned pointer", who, l);
+    TDN_CHECK(!(what & 1) || (L.x && aligned(L.x, 16)), "%s: level %d: x must be a 16-byte aligned pointer", who, l);
+    TDN_CHECK(!(what & 2) || (L.out && aligned(L.out, 16)), "%s: level %d: out must be a 16-byte aligned pointer", who, l);
+    TDN_CHECK(!(what & 4) || (L.g && aligned(L.g, 16)), "%s: level %d: g must be a 16-byte aligned pointer", who, l);
+    TDN_CHECK(!(what & 8) || (L.dx && aligned(L.dx, 16)), "%s: level %d: dx must be a 16-byte aligned pointer", who, l);
     p.x[l] = (const bf16_t*)L.x;
     p.g[l] = (const bf16_t*)L.g;
     p.out[l] = (bf16_t*)((what & 8) ? L.dx : L.out);
     p.H[l] = L.H;
     p.W[l] = L.W;
-    p.first_wg[l] = (int)wg;
-    wg += ((int64_t)B * L.H * L.W * (C / 8) + kThreads - 1) / kThreads;
+    lanes[l] = (int64_t)B * L.H * L.W * (C / 8);
   }
+  const int64_t wg = fill_first(lanes, n, kThreads, p.first_wg, MAXL);
   TDN_CHECK(wg < ((int64_t)1 << 31), "%s: the pyramid needs 2^31 workgroups or more", who);
-  for (int l = n; l <= MAXL; ++l) p.first_wg[l] = (int)wg;
   p.n = n; p.B = B; p.C8 = C / 8;
   p.Hg = levels[refine].H; p.Wg = levels[refine].W;
   p.num_levels = (float)n;
@@ -297,7 +287,7 @@ extern "C" int tdn_bfp_gather_fwd(const tdn_bfp_level* levels, int num_levels, i
   TDN_CHECK_DTYPE(dtype);
   BfpArgs p;
   if (fill_args(who, levels, num_levels, refine_level, B, C, 1, p) != 0) return -1;
-  TDN_CHECK(bsf && aligned16(bsf), "%s: bsf must be a 16-byte aligned pointer", who);
+  TDN_CHECK(bsf && aligned(bsf, 16), "%s: bsf must be a 16-byte aligned pointer", who);
   TDN_LAUNCH_T(bfp_gather_fwd_kernel, dtype, dim3(grid_g(p)), dim3(kThreads), stream, p, (bf16_t*)bsf);
   TDN_LAUNCH_CHECK();
   return 0;
@@ -309,7 +299,7 @@ extern "C" int tdn_bfp_scatter_fwd(const tdn_bfp_level* levels, int num_levels, 
   TDN_CHECK_DTYPE(dtype);
   BfpArgs p;
   if (fill_args(who, levels, num_levels, refine_level, B, C, 1 | 2, p) != 0) return -1;
-  TDN_CHECK(bsf && aligned16(bsf), "%s: bsf must be a 16-byte aligned pointer", who);
+  TDN_CHECK(bsf && aligned(bsf, 16), "%s: bsf must be a 16-byte aligned pointer", who);
   TDN_LAUNCH_T(bfp_scatter_fwd_kernel, dtype, dim3(p.first_wg[MAXL]), dim3(kThreads), stream, p, (const bf16_t*)bsf);
   TDN_LAUNCH_CHECK();
   return 0;
@@ -321,7 +311,7 @@ extern "C" int tdn_bfp_scatter_bwd(const tdn_bfp_level* levels, int num_levels, 
   TDN_CHECK_DTYPE(dtype);
   BfpArgs p;
   if (fill_args(who, levels, num_levels, refine_level, B, C, 4, p) != 0) return -1;
-  TDN_CHECK(bsf && aligned16(bsf) && dbsf && aligned16(dbsf), "%s: bsf and dbsf must be 16-byte aligned pointers", who);
+  TDN_CHECK(bsf && aligned(bsf, 16) && dbsf && aligned(dbsf, 16), "%s: bsf and dbsf must be 16-byte aligned pointers", who);
   TDN_LAUNCH_T(bfp_scatter_bwd_kernel, dtype, dim3(grid_g(p)), dim3(kThreads), stream, p, (const bf16_t*)bsf,
                (bf16_t*)dbsf);
   TDN_LAUNCH_CHECK();
@@ -334,7 +324,7 @@ extern "C" int tdn_bfp_gather_bwd(const tdn_bfp_level* levels, int num_levels, i
   TDN_CHECK_DTYPE(dtype);
   BfpArgs p;
   if (fill_args(who, levels, num_levels, refine_level, B, C, 1 | 4 | 8, p) != 0) return -1;
-  TDN_CHECK(dbsf && aligned16(dbsf), "%s: dbsf must be a 16-byte aligned pointer", who);
+  TDN_CHECK(dbsf && aligned(dbsf, 16), "%s: dbsf must be a 16-byte aligned pointer", who);
   TDN_LAUNCH_T(bfp_gather_bwd_kernel, dtype, dim3(p.first_wg[MAXL]), dim3(kThreads), stream, p, (const bf16_t*)dbsf);
   TDN_LAUNCH_CHECK();
   return 0;

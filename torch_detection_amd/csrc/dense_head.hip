@@ -15,12 +15,12 @@
 //
 // One launch covers all levels: the workgroups are numbered over the concatenated 128-row tiles of the levels and look
 // their (level, first row) up in a table that travels in the kernel arguments.  Row offsets are 64-bit.
-#include "common.h"
+#include "pyramid_core.h"
 
 namespace {
 
 constexpr int NT = 256;               // 4 waves
-constexpr int RT = 128;               // rows per workgroup (forward, dgrad): 2 x 16 rows per wave; rows per wgrad step
+constexpr int RT = LEVEL_TILE;        // rows per workgroup (forward, dgrad): 2 x 16 rows per wave; rows per wgrad step
 constexpr int MAXL = TDN_PRED_MAX_LEVELS;
 constexpr int CT = 64;                // channels per wgrad workgroup
 constexpr int HRB = CT * 2 + 32;      // LDS row bytes of wgrad's h tile: the pad spreads 4 rows over distinct banks
@@ -43,16 +43,6 @@ struct PredArgs {
   float* colsum;                      // [slice][Op]
 };
 
-// the level that workgroup / slice b belongs to: the last one whose first index is <= b (empty levels own no index)
-__device__ __forceinline__ int find_level(const PredArgs& p, int b) {
-  int l = 0;
-  for (int i = 1; i < p.n; ++i)
-    if (b >= p.first[i]) l = i;
-  return __builtin_amdgcn_readfirstlane(l);
-}
-
-__device__ __forceinline__ bf16x8_t zero8() { return __builtin_bit_cast(bf16x8_t, (s16x8_t){0, 0, 0, 0, 0, 0, 0, 0}); }
-
 // ---- forward ------------------------------------------------------------------------------------------------------------
 // LDS: w_fwd [16 NB][C], 16-byte piece pc of row r at position pc ^ (r & 7).  A lane (r = lane & 15, q = lane >> 4) owns
 // row r of its 16-row block and, of every 128-byte chunk of that row, the 32 bytes q: two MFMA steps per chunk.
@@ -67,7 +57,7 @@ __global__ __launch_bounds__(NT) void pred_fwd_kernel(const PredArgs p) {
     *(bf16x8_t*)(smem + row * C * 2 + ((pc ^ (row & 7)) << 4)) = *(const bf16x8_t*)(p.w + (int64_t)row * C + pc * 8);
   }
   __syncthreads();
-  const int l = find_level(p, (int)blockIdx.x);
+  const int l = find_level(p.first, p.n, (int)blockIdx.x);
   const int64_t M = p.rows[l];
   const int64_t row0 = (int64_t)((int)blockIdx.x - p.first[l]) * RT + wave * 32;
   const int r = lane & 15, q = lane >> 4;
@@ -157,7 +147,7 @@ __global__ __launch_bounds__(NT) void pred_dgrad_kernel(const PredArgs p) {
     *(bf16x8_t*)(smem + c * KP * 2 + ((pc ^ dg_swz<KS>(c)) << 4)) = *(const bf16x8_t*)(p.w + (int64_t)c * KP + pc * 8);
   }
   __syncthreads();
-  const int l = find_level(p, (int)blockIdx.x);
+  const int l = find_level(p.first, p.n, (int)blockIdx.x);
   const int64_t M = p.rows[l];
   const int64_t row0 = (int64_t)((int)blockIdx.x - p.first[l]) * RT + wave * 32;
   const int r = lane & 15, q = lane >> 4;
@@ -233,7 +223,7 @@ __global__ __launch_bounds__(NT) void pred_wgrad_kernel(const PredArgs p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int sidx = (int)blockIdx.x / p.ctiles, ct = (int)blockIdx.x - sidx * p.ctiles;
-  const int l = find_level(p, sidx);
+  const int l = find_level(p.first, p.n, sidx);
   const int C = p.C, A = p.A, O = p.O, R4 = O - A;
   const int64_t m_begin = (int64_t)(sidx - p.first[l]) * p.slice_rows;
   const int64_t m_end = min(p.rows[l], m_begin + p.slice_rows);
@@ -290,10 +280,10 @@ __global__ __launch_bounds__(NT) void pred_wgrad_kernel(const PredArgs p) {
     acc1[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   }
   const bool do_colsum = ct == 0 && wave == 0;
-  bf16x8_t ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = f32_to_elem<F16>(1.0f);
+  const bf16x8_t ones = wg_ones<F16>();
 
+  // the text of pyramid_core.h's wg_slice, kept private: through it these kernels come out 13 to 62 VGPRs smaller, in
+  // another schedule than the measured one, and <.., 3> spills two SGPRs (profiles/pyramid_core_refactor_checks.md)
   const int T = (int)((m_end - m_begin + RT - 1) / RT);
   if (T > 0) {
     load_tile(m_begin);
@@ -304,18 +294,11 @@ __global__ __launch_bounds__(NT) void pred_wgrad_kernel(const PredArgs p) {
       if (more) load_tile(m_begin + (int64_t)(t + 1) * RT);
 #pragma unroll
       for (int kk = 0; kk < RT / 32; ++kk) {
-        const s16x4_t xlo = lds_read_tr16(sH + x_off + kk * 32 * HRB);
-        const s16x4_t xhi = lds_read_tr16(sH + x_off + (kk * 32 + 4) * HRB);
-        const bf16x8_t xf = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(xlo, xhi, 0, 1, 2, 3, 4, 5, 6, 7));
+        const bf16x8_t xf = wg_frag<HRB>(sH + x_off + kk * 32 * HRB);
+        // D[row = channel][col = o] += sum_m h[m][c] * g[m][o]
 #pragma unroll
-        for (int i = 0; i < NB; ++i) {
-          const s16x4_t lo = lds_read_tr16(sG + g_off + i * 32 + kk * 32 * GRB);
-          const s16x4_t hi = lds_read_tr16(sG + g_off + i * 32 + (kk * 32 + 4) * GRB);
-          const bf16x8_t gf = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-          // D[row = channel][col = o] += sum_m h[m][c] * g[m][o]
-          acc[i] = mfma16<F16>(xf, gf, acc[i]);
-          if (do_colsum) acc1[i] = mfma16<F16>(ones, gf, acc1[i]);
-        }
+        for (int i = 0; i < NB; ++i)
+          wg_mma<F16, GRB>(xf, sG + g_off + i * 32 + kk * 32 * GRB, do_colsum, ones, acc[i], acc1[i]);
       }
       __syncthreads();                      // every wave has read step t
       if (more) store_tile();
@@ -376,16 +359,15 @@ __global__ __launch_bounds__(NT) void pred_pack_kernel(const float* __restrict__
 // ---- host -----------------------------------------------------------------------------------------------------------------
 struct PredPlan {
   int Op, Kp, NB, KS;
-  int wgs;                 // forward / dgrad workgroups
-  int slices, slice_rows, ctiles;
-  int launches;
+  LevelCut cut;            // forward / dgrad workgroups, wgrad slices
+  int ctiles;
   int first[MAXL + 1];
   int64_t slab_bytes;
 };
 
 int check_shape(const char* who, int kind, const int64_t* rows, int n, int C, int A) {
   TDN_CHECK(kind >= 0 && kind <= 2, "%s: kind %d is none of 0 (forward), 1 (dgrad), 2 (wgrad)", who, kind);
-  TDN_CHECK(n >= 1 && n <= MAXL, "%s: num_levels=%d out of 1..%d", who, n, MAXL);
+  if (check_levels(who, n, MAXL) != 0) return -1;
   TDN_CHECK(rows, "%s: NULL rows", who);
   TDN_CHECK(C >= 64 && C <= 512 && C % 64 == 0, "%s: C=%d must be a multiple of 64 in 64..512", who, C);
   TDN_CHECK(A >= 1 && A <= 12, "%s: A=%d out of 1..12", who, A);
@@ -394,8 +376,7 @@ int check_shape(const char* who, int kind, const int64_t* rows, int n, int C, in
     TDN_CHECK(rows[l] >= 0 && rows[l] < MAX_ROWS, "%s: rows[%d]=%lld out of 0..2^31-1", who, l, (long long)rows[l]);
     tiles += (rows[l] + RT - 1) / RT;
   }
-  TDN_CHECK(tiles < ((int64_t)1 << 28), "%s: %lld row tiles in all, at most 2^28 - 1", who, (long long)tiles);
-  return 0;
+  return check_tiles(who, tiles, "row");
 }
 
 void make_plan(int kind, const int64_t* rows, int n, int C, int A, PredPlan& pl) {
@@ -405,39 +386,13 @@ void make_plan(int kind, const int64_t* rows, int n, int C, int A, PredPlan& pl)
   pl.NB = pl.Op / 16;
   pl.KS = pl.Kp / 32;
   pl.ctiles = C / CT;
-  int64_t total = 0;
-  for (int l = 0; l < n; ++l) total += rows[l];
-  // the slice length depends on the shapes alone: about SLICE_TARGET slices, whole 128-row steps
-  int64_t sr = (total + SLICE_TARGET - 1) / SLICE_TARGET;
-  sr = (sr + RT - 1) / RT * RT;
-  if (sr < RT) sr = RT;
-  pl.slice_rows = (int)sr;
-  int wg = 0, sl = 0;
-  for (int l = 0; l < n; ++l) {
-    pl.first[l] = kind == 2 ? sl : wg;
-    wg += (int)((rows[l] + RT - 1) / RT);
-    sl += (int)((rows[l] + sr - 1) / sr);
-  }
-  for (int l = n; l <= MAXL; ++l) pl.first[l] = kind == 2 ? sl : wg;
-  pl.wgs = wg;
-  pl.slices = sl;
-  pl.launches = kind == 2 ? (sl > 0 ? 2 : 1) : (wg > 0 ? 1 : 0);
-  pl.slab_bytes = kind == 2 ? (int64_t)sl * pl.Op * C * 4 : 0;
+  pl.cut = cut_levels(kind == 2, rows, n, SLICE_TARGET, pl.first, MAXL);
+  pl.slab_bytes = kind == 2 ? (int64_t)pl.cut.slices * pl.Op * C * 4 : 0;
 }
 
-struct PredWs { float* slab; float* colsum; int64_t bytes; };
-PredWs ws_layout(int kind, const PredPlan& pl, void* base) {
-  tdn_carver c{(char*)base, 0};
-  PredWs w{nullptr, nullptr, 0};
-  if (kind == 2 && pl.slices > 0) {
-    w.slab = c.take<float>(pl.slab_bytes / 4);
-    w.colsum = c.take<float>((int64_t)pl.slices * pl.Op);
-  }
-  w.bytes = c.off;
-  return w;
+SlabWs ws_layout(int kind, const PredPlan& pl, void* base) {
+  return slab_layout(kind == 2 ? pl.cut.slices : 0, pl.slab_bytes, pl.Op, base);
 }
-
-bool aligned(const void* p, int a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 int fill_args(const char* who, int kind, const tdn_pred_level* levels, int n, int C, int A, const PredPlan& pl, PredArgs& p) {
   p = PredArgs{};
@@ -453,13 +408,13 @@ int fill_args(const char* who, int kind, const tdn_pred_level* levels, int n, in
   }
   for (int l = 0; l <= MAXL; ++l) p.first[l] = pl.first[l];
   p.n = n; p.C = C; p.A = A; p.O = 5 * A;
-  p.slice_rows = pl.slice_rows; p.ctiles = pl.ctiles;
+  p.slice_rows = pl.cut.slice_rows; p.ctiles = pl.ctiles;
   return 0;
 }
 
 int rows_of(const char* who, const tdn_pred_level* levels, int n, int64_t* rows) {
   TDN_CHECK(levels, "%s: NULL levels", who);
-  TDN_CHECK(n >= 1 && n <= MAXL, "%s: num_levels=%d out of 1..%d", who, n, MAXL);
+  if (check_levels(who, n, MAXL) != 0) return -1;
   for (int l = 0; l < n; ++l) rows[l] = levels[l].rows;
   return 0;
 }
@@ -506,15 +461,14 @@ extern "C" int tdn_pred_plan(int kind, const int64_t* rows, int num_levels, int 
   make_plan(kind, rows, num_levels, C, A, pl);
   const int64_t ws = ws_layout(kind, pl, nullptr).bytes;
   out[0] = RT;
-  out[1] = kind == 2 ? pl.slices * pl.ctiles : pl.wgs;
-  out[2] = kind == 2 ? pl.slices : 0;
-  out[3] = kind == 2 ? pl.slice_rows : 0;
-  out[4] = pl.launches;
+  out[1] = kind == 2 ? pl.cut.slices * pl.ctiles : pl.cut.tiles;
+  out[2] = kind == 2 ? pl.cut.slices : 0;
+  out[3] = kind == 2 ? pl.cut.slice_rows : 0;
+  out[4] = pl.cut.launches;
   out[5] = pl.Op; out[6] = pl.Kp; out[7] = kind == 2 ? pl.ctiles : 1;
   out[8] = kind == 0 ? pl.Op * C * 2 : (kind == 1 ? C * pl.Kp * 2 : RT * HRB + RT * (pl.Op * 2 + 32));
   out[9] = out[10] = out[11] = 0;
-  out[12] = (int32_t)(pl.slab_bytes & 0x7fffffff); out[13] = (int32_t)(pl.slab_bytes >> 31);
-  out[14] = (int32_t)(ws & 0x7fffffff); out[15] = (int32_t)(ws >> 31);
+  put_sizes(out, pl.slab_bytes, ws);
   return 0;
 }
 
@@ -526,7 +480,7 @@ extern "C" int tdn_pred_fwd(const tdn_pred_level* levels, int num_levels, const 
   if (rows_of(who, levels, num_levels, rows) != 0 || check_shape(who, 0, rows, num_levels, C, A) != 0) return -1;
   PredPlan pl;
   make_plan(0, rows, num_levels, C, A, pl);
-  if (pl.wgs == 0) return 0;
+  if (pl.cut.tiles == 0) return 0;
   TDN_CHECK(w_fwd && bias_cls && bias_reg, "%s: NULL pointer", who);
   TDN_CHECK(aligned(w_fwd, 16) && aligned(bias_cls, 4) && aligned(bias_reg, 4), "%s: w_fwd must be 16-byte aligned", who);
   PredArgs p;
@@ -535,7 +489,7 @@ extern "C" int tdn_pred_fwd(const tdn_pred_level* levels, int num_levels, const 
   const int lds = pl.Op * C * 2;
 #define PRED_FWD(F16, NBV)                                                                                   \
   if (tdn_allow_lds<pred_fwd_kernel<F16, NBV>>(65536, "pred_fwd_kernel") < 0) return -1;                     \
-  TDN_LAUNCH((pred_fwd_kernel<F16, NBV>), dim3((unsigned)pl.wgs), dim3(NT), lds, stream, p)
+  TDN_LAUNCH((pred_fwd_kernel<F16, NBV>), dim3((unsigned)pl.cut.tiles), dim3(NT), lds, stream, p)
   if (dtype == TDN_F16) { PRED_BY_NB(true, pl.NB, PRED_FWD) } else { PRED_BY_NB(false, pl.NB, PRED_FWD) }
 #undef PRED_FWD
   TDN_LAUNCH_CHECK();
@@ -550,7 +504,7 @@ extern "C" int tdn_pred_dgrad(const tdn_pred_level* levels, int num_levels, cons
   if (rows_of(who, levels, num_levels, rows) != 0 || check_shape(who, 1, rows, num_levels, C, A) != 0) return -1;
   PredPlan pl;
   make_plan(1, rows, num_levels, C, A, pl);
-  if (pl.wgs == 0) return 0;
+  if (pl.cut.tiles == 0) return 0;
   TDN_CHECK(w_dgrad && aligned(w_dgrad, 16), "%s: w_dgrad must be a 16-byte aligned pointer", who);
   PredArgs p;
   if (fill_args(who, 1, levels, num_levels, C, A, pl, p) != 0) return -1;
@@ -558,7 +512,7 @@ extern "C" int tdn_pred_dgrad(const tdn_pred_level* levels, int num_levels, cons
   const int lds = C * pl.Kp * 2;
 #define PRED_DGRAD(F16, KSV)                                                                                 \
   if (tdn_allow_lds<pred_dgrad_kernel<F16, KSV>>(65536, "pred_dgrad_kernel") < 0) return -1;                 \
-  TDN_LAUNCH((pred_dgrad_kernel<F16, KSV>), dim3((unsigned)pl.wgs), dim3(NT), lds, stream, p)
+  TDN_LAUNCH((pred_dgrad_kernel<F16, KSV>), dim3((unsigned)pl.cut.tiles), dim3(NT), lds, stream, p)
   if (dtype == TDN_F16) {
     if (pl.KS == 1) { PRED_DGRAD(true, 1); } else { PRED_DGRAD(true, 2); }
   } else {
@@ -579,20 +533,20 @@ extern "C" int tdn_pred_wgrad(const tdn_pred_level* levels, int num_levels, floa
   TDN_CHECK(dw_cls && dbias_cls && dw_reg && dbias_reg, "%s: NULL pointer", who);
   PredPlan pl;
   make_plan(2, rows, num_levels, C, A, pl);
-  const PredWs w = ws_layout(2, pl, workspace);
+  const SlabWs w = ws_layout(2, pl, workspace);
   if (w.bytes && tdn_check_ws(who, workspace, workspace_bytes, w.bytes) != 0) return -1;
   PredArgs p;
   if (fill_args(who, 2, levels, num_levels, C, A, pl, p) != 0) return -1;
   p.slab = w.slab; p.colsum = w.colsum;
-  if (pl.slices > 0) {
+  if (pl.cut.slices > 0) {
     const int lds = RT * HRB + RT * (pl.Op * 2 + 32);
-    const dim3 grid((unsigned)(pl.slices * pl.ctiles));
+    const dim3 grid((unsigned)(pl.cut.slices * pl.ctiles));
 #define PRED_WGRAD(F16, NBV) TDN_LAUNCH((pred_wgrad_kernel<F16, NBV>), grid, dim3(NT), lds, stream, p)
     if (dtype == TDN_F16) { PRED_BY_NB(true, pl.NB, PRED_WGRAD) } else { PRED_BY_NB(false, pl.NB, PRED_WGRAD) }
 #undef PRED_WGRAD
     TDN_LAUNCH_CHECK();
   }
-  const int slices = pl.slices, Op = pl.Op;
+  const int slices = pl.cut.slices, Op = pl.Op;
   TDN_LAUNCH(pred_wgrad_finalize_kernel, dim3(tdn_grid_1d((int64_t)5 * A * C, NT, 4096)), dim3(NT), 0, stream, p, slices, Op,
              dw_cls, dbias_cls, dw_reg, dbias_reg);
   TDN_LAUNCH_CHECK();

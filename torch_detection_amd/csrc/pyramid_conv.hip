@@ -18,13 +18,14 @@
 //
 // The workgroups are numbered over the concatenated 128-pixel tiles of the levels and look their (level, first pixel)
 // up in a table that travels in the kernel arguments, as in dense_head.hip.  Pixel offsets are 64-bit.
-#include "common.h"
+#include "pyramid_core.h"
 
 namespace {
 
 constexpr int NT = 256;               // 4 waves
 constexpr int PB = 2;                 // 16-pixel blocks per wave (4 measured 15-20 % slower at the workload pyramid)
-constexpr int PT = 64 * PB;           // pixels per workgroup (forward, dgrad); pixels per wgrad step
+constexpr int PT = LEVEL_TILE;        // pixels per workgroup (forward, dgrad); pixels per wgrad step
+static_assert(PT == 64 * PB, "4 waves x PB 16-pixel blocks");
 constexpr int CT = 64;                // output columns per workgroup; channels per wgrad tile
 constexpr int KC = 64;                // reduction elements per step
 constexpr int MAXL = TDN_PYR_MAX_LEVELS;
@@ -54,15 +55,6 @@ struct PyrArgs {
   float* colsum;                      // [slice][Cp]
 };
 
-__device__ __forceinline__ int find_level(const PyrArgs& p, int b) {
-  int l = 0;
-  for (int i = 1; i < p.n; ++i)
-    if (b >= p.first[i]) l = i;
-  return __builtin_amdgcn_readfirstlane(l);
-}
-
-__device__ __forceinline__ bf16x8_t zero8() { return __builtin_bit_cast(bf16x8_t, (s16x8_t){0, 0, 0, 0, 0, 0, 0, 0}); }
-
 // 8 elements k0 .. k0 + 7 of a Kin-element row; what lies at or beyond Kin reads as zero and is not touched
 __device__ __forceinline__ bf16x8_t load_run(const bf16_t* row, int k0, int Kin, bool ragged) {
   if (!ragged) return k0 < Kin ? *(const bf16x8_t*)(row + k0) : zero8();
@@ -86,7 +78,7 @@ __global__ __launch_bounds__(NT) void pyr_conv_kernel(const PyrArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[2 * CT * KC * 2];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l = find_level(p, (int)blockIdx.x);
+  const int l = find_level(p.first, p.n, (int)blockIdx.x);
   const int n0 = (int)blockIdx.y * CT;
   const int64_t M = p.rows[l];
   const int H = p.H[l], W = p.W[l];
@@ -283,7 +275,7 @@ __global__ __launch_bounds__(NT) void pyr_wgrad_kernel(const PyrArgs p) {
   const int ot = unit / (9 * p.ctiles), rem = unit - ot * 9 * p.ctiles;
   const int tap = rem / p.ctiles, ct = rem - tap * p.ctiles;
   const int dh = tap / 3 - 1, dw = tap - (tap / 3) * 3 - 1;
-  const int l = find_level(p, sidx);
+  const int l = find_level(p.first, p.n, sidx);
   const int Cin = p.Cin, Cout = p.Cout, H = p.H[l], W = p.W[l];
   const bool ragged = p.ragged;
   const int64_t m_begin = (int64_t)(sidx - p.first[l]) * p.slice_rows;
@@ -328,38 +320,14 @@ __global__ __launch_bounds__(NT) void pyr_wgrad_kernel(const PyrArgs p) {
     acc1[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   }
   const bool do_colsum = ct == 0 && tap == 0 && wave == 0;
-  bf16x8_t ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = f32_to_elem<F16>(1.0f);
+  const bf16x8_t ones = wg_ones<F16>();
 
   const int T = (int)((m_end - m_begin + PT - 1) / PT);
-  if (T > 0) {
-    load_tile(m_begin);
-    store_tile();
-    __syncthreads();
-    for (int t = 0; t < T; ++t) {
-      const bool more = t + 1 < T;
-      if (more) load_tile(m_begin + (int64_t)(t + 1) * PT);
-#pragma unroll
-      for (int kk = 0; kk < PT / 32; ++kk) {
-        const s16x4_t xlo = lds_read_tr16(sH + x_off + kk * 32 * TRB);
-        const s16x4_t xhi = lds_read_tr16(sH + x_off + (kk * 32 + 4) * TRB);
-        const bf16x8_t xf = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(xlo, xhi, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const s16x4_t lo = lds_read_tr16(sG + g_off + i * 32 + kk * 32 * TRB);
-          const s16x4_t hi = lds_read_tr16(sG + g_off + i * 32 + (kk * 32 + 4) * TRB);
-          const bf16x8_t gf = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-          // D[row = channel][col = o] += sum_m x[m + tap][c] * g[m][o]
-          acc[i] = mfma16<F16>(xf, gf, acc[i]);
-          if (do_colsum) acc1[i] = mfma16<F16>(ones, gf, acc1[i]);
-        }
-      }
-      __syncthreads();                      // every wave has read step t
-      if (more) store_tile();
-      __syncthreads();
-    }
-  }
+  // D[row = channel][col = o] += sum_m x[m + tap][c] * g[m][o]
+  wg_slice<4, TRB, TRB>(sH, sG, m_begin, T, load_tile, store_tile, x_off, g_off,
+                        [&](int i, const bf16x8_t& xf, const char* gp) {
+                          wg_mma<F16, TRB>(xf, gp, do_colsum, ones, acc[i], acc1[i]);
+                        });
   // a lane holds channels c .. c + 3 of output row o
   const int fr = lane & 15;
 #pragma unroll
@@ -417,9 +385,10 @@ __global__ __launch_bounds__(NT) void pyr_pack_kernel(const float* __restrict__ 
 // ---- host -----------------------------------------------------------------------------------------------------------------
 struct PyrPlan {
   int Cp;
-  int tiles, coltiles;     // forward / dgrad grid
-  int slices, slice_rows, units, ctiles;
-  int launches, lds;
+  LevelCut cut;            // forward / dgrad pixel tiles, wgrad slices
+  int coltiles;            // forward / dgrad grid: cut.tiles x coltiles
+  int units, ctiles;
+  int lds;
   int first[MAXL + 1];
   int64_t rows[MAXL];
   int64_t slab_bytes;
@@ -427,7 +396,7 @@ struct PyrPlan {
 
 int check_shape(const char* who, int kind, int B, const int32_t* hw, int n, int Cin, int Cout) {
   TDN_CHECK(kind >= 0 && kind <= 2, "%s: kind %d is none of 0 (forward), 1 (dgrad), 2 (wgrad)", who, kind);
-  TDN_CHECK(n >= 1 && n <= MAXL, "%s: num_levels=%d out of 1..%d", who, n, MAXL);
+  if (check_levels(who, n, MAXL) != 0) return -1;
   TDN_CHECK(hw, "%s: NULL level sizes", who);
   TDN_CHECK(B >= 0, "%s: B=%d is negative", who, B);
   TDN_CHECK(Cin >= 64 && Cin <= 512 && Cin % 64 == 0, "%s: Cin=%d must be a multiple of 64 in 64..512", who, Cin);
@@ -440,8 +409,7 @@ int check_shape(const char* who, int kind, int B, const int32_t* hw, int n, int 
     TDN_CHECK(H * W < MAX_ROWS && (int64_t)B * H * W < MAX_ROWS, "%s: level %d: B*H*W out of 0..2^31-1", who, l);
     tiles += ((int64_t)B * H * W + PT - 1) / PT;
   }
-  TDN_CHECK(tiles < ((int64_t)1 << 28), "%s: %lld pixel tiles in all, at most 2^28 - 1", who, (long long)tiles);
-  return 0;
+  return check_tiles(who, tiles, "pixel");
 }
 
 void make_plan(int kind, int B, const int32_t* hw, int n, int Cin, int Cout, PyrPlan& pl) {
@@ -449,50 +417,22 @@ void make_plan(int kind, int B, const int32_t* hw, int n, int Cin, int Cout, Pyr
   pl.ctiles = Cin / CT;
   pl.coltiles = kind == 1 ? pl.ctiles : pl.Cp / CT;
   pl.units = (pl.Cp / CT) * 9 * pl.ctiles;
-  int64_t total = 0;
-  for (int l = 0; l < n; ++l) {
-    pl.rows[l] = (int64_t)B * hw[2 * l] * hw[2 * l + 1];
-    total += pl.rows[l];
-  }
-  // the slice length depends on the shapes alone: as many slices as bring the grid to about WG_TARGET workgroups (at
-  // most MAX_SLICES), whole 128-pixel steps
+  for (int l = 0; l < n; ++l) pl.rows[l] = (int64_t)B * hw[2 * l] * hw[2 * l + 1];
+  // as many slices as bring the grid to about WG_TARGET workgroups, at most MAX_SLICES
   int target = (WG_TARGET + pl.units - 1) / pl.units;
   if (target > MAX_SLICES) target = MAX_SLICES;
-  int64_t sr = (total + target - 1) / target;
-  sr = (sr + PT - 1) / PT * PT;
-  if (sr < PT) sr = PT;
-  pl.slice_rows = (int)sr;
-  int wg = 0, sl = 0;
-  for (int l = 0; l < n; ++l) {
-    pl.first[l] = kind == 2 ? sl : wg;
-    wg += (int)((pl.rows[l] + PT - 1) / PT);
-    sl += (int)((pl.rows[l] + sr - 1) / sr);
-  }
-  for (int l = n; l <= MAXL; ++l) pl.first[l] = kind == 2 ? sl : wg;
-  pl.tiles = wg;
-  pl.slices = sl;
-  pl.launches = kind == 2 ? (sl > 0 ? 2 : 1) : (wg > 0 ? 1 : 0);
+  pl.cut = cut_levels(kind == 2, pl.rows, n, target, pl.first, MAXL);
   pl.lds = kind == 2 ? 2 * PT * TRB : 2 * CT * KC * 2;
-  pl.slab_bytes = kind == 2 ? (int64_t)sl * pl.Cp * 9 * Cin * 4 : 0;
+  pl.slab_bytes = kind == 2 ? (int64_t)pl.cut.slices * pl.Cp * 9 * Cin * 4 : 0;
 }
 
-struct PyrWs { float* slab; float* colsum; int64_t bytes; };
-PyrWs ws_layout(int kind, const PyrPlan& pl, void* base) {
-  tdn_carver c{(char*)base, 0};
-  PyrWs w{nullptr, nullptr, 0};
-  if (kind == 2 && pl.slices > 0) {
-    w.slab = c.take<float>(pl.slab_bytes / 4);
-    w.colsum = c.take<float>((int64_t)pl.slices * pl.Cp);
-  }
-  w.bytes = c.off;
-  return w;
+SlabWs ws_layout(int kind, const PyrPlan& pl, void* base) {
+  return slab_layout(kind == 2 ? pl.cut.slices : 0, pl.slab_bytes, pl.Cp, base);
 }
-
-bool aligned(const void* p, int a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 int sizes_of(const char* who, const tdn_pyr_level* levels, int n, int32_t* hw) {
   TDN_CHECK(levels, "%s: NULL levels", who);
-  TDN_CHECK(n >= 1 && n <= MAXL, "%s: num_levels=%d out of 1..%d", who, n, MAXL);
+  if (check_levels(who, n, MAXL) != 0) return -1;
   for (int l = 0; l < n; ++l) {
     hw[2 * l] = levels[l].H;
     hw[2 * l + 1] = levels[l].W;
@@ -537,7 +477,7 @@ int fill_args(const char* who, int kind, const tdn_pyr_level* levels, int n, int
   p.N = kind == 1 ? Cin : Cout;
   p.ragged = ragged ? 1 : 0;
   p.Cin = Cin; p.Cout = Cout; p.Cp = pl.Cp;
-  p.slice_rows = pl.slice_rows; p.units = pl.units; p.ctiles = pl.ctiles;
+  p.slice_rows = pl.cut.slice_rows; p.units = pl.units; p.ctiles = pl.ctiles;
   return 0;
 }
 
@@ -574,25 +514,24 @@ extern "C" int tdn_pyr_plan(int kind, int B, const int32_t* hw, int num_levels, 
   make_plan(kind, B, hw, num_levels, Cin, Cout, pl);
   const int64_t ws = ws_layout(kind, pl, nullptr).bytes;
   out[0] = PT;
-  out[1] = kind == 2 ? pl.slices * pl.units : pl.tiles * pl.coltiles;
-  out[2] = kind == 2 ? pl.slices : 0;
-  out[3] = kind == 2 ? pl.slice_rows : 0;
-  out[4] = pl.launches;
+  out[1] = kind == 2 ? pl.cut.slices * pl.units : pl.cut.tiles * pl.coltiles;
+  out[2] = kind == 2 ? pl.cut.slices : 0;
+  out[3] = kind == 2 ? pl.cut.slice_rows : 0;
+  out[4] = pl.cut.launches;
   out[5] = CT;
   out[6] = pl.Cp;
   out[7] = kind == 1 ? pl.Cp : Cin;
   out[8] = pl.lds;
   out[9] = kind == 2 ? pl.units : pl.coltiles;
-  out[10] = pl.tiles;
+  out[10] = pl.cut.tiles;
   out[11] = 0;
-  out[12] = (int32_t)(pl.slab_bytes & 0x7fffffff); out[13] = (int32_t)(pl.slab_bytes >> 31);
-  out[14] = (int32_t)(ws & 0x7fffffff); out[15] = (int32_t)(ws >> 31);
+  put_sizes(out, pl.slab_bytes, ws);
   return 0;
 }
 
 #define PYR_CONV(DG)                                                                                     \
   do {                                                                                                   \
-    const dim3 grid((unsigned)pl.tiles, (unsigned)pl.coltiles);                                          \
+    const dim3 grid((unsigned)pl.cut.tiles, (unsigned)pl.coltiles);                                          \
     if (DG && p.ragged) {                                                                                \
       if (dtype == TDN_F16) TDN_LAUNCH((pyr_conv_kernel<true, DG, DG>), grid, dim3(NT), 0, stream, p);   \
       else TDN_LAUNCH((pyr_conv_kernel<false, DG, DG>), grid, dim3(NT), 0, stream, p);                   \
@@ -610,7 +549,7 @@ extern "C" int tdn_pyr_conv_fwd(const tdn_pyr_level* levels, int num_levels, int
   if (sizes_of(who, levels, num_levels, hw) != 0 || check_shape(who, 0, B, hw, num_levels, Cin, Cout) != 0) return -1;
   PyrPlan pl;
   make_plan(0, B, hw, num_levels, Cin, Cout, pl);
-  if (pl.tiles == 0) return 0;
+  if (pl.cut.tiles == 0) return 0;
   TDN_CHECK(w_fwd && aligned(w_fwd, 16) && aligned(bias, 4), "%s: w_fwd must be a 16-byte aligned pointer", who);
   PyrArgs p;
   if (fill_args(who, 0, levels, num_levels, Cin, Cout, pl, p) != 0) return -1;
@@ -628,7 +567,7 @@ extern "C" int tdn_pyr_conv_dgrad(const tdn_pyr_level* levels, int num_levels, i
   if (sizes_of(who, levels, num_levels, hw) != 0 || check_shape(who, 1, B, hw, num_levels, Cin, Cout) != 0) return -1;
   PyrPlan pl;
   make_plan(1, B, hw, num_levels, Cin, Cout, pl);
-  if (pl.tiles == 0) return 0;
+  if (pl.cut.tiles == 0) return 0;
   TDN_CHECK(w_dgrad && aligned(w_dgrad, 16), "%s: w_dgrad must be a 16-byte aligned pointer", who);
   PyrArgs p;
   if (fill_args(who, 1, levels, num_levels, Cin, Cout, pl, p) != 0) return -1;
@@ -648,18 +587,18 @@ extern "C" int tdn_pyr_conv_wgrad(const tdn_pyr_level* levels, int num_levels, i
   TDN_CHECK(dw && dbias, "%s: NULL pointer", who);
   PyrPlan pl;
   make_plan(2, B, hw, num_levels, Cin, Cout, pl);
-  const PyrWs w = ws_layout(2, pl, workspace);
+  const SlabWs w = ws_layout(2, pl, workspace);
   if (w.bytes && tdn_check_ws(who, workspace, workspace_bytes, w.bytes) != 0) return -1;
   PyrArgs p;
   if (fill_args(who, 2, levels, num_levels, Cin, Cout, pl, p) != 0) return -1;
   p.slab = w.slab; p.colsum = w.colsum;
-  if (pl.slices > 0) {
-    const dim3 grid((unsigned)(pl.slices * pl.units));
+  if (pl.cut.slices > 0) {
+    const dim3 grid((unsigned)(pl.cut.slices * pl.units));
     if (dtype == TDN_F16) TDN_LAUNCH((pyr_wgrad_kernel<true>), grid, dim3(NT), 0, stream, p);
     else TDN_LAUNCH((pyr_wgrad_kernel<false>), grid, dim3(NT), 0, stream, p);
     TDN_LAUNCH_CHECK();
   }
-  const int slices = pl.slices;
+  const int slices = pl.cut.slices;
   TDN_LAUNCH(pyr_wgrad_finalize_kernel, dim3(tdn_grid_1d((int64_t)Cout * 9 * Cin, NT, 4096)), dim3(NT), 0, stream, p, slices,
              dw, s_o, s_c, s_h, s_w, dbias);
   TDN_LAUNCH_CHECK();

@@ -17,6 +17,7 @@
 // level gives the same bits launched alone, inside a pyramid, or through gn.hip.  Partials are plain stores; every
 // reduction runs in a fixed order; no atomics, no counters, no memset.  All passes are HBM-bound, 16 bytes per lane.
 #include "norm_core.h"
+#include "pyramid_core.h"
 
 namespace {
 
@@ -35,14 +36,6 @@ struct PgnArgs {
   int first_tile[MAXL + 1];           // first workgroup of a level in the apply launch
   int n, B, C, C8, cpg, ppp, relu;
 };
-
-// the level of workgroup b: a scan of at most MAXL entries; an empty level shares its `first` with the next and loses
-__device__ __forceinline__ int find_level(const int* first, int n, int b) {
-  int l = 0;
-  for (int i = 1; i < n; ++i)
-    if (b >= first[i]) l = i;
-  return __builtin_amdgcn_readfirstlane(l);
-}
 
 // [1] / [1']: partial per-channel sums over one pixel chunk of one (level, image); part layout [workgroup][2][C]
 //   MODE 0: (sum d, sum d^2), d = z - K, K = z at pixel 0 of the (level, image)
@@ -328,7 +321,7 @@ struct PgnPlan {
 
 int check_shape(const char* who, int kind, int B, const int32_t* hw, int n, int C, int G) {
   TDN_CHECK(kind == 0 || kind == 1, "%s: kind %d is neither 0 (forward) nor 1 (backward)", who, kind);
-  TDN_CHECK(n >= 1 && n <= MAXL, "%s: num_levels=%d out of 1..%d", who, n, MAXL);
+  if (check_levels(who, n, MAXL) != 0) return -1;
   TDN_CHECK(hw, "%s: NULL level sizes", who);
   TDN_CHECK(B >= 0 && B <= 65535 / MAXL, "%s: B=%d out of 0..%d", who, B, 65535 / MAXL);
   TDN_CHECK(C == 64 || C == 128 || C == 256 || C == 512, "%s: C=%d is none of 64, 128, 256, 512", who, C);
@@ -352,11 +345,11 @@ void make_plan(int B, const int32_t* hw, int n, int C, int G, PgnPlan& pl) {
   pl.cpg = C / G;
   pl.ppp = pixel_lanes(pl.C8);
   pl.CB = pl.cpg > 32 ? pl.cpg : 32;
-  int wg = 0, tl = 0;
+  int wg = 0;
+  int64_t lanes[MAXL] = {};
   pl.live = 0;
   for (int l = 0; l < MAXL; ++l) {
     pl.first_wg[l] = wg;
-    pl.first_tile[l] = tl;
     pl.HW[l] = pl.chunks[l] = pl.chunk_px[l] = 0;
     if (l >= n) continue;
     const int HW = B > 0 ? hw[2 * l] * hw[2 * l + 1] : 0;
@@ -366,13 +359,12 @@ void make_plan(int B, const int32_t* hw, int n, int C, int G, PgnPlan& pl) {
     pl.chunk_px[l] = cut.chunk_px;
     pl.chunks[l] = cut.chunks;
     wg += B * pl.chunks[l];
-    tl += (int)(((int64_t)B * HW * pl.C8 + TILE - 1) / TILE);
+    lanes[l] = (int64_t)B * HW * pl.C8;
     ++pl.live;
   }
   pl.first_wg[MAXL] = wg;
-  pl.first_tile[MAXL] = tl;
   pl.wgs = wg;
-  pl.tiles = tl;
+  pl.tiles = (int)fill_first(lanes, n, TILE, pl.first_tile, MAXL);
 }
 
 // workspace: part [workgroup][2][C] | coef [level][B][3][C] | backward only: sums [level][B][2][C]
@@ -389,22 +381,20 @@ PgnWs ws_layout(int kind, const PgnPlan& pl, int n, int B, int C, void* base) {
   return w;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 int fill_args(const char* who, int kind, const tdn_pyr_gn_level* levels, int n, int B, int C, int relu,
               const PgnPlan& pl, PgnArgs& p) {
   p = PgnArgs{};
   for (int l = 0; l < n; ++l) {
     if (pl.HW[l] == 0) continue;                         // skipped: its pointers are not looked at
     const tdn_pyr_gn_level& L = levels[l];
-    TDN_CHECK(L.z && aligned16(L.z), "%s: level %d: z must be a 16-byte aligned pointer", who, l);
+    TDN_CHECK(L.z && aligned(L.z, 16), "%s: level %d: z must be a 16-byte aligned pointer", who, l);
     if (kind == 0) {
-      TDN_CHECK(L.y && aligned16(L.y), "%s: level %d: y must be a 16-byte aligned pointer", who, l);
+      TDN_CHECK(L.y && aligned(L.y, 16), "%s: level %d: y must be a 16-byte aligned pointer", who, l);
       p.out[l] = (bf16_t*)L.y;
     } else {
-      TDN_CHECK(L.g && aligned16(L.g) && L.dz && aligned16(L.dz), "%s: level %d: g and dz must be 16-byte aligned pointers",
+      TDN_CHECK(L.g && aligned(L.g, 16) && L.dz && aligned(L.dz, 16), "%s: level %d: g and dz must be 16-byte aligned pointers",
                 who, l);
-      TDN_CHECK(!relu || (L.y && aligned16(L.y)), "%s: level %d: y (the ReLU mask source) must be a 16-byte aligned pointer",
+      TDN_CHECK(!relu || (L.y && aligned(L.y, 16)), "%s: level %d: y (the ReLU mask source) must be a 16-byte aligned pointer",
                 who, l);
       p.g[l] = (const bf16_t*)L.g;
       p.y[l] = (const bf16_t*)L.y;
@@ -420,7 +410,7 @@ int fill_args(const char* who, int kind, const tdn_pyr_gn_level* levels, int n, 
 
 int sizes_of(const char* who, const tdn_pyr_gn_level* levels, int n, int32_t* hw) {
   TDN_CHECK(levels, "%s: NULL levels", who);
-  TDN_CHECK(n >= 1 && n <= MAXL, "%s: num_levels=%d out of 1..%d", who, n, MAXL);
+  if (check_levels(who, n, MAXL) != 0) return -1;
   for (int l = 0; l < n; ++l) { hw[2 * l] = levels[l].H; hw[2 * l + 1] = levels[l].W; }
   return 0;
 }
@@ -462,7 +452,7 @@ extern "C" int tdn_pyr_gn_plan(int kind, int B, const int32_t* hw, int num_level
   out[19] = pl.wgs > 0 ? 3 : (kind == 1 ? 1 : 0);
   out[20] = TILE;
   out[21] = pl.CB;
-  out[22] = (int32_t)(ws & 0x7fffffff); out[23] = (int32_t)(ws >> 31);
+  put_size(out + 22, ws);
   for (int i = 24; i < 32; ++i) out[i] = 0;
   return 0;
 }
@@ -504,7 +494,7 @@ extern "C" int tdn_pyr_gn_bwd(const tdn_pyr_gn_level* levels, int num_levels, in
   TDN_CHECK(gamma && dgamma && dbeta, "%s: NULL pointer", who);
   PgnPlan pl;
   make_plan(B, hw, num_levels, C, G, pl);
-  TDN_CHECK(pl.wgs == 0 || (stats && aligned16(stats)), "%s: stats must be a 16-byte aligned pointer", who);
+  TDN_CHECK(pl.wgs == 0 || (stats && aligned(stats, 16)), "%s: stats must be a 16-byte aligned pointer", who);
   const PgnWs ws = ws_layout(1, pl, num_levels, B, C, workspace);
   if (pl.wgs > 0 && tdn_check_ws(who, workspace, workspace_bytes, ws.bytes) != 0) return -1;
   PgnArgs p;

@@ -122,8 +122,7 @@ def pred_plan(kind, rows, C, A):
     pl = PredPlan()
     (pl.rows_per_workgroup, pl.workgroups, pl.slices, pl.rows_per_slice, pl.launches, pl.Op, pl.Kp, pl.channel_tiles,
      pl.lds_bytes) = list(out)[:9]
-    pl.slab_bytes = out[12] + (out[13] << 31)
-    pl.workspace_bytes = out[14] + (out[15] << 31)
+    pl.slab_bytes, pl.workspace_bytes = _lib.size_word(out, 12), _lib.size_word(out, 14)
     return pl
 
 

@@ -93,14 +93,18 @@ class PyramidPlan(object):
                  "Cp", "Kp", "lds_bytes", "col_tiles", "pixel_tiles", "slab_bytes", "workspace_bytes")
 
 
-def _geometry(B, sizes):
-    B = integer(B, "B", 0)
+def _geometry(B, sizes, min_side=1, max_B=None):
+    """(B, [(H, W)]) checked: 1..MAX_LEVELS levels, sides >= ``min_side`` (0: a level may be empty), B in 0..``max_B``.
+    Where B is capped (the GroupNorm entry points, which keep H*W in an int of its own) H*W is refused before B*H*W."""
+    B = integer(B, "B", 0, max_B)
     if not isinstance(sizes, (list, tuple)) or not 1 <= len(sizes) <= MAX_LEVELS:
         raise ValueError("sizes must be a list of 1..%d (H, W) pairs, got %s" % (
             MAX_LEVELS, len(sizes) if isinstance(sizes, (list, tuple)) else type(sizes).__name__))
     out = []
     for l, hw in enumerate(sizes):
-        H, W = integer(hw[0], "sizes[%d][0]" % l, 1), integer(hw[1], "sizes[%d][1]" % l, 1)
+        H, W = integer(hw[0], "sizes[%d][0]" % l, min_side), integer(hw[1], "sizes[%d][1]" % l, min_side)
+        if max_B is not None:
+            integer(H * W, "sizes[%d]: H*W" % l, 0, MAX_ROWS)
         integer(B * H * W, "sizes[%d]: B*H*W" % l, 0, MAX_ROWS)
         out.append((H, W))
     return B, out
@@ -120,8 +124,7 @@ def pyramid_conv_plan(kind, B, sizes, Cin, Cout):
     pl = PyramidPlan()
     (pl.pixels_per_workgroup, pl.workgroups, pl.slices, pl.pixels_per_slice, pl.launches, pl.cols_per_workgroup, pl.Cp,
      pl.Kp, pl.lds_bytes, pl.col_tiles, pl.pixel_tiles) = list(out)[:11]
-    pl.slab_bytes = out[12] + (out[13] << 31)
-    pl.workspace_bytes = out[14] + (out[15] << 31)
+    pl.slab_bytes, pl.workspace_bytes = _lib.size_word(out, 12), _lib.size_word(out, 14)
     return pl
 
 
@@ -236,6 +239,7 @@ def pyramid_conv_wgrad(xs, gs, channels_last=True):
 GN_FWD, GN_BWD = 0, 1
 GN_CHANNELS = (64, 128, 256, 512)
 GN_MAX_CPG = 256
+GN_MAX_B = 65535 // MAX_LEVELS
 
 
 def _gn_channels(C, G):
@@ -248,21 +252,6 @@ def _gn_channels(C, G):
     return C, G
 
 
-def _gn_geometry(B, sizes):
-    """As ``_geometry``, but a level may be empty (H or W zero)."""
-    B = integer(B, "B", 0, 65535 // MAX_LEVELS)
-    if not isinstance(sizes, (list, tuple)) or not 1 <= len(sizes) <= MAX_LEVELS:
-        raise ValueError("sizes must be a list of 1..%d (H, W) pairs, got %s" % (
-            MAX_LEVELS, len(sizes) if isinstance(sizes, (list, tuple)) else type(sizes).__name__))
-    out = []
-    for l, hw in enumerate(sizes):
-        H, W = integer(hw[0], "sizes[%d][0]" % l, 0), integer(hw[1], "sizes[%d][1]" % l, 0)
-        integer(H * W, "sizes[%d]: H*W" % l, 0, MAX_ROWS)
-        integer(B * H * W, "sizes[%d]: B*H*W" % l, 0, MAX_ROWS)
-        out.append((H, W))
-    return B, out
-
-
 def _gn_maps(zs, name="zs"):
     """The raw conv outputs: -> (list, dtype, B, C, [(H, W)]).  One dtype, one batch size, one channel count."""
     zs = _levels(zs, name)
@@ -272,7 +261,7 @@ def _gn_maps(zs, name="zs"):
     for l, z in enumerate(zs):
         _, _, H, W = _nhwc(z, "%s[%d]" % (name, l), dtype, (B, C, "H", "W"))
         sizes.append((H, W))
-    B, sizes = _gn_geometry(B, sizes)
+    B, sizes = _geometry(B, sizes, 0, GN_MAX_B)
     return zs, dtype, B, C, sizes
 
 
@@ -304,7 +293,7 @@ def pyramid_gn_plan(kind, B, sizes, C, groups):
     size B is cut.  Refusals are ValueErrors."""
     if kind not in (GN_FWD, GN_BWD):
         raise ValueError("kind must be GN_FWD (0) or GN_BWD (1), got %r" % (kind,))
-    B, sizes = _gn_geometry(B, sizes)
+    B, sizes = _geometry(B, sizes, 0, GN_MAX_B)
     C, G = _gn_channels(C, groups)
     out = (ctypes.c_int32 * 32)()
     if _lib.load().tdn_pyr_gn_plan(int(kind), B, _hw(sizes), len(sizes), C, G, out) != 0:
@@ -314,7 +303,7 @@ def pyramid_gn_plan(kind, B, sizes, C, groups):
     pl.chunks, pl.chunk_pixels = list(out)[:n], list(out)[MAX_LEVELS:MAX_LEVELS + n]
     pl.workgroups, pl.launches = tuple(out[16:19]), out[19]
     pl.lanes_per_workgroup, pl.channels_per_block = out[20], out[21]
-    pl.workspace_bytes = out[22] + (out[23] << 31)
+    pl.workspace_bytes = _lib.size_word(out, 22)
     return pl
 
 
