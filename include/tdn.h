@@ -574,7 +574,7 @@ int tdn_sample_rois(const float* proposals, const int32_t* counts, const float* 
                     float* rois, int64_t* labels, float* label_weights, float* bbox_targets, float* bbox_weights,
                     int32_t* pos_gt_inds, int32_t* num_pos, int32_t* num_neg, void* workspace,
                     int64_t workspace_bytes, void* stream);
-/* IoU-balanced negative sampling (Libra R-CNN; DESIGN.md §4r): tdn_sample_assigned and tdn_sample_rois with ONLY the
+/* IoU-balanced negative sampling (Libra R-CNN; DESIGN.md §4u): tdn_sample_assigned and tdn_sample_rois with ONLY the
  * choice of negatives replaced; assignment, positives, row layout, labels, targets, weights and the launch counts are
  * theirs.  "Choose k of a set at random" is "the k smallest (key, index) of the set" with tdn_sample_assigned's keys.
  * Per image, o_i = max_overlaps of candidate i, n = the number of negatives tdn_sample_assigned would take at most:
@@ -661,7 +661,7 @@ int tdn_loss_roi_fwd(const void* cls, const void* reg, int dtype, int R, int C, 
 int tdn_loss_roi_bwd(const void* cls, const void* reg, int dtype, int R, int C, int reg_cols, const int64_t* labels,
                      const float* label_weights, const float* bbox_targets, const float* bbox_weights, float beta,
                      const float* g, const float* avg_in, void* dcls, void* dreg, void* stream);
-/* The same two entry points with balanced L1 (Libra R-CNN; DESIGN.md §4r) in place of smooth L1 as the box term; the
+/* The same two entry points with balanced L1 (Libra R-CNN; DESIGN.md §4u) in place of smooth L1 as the box term; the
  * classification term, the divisor, the weight-0 rule, the column rule, the reduction and the workspace
  * (tdn_loss_roi_workspace_bytes) are the same.  Per element, fp32, in the order written, d = pred - target, a = |d|:
  *   a <  beta:  t = log1pf((b a) / beta);  l = ((alpha / b) (b a + 1)) t - alpha a;
@@ -692,7 +692,8 @@ int tdn_loss_roi_balanced_bwd(const void* cls, const void* reg, int dtype, int R
  * TDN_NMS_SEG_MAX candidates gets counts[b] = -1 and empty rows.  NaN scores are unsupported.
  * Limits: 1 <= B <= 64, 2 <= C <= TDN_DET_MAX_CLASSES, N <= TDN_DET_MAX_ROWS, 1 <= max_num <= TDN_RPN_MAX_NUM, finite
  * thresholds, B (C - 1) min(N, TDN_NMS_SEG_MAX) < 2^31.  Four launches; no host synchronisation, no memset, no float
- * atomics.  workspace: tdn_multiclass_nms_workspace_bytes() bytes, 256-aligned. */
+ * atomics.  workspace: tdn_multiclass_nms_workspace_bytes() bytes, 256-aligned.  Soft-NMS in place of the greedy NMS:
+ * the _soft entry points further down. */
 #define TDN_DET_MAX_CLASSES 1024
 #define TDN_DET_MAX_ROWS (1 << 18)
 int64_t tdn_multiclass_nms_workspace_bytes(int N, int C, int B);
@@ -917,6 +918,71 @@ int tdn_fcos_detections(const tdn_fcos_level* levels, int nlevels, int B, const 
                         float* dense_scores, float* dense_boxes, int32_t* batch_idx, int64_t* dense_point_idx,
                         float* dets, int64_t* labels, int64_t* row_idx, int64_t* point_idx, int32_t* counts,
                         void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- soft-NMS in place of the greedy NMS of the five test-time entry points above (the project's own
+ *      spec in the lineage of mmdetection v1's soft_nms_cpu; '+1' boxes, strict fp32 in the spec's operation order) ----
+ * One (image, class) segment of candidates (score > score_thr, as above), repeated until no candidate is alive:
+ *   select  the alive candidate with the largest current score, ties to the lowest source row; it is retired and is the
+ *           segment's next survivor, with its current score;
+ *   decay   for every other alive candidate j, with w, h, inter, uni and ov = inter / uni formed as tdn_nms forms the IoU
+ *           of (selected, j): if w > 0 and h > 0, score_j = weight * score_j (one fp32 product), and j is dropped for
+ *           good if the product is < min_score.
+ * weight: TDN_SOFT_LINEAR ov > iou_thr ? 1 - ov : 1; TDN_SOFT_NAIVE ov > iou_thr ? 0 : 1 (greedy NMS when
+ * 0 < min_score <= score_thr); TDN_SOFT_GAUSSIAN soft_exp(-(ov * ov) / sigma), soft_exp the library's own fp32
+ * exponential on [-64, 0] (range reduction, degree-7 polynomial, exact scaling; relative error <= 4 * 2^-24), the same
+ * bits on every run and in the CPU oracle.  A segment's survivors keep their selection order; per image the best
+ * min(max_num, survivors) by (final score desc, class asc, selection order).  dets[..][4] is the final score; every
+ * other output, limit and the counts = -1 rule are those of the entry point without _soft.
+ * Refused (-1, tdn_last_error): method not one of the three; a non-finite iou_thr, sigma or min_score; sigma outside
+ * [1/64, 64]; min_score < 0.  Each entry point takes the arguments of its namesake with `soft` in place of nms_thr (the
+ * config structs' nms_thr is not read) and has a workspace query of its own: there is no suppression mask, so the
+ * workspace is smaller.  One launch fewer than the namesake: the segment launch, one workgroup per segment for the whole
+ * soft-NMS, the merge.  No host synchronisation, no memset, no float atomics, no inter-workgroup waits. */
+#define TDN_SOFT_NAIVE 0
+#define TDN_SOFT_LINEAR 1
+#define TDN_SOFT_GAUSSIAN 2
+typedef struct tdn_soft_nms_config {
+  int32_t method;              /* TDN_SOFT_NAIVE / TDN_SOFT_LINEAR / TDN_SOFT_GAUSSIAN */
+  float iou_thr;               /* linear and naive: pairs with ov > iou_thr decay */
+  float sigma;                 /* gaussian; in [1/64, 64] */
+  float min_score;             /* >= 0: a decayed score below it drops the candidate */
+} tdn_soft_nms_config;
+int64_t tdn_multiclass_nms_soft_workspace_bytes(int N, int C, int B);
+int tdn_multiclass_nms_soft(const float* boxes, int box_cols, const float* scores, const void* batch_idx,
+                            int batch_idx_bytes, int N, int C, int B, float score_thr, const tdn_soft_nms_config* soft,
+                            int max_num, float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int64_t tdn_bbox_detections_soft_workspace_bytes(int R, int C, int B);
+int tdn_bbox_detections_soft(const float* rois, const void* cls, const void* reg, int dtype, int R, int C, int reg_cols,
+                             int B, const int32_t* img_shapes, const float* scale_factors, float scale_factor,
+                             const float* means4, const float* stds4, double wh_ratio_clip, float score_thr,
+                             const tdn_soft_nms_config* soft, int max_num, float* dense_scores, float* dense_boxes,
+                             float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int64_t tdn_cascade_detections_soft_workspace_bytes(int R, int C, int B);
+int tdn_cascade_detections_soft(const float* rois, const void* const* cls, int num_stages, const void* reg, int dtype,
+                                int R, int C, int reg_cols, int B, const int32_t* img_shapes,
+                                const float* scale_factors, float scale_factor, const float* means4,
+                                const float* stds4, double wh_ratio_clip, float score_thr,
+                                const tdn_soft_nms_config* soft, int max_num, float* dense_scores, float* dense_boxes,
+                                float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
+                                int64_t workspace_bytes, void* stream);
+int64_t tdn_dense_detections_soft_workspace_bytes(const tdn_dense_level* levels, int nlevels, int B,
+                                                  const tdn_dense_config* cfg);
+int tdn_dense_detections_soft(const tdn_dense_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                              const float* scale_factors, const tdn_dense_config* cfg,
+                              const tdn_soft_nms_config* soft, float* dense_scores, float* dense_boxes,
+                              int32_t* batch_idx, int64_t* dense_anchor_idx, float* dets, int64_t* labels,
+                              int64_t* row_idx, int64_t* anchor_idx, int32_t* counts, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+int64_t tdn_fcos_detections_soft_workspace_bytes(const tdn_fcos_level* levels, int nlevels, int B,
+                                                 const tdn_fcos_det_config* cfg);
+int tdn_fcos_detections_soft(const tdn_fcos_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                             const float* scale_factors, const float* scales, const tdn_fcos_det_config* cfg,
+                             const tdn_soft_nms_config* soft, float* dense_scores, float* dense_boxes,
+                             int32_t* batch_idx, int64_t* dense_point_idx, float* dets, int64_t* labels,
+                             int64_t* row_idx, int64_t* point_idx, int32_t* counts, void* workspace,
+                             int64_t workspace_bytes, void* stream);
 
 /* ---- the mask branch of Mask R-CNN: polygon mask targets, mask loss, mask paste (the project's own
  *      spec in the mmdetection-v1 lineage of mask_target / FCNMaskHead.loss / get_seg_masks) ----
@@ -1332,7 +1398,7 @@ int tdn_pyr_gn_bwd(const tdn_pyr_gn_level* levels, int num_levels, int B, const 
                    int G, int relu, float* dgamma, float* dbeta, float acc, void* workspace, int64_t workspace_bytes,
                    int dtype, void* stream);
 
-/* ---- Balanced Feature Pyramid, Libra R-CNN's BFP neck (csrc/bfp.hip, DESIGN.md §4r) ------------------------------------------
+/* ---- Balanced Feature Pyramid, Libra R-CNN's BFP neck (csrc/bfp.hip, DESIGN.md §4u) ------------------------------------------
  * levels: HOST array of 1..TDN_PYR_MAX_LEVELS entries of one batch size B (1..64), one channel count C (a multiple of 8 in
  * 8..1024) and a map size (H, W) each, 1 <= H, W <= 32767 and B H W C < 2^31, in ANY relation to one another.  All maps
  * are dense NHWC (B, H, W, C), 16-bit, 16-byte aligned, finite.  (Hg, Wg) is the size of level refine_level; bsf and dbsf

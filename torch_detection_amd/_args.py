@@ -66,6 +66,49 @@ def f4(vals, name):
     return (ctypes.c_float * 4)(*vals)
 
 
+SOFT_METHODS = {"naive": _lib.SOFT_NAIVE, "linear": _lib.SOFT_LINEAR, "gaussian": _lib.SOFT_GAUSSIAN}
+_NMS_KEYS = {"nms": ("type", "iou_thr"), "soft_nms": ("type", "iou_thr", "min_score", "method", "sigma")}
+
+
+def nms_config(nms, nms_thr, default_thr=0.5):
+    """The ``nms`` / ``nms_thr`` pair of the test-time detections -> ``(nms_thr, soft)``.  ``nms=None``:
+    ``nms_thr`` as given and ``soft=None``, the greedy path; ``dict(type='nms', iou_thr=t)``: the same with ``t``;
+    ``dict(type='soft_nms', iou_thr=0.5, min_score=0.001, method='linear', sigma=0.5)`` (mmdetection's defaults):
+    ``soft`` is the ``tdn_soft_nms_config`` of the soft path.  Giving ``nms`` and a ``nms_thr`` other than the default
+    is refused, as is every value the library would refuse."""
+    if nms is None:
+        return number(nms_thr, "nms_thr"), None
+    if not isinstance(nms, dict):
+        raise ValueError("nms must be None or a dict like dict(type='soft_nms', iou_thr=0.5), got %s" % type(nms).__name__)
+    if number(nms_thr, "nms_thr") != default_thr:
+        raise ValueError("give the threshold either as nms_thr or in nms['iou_thr'], not both (nms_thr=%r)" % (nms_thr,))
+    kind = nms.get("type")
+    if kind not in _NMS_KEYS:
+        raise ValueError("nms: unknown type %r (one of 'nms', 'soft_nms')" % (kind,))
+    extra = sorted(k for k in nms if k not in _NMS_KEYS[kind])
+    if extra:
+        raise ValueError("nms: unknown key %s for type %r (it takes %s)" % (", ".join(map(repr, extra)), kind,
+                                                                            ", ".join(_NMS_KEYS[kind])))
+    iou_thr = number(nms.get("iou_thr", 0.5), "nms['iou_thr']")
+    if kind == "nms":
+        return iou_thr, None
+    method = nms.get("method", "linear")
+    if not isinstance(method, str) or method not in SOFT_METHODS:
+        raise ValueError("nms: method %r is not one of 'linear', 'gaussian', 'naive'" % (method,))
+    soft = _lib.SoftNmsConfig()
+    soft.method, soft.iou_thr = SOFT_METHODS[method], iou_thr
+    soft.sigma = number(nms.get("sigma", 0.5), "nms['sigma']")
+    soft.min_score = number(nms.get("min_score", 0.001), "nms['min_score']")
+    for key in ("iou_thr", "min_score"):            # finite as the float32 the kernel reads, too
+        if not math.isfinite(getattr(soft, key)):
+            raise ValueError("nms[%r] must be finite, got %r" % (key, nms.get(key)))
+    if not _lib.SOFT_SIGMA_MIN <= soft.sigma <= _lib.SOFT_SIGMA_MAX:
+        raise ValueError("nms['sigma'] must lie in [1/64, 64], got %r" % (nms.get("sigma"),))
+    if soft.min_score < 0:
+        raise ValueError("nms['min_score'] must be >= 0, got %r" % (nms.get("min_score"),))
+    return iou_thr, soft
+
+
 def batch(B):
     """The batch limit of every head entry point (``tdn_check_batch``)."""
     if not 1 <= B <= 64:

@@ -331,6 +331,17 @@ _FL = ctypes.POINTER(FcosLevel)
 _FLC = ctypes.POINTER(FcosLossConfig)
 _FDC = ctypes.POINTER(FcosDetConfig)
 
+SOFT_NAIVE, SOFT_LINEAR, SOFT_GAUSSIAN = 0, 1, 2
+SOFT_SIGMA_MIN, SOFT_SIGMA_MAX = 1.0 / 64, 64.0
+
+
+class SoftNmsConfig(ctypes.Structure):
+    """Mirror of ``tdn_soft_nms_config`` (include/tdn.h)."""
+    _fields_ = [("method", ctypes.c_int32), ("iou_thr", c_float), ("sigma", c_float), ("min_score", c_float)]
+
+
+_SNC = ctypes.POINTER(SoftNmsConfig)
+
 # name -> (restype, argtypes); must list every symbol of include/tdn.h (tests/test_abi.py checks this)
 SIGNATURES = {
     "tdn_last_error": (ctypes.c_char_p, []),
@@ -445,6 +456,23 @@ SIGNATURES = {
     "tdn_fcos_detections_workspace_bytes": (c_i64, [_FL, c_int, c_int, _FDC]),
     "tdn_fcos_detections": (c_int, [_FL, c_int, c_int, c_void_p, c_void_p, c_void_p, _FDC] + [c_void_p] * 10 +
                             [c_i64, c_void_p]),
+    "tdn_multiclass_nms_soft_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "tdn_multiclass_nms_soft": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, _SNC,
+                                        c_int] + [c_void_p] * 5 + [c_i64, c_void_p]),
+    "tdn_bbox_detections_soft_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "tdn_bbox_detections_soft": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_float,
+                                         ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.c_double, c_float,
+                                         _SNC, c_int] + [c_void_p] * 7 + [c_i64, c_void_p]),
+    "tdn_cascade_detections_soft_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "tdn_cascade_detections_soft": (c_int, [c_void_p, ctypes.POINTER(c_void_p), c_int, c_void_p] + [c_int] * 5 +
+                                    [c_void_p, c_void_p, c_float, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
+                                     ctypes.c_double, c_float, _SNC, c_int] + [c_void_p] * 7 + [c_i64, c_void_p]),
+    "tdn_dense_detections_soft_workspace_bytes": (c_i64, [_DL, c_int, c_int, _DC]),
+    "tdn_dense_detections_soft": (c_int, [_DL, c_int, c_int, c_void_p, c_void_p, _DC, _SNC] + [c_void_p] * 10 +
+                                  [c_i64, c_void_p]),
+    "tdn_fcos_detections_soft_workspace_bytes": (c_i64, [_FL, c_int, c_int, _FDC]),
+    "tdn_fcos_detections_soft": (c_int, [_FL, c_int, c_int, c_void_p, c_void_p, c_void_p, _FDC, _SNC] +
+                                 [c_void_p] * 10 + [c_i64, c_void_p]),
     "tdn_mask_target": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p]),
     "tdn_mask_loss_workspace_bytes": (c_i64, [c_int]),

@@ -56,17 +56,17 @@ def refine_bboxes(rois, bbox_pred, img_shapes, labels=None, cls_score=None, pos_
 
 def cascade_detections(rois, cls_scores, bbox_pred, img_shapes, scale_factors=None, score_thr=0.05, nms_thr=0.5,
                        max_per_img=100, target_means=(0, 0, 0, 0), target_stds=(0.1, 0.1, 0.2, 0.2),
-                       wh_ratio_clip=16 / 1000, return_dense=False):
+                       wh_ratio_clip=16 / 1000, return_dense=False, nms=None):
     """Detections from several stages' class logits (mmdetection v1's ``CascadeRCNN.simple_test`` for a whole batch).
 
     ``cls_scores``: a list of S = 1..8 (R, C) tensors of one dtype (float32 / bfloat16 / float16), all on the rows of
     ``rois``; the logit of (r, c) is ``(((x_0 + x_1) + ...) + x_{S-1}) / float(S)`` — fp32 additions in stage order, one
     fp32 division.  From there on it is :func:`bbox_head_detections` operation for operation, with ``bbox_pred`` the
     last stage's deltas against ``rois``, the last stage's input RoIs; same launch count for any S, same outputs and
-    limits, and with one stage the same bits."""
+    limits, and with one stage the same bits.  ``nms``: as :func:`multiclass_nms` takes it."""
     out = _c.cascade_detections(rois, [_detached(x) for x in cls_scores] if isinstance(cls_scores, (list, tuple))
                                 else cls_scores, _detached(bbox_pred), img_shapes, scale_factors, score_thr, nms_thr,
-                                max_per_img, target_means, target_stds, wh_ratio_clip)
+                                max_per_img, target_means, target_stds, wh_ratio_clip, nms)
     return out if return_dense else out[:4]
 
 
@@ -192,9 +192,10 @@ class CascadeRoIHead(nn.Module):
 
     @torch.no_grad()
     def simple_test(self, feats, proposals, counts, img_shapes, scale_factors=None, score_thr=0.05, nms_thr=0.5,
-                    max_per_img=100):
+                    max_per_img=100, nms=None):
         """-> ``(dets, labels, row_idx, counts)`` of :func:`cascade_detections`: every stage's logits on the RoIs it
-        was given, averaged; boxes from the last stage's deltas against the last stage's input RoIs."""
+        was given, averaged; boxes from the last stage's deltas against the last stage's input RoIs.  ``nms``: the
+        ``test_cfg``'s ``nms`` dict, as :func:`cascade_detections` takes it."""
         self._check_supported()
         rois = rois_from_proposals(proposals, counts)
         scores = []
@@ -207,4 +208,4 @@ class CascadeRoIHead(nn.Module):
                 rois = refine_bboxes(rois, bbox_pred, img_shapes, cls_score=cls_score,
                                      target_means=self.target_means[i], target_stds=self.target_stds[i])
         return cascade_detections(rois, scores, bbox_pred, img_shapes, scale_factors, score_thr, nms_thr, max_per_img,
-                                  self.target_means[last], self.target_stds[last])
+                                  self.target_means[last], self.target_stds[last], nms=nms)

@@ -76,8 +76,9 @@ def refine_bboxes(rois, bbox_pred, img_shapes, labels, cls_score, pos_assigned_g
 
 
 def cascade_detections(rois, cls_scores, bbox_pred, img_shapes, scale_factors, score_thr, nms_thr, max_per_img,
-                       target_means, target_stds, wh_ratio_clip):
-    """``detect_ops.bbox_head_detections`` on the mean of the stages' class logits (tdn_cascade_detections).  Returns
+                       target_means, target_stds, wh_ratio_clip, nms=None):
+    """``detect_ops.bbox_head_detections`` on the mean of the stages' class logits (tdn_cascade_detections; with a soft
+    ``nms`` tdn_cascade_detections_soft).  Returns
     (dets, labels, row_idx, counts) and the dense (R, C) float32 scores and (R, 4(C-1)) or (R, 4) float32 boxes."""
     if not isinstance(cls_scores, (list, tuple)) or not 1 <= len(cls_scores) <= _lib.CASCADE_MAX_STAGES:
         raise ValueError("cls_scores must be a list of 1..%d tensors" % _lib.CASCADE_MAX_STAGES)
@@ -87,7 +88,7 @@ def cascade_detections(rois, cls_scores, bbox_pred, img_shapes, scale_factors, s
     for s, x in enumerate(cls_scores[1:], 1):
         tensor(x, "cls_scores[%d]" % s, dtype, (R, C))
     B = tensor(img_shapes, "img_shapes", torch.int32, ("B", 2))[0]          # (h, w)
-    max_num, score_thr, nms_thr = _limits(R, C, B, max_per_img, score_thr, nms_thr, "cls_scores[0]")
+    max_num, score_thr, nms_thr, soft = _limits(R, C, B, max_per_img, score_thr, nms_thr, "cls_scores[0]", nms)
     cols = tensor(bbox_pred, "bbox_pred", dtype, (R, (4 * C, 4)))[1]
     scale_t, scale_v = None, 0.0
     if torch.is_tensor(scale_factors):              # or None, or a positive number
@@ -101,7 +102,8 @@ def cascade_detections(rois, cls_scores, bbox_pred, img_shapes, scale_factors, s
               [("cls_scores[%d]" % s, x) for s, x in enumerate(cls_scores)])
     dev = rois.device
     lib = _lib.load()
-    nbytes = _lib.ws_bytes(lib.tdn_bbox_detections_workspace_bytes(R, C, B), "cascade_detections")
+    query = lib.tdn_cascade_detections_soft_workspace_bytes if soft else lib.tdn_bbox_detections_workspace_bytes
+    nbytes = _lib.ws_bytes(query(R, C, B), "cascade_detections")
     dets = torch.empty(B, max_num, 5, dtype=torch.float32, device=dev)
     labels = torch.empty(B, max_num, dtype=torch.int64, device=dev)
     row_idx = torch.empty(B, max_num, dtype=torch.int64, device=dev)
@@ -110,9 +112,10 @@ def cascade_detections(rois, cls_scores, bbox_pred, img_shapes, scale_factors, s
     boxes = torch.empty(R, 4 if cols == 4 else 4 * (C - 1), dtype=torch.float32, device=dev)
     ws, wp = _aligned_ws(nbytes, dev)
     stages = (ctypes.c_void_p * len(cls_scores))(*[x.data_ptr() for x in cls_scores])
-    _lib.check(lib.tdn_cascade_detections(_ptr(rois), stages, len(cls_scores), _ptr(bbox_pred), CODES[dtype], R, C,
-                                          cols, B, _ptr(img_shapes), _ptr(scale_t), scale_v, means, stds, clip,
-                                          score_thr, nms_thr, max_num, _ptr(scores), _ptr(boxes), _ptr(dets),
-                                          _ptr(labels), _ptr(row_idx), _ptr(counts), wp, nbytes, _lib.stream_ptr()),
-               "tdn_cascade_detections")
+    fn, what = (lib.tdn_cascade_detections_soft, "tdn_cascade_detections_soft") if soft else \
+        (lib.tdn_cascade_detections, "tdn_cascade_detections")
+    _lib.check(fn(_ptr(rois), stages, len(cls_scores), _ptr(bbox_pred), CODES[dtype], R, C, cols, B, _ptr(img_shapes),
+                  _ptr(scale_t), scale_v, means, stds, clip, score_thr, ctypes.byref(soft) if soft else nms_thr, max_num,
+                  _ptr(scores), _ptr(boxes), _ptr(dets), _ptr(labels), _ptr(row_idx), _ptr(counts), wp, nbytes,
+                  _lib.stream_ptr()), what)
     return dets, labels, row_idx, counts, scores, boxes

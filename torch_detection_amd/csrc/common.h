@@ -186,6 +186,18 @@ static inline int tdn_check_batch(const char* who, int B) {
   TDN_CHECK(B >= 1 && B <= 64, "%s: B=%d out of 1..64", who, B);
   return 0;
 }
+// the refusals every _soft detection entry point shares, made before its first launch
+static inline int tdn_soft_nms_check(const char* who, const tdn_soft_nms_config* soft) {
+  TDN_CHECK(soft, "%s: NULL soft-NMS config", who);
+  TDN_CHECK(soft->method == TDN_SOFT_NAIVE || soft->method == TDN_SOFT_LINEAR || soft->method == TDN_SOFT_GAUSSIAN,
+            "%s: soft-NMS method %d is not naive (0), linear (1) or gaussian (2)", who, soft->method);
+  TDN_CHECK(soft->iou_thr - soft->iou_thr == 0.f && soft->min_score - soft->min_score == 0.f &&
+                soft->sigma - soft->sigma == 0.f, "%s: soft-NMS iou_thr / min_score / sigma must be finite", who);
+  TDN_CHECK(soft->sigma >= 1.f / 64.f && soft->sigma <= 64.f, "%s: soft-NMS sigma=%g outside [1/64, 64]", who,
+            (double)soft->sigma);
+  TDN_CHECK(soft->min_score >= 0.f, "%s: soft-NMS min_score=%g is negative", who, (double)soft->min_score);
+  return 0;
+}
 // A caller's workspace is laid out by ONE function per entry point (nms_layout, rpn_layout, ...): it carves the regions
 // in order, each from a 256-byte boundary, and returns their pointers with the total.  With a null base the pointers
 // are null and the pass is the size query; with the caller's pointer it is the launch path.

@@ -15,7 +15,8 @@
 //                              (select_core.h), ordered compaction of the kept anchors in ANCHOR order, then per kept
 //                              row the decode (delta_core.h), the background column, batch_idx, anchor_idx, and per
 //                              (row, class) the sigmoid: the dense tensors, each element written once.
-//   3-6                        tdn_multiclass_nms (detect.hip) on the dense tensors.
+//   3-6                        tdn_multiclass_nms (detect.hip) on the dense tensors; tdn_dense_detections_soft:
+//                              tdn_multiclass_nms_soft there, three launches.
 //   7 dd_anchor_gather_kernel  anchor_idx[b][j] = dense_anchor_idx[row_idx[b][j]], -1 on unused rows.
 // tdn_anchor_target_all is the assignment launches of tdn_anchor_target (target.hip, through target_host.h) plus
 //   dd_target_fill_kernel      labels, weights, encode and the per-image counts: one returning 64-bit integer atomic add
@@ -339,7 +340,7 @@ struct DdPlan {
 };
 
 // the checks and the geometry the plan query, the workspace query and the call share; pointers may be null
-int dd_plan(const char* who, const tdn_dense_level* levels, int L, int B, const tdn_dense_config* cfg, DdPlan* out) {
+int dd_plan(const char* who, const tdn_dense_level* levels, int L, int B, const tdn_dense_config* cfg, DdPlan* out, bool soft = false) {
   TDN_CHECK(levels && cfg, "%s: NULL levels / config", who);
   TDN_CHECK(L >= 1 && L <= TDN_DENSE_MAX_LEVELS, "%s: %d levels (1..%d)", who, L, TDN_DENSE_MAX_LEVELS);
   if (tdn_check_batch(who, B) != 0) return -1;
@@ -351,7 +352,7 @@ int dd_plan(const char* who, const tdn_dense_level* levels, int L, int B, const 
             DD_SEG_MAX);
   TDN_CHECK(cfg->max_num >= 1 && cfg->max_num <= TDN_RPN_MAX_NUM, "%s: max_num=%d out of 1..%d", who, cfg->max_num,
             TDN_RPN_MAX_NUM);
-  TDN_CHECK(cfg->score_thr - cfg->score_thr == 0.f && cfg->nms_thr - cfg->nms_thr == 0.f,
+  TDN_CHECK(cfg->score_thr - cfg->score_thr == 0.f && (soft || cfg->nms_thr - cfg->nms_thr == 0.f),
             "%s: score_thr / nms_thr must be finite", who);
   TDN_CHECK(cfg->wh_ratio_clip > 0.0 && cfg->wh_ratio_clip < 1.0, "%s: wh_ratio_clip must be in (0, 1)", who);
   memset(out, 0, sizeof(*out));
@@ -408,7 +409,8 @@ int dd_plan(const char* who, const tdn_dense_level* levels, int L, int B, const 
   P.max_ratio = (float)fabs(log(cfg->wh_ratio_clip));   // as tdn_delta2bbox: in double, rounded to fp32
   P.means = host_f4(cfg->means);
   P.stds = host_f4(cfg->stds);
-  out->nms_bytes = tdn_multiclass_nms_workspace_bytes((int)out->rows, C + 1, B);
+  out->nms_bytes = soft ? tdn_multiclass_nms_soft_workspace_bytes((int)out->rows, C + 1, B)
+                        : tdn_multiclass_nms_workspace_bytes((int)out->rows, C + 1, B);
   return out->nms_bytes < 0 ? -1 : 0;
 }
 
@@ -445,14 +447,22 @@ extern "C" int64_t tdn_dense_detections_workspace_bytes(const tdn_dense_level* l
   return dd_layout(p, nullptr).bytes;
 }
 
-extern "C" int tdn_dense_detections(const tdn_dense_level* levels, int nlevels, int B, const int32_t* img_shapes,
-                                    const float* scale_factors, const tdn_dense_config* cfg, float* dense_scores,
-                                    float* dense_boxes, int32_t* batch_idx, int64_t* dense_anchor_idx, float* dets,
-                                    int64_t* labels, int64_t* row_idx, int64_t* anchor_idx, int32_t* counts,
-                                    void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* who = "tdn_dense_detections";
+extern "C" int64_t tdn_dense_detections_soft_workspace_bytes(const tdn_dense_level* levels, int nlevels, int B,
+                                                             const tdn_dense_config* cfg) {
   DdPlan p;
-  if (dd_plan(who, levels, nlevels, B, cfg, &p) != 0) return -1;
+  if (dd_plan("tdn_dense_detections_soft", levels, nlevels, B, cfg, &p, true) != 0) return -1;
+  return dd_layout(p, nullptr).bytes;
+}
+
+namespace {
+// tdn_dense_detections (soft == null) and tdn_dense_detections_soft
+int dd_run(const char* who, const tdn_dense_level* levels, int nlevels, int B, const int32_t* img_shapes,
+           const float* scale_factors, const tdn_dense_config* cfg, const tdn_soft_nms_config* soft, float* dense_scores,
+           float* dense_boxes, int32_t* batch_idx, int64_t* dense_anchor_idx, float* dets, int64_t* labels,
+           int64_t* row_idx, int64_t* anchor_idx, int32_t* counts, void* workspace, int64_t workspace_bytes,
+           void* stream) {
+  DdPlan p;
+  if (dd_plan(who, levels, nlevels, B, cfg, &p, soft != nullptr) != 0) return -1;
   TDN_CHECK(scale_factors || cfg->scale_factor == 0.f ||
                 (cfg->scale_factor > 0.f && cfg->scale_factor - cfg->scale_factor == 0.f),
             "%s: scale_factor must be positive and finite (0: none)", who);
@@ -474,14 +484,41 @@ extern "C" int tdn_dense_detections(const tdn_dense_level* levels, int nlevels, 
   TDN_LAUNCH(dd_select_decode_kernel, dim3(B * nlevels), dim3(BLK), 0, st, P, (const uint32_t*)w.keys, dense_scores,
              dense_boxes, batch_idx, dense_anchor_idx);
   TDN_LAUNCH_CHECK();
-  const int rc = tdn_multiclass_nms(dense_boxes, 4, dense_scores, batch_idx, 4, (int)p.rows, P.C + 1, B, cfg->score_thr,
-                                    cfg->nms_thr, cfg->max_num, dets, labels, row_idx, counts, w.nms, p.nms_bytes, stream);
+  const int rc = soft ? tdn_multiclass_nms_soft(dense_boxes, 4, dense_scores, batch_idx, 4, (int)p.rows, P.C + 1, B,
+                                                cfg->score_thr, soft, cfg->max_num, dets, labels, row_idx, counts, w.nms,
+                                                p.nms_bytes, stream)
+                      : tdn_multiclass_nms(dense_boxes, 4, dense_scores, batch_idx, 4, (int)p.rows, P.C + 1, B,
+                                           cfg->score_thr, cfg->nms_thr, cfg->max_num, dets, labels, row_idx, counts,
+                                           w.nms, p.nms_bytes, stream);
   if (rc != 0) return rc;
   const int nd = B * cfg->max_num;
   TDN_LAUNCH(dd_anchor_gather_kernel, dim3((nd + 255) / 256), dim3(256), 0, st, (const int64_t*)row_idx,
              (const int64_t*)dense_anchor_idx, nd, anchor_idx);
   TDN_LAUNCH_CHECK();
   return 0;
+}
+}  // namespace
+
+extern "C" int tdn_dense_detections(const tdn_dense_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                                    const float* scale_factors, const tdn_dense_config* cfg, float* dense_scores,
+                                    float* dense_boxes, int32_t* batch_idx, int64_t* dense_anchor_idx, float* dets,
+                                    int64_t* labels, int64_t* row_idx, int64_t* anchor_idx, int32_t* counts,
+                                    void* workspace, int64_t workspace_bytes, void* stream) {
+  return dd_run("tdn_dense_detections", levels, nlevels, B, img_shapes, scale_factors, cfg, nullptr, dense_scores,
+                dense_boxes, batch_idx, dense_anchor_idx, dets, labels, row_idx, anchor_idx, counts, workspace,
+                workspace_bytes, stream);
+}
+
+extern "C" int tdn_dense_detections_soft(const tdn_dense_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                                         const float* scale_factors, const tdn_dense_config* cfg,
+                                         const tdn_soft_nms_config* soft, float* dense_scores, float* dense_boxes,
+                                         int32_t* batch_idx, int64_t* dense_anchor_idx, float* dets, int64_t* labels,
+                                         int64_t* row_idx, int64_t* anchor_idx, int32_t* counts, void* workspace,
+                                         int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_dense_detections_soft";
+  if (tdn_soft_nms_check(who, soft) != 0) return -1;  // before the first launch
+  return dd_run(who, levels, nlevels, B, img_shapes, scale_factors, cfg, soft, dense_scores, dense_boxes, batch_idx,
+                dense_anchor_idx, dets, labels, row_idx, anchor_idx, counts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t tdn_anchor_target_all_workspace_bytes(int B, int N, int G) {

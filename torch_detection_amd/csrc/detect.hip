@@ -16,10 +16,14 @@
 //   3 det_nms_scan_kernel        nms_scan_block of nms_core.h, one workgroup per segment; rows already are in key order.
 //   4 det_merge_kernel           one workgroup per image: block_topk over the classes' survivors by (score key desc,
 //                                class asc, row asc); writes the padded outputs and the count.
+// With soft-NMS launches 2 and 3 are one:
+//   2s det_soft_nms_kernel       soft_nms_segment of soft_nms_core.h, one workgroup per segment: the survivors in
+//                                selection order, and every row's final score and its key, which the merge then reads.
 // No memset, no float atomics, no inter-workgroup waits, no allocation; the integer LDS atomics of the radix select only
 // count, so every output is a pure function of the inputs.
 #include "nms_core.h"
 #include "select_core.h"
+#include "soft_nms_core.h"
 #include "delta_core.h"
 #include <math.h>
 #include <string.h>
@@ -238,6 +242,33 @@ __global__ __launch_bounds__(BLK) void det_nms_scan_kernel(const unsigned long l
   nms_scan_block(mask + start * pitch, nullptr, n, (n + 63) / 64, pitch, nullptr, kept + start, num_kept + s, sm);
 }
 
+// ---- 2s: soft-NMS of every segment (the body is soft_nms_core.h's) -----------------------------------------------------
+// seg_key is rewritten in place: on return seg_key[r] / seg_score[r] are the final score's key / the final score of row r
+__global__ __launch_bounds__(BLK) void det_soft_nms_kernel(const DetArgs A, const SoftArgs P,
+                                                           const f32x4_t* __restrict__ seg_box,
+                                                           const int* __restrict__ seg_row, const int* seg_start,
+                                                           const int* seg_count, uint32_t* seg_key, float* seg_score,
+                                                           int64_t* kept, int* num_kept) {
+  __shared__ SoftLds sh;
+  const int s = blockIdx.x;
+  const int n = __builtin_amdgcn_readfirstlane(seg_count[s]);
+  if (n <= 0) {
+    if (threadIdx.x == 0) num_kept[s] = n < 0 ? -1 : 0;
+    return;
+  }
+  const int64_t start = seg_start[s];
+  const int Cf = A.C - 1;
+  const float* scol = A.scores + (s - (s / Cf) * Cf + 1);       // the class's column
+  if (n <= SOFT_WAVE_MAX) {
+    if (threadIdx.x >= 64) return;                    // no barrier is reached on this path
+    soft_nms_segment<true>(P, seg_box + start, seg_row + start, scol, A.C, n, seg_key + start, seg_score + start,
+                           kept + start, num_kept + s, &sh);
+  } else {
+    soft_nms_segment<false>(P, seg_box + start, seg_row + start, scol, A.C, n, seg_key + start, seg_score + start,
+                            kept + start, num_kept + s, &sh);
+  }
+}
+
 // ---- 4: per image, the best max_num of the classes' survivors ------------------------------------------------------
 // candidate j of an image: survivor j - cum[c] of class c, classes in order; among equal keys the candidate order is
 // (class asc, row asc), because a segment's survivors keep its (key desc, row asc) order
@@ -270,6 +301,8 @@ size_t merge_lds(int max_num, int C) {
   return (size_t)pow2_ceil(max_num) * 8 + TK_BINS * 4 + TK_MISC * 4 + (size_t)(C + 1) * 4;
 }
 
+// SOFT: seg_key holds the final scores' keys and A.scores IS the per-row array of final scores (det_run_soft)
+template <bool SOFT>
 __global__ __launch_bounds__(BLK) void det_merge_kernel(const DetArgs A, const f32x4_t* __restrict__ seg_box,
                                                         const uint32_t* __restrict__ seg_key,
                                                         const int* __restrict__ seg_row,
@@ -307,7 +340,8 @@ __global__ __launch_bounds__(BLK) void det_merge_kernel(const DetArgs A, const f
       o[1] = bx[1];
       o[2] = bx[2];
       o[3] = bx[3];
-      o[4] = A.scores[(size_t)src * A.C + c + 1];     // the stored score itself (-0.0 stays -0.0)
+      if constexpr (SOFT) o[4] = A.scores[r];
+      else o[4] = A.scores[(size_t)src * A.C + c + 1];     // the stored score itself (-0.0 stays -0.0)
       labels[q] = c;
       row_idx[q] = src;
     } else {
@@ -354,9 +388,27 @@ DetWs det_layout(const DetPlan& p, void* base) {   // a braced list is evaluated
           c.take<int>(p.S), c.take<int>(p.S), c.take<int>(p.S), c.take<u64>(p.rows * p.A.pitch), c.off};
 }
 
-// launches 1..4 on dense fp32 boxes and scores
+// soft-NMS: no mask, the rows' final scores instead
+struct SoftWs {
+  f32x4_t* seg_box; uint32_t* seg_key; int* seg_row; int64_t* kept; float* seg_score;
+  int *seg_start, *seg_count, *num_kept; int64_t bytes;
+};
+SoftWs soft_layout(const DetPlan& p, void* base) {   // a braced list is evaluated left to right
+  tdn_carver c{(char*)base, 0};
+  return {c.take<f32x4_t>(p.rows), c.take<uint32_t>(p.rows), c.take<int>(p.rows), c.take<int64_t>(p.rows),
+          c.take<float>(p.rows), c.take<int>(p.S), c.take<int>(p.S), c.take<int>(p.S), c.off};
+}
+
+int det_run_soft(const char* who, DetPlan& p, float score_thr, const tdn_soft_nms_config* soft, int max_num,
+                 float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
+                 int64_t workspace_bytes, void* stream);
+
+// launches 1..4 on dense fp32 boxes and scores; soft != null: launches 1, 2s, 4
 int det_run(const char* who, DetPlan& p, float score_thr, float nms_thr, int max_num, float* dets, int64_t* labels,
-            int64_t* row_idx, int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+            int64_t* row_idx, int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream,
+            const tdn_soft_nms_config* soft = nullptr) {
+  if (soft) return det_run_soft(who, p, score_thr, soft, max_num, dets, labels, row_idx, counts, workspace,
+                                workspace_bytes, stream);
   TDN_CHECK(max_num >= 1 && max_num <= TDN_RPN_MAX_NUM, "%s: max_num=%d out of 1..%d", who, max_num, TDN_RPN_MAX_NUM);
   TDN_CHECK(score_thr - score_thr == 0.f && nms_thr - nms_thr == 0.f, "%s: score_thr / nms_thr must be finite", who);
   TDN_CHECK(dets && labels && row_idx && counts, "%s: NULL output", who);
@@ -380,27 +432,68 @@ int det_run(const char* who, DetPlan& p, float score_thr, float nms_thr, int max
              w.num_kept);
   TDN_LAUNCH_CHECK();
   // at most 78 KB (max_num = 8192, C = 1024); the kernel also has a few static bytes, so not the full 160 KB
-  if (tdn_allow_lds<det_merge_kernel>((int)merge_lds(TDN_RPN_MAX_NUM, TDN_DET_MAX_CLASSES), "det_merge") < 0) return -1;
-  TDN_LAUNCH(det_merge_kernel, dim3(A.B), dim3(BLK), merge_lds(max_num, A.C), st, A, (const f32x4_t*)w.seg_box,
+  if (tdn_allow_lds<det_merge_kernel<false>>((int)merge_lds(TDN_RPN_MAX_NUM, TDN_DET_MAX_CLASSES), "det_merge") < 0)
+    return -1;
+  TDN_LAUNCH(det_merge_kernel<false>, dim3(A.B), dim3(BLK), merge_lds(max_num, A.C), st, A, (const f32x4_t*)w.seg_box,
              (const uint32_t*)w.seg_key, (const int*)w.seg_row, (const int64_t*)w.kept, (const int*)w.num_kept, dets,
              labels, row_idx, counts);
   TDN_LAUNCH_CHECK();
   return 0;
 }
 
+int det_run_soft(const char* who, DetPlan& p, float score_thr, const tdn_soft_nms_config* soft, int max_num,
+                 float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
+                 int64_t workspace_bytes, void* stream) {
+  if (tdn_soft_nms_check(who, soft) != 0) return -1;
+  TDN_CHECK(max_num >= 1 && max_num <= TDN_RPN_MAX_NUM, "%s: max_num=%d out of 1..%d", who, max_num, TDN_RPN_MAX_NUM);
+  TDN_CHECK(score_thr - score_thr == 0.f, "%s: score_thr must be finite", who);
+  TDN_CHECK(dets && labels && row_idx && counts, "%s: NULL output", who);
+  TDN_CHECK(p.rows < (1ll << 31), "%s: B * (C - 1) * min(N, %d) segment rows do not fit 31 bits", who, DET_SEG_MAX);
+  DetArgs& A = p.A;
+  A.score_thr = score_thr;
+  A.nms_thr = soft->iou_thr;
+  A.max_num = max_num;
+  const SoftArgs P{soft->method, soft->iou_thr, soft->sigma, soft->min_score};
+  const SoftWs w = soft_layout(p, workspace);
+  if (tdn_check_ws(who, workspace, workspace_bytes, w.bytes) != 0) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  TDN_LAUNCH(det_segment_kernel, dim3(p.S), dim3(BLK), SEG_LDS, st, A, w.seg_box, w.seg_key, w.seg_row, w.seg_start,
+             w.seg_count);
+  TDN_LAUNCH_CHECK();
+  TDN_LAUNCH(det_soft_nms_kernel, dim3(p.S), dim3(BLK), 0, st, A, P, (const f32x4_t*)w.seg_box, (const int*)w.seg_row,
+             (const int*)w.seg_start, (const int*)w.seg_count, w.seg_key, w.seg_score, w.kept, w.num_kept);
+  TDN_LAUNCH_CHECK();
+  DetArgs M = A;                                      // the merge reads a row's score at scores[row of the segment arrays]
+  M.scores = w.seg_score;
+  if (tdn_allow_lds<det_merge_kernel<true>>((int)merge_lds(TDN_RPN_MAX_NUM, TDN_DET_MAX_CLASSES), "det_merge_soft") < 0)
+    return -1;
+  TDN_LAUNCH(det_merge_kernel<true>, dim3(A.B), dim3(BLK), merge_lds(max_num, A.C), st, M, (const f32x4_t*)w.seg_box,
+             (const uint32_t*)w.seg_key, (const int*)w.seg_row, (const int64_t*)w.kept, (const int*)w.num_kept, dets,
+             labels, row_idx, counts);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+int64_t det_ws_query(const char* who, int N, int C, int B, bool soft) {
+  DetPlan p;
+  if (det_plan(who, N, C, B, &p) != 0) return -1;
+  return soft ? soft_layout(p, nullptr).bytes : det_layout(p, nullptr).bytes;
+}
+
 }  // namespace
 
 extern "C" int64_t tdn_multiclass_nms_workspace_bytes(int N, int C, int B) {
-  DetPlan p;
-  if (det_plan("tdn_multiclass_nms", N, C, B, &p) != 0) return -1;
-  return det_layout(p, nullptr).bytes;
+  return det_ws_query("tdn_multiclass_nms", N, C, B, false);
+}
+extern "C" int64_t tdn_multiclass_nms_soft_workspace_bytes(int N, int C, int B) {
+  return det_ws_query("tdn_multiclass_nms_soft", N, C, B, true);
 }
 
-extern "C" int tdn_multiclass_nms(const float* boxes, int box_cols, const float* scores, const void* batch_idx,
-                                  int batch_idx_bytes, int N, int C, int B, float score_thr, float nms_thr,
-                                  int max_num, float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts,
-                                  void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* who = "tdn_multiclass_nms";
+namespace {
+int multiclass_run(const char* who, const float* boxes, int box_cols, const float* scores, const void* batch_idx,
+                   int batch_idx_bytes, int N, int C, int B, float score_thr, float nms_thr,
+                   const tdn_soft_nms_config* soft, int max_num, float* dets, int64_t* labels, int64_t* row_idx,
+                   int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
   DetPlan p;
   if (det_plan(who, N, C, B, &p) != 0) return -1;
   TDN_CHECK(box_cols == 4 || box_cols == 4 * (C - 1), "%s: box_cols=%d is neither 4 nor 4 * (C - 1)", who, box_cols);
@@ -412,13 +505,38 @@ extern "C" int tdn_multiclass_nms(const float* boxes, int box_cols, const float*
   p.A.idx = batch_idx;
   p.A.idx_kind = !batch_idx ? IDX_NONE : (batch_idx_bytes == 4 ? IDX_I32 : IDX_I64);
   p.A.box_cols = box_cols;
-  return det_run(who, p, score_thr, nms_thr, max_num, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
+  return det_run(who, p, score_thr, nms_thr, max_num, dets, labels, row_idx, counts, workspace, workspace_bytes, stream,
+                 soft);
+}
+}  // namespace
+
+extern "C" int tdn_multiclass_nms(const float* boxes, int box_cols, const float* scores, const void* batch_idx,
+                                  int batch_idx_bytes, int N, int C, int B, float score_thr, float nms_thr,
+                                  int max_num, float* dets, int64_t* labels, int64_t* row_idx, int32_t* counts,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  return multiclass_run("tdn_multiclass_nms", boxes, box_cols, scores, batch_idx, batch_idx_bytes, N, C, B, score_thr,
+                        nms_thr, nullptr, max_num, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tdn_multiclass_nms_soft(const float* boxes, int box_cols, const float* scores, const void* batch_idx,
+                                       int batch_idx_bytes, int N, int C, int B, float score_thr,
+                                       const tdn_soft_nms_config* soft, int max_num, float* dets, int64_t* labels,
+                                       int64_t* row_idx, int32_t* counts, void* workspace, int64_t workspace_bytes,
+                                       void* stream) {
+  const char* who = "tdn_multiclass_nms_soft";
+  if (tdn_soft_nms_check(who, soft) != 0) return -1;
+  return multiclass_run(who, boxes, box_cols, scores, batch_idx, batch_idx_bytes, N, C, B, score_thr, 0.f, soft,
+                        max_num, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t tdn_bbox_detections_workspace_bytes(int R, int C, int B) {
-  DetPlan p;
-  if (det_plan("tdn_bbox_detections", R, C, B, &p) != 0) return -1;
-  return det_layout(p, nullptr).bytes;
+  return det_ws_query("tdn_bbox_detections", R, C, B, false);
+}
+extern "C" int64_t tdn_bbox_detections_soft_workspace_bytes(int R, int C, int B) {
+  return det_ws_query("tdn_bbox_detections_soft", R, C, B, true);
+}
+extern "C" int64_t tdn_cascade_detections_soft_workspace_bytes(int R, int C, int B) {
+  return det_ws_query("tdn_cascade_detections_soft", R, C, B, true);
 }
 
 namespace {
@@ -436,7 +554,9 @@ int head_detections(const char* who, bool stages, const float* rois, const void*
                     int dtype, int R, int C, int reg_cols, int B, const int32_t* img_shapes, const float* scale_factors,
                     float scale_factor, const float* means4, const float* stds4, double wh_ratio_clip, float score_thr,
                     float nms_thr, int max_num, float* dense_scores, float* dense_boxes, float* dets, int64_t* labels,
-                    int64_t* row_idx, int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+                    int64_t* row_idx, int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream,
+                    const tdn_soft_nms_config* soft = nullptr) {
+  if (soft && tdn_soft_nms_check(who, soft) != 0) return -1;  // before the first launch
   DetPlan p;
   if (det_plan(who, R, C, B, &p) != 0) return -1;
   TDN_CHECK(dtype == TDN_F32 || dtype == TDN_BF16 || dtype == TDN_F16, "%s: dtype %d", who, dtype);
@@ -476,7 +596,8 @@ int head_detections(const char* who, bool stages, const float* rois, const void*
   p.A.idx = rois;
   p.A.idx_kind = IDX_ROI;
   p.A.box_cols = reg_cols == 4 ? 4 : 4 * (C - 1);
-  return det_run(who, p, score_thr, nms_thr, max_num, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
+  return det_run(who, p, score_thr, nms_thr, max_num, dets, labels, row_idx, counts, workspace, workspace_bytes, stream,
+                 soft);
 }
 
 }  // namespace
@@ -505,6 +626,36 @@ extern "C" int tdn_cascade_detections(const float* rois, const void* const* cls,
   return head_detections(who, true, rois, cls, num_stages, reg, dtype, R, C, reg_cols, B, img_shapes, scale_factors,
                          scale_factor, means4, stds4, wh_ratio_clip, score_thr, nms_thr, max_num, dense_scores,
                          dense_boxes, dets, labels, row_idx, counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tdn_bbox_detections_soft(const float* rois, const void* cls, const void* reg, int dtype, int R, int C,
+                                        int reg_cols, int B, const int32_t* img_shapes, const float* scale_factors,
+                                        float scale_factor, const float* means4, const float* stds4,
+                                        double wh_ratio_clip, float score_thr, const tdn_soft_nms_config* soft,
+                                        int max_num, float* dense_scores, float* dense_boxes, float* dets,
+                                        int64_t* labels, int64_t* row_idx, int32_t* counts, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_bbox_detections_soft";
+  if (tdn_soft_nms_check(who, soft) != 0) return -1;
+  return head_detections(who, false, rois, &cls, 1, reg, dtype, R, C, reg_cols, B, img_shapes, scale_factors,
+                         scale_factor, means4, stds4, wh_ratio_clip, score_thr, 0.f, max_num, dense_scores, dense_boxes,
+                         dets, labels, row_idx, counts, workspace, workspace_bytes, stream, soft);
+}
+
+extern "C" int tdn_cascade_detections_soft(const float* rois, const void* const* cls, int num_stages, const void* reg,
+                                           int dtype, int R, int C, int reg_cols, int B, const int32_t* img_shapes,
+                                           const float* scale_factors, float scale_factor, const float* means4,
+                                           const float* stds4, double wh_ratio_clip, float score_thr,
+                                           const tdn_soft_nms_config* soft, int max_num, float* dense_scores,
+                                           float* dense_boxes, float* dets, int64_t* labels, int64_t* row_idx,
+                                           int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "tdn_cascade_detections_soft";
+  if (tdn_soft_nms_check(who, soft) != 0) return -1;
+  TDN_CHECK(cls && num_stages >= 1 && num_stages <= TDN_CASCADE_MAX_STAGES, "%s: %d stages (1..%d)", who, num_stages,
+            TDN_CASCADE_MAX_STAGES);
+  return head_detections(who, true, rois, cls, num_stages, reg, dtype, R, C, reg_cols, B, img_shapes, scale_factors,
+                         scale_factor, means4, stds4, wh_ratio_clip, score_thr, 0.f, max_num, dense_scores, dense_boxes,
+                         dets, labels, row_idx, counts, workspace, workspace_bytes, stream, soft);
 }
 
 // ---- box refinement between the stages of a cascade ---------------------------------------------------

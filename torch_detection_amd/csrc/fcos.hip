@@ -536,7 +536,8 @@ int fl_pointers(const char* who, const tdn_fcos_level* levels, int L, const int6
 
 // ---- detections ----------------------------------------------------------------------------------------------------------
 // The architecture of dense_detect.hip with A = 1: a key launch over the levels that select, one workgroup per (image,
-// level) for the radix threshold, the ordered compaction and the dense rows, tdn_multiclass_nms, a gather.
+// level) for the radix threshold, the ordered compaction and the dense rows, tdn_multiclass_nms (tdn_fcos_detections_soft:
+// tdn_multiclass_nms_soft), a gather.
 constexpr int FD_SEG_MAX = TDN_NMS_SEG_MAX;
 constexpr int KEY_THREADS = 256;
 constexpr int KEY_TILE = 8192;                 // floats of LDS per workgroup of the key kernel (32 KB)
@@ -761,7 +762,7 @@ struct FdPlan {
 };
 
 // the checks and the geometry the plan query, the workspace query and the call share; pointers may be null
-int fd_plan(const char* who, const tdn_fcos_level* levels, int L, int B, const tdn_fcos_det_config* cfg, FdPlan* out) {
+int fd_plan(const char* who, const tdn_fcos_level* levels, int L, int B, const tdn_fcos_det_config* cfg, FdPlan* out, bool soft = false) {
   FcGeo G;
   if (fc_geo(who, levels, L, false, &G) != 0) return -1;
   TDN_CHECK(cfg, "%s: NULL config", who);
@@ -773,7 +774,7 @@ int fd_plan(const char* who, const tdn_fcos_level* levels, int L, int B, const t
             FD_SEG_MAX);
   TDN_CHECK(cfg->max_num >= 1 && cfg->max_num <= TDN_RPN_MAX_NUM, "%s: max_num=%d out of 1..%d", who, cfg->max_num,
             TDN_RPN_MAX_NUM);
-  TDN_CHECK(cfg->score_thr - cfg->score_thr == 0.f && cfg->nms_thr - cfg->nms_thr == 0.f,
+  TDN_CHECK(cfg->score_thr - cfg->score_thr == 0.f && (soft || cfg->nms_thr - cfg->nms_thr == 0.f),
             "%s: score_thr / nms_thr must be finite", who);
   memset(out, 0, sizeof(*out));
   FdArgs& P = out->A;
@@ -820,7 +821,8 @@ int fd_plan(const char* who, const tdn_fcos_level* levels, int L, int B, const t
   P.N = G.N;
   P.NK = (int)NK;
   out->key_blocks = (int)blocks;
-  out->nms_bytes = tdn_multiclass_nms_workspace_bytes((int)out->rows, C + 1, B);
+  out->nms_bytes = soft ? tdn_multiclass_nms_soft_workspace_bytes((int)out->rows, C + 1, B)
+                        : tdn_multiclass_nms_workspace_bytes((int)out->rows, C + 1, B);
   return out->nms_bytes < 0 ? -1 : 0;
 }
 
@@ -864,15 +866,22 @@ extern "C" int64_t tdn_fcos_detections_workspace_bytes(const tdn_fcos_level* lev
   return fd_layout(p, nullptr).bytes;
 }
 
-extern "C" int tdn_fcos_detections(const tdn_fcos_level* levels, int nlevels, int B, const int32_t* img_shapes,
-                                   const float* scale_factors, const float* scales, const tdn_fcos_det_config* cfg,
-                                   float* dense_scores, float* dense_boxes, int32_t* batch_idx,
-                                   int64_t* dense_point_idx, float* dets, int64_t* labels, int64_t* row_idx,
-                                   int64_t* point_idx, int32_t* counts, void* workspace, int64_t workspace_bytes,
-                                   void* stream) {
-  const char* who = "tdn_fcos_detections";
+extern "C" int64_t tdn_fcos_detections_soft_workspace_bytes(const tdn_fcos_level* levels, int nlevels, int B,
+                                                            const tdn_fcos_det_config* cfg) {
   FdPlan p;
-  if (fd_plan(who, levels, nlevels, B, cfg, &p) != 0) return -1;
+  if (fd_plan("tdn_fcos_detections_soft", levels, nlevels, B, cfg, &p, true) != 0) return -1;
+  return fd_layout(p, nullptr).bytes;
+}
+
+namespace {
+// tdn_fcos_detections (soft == null) and tdn_fcos_detections_soft
+int fd_run(const char* who, const tdn_fcos_level* levels, int nlevels, int B, const int32_t* img_shapes,
+           const float* scale_factors, const float* scales, const tdn_fcos_det_config* cfg,
+           const tdn_soft_nms_config* soft, float* dense_scores, float* dense_boxes, int32_t* batch_idx,
+           int64_t* dense_point_idx, float* dets, int64_t* labels, int64_t* row_idx, int64_t* point_idx,
+           int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+  FdPlan p;
+  if (fd_plan(who, levels, nlevels, B, cfg, &p, soft != nullptr) != 0) return -1;
   TDN_CHECK(scale_factors || cfg->scale_factor == 0.f ||
                 (cfg->scale_factor > 0.f && cfg->scale_factor - cfg->scale_factor == 0.f),
             "%s: scale_factor must be positive and finite (0: none)", who);
@@ -895,14 +904,43 @@ extern "C" int tdn_fcos_detections(const tdn_fcos_level* levels, int nlevels, in
   FD_LAUNCH(fcos_select_decode_kernel, cfg->dtype, dim3(B * nlevels), dim3(BLK), st, P, (const uint32_t*)w.keys,
             dense_scores, dense_boxes, batch_idx, dense_point_idx);
   TDN_LAUNCH_CHECK();
-  const int rc = tdn_multiclass_nms(dense_boxes, 4, dense_scores, batch_idx, 4, (int)p.rows, P.C + 1, B, cfg->score_thr,
-                                    cfg->nms_thr, cfg->max_num, dets, labels, row_idx, counts, w.nms, p.nms_bytes, stream);
+  const int rc = soft ? tdn_multiclass_nms_soft(dense_boxes, 4, dense_scores, batch_idx, 4, (int)p.rows, P.C + 1, B,
+                                                cfg->score_thr, soft, cfg->max_num, dets, labels, row_idx, counts, w.nms,
+                                                p.nms_bytes, stream)
+                      : tdn_multiclass_nms(dense_boxes, 4, dense_scores, batch_idx, 4, (int)p.rows, P.C + 1, B,
+                                           cfg->score_thr, cfg->nms_thr, cfg->max_num, dets, labels, row_idx, counts,
+                                           w.nms, p.nms_bytes, stream);
   if (rc != 0) return rc;
   const int nd = B * cfg->max_num;
   TDN_LAUNCH(fcos_point_gather_kernel, dim3((nd + 255) / 256), dim3(256), 0, st, (const int64_t*)row_idx,
              (const int64_t*)dense_point_idx, nd, point_idx);
   TDN_LAUNCH_CHECK();
   return 0;
+}
+}  // namespace
+
+extern "C" int tdn_fcos_detections(const tdn_fcos_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                                   const float* scale_factors, const float* scales, const tdn_fcos_det_config* cfg,
+                                   float* dense_scores, float* dense_boxes, int32_t* batch_idx,
+                                   int64_t* dense_point_idx, float* dets, int64_t* labels, int64_t* row_idx,
+                                   int64_t* point_idx, int32_t* counts, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  return fd_run("tdn_fcos_detections", levels, nlevels, B, img_shapes, scale_factors, scales, cfg, nullptr, dense_scores,
+                dense_boxes, batch_idx, dense_point_idx, dets, labels, row_idx, point_idx, counts, workspace,
+                workspace_bytes, stream);
+}
+
+extern "C" int tdn_fcos_detections_soft(const tdn_fcos_level* levels, int nlevels, int B, const int32_t* img_shapes,
+                                        const float* scale_factors, const float* scales,
+                                        const tdn_fcos_det_config* cfg, const tdn_soft_nms_config* soft,
+                                        float* dense_scores, float* dense_boxes, int32_t* batch_idx,
+                                        int64_t* dense_point_idx, float* dets, int64_t* labels, int64_t* row_idx,
+                                        int64_t* point_idx, int32_t* counts, void* workspace, int64_t workspace_bytes,
+                                        void* stream) {
+  const char* who = "tdn_fcos_detections_soft";
+  if (tdn_soft_nms_check(who, soft) != 0) return -1;  // before the first launch
+  return fd_run(who, levels, nlevels, B, img_shapes, scale_factors, scales, cfg, soft, dense_scores, dense_boxes,
+                batch_idx, dense_point_idx, dets, labels, row_idx, point_idx, counts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t tdn_fcos_loss_workspace_bytes(const tdn_fcos_level* levels, int nlevels, int B,

@@ -16,7 +16,7 @@ anchor_head_detections_plan = _d.anchor_head_detections_plan
 
 def anchor_head_detections(cls_scores, bbox_preds, anchors, img_shapes, scale_factors=None, nms_pre=1000,
                            score_thr=0.05, nms_thr=0.5, max_per_img=100, target_means=(0, 0, 0, 0),
-                           target_stds=(1, 1, 1, 1), wh_ratio_clip=16 / 1000, return_dense=False):
+                           target_stds=(1, 1, 1, 1), wh_ratio_clip=16 / 1000, return_dense=False, nms=None):
     """Detections from a sigmoid anchor head's outputs (mmdetection's ``AnchorHead.get_bboxes`` for a whole batch).
 
     ``cls_scores[l]``: (B, A*C, H_l, W_l) logits, class channel ``a*C + c``; ``bbox_preds[l]``: (B, 4A, H_l, W_l)
@@ -35,9 +35,9 @@ def anchor_head_detections(cls_scores, bbox_preds, anchors, img_shapes, scale_fa
     ``dense_boxes`` (B*K, 4), ``batch_idx`` (B*K,) int32, ``dense_anchor_idx`` (B*K,) int64 and ``row_idx``
     (B, max_per_img) int64: ``multiclass_nms(dense_boxes, dense_scores, batch_idx, B, ...)`` reproduces the first
     outputs bit for bit.  Limits: 1..8 levels, B 1..64, C 1..1023, ``nms_pre`` 0..4096, B*K <= 2^18, ``max_per_img``
-    1..8192.  NaN logits are unsupported."""
+    1..8192.  NaN logits are unsupported.  ``nms``: as :func:`multiclass_nms` takes it (soft-NMS: one launch fewer)."""
     out = _d.anchor_head_detections(cls_scores, bbox_preds, anchors, img_shapes, scale_factors, nms_pre, score_thr,
-                                    nms_thr, max_per_img, target_means, target_stds, wh_ratio_clip)
+                                    nms_thr, max_per_img, target_means, target_stds, wh_ratio_clip, nms)
     return out if return_dense else out[:4]
 
 

@@ -11,7 +11,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._args import CODES, batch, f4, integer, number, on_device, tensor
+from ._args import CODES, batch, f4, integer, nms_config, number, on_device, tensor
 from .ops import _aligned_ws, _clip, _ptr, _workspace  # noqa: F401  (_workspace: swapped by the guard)
 from .target_ops import _boxes, _gt, _thresholds, _valid
 
@@ -33,15 +33,17 @@ def _levels(level_shapes, num_anchors, num_classes):
     return arr, L, A, C
 
 
-def _config(dtype, A, C, nms_pre, max_per_img, score_thr, nms_thr, means, stds, wh_ratio_clip):
+def _config(dtype, A, C, nms_pre, max_per_img, score_thr, nms_thr, means, stds, wh_ratio_clip, nms=None):
+    """-> (tdn_dense_config, soft); ``soft`` is None on the greedy path, else ``nms``' tdn_soft_nms_config."""
     cfg = _lib.DenseConfig()
     cfg.dtype, cfg.num_anchors, cfg.num_classes = CODES[dtype], A, C
     cfg.nms_pre = integer(nms_pre, "nms_pre", 0, _lib.NMS_SEG_MAX)
     cfg.max_num = integer(max_per_img, "max_per_img", 1, _lib.RPN_MAX_NUM)
-    cfg.score_thr, cfg.nms_thr = number(score_thr, "score_thr"), number(nms_thr, "nms_thr")
+    cfg.score_thr = number(score_thr, "score_thr")
+    cfg.nms_thr, soft = nms_config(nms, nms_thr)
     cfg.means, cfg.stds = f4(means, "target_means"), f4(stds, "target_stds")
     cfg.wh_ratio_clip = _clip(wh_ratio_clip)
-    return cfg
+    return cfg, soft
 
 
 def _kept(arr, L, B, A, C, nms_pre):
@@ -68,7 +70,7 @@ def anchor_head_detections_plan(level_shapes, num_imgs, num_anchors, num_classes
     kept (k_l per level)."""
     arr, L, A, C = _levels(level_shapes, num_anchors, num_classes)
     B = batch(int(num_imgs))
-    cfg = _config(F32, A, C, nms_pre, 1, 0.0, 0.5, (0, 0, 0, 0), (1, 1, 1, 1), 16 / 1000)
+    cfg, _ = _config(F32, A, C, nms_pre, 1, 0.0, 0.5, (0, 0, 0, 0), (1, 1, 1, 1), 16 / 1000)
     _kept(arr, L, B, A, C, cfg.nms_pre)
     out = (ctypes.c_int32 * 16)()
     if _lib.load().tdn_dense_detections_plan(arr, L, B, ctypes.byref(cfg), out) != 0:
@@ -78,9 +80,9 @@ def anchor_head_detections_plan(level_shapes, num_imgs, num_anchors, num_classes
 
 
 def anchor_head_detections(cls_scores, bbox_preds, anchors, img_shapes, scale_factors, nms_pre, score_thr, nms_thr,
-                           max_per_img, target_means, target_stds, wh_ratio_clip):
+                           max_per_img, target_means, target_stds, wh_ratio_clip, nms=None):
     """Sigmoid scores, decode, per-level top-nms_pre, per-class NMS and per-image top-k of a single-stage head's outputs
-    (tdn_dense_detections).  Returns (dets, labels, anchor_idx, counts, dense_scores, dense_boxes, batch_idx,
+    (tdn_dense_detections; with a soft ``nms`` tdn_dense_detections_soft).  Returns (dets, labels, anchor_idx, counts, dense_scores, dense_boxes, batch_idx,
     dense_anchor_idx, row_idx)."""
     L = len(cls_scores)
     if not (1 <= L <= _lib.DENSE_MAX_LEVELS) or len(bbox_preds) != L:
@@ -97,7 +99,8 @@ def anchor_head_detections(cls_scores, bbox_preds, anchors, img_shapes, scale_fa
     C = AC // A
     if not 1 <= C <= _lib.DET_MAX_CLASSES - 1:
         raise ValueError("C = %d classes: must be in 1..%d" % (C, _lib.DET_MAX_CLASSES - 1))
-    cfg = _config(dtype, A, C, nms_pre, max_per_img, score_thr, nms_thr, target_means, target_stds, wh_ratio_clip)
+    cfg, soft = _config(dtype, A, C, nms_pre, max_per_img, score_thr, nms_thr, target_means, target_stds, wh_ratio_clip,
+                        nms)
     arr = (_lib.DenseLevel * L)()
     named, sizes = [], []
     for l, (c, d) in enumerate(zip(cls_scores, bbox_preds)):
@@ -136,8 +139,8 @@ def anchor_head_detections(cls_scores, bbox_preds, anchors, img_shapes, scale_fa
     on_device(named + [("img_shapes", img_shapes), ("scale_factors", scale_t)])
     dev = cls_scores[0].device
     lib = _lib.load()
-    nbytes = _lib.ws_bytes(lib.tdn_dense_detections_workspace_bytes(arr, L, B, ctypes.byref(cfg)),
-                           "anchor_head_detections")
+    query = lib.tdn_dense_detections_soft_workspace_bytes if soft else lib.tdn_dense_detections_workspace_bytes
+    nbytes = _lib.ws_bytes(query(arr, L, B, ctypes.byref(cfg)), "anchor_head_detections")
     M = cfg.max_num
     dense_scores = torch.empty(B * K, C + 1, dtype=F32, device=dev)
     dense_boxes = torch.empty(B * K, 4, dtype=F32, device=dev)
@@ -149,10 +152,14 @@ def anchor_head_detections(cls_scores, bbox_preds, anchors, img_shapes, scale_fa
     anchor_idx = torch.empty(B, M, dtype=torch.int64, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     ws, wp = _aligned_ws(nbytes, dev)
-    _lib.check(lib.tdn_dense_detections(arr, L, B, _ptr(img_shapes), _ptr(scale_t), ctypes.byref(cfg),
-                                        _ptr(dense_scores), _ptr(dense_boxes), _ptr(batch_idx), _ptr(dense_anchor_idx),
-                                        _ptr(dets), _ptr(labels), _ptr(row_idx), _ptr(anchor_idx), _ptr(counts), wp,
-                                        nbytes, _lib.stream_ptr()), "tdn_dense_detections")
+    outs = (_ptr(dense_scores), _ptr(dense_boxes), _ptr(batch_idx), _ptr(dense_anchor_idx), _ptr(dets), _ptr(labels),
+            _ptr(row_idx), _ptr(anchor_idx), _ptr(counts), wp, nbytes, _lib.stream_ptr())
+    if soft:
+        _lib.check(lib.tdn_dense_detections_soft(arr, L, B, _ptr(img_shapes), _ptr(scale_t), ctypes.byref(cfg),
+                                                 ctypes.byref(soft), *outs), "tdn_dense_detections_soft")
+    else:
+        _lib.check(lib.tdn_dense_detections(arr, L, B, _ptr(img_shapes), _ptr(scale_t), ctypes.byref(cfg), *outs),
+                   "tdn_dense_detections")
     return dets, labels, anchor_idx, counts, dense_scores, dense_boxes, batch_idx, dense_anchor_idx, row_idx
 
 

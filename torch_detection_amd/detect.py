@@ -13,7 +13,8 @@ from . import detect_ops as _d
 __all__ = ["multiclass_nms", "bbox_head_detections"]
 
 
-def multiclass_nms(multi_bboxes, multi_scores, batch_idx, num_imgs, score_thr=0.05, nms_thr=0.5, max_num=100):
+def multiclass_nms(multi_bboxes, multi_scores, batch_idx, num_imgs, score_thr=0.05, nms_thr=0.5, max_num=100,
+                   nms=None):
     """Per-class NMS and per-image top-k.
 
     ``multi_bboxes``: (N, 4(C-1)) float32 class-specific boxes (class ``c`` reads columns ``4(c-1)..``) or (N, 4)
@@ -27,13 +28,18 @@ def multiclass_nms(multi_bboxes, multi_scores, batch_idx, num_imgs, score_thr=0.
     in that order.  Returns ``dets`` (B, max_num, 5) float32 = [x1, y1, x2, y2, score], ``labels`` (B, max_num) int64
     (``c - 1``), ``row_idx`` (B, max_num) int64 (the source row) and ``counts`` (B,) int32; unused rows are 0 / -1 / -1.
     A segment holds at most 4096 candidates: an image with a longer one gets ``counts[b] = -1`` and empty rows.  NaN
-    scores are unsupported.  Limits: ``num_imgs`` 1..64, C 2..1024, N <= 2^18, ``max_num`` 1..8192."""
-    return _d.multiclass_nms(multi_bboxes, multi_scores, batch_idx, num_imgs, score_thr, nms_thr, max_num)
+    scores are unsupported.  Limits: ``num_imgs`` 1..64, C 2..1024, N <= 2^18, ``max_num`` 1..8192.
+
+    ``nms``: ``None`` (greedy NMS at ``nms_thr``), ``dict(type='nms', iou_thr=t)`` (the same at ``t``) or
+    ``dict(type='soft_nms', iou_thr=0.5, min_score=0.001, method='linear', sigma=0.5)`` (``method`` 'linear', 'gaussian'
+    or 'naive'): soft-NMS per (image, class), ``dets[..., 4]`` is then the decayed score and the order is
+    by it.  Giving ``nms`` together with a ``nms_thr`` other than 0.5 is refused."""
+    return _d.multiclass_nms(multi_bboxes, multi_scores, batch_idx, num_imgs, score_thr, nms_thr, max_num, nms)
 
 
 def bbox_head_detections(rois, cls_score, bbox_pred, img_shapes, scale_factors=None, score_thr=0.05, nms_thr=0.5,
                          max_per_img=100, target_means=(0, 0, 0, 0), target_stds=(0.1, 0.1, 0.2, 0.2),
-                         wh_ratio_clip=16 / 1000, return_dense=False):
+                         wh_ratio_clip=16 / 1000, return_dense=False, nms=None):
     """Detections from the box head's outputs (mmdetection's ``get_det_bboxes`` for a whole batch).
 
     ``rois``: (R, 5) float32 = (batch_idx, x1, y1, x2, y2) as ``roi_align`` takes them (rows with an index outside
@@ -46,7 +52,7 @@ def bbox_head_detections(rois, cls_score, bbox_pred, img_shapes, scale_factors=N
     then divided by the image's scale factor when one is given; then :func:`multiclass_nms` with ``batch_idx =
     rois[:, 0]``.  Returns ``(dets, labels, row_idx, counts)`` as :func:`multiclass_nms`; with ``return_dense=True``
     also the (R, C) float32 scores and the (R, 4(C-1)) or (R, 4) float32 boxes the selection read (rows of ignored RoIs
-    are 0).  Limits: those of :func:`multiclass_nms`, R <= 2^18."""
+    are 0).  ``nms``: as :func:`multiclass_nms` takes it.  Limits: those of :func:`multiclass_nms`, R <= 2^18."""
     out = _d.bbox_head_detections(rois, cls_score, bbox_pred, img_shapes, scale_factors, score_thr, nms_thr, max_per_img,
-                                  target_means, target_stds, wh_ratio_clip)
+                                  target_means, target_stds, wh_ratio_clip, nms)
     return out if return_dense else out[:4]

@@ -99,7 +99,7 @@ def fcos_loss(cls_scores, bbox_preds, centernesses, labels, bbox_targets, scales
 
 
 def fcos_detections(cls_scores, bbox_preds, centernesses, strides, img_shapes, scales=None, scale_factors=None,
-                    nms_pre=1000, score_thr=0.05, nms_thr=0.5, max_per_img=100, return_dense=False):
+                    nms_pre=1000, score_thr=0.05, nms_thr=0.5, max_per_img=100, return_dense=False, nms=None):
     """Detections from an FCOS head's outputs (mmdetection v1's ``FCOSHead.get_bboxes`` for a whole batch).
 
     Head outputs and ``scales`` as in :func:`fcos_loss`; ``strides``: one integer per level; ``img_shapes``: CUDA int32
@@ -116,7 +116,7 @@ def fcos_detections(cls_scores, bbox_preds, centernesses, strides, img_shapes, s
     (B*K,) int32, ``dense_point_idx`` (B*K,) int64 and ``row_idx`` (B, max_per_img) int64:
     ``multiclass_nms(dense_boxes, dense_scores, batch_idx, B, ...)`` reproduces the first outputs bit for bit.  Limits:
     1..8 levels, B 1..64, C 1..1023, ``nms_pre`` 0..4096, B*K <= 2^18, ``max_per_img`` 1..8192.  NaN logits are
-    unsupported."""
+    unsupported.  ``nms``: as :func:`multiclass_nms` takes it (soft-NMS: one launch fewer)."""
     out = _f.fcos_detections(cls_scores, bbox_preds, centernesses, strides, img_shapes, scales, scale_factors, nms_pre,
-                             score_thr, nms_thr, max_per_img)
+                             score_thr, nms_thr, max_per_img, nms)
     return out if return_dense else out[:4]

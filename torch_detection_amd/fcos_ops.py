@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _lib
-from ._args import CODES, batch, integer, number, on_device, tensor
+from ._args import CODES, batch, integer, nms_config, number, on_device, tensor
 from .loss_ops import _layout
 from .ops import _aligned_ws, _ptr, _workspace  # noqa: F401  (_workspace: swapped by the guard)
 from .target_ops import _gt
@@ -208,13 +208,15 @@ def fcos_loss_bwd(cls_scores, bbox_preds, centernesses, labels, bbox_targets, sc
     return dcls, dreg, dctr, dscales
 
 
-def _det_config(dtype, C, nms_pre, max_per_img, score_thr, nms_thr):
+def _det_config(dtype, C, nms_pre, max_per_img, score_thr, nms_thr, nms=None):
+    """-> (tdn_fcos_det_config, soft); ``soft`` is None on the greedy path, else ``nms``' tdn_soft_nms_config."""
     cfg = _lib.FcosDetConfig()
     cfg.dtype, cfg.num_classes = CODES[dtype], C
     cfg.nms_pre = integer(nms_pre, "nms_pre", 0, _lib.NMS_SEG_MAX)
     cfg.max_num = integer(max_per_img, "max_per_img", 1, _lib.RPN_MAX_NUM)
-    cfg.score_thr, cfg.nms_thr = number(score_thr, "score_thr"), number(nms_thr, "nms_thr")
-    return cfg
+    cfg.score_thr = number(score_thr, "score_thr")
+    cfg.nms_thr, soft = nms_config(nms, nms_thr)
+    return cfg, soft
 
 
 def _kept(arr, L, B, C, nms_pre):
@@ -243,7 +245,7 @@ def fcos_detections_plan(featmap_sizes, num_imgs, num_classes, nms_pre):
     C = integer(num_classes, "num_classes", 1, _lib.DET_MAX_CLASSES - 1)
     for l in range(L):
         arr[l].cls_nhwc = 1
-    cfg = _det_config(F32, C, nms_pre, 1, 0.0, 0.5)
+    cfg, _ = _det_config(F32, C, nms_pre, 1, 0.0, 0.5)
     _kept(arr, L, B, C, cfg.nms_pre)
     out = (ctypes.c_int32 * 16)()
     if _lib.load().tdn_fcos_detections_plan(arr, L, B, ctypes.byref(cfg), out) != 0:
@@ -253,13 +255,13 @@ def fcos_detections_plan(featmap_sizes, num_imgs, num_classes, nms_pre):
 
 
 def fcos_detections(cls_scores, bbox_preds, centernesses, strides, img_shapes, scales, scale_factors, nms_pre,
-                    score_thr, nms_thr, max_per_img):
+                    score_thr, nms_thr, max_per_img, nms=None):
     """Centre-ness weighted sigmoid scores, point +- distance decode, per-level top-nms_pre, per-class NMS and per-image
-    top-k of an FCOS head's outputs (tdn_fcos_detections).  Returns (dets, labels, point_idx, counts, dense_scores,
+    top-k of an FCOS head's outputs (tdn_fcos_detections; with a soft ``nms`` tdn_fcos_detections_soft).  Returns (dets, labels, point_idx, counts, dense_scores,
     dense_boxes, batch_idx, dense_point_idx, row_idx)."""
     arr, L, B, C, N, dtype, named = _heads(cls_scores, bbox_preds, centernesses, list(strides), "fcos_detections",
                                            _lib.DET_MAX_CLASSES - 1)
-    cfg = _det_config(dtype, C, nms_pre, max_per_img, score_thr, nms_thr)
+    cfg, soft = _det_config(dtype, C, nms_pre, max_per_img, score_thr, nms_thr, nms)
     tensor(img_shapes, "img_shapes", torch.int32, (B, 2))
     _scales(scales, L)
     scale_t = None
@@ -272,7 +274,8 @@ def fcos_detections(cls_scores, bbox_preds, centernesses, strides, img_shapes, s
     on_device(named + [("img_shapes", img_shapes), ("scales", scales), ("scale_factors", scale_t)])
     dev = cls_scores[0].device
     lib = _lib.load()
-    nbytes = _lib.ws_bytes(lib.tdn_fcos_detections_workspace_bytes(arr, L, B, ctypes.byref(cfg)), "fcos_detections")
+    query = lib.tdn_fcos_detections_soft_workspace_bytes if soft else lib.tdn_fcos_detections_workspace_bytes
+    nbytes = _lib.ws_bytes(query(arr, L, B, ctypes.byref(cfg)), "fcos_detections")
     M = cfg.max_num
     dense_scores = torch.empty(B * K, C + 1, dtype=F32, device=dev)
     dense_boxes = torch.empty(B * K, 4, dtype=F32, device=dev)
@@ -284,8 +287,12 @@ def fcos_detections(cls_scores, bbox_preds, centernesses, strides, img_shapes, s
     point_idx = torch.empty(B, M, dtype=torch.int64, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     ws, wp = _aligned_ws(nbytes, dev)
-    _lib.check(lib.tdn_fcos_detections(arr, L, B, _ptr(img_shapes), _ptr(scale_t), _ptr(scales), ctypes.byref(cfg),
-                                       _ptr(dense_scores), _ptr(dense_boxes), _ptr(batch_idx), _ptr(dense_point_idx),
-                                       _ptr(dets), _ptr(labels), _ptr(row_idx), _ptr(point_idx), _ptr(counts), wp,
-                                       nbytes, _lib.stream_ptr()), "tdn_fcos_detections")
+    outs = (_ptr(dense_scores), _ptr(dense_boxes), _ptr(batch_idx), _ptr(dense_point_idx), _ptr(dets), _ptr(labels),
+            _ptr(row_idx), _ptr(point_idx), _ptr(counts), wp, nbytes, _lib.stream_ptr())
+    if soft:
+        _lib.check(lib.tdn_fcos_detections_soft(arr, L, B, _ptr(img_shapes), _ptr(scale_t), _ptr(scales),
+                                                ctypes.byref(cfg), ctypes.byref(soft), *outs), "tdn_fcos_detections_soft")
+    else:
+        _lib.check(lib.tdn_fcos_detections(arr, L, B, _ptr(img_shapes), _ptr(scale_t), _ptr(scales), ctypes.byref(cfg),
+                                           *outs), "tdn_fcos_detections")
     return dets, labels, point_idx, counts, dense_scores, dense_boxes, batch_idx, dense_point_idx, row_idx

@@ -1000,7 +1000,7 @@ class RetinaHead(nn.Module):
 
     def get_bboxes(self, cls_scores, bbox_preds, anchors, img_shapes, scale_factors=None, **test_cfg):
         """``anchor_head_detections`` with the head's means / stds on the head's outputs, in place; defaults nms_pre 1000,
-        score_thr 0.05, nms_thr 0.5, max_per_img 100."""
+        score_thr 0.05, nms_thr 0.5, max_per_img 100.  ``nms=dict(type='soft_nms', ...)`` is forwarded as it is."""
         cfg = dict(nms_pre=1000, score_thr=0.05, nms_thr=0.5, max_per_img=100, target_means=self.target_means,
                    target_stds=self.target_stds)
         cfg.update(test_cfg)
@@ -1386,7 +1386,7 @@ class FCOSHead(nn.Module):
 
     def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_shapes, scale_factors=None, **test_cfg):
         """``fcos_detections`` with the head's strides and ``Scale``s on the head's outputs, in place; defaults nms_pre
-        1000, score_thr 0.05, nms_thr 0.5, max_per_img 100."""
+        1000, score_thr 0.05, nms_thr 0.5, max_per_img 100.  ``nms=dict(type='soft_nms', ...)`` is forwarded as it is."""
         n = len(cls_scores)
         cfg = dict(nms_pre=1000, score_thr=0.05, nms_thr=0.5, max_per_img=100)
         cfg.update(test_cfg)
