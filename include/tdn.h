@@ -984,6 +984,52 @@ int tdn_fcos_detections_soft(const tdn_fcos_level* levels, int nlevels, int B, c
                              int64_t* row_idx, int64_t* point_idx, int32_t* counts, void* workspace,
                              int64_t workspace_bytes, void* stream);
 
+/* ---- gradient-harmonised losses of the dense anchor heads: GHM-C and GHM-R with their gradients (the
+ *      project's own spec in the lineage of mmdetection v1's GHMC / GHMR; tests/ghm_ref.py restates it) ----
+ * levels, labels, label_weights, bbox_targets and bbox_weights are tdn_loss_dense_fwd's.  A class element (b, n, c) is
+ * valid iff label_weights[b][n] > 0, a box element (b, n, j) iff bbox_weights[b][n][j] > 0; a weight's value is used for
+ * nothing else and an invalid element is never evaluated (loss 0, gradient exactly 0, whatever its logit).  Rows: with
+ * TDN_GHM_SCOPE_LEVEL every level is a row, with TDN_GHM_SCOPE_BATCH all levels are one; tot[r] = max(valid elements of
+ * row r, 1).  Per valid element, fp32 in the order written:
+ *   GHM-C  e = soft_exp(-|x|) (the library's own fp32 exponential, as in tdn_multiclass_nms_soft); sigma(z) = z >= 0 ?
+ *          1 / (1 + e) : e / (1 + e); g = t ? sigma(-x) : sigma(x); l = max(t ? -x : x, 0) + log1pf(e); dl = t ? -g : g
+ *   GHM-R  d = pred - target; q = sqrt(d d + mu2), mu2 = fp32(mu mu in double); g = |d| / q; l = (d d) / (q + mu);
+ *          dl = d / q
+ *   bin    the i in [0, bins) with edge[i] <= g < edge[i + 1], edge[i] = fp32(i) / fp32(bins), the last bin closed above;
+ *          a NaN g lies in no bin: the element counts in tot and its loss term and gradient are that NaN
+ * Weights, per kind, rows in order, bins in order, skipping bins with cnt[r][i] == 0: with momentum > 0
+ * acc[i] = momentum acc[i] + (1 - momentum) float(cnt) and w = float(tot) / acc[i], else w = float(tot) / float(cnt);
+ * beta[r][i] = w / float(non-empty bins of row r).  acc_cls fp32 [bins_cls] / acc_reg fp32 [bins_reg] are the caller's
+ * state, updated in place row after row by every forward call (NULL allowed iff that momentum is 0).
+ * losses fp32 [2] = per kind sum over rows of (fp64 sum of fp32 beta l) / tot[r], in an order fixed by the shapes,
+ * rounded once.  table fp32 [2][TDN_LOSS_MAX_LEVELS][TDN_GHM_TABLE_STRIDE], written in full by the forward and read by
+ * the backward: per (kind, row) beta [64], float(cnt) [64], float(tot), the number of non-empty bins, the number of valid
+ * elements in no bin, zeros.  Backward: d x = (beta dl) (g[kind] / float(tot[r])), rounded to nearest even into the
+ * head's dtype; it touches neither the counts nor acc.  Forward: four launches, backward: one; no float atomics, no
+ * host synchronisation.  Limits: tdn_loss_dense_fwd's, bins 1..TDN_GHM_MAX_BINS, momentum in [0, 1), mu finite and > 0.
+ * workspace: tdn_ghm_workspace_bytes() bytes, 256-aligned. */
+#define TDN_GHM_MAX_BINS 64
+#define TDN_GHM_TABLE_STRIDE 136
+#define TDN_GHM_SCOPE_LEVEL 0
+#define TDN_GHM_SCOPE_BATCH 1
+typedef struct tdn_ghm_config {
+  int32_t dtype;               /* TDN_BF16 / TDN_F16 / TDN_F32, of every head output and gradient */
+  int32_t num_anchors;         /* A */
+  int32_t num_classes;         /* C: label k in 1..C is one-hot on class channel k-1, 0 is background */
+  int32_t bins_cls, bins_reg;  /* 1..TDN_GHM_MAX_BINS */
+  int32_t scope;               /* TDN_GHM_SCOPE_LEVEL / TDN_GHM_SCOPE_BATCH */
+  float momentum_cls, momentum_reg; /* in [0, 1) */
+  float mu;                    /* GHM-R's knee, finite and > 0 */
+  int32_t reserved;
+} tdn_ghm_config;
+int64_t tdn_ghm_workspace_bytes(const tdn_loss_level* levels, int num_levels, int B, const tdn_ghm_config* cfg);
+int tdn_ghm_fwd(const tdn_loss_level* levels, int num_levels, int B, const tdn_ghm_config* cfg, const int64_t* labels,
+                const float* label_weights, const float* bbox_targets, const float* bbox_weights, float* acc_cls,
+                float* acc_reg, float* losses, float* table, void* workspace, int64_t workspace_bytes, void* stream);
+int tdn_ghm_bwd(const tdn_loss_level* levels, int num_levels, int B, const tdn_ghm_config* cfg, const int64_t* labels,
+                const float* label_weights, const float* bbox_targets, const float* bbox_weights, const float* g,
+                const float* table, void* stream);
+
 /* ---- the mask branch of Mask R-CNN: polygon mask targets, mask loss, mask paste (the project's own
  *      spec in the mmdetection-v1 lineage of mask_target / FCNMaskHead.loss / get_seg_masks) ----
  * Polygons: poly_xy fp32 [P][2] vertices in the network-input frame; poly_offsets int32 [Q + 1]: polygon q owns vertices

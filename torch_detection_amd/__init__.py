@@ -17,7 +17,8 @@ conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask 
 ``DeformConv`` / ``ModulatedDeformConv`` / ``DeformConvPack`` / ``ModulatedDeformConvPack``, and Cascade R-CNN's
 ``refine_bboxes`` / ``cascade_detections`` / ``CascadeRoIHead``, and Libra R-CNN's ``BFP`` neck,
 ``sample_assigned_iou_balanced`` / ``sample_rois(neg_sampler='iou_balanced')`` and ``bbox_head_loss(reg_loss='balanced_l1')``,
-and Mask Scoring R-CNN's ``MaskIoUHead`` with ``mask_iou_stem`` / ``mask_iou_target`` / ``mask_iou_loss`` / ``mask_scores``, and CARAFE upsampling: the ``carafe`` op, ``CARAFEPack`` and the ``FPN_CARAFE`` neck).  Everything computes through libtdn.so
+and Mask Scoring R-CNN's ``MaskIoUHead`` with ``mask_iou_stem`` / ``mask_iou_target`` / ``mask_iou_loss`` / ``mask_scores``, and CARAFE upsampling: the ``carafe`` op, ``CARAFEPack`` and the ``FPN_CARAFE`` neck, and the gradient-harmonised losses ``ghm_head_loss`` / ``GHMC`` / ``GHMR`` that
+``RetinaHead(loss_cls=..., loss_bbox=...)`` trains with).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -40,6 +41,7 @@ from .target import (anchor_target, assign_max_iou, sample_assigned, sample_assi
                      sample_rois)
 from .losses import (AnchorHeadLossFunction, BalancedBBoxHeadLossFunction, BBoxHeadLossFunction,  # noqa: F401
                      anchor_head_loss, bbox_head_loss, rpn_loss)
+from .ghm import GHMC, GHMR, GHMHeadLossFunction, ghm_head_loss  # noqa: F401
 from .detect import bbox_head_detections, multiclass_nms  # noqa: F401
 from .dense_detect import (anchor_head_detections, anchor_head_detections_plan,  # noqa: F401
                            anchor_target_all)

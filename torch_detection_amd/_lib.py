@@ -32,6 +32,9 @@ PYR_MAX_LEVELS = 8
 LOSS_MAX_CLASSES = 1024
 LOSS_MAX_ROWS = 1 << 20
 LOSS_MAX_AVG = 64
+GHM_MAX_BINS = 64
+GHM_TABLE_STRIDE = 136
+GHM_SCOPE_LEVEL, GHM_SCOPE_BATCH = 0, 1
 DET_MAX_CLASSES = 1024
 DET_MAX_ROWS = 1 << 18
 CASCADE_MAX_STAGES = 8
@@ -342,6 +345,16 @@ class SoftNmsConfig(ctypes.Structure):
 
 _SNC = ctypes.POINTER(SoftNmsConfig)
 
+
+class GhmConfig(ctypes.Structure):
+    """Mirror of ``tdn_ghm_config`` (include/tdn.h)."""
+    _fields_ = [("dtype", ctypes.c_int32), ("num_anchors", ctypes.c_int32), ("num_classes", ctypes.c_int32),
+                ("bins_cls", ctypes.c_int32), ("bins_reg", ctypes.c_int32), ("scope", ctypes.c_int32),
+                ("momentum_cls", c_float), ("momentum_reg", c_float), ("mu", c_float), ("reserved", ctypes.c_int32)]
+
+
+_GC = ctypes.POINTER(GhmConfig)
+
 # name -> (restype, argtypes); must list every symbol of include/tdn.h (tests/test_abi.py checks this)
 SIGNATURES = {
     "tdn_last_error": (ctypes.c_char_p, []),
@@ -417,6 +430,9 @@ SIGNATURES = {
     "tdn_loss_dense_fwd": (c_int, [_LL, c_int, c_int, _LC] + [c_void_p] * 4 + [_LA, c_void_p, c_void_p, c_void_p, c_i64,
                                                                               c_void_p]),
     "tdn_loss_dense_bwd": (c_int, [_LL, c_int, c_int, _LC] + [c_void_p] * 7),
+    "tdn_ghm_workspace_bytes": (c_i64, [_LL, c_int, c_int, _GC]),
+    "tdn_ghm_fwd": (c_int, [_LL, c_int, c_int, _GC] + [c_void_p] * 9 + [c_i64, c_void_p]),
+    "tdn_ghm_bwd": (c_int, [_LL, c_int, c_int, _GC] + [c_void_p] * 7),
     "tdn_loss_roi_workspace_bytes": (c_i64, [c_int]),
     "tdn_loss_roi_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4 +
                          [c_float, _LA, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),

@@ -15,7 +15,7 @@ constexpr int LT = 1024;          // threads per workgroup: 16 waves, four per S
 constexpr int LWAVES = LT / 64;
 constexpr int LMAX_BLOCKS = 256;  // one workgroup per CU at most: that many partials for the last launch
 constexpr int PART = 4;           // doubles per partial: loss_cls, loss_bbox, rows with weight > 0, unused
-constexpr int MAXSEG = 2 * TDN_LOSS_MAX_LEVELS;
+constexpr int MAXSEG = HEAD_MAXSEG;
 
 // ---- elementwise spec: the sigmoid classification terms are loss_core.h ----------------------------------------------
 template <bool GRAD>
@@ -57,20 +57,9 @@ __device__ __forceinline__ void block_partial(double a0, double a1, double a2, d
 }
 
 // ---- dense heads ----------------------------------------------------------------------------------------------------
-// One segment = one head tensor of one level, walked as the flat array it is in memory, in chunks of V elements
-// (16 bytes).  Chunk indices run through all segments; a workgroup takes 1024 consecutive chunks per grid stride.
-struct DenseSeg {
-  const void* x;
-  void* dx;
-  uint32_t n;        // elements
-  uint32_t nchunks;
-  int64_t chunk0;    // index of the segment's first chunk
-  int32_t Ch, HW;    // channels, H*W
-  int32_t nhwc;      // memory order: 0 (b, c, p), 1 (b, p, c)
-  int32_t reg;       // 0: class logits, 1: box deltas
-  int32_t off;       // index of the level's first anchor within an image
-  int32_t vec;       // x (and dx) are 16-byte aligned
-};
+// The segments and their walk are loss_core.h's.  Chunk indices run through all segments; a workgroup takes 1024
+// consecutive chunks per grid stride.
+typedef HeadSeg DenseSeg;
 struct DenseArgs {
   DenseSeg seg[MAXSEG];
   int32_t nseg;
@@ -92,29 +81,11 @@ __device__ __forceinline__ double dense_chunk(const DenseSeg& S, const DenseArgs
   constexpr int V = E::V;
   const uint32_t m0 = lc * (uint32_t)V;
   const int cnt = (int)min((uint32_t)V, S.n - m0);
-  const T* xp = (const T*)S.x + m0;
-  Vec<T, V> in, out;
-  if (S.vec && cnt == V) {
-    in = *(const Vec<T, V>*)xp;
-  } else {
-#pragma unroll
-    for (int e = 0; e < V; ++e) in.v[e] = e < cnt ? xp[e] : E::st(0.f);
-  }
+  const Vec<T, V> in = head_load<DT>(S, m0, cnt);
+  Vec<T, V> out;
   // coordinates of the chunk's first element; the following elements advance them
   const int div = S.reg ? 4 : A.C;               // channels per anchor
-  uint32_t b, c, p;
-  if (S.nhwc) {
-    const uint32_t q = m0 / (uint32_t)S.Ch;
-    c = m0 - q * (uint32_t)S.Ch;
-    b = q / (uint32_t)S.HW;
-    p = q - b * (uint32_t)S.HW;
-  } else {
-    const uint32_t q = m0 / (uint32_t)S.HW;
-    p = m0 - q * (uint32_t)S.HW;
-    b = q / (uint32_t)S.Ch;
-    c = q - b * (uint32_t)S.Ch;
-  }
-  int a = (int)c / div, k = (int)c - a * div;
+  HeadPos P = head_pos(S, m0, div);
   int last_idx = -1;
   float last_w = 0.f;
   long long last_lab = 0;
@@ -123,7 +94,8 @@ __device__ __forceinline__ double dense_chunk(const DenseSeg& S, const DenseArgs
   for (int e = 0; e < V; ++e) {
     float res = 0.f;
     if (e < cnt) {
-      const int idx = (int)b * A.N + S.off + (int)p * A.A + a;     // < 64 * 2^20
+      const int idx = (int)P.b * A.N + S.off + (int)P.p * A.A + P.a;     // < 64 * 2^20
+      const int k = P.k;
       const float x = E::ld(in.v[e]);
       if (S.reg) {
         const float w = A.bw[(size_t)idx * 4 + k];
@@ -144,34 +116,11 @@ __device__ __forceinline__ double dense_chunk(const DenseSeg& S, const DenseArgs
           else sum += (double)__fmul_rn(last_w, v);
         }
       }
-      if (S.nhwc) {
-        ++c; ++k;
-        if (k == div) { k = 0; ++a; }
-        if (c == (uint32_t)S.Ch) {
-          c = 0; a = 0; k = 0; ++p;
-          if (p == (uint32_t)S.HW) { p = 0; ++b; }
-        }
-      } else {
-        ++p;
-        if (p == (uint32_t)S.HW) {
-          p = 0; ++c; ++k;
-          if (k == div) { k = 0; ++a; }
-          if (c == (uint32_t)S.Ch) { c = 0; a = 0; k = 0; ++b; }
-        }
-      }
+      head_next(S, div, P);
     }
     if (GRAD) out.v[e] = E::st(res);
   }
-  if (GRAD) {
-    T* dp = (T*)S.dx + m0;
-    if (S.vec && cnt == V) {
-      *(Vec<T, V>*)dp = out;
-    } else {
-#pragma unroll
-      for (int e = 0; e < V; ++e)
-        if (e < cnt) dp[e] = out.v[e];
-    }
-  }
+  if (GRAD) head_store<DT>(S, m0, cnt, out);
   return sum;
 }
 
@@ -358,8 +307,6 @@ PartialsWs partials_layout(int blocks, void* base) {   // a braced list is evalu
   return {c.take<double>((int64_t)blocks * PART), c.off};
 }
 
-int elem_bytes(int dtype) { return dtype == TDN_F32 ? 4 : 2; }
-
 int check_avg(const char* who, const tdn_loss_avg* avg, bool roi, AvgArgs* out) {
   TDN_CHECK(avg != nullptr, "%s: NULL avg", who);
   TDN_CHECK(avg->mode == 0 || avg->mode == 1 || (roi && avg->mode == 2), "%s: avg mode %d", who, avg->mode);
@@ -388,32 +335,11 @@ int dense_shape(const char* who, const tdn_loss_level* levels, int L, int B, con
   TDN_CHECK(cfg->num_anchors >= 1 && cfg->num_classes >= 1 && cfg->num_classes <= TDN_LOSS_MAX_CLASSES,
             "%s: A=%d, C=%d (C in 1..%d)", who, cfg->num_anchors, cfg->num_classes, TDN_LOSS_MAX_CLASSES);
   memset(D, 0, sizeof(*D));
-  const int A = cfg->num_anchors, C = cfg->num_classes, V = 16 / elem_bytes(cfg->dtype);
-  int64_t N = 0, chunk = 0;
-  int ns = 0;
-  for (int l = 0; l < L; ++l) {
-    const tdn_loss_level& lv = levels[l];
-    TDN_CHECK(lv.H >= 1 && lv.W >= 1, "%s: level %d is %d x %d", who, l, lv.H, lv.W);
-    const int64_t HW = (int64_t)lv.H * lv.W;
-    for (int k = 0; k < 2; ++k) {
-      const int64_t Ch = k ? 4ll * A : (int64_t)A * C;
-      const int64_t n = (int64_t)B * Ch * HW;
-      TDN_CHECK(n < (1ll << 31), "%s: level %d holds %lld elements (2^31 or more)", who, l, (long long)n);
-      DenseSeg& S = D->seg[ns++];
-      S.n = (uint32_t)n;
-      S.nchunks = (uint32_t)((n + V - 1) / V);
-      S.chunk0 = chunk;
-      S.Ch = (int32_t)Ch;
-      S.HW = (int32_t)HW;
-      S.nhwc = (k ? lv.reg_nhwc : lv.cls_nhwc) ? 1 : 0;
-      S.reg = k;
-      S.off = (int32_t)N;
-      chunk += S.nchunks;
-    }
-    N += HW * A;
-    TDN_CHECK(N <= TDN_LOSS_MAX_ROWS, "%s: more than %d anchors per image", who, TDN_LOSS_MAX_ROWS);
-  }
-  D->nseg = ns;
+  const int A = cfg->num_anchors, C = cfg->num_classes;
+  int64_t chunk = 0;
+  const int64_t N = head_segments(who, levels, L, B, cfg->dtype, A, C, D->seg, &chunk);
+  if (N < 0) return -1;
+  D->nseg = 2 * L;
   D->nchunks = chunk;
   D->N = (int32_t)N;
   D->A = A;
@@ -431,16 +357,7 @@ int dense_plan(const char* who, const tdn_loss_level* levels, int L, int B, cons
   if (cfg->focal)
     TDN_CHECK(cfg->gamma >= 0.f && cfg->gamma < INFINITY && cfg->alpha >= 0.f && cfg->alpha <= 1.f,
               "%s: focal needs gamma >= 0 and alpha in [0, 1]", who);
-  for (int l = 0; l < L; ++l) {
-    const tdn_loss_level& lv = levels[l];
-    TDN_CHECK(lv.cls && lv.reg && (!grad || (lv.dcls && lv.dreg)), "%s: level %d: NULL pointer", who, l);
-    for (int k = 0; k < 2; ++k) {
-      DenseSeg& S = D->seg[2 * l + k];
-      S.x = k ? lv.reg : lv.cls;
-      S.dx = k ? lv.dreg : lv.dcls;
-      S.vec = (((uintptr_t)S.x | (grad ? (uintptr_t)S.dx : 0)) & 15) == 0;
-    }
-  }
+  if (head_pointers(who, levels, L, grad, D->seg) != 0) return -1;
   D->beta = cfg->beta;
   D->P = {cfg->focal ? 1 : 0, cfg->gamma, cfg->alpha, 1.f - cfg->alpha};
   return blocks;

@@ -40,6 +40,7 @@ from .deconv import DeconvUnit
 from .deconv import check_params as check_deconv_params
 from .functional import pick_dtype
 from .fcos import fcos_detections, fcos_loss, fcos_points, fcos_target
+from .ghm import GHMC, GHMR, ghm_head_loss
 from .layers import ConvModule, Scale
 from .linear import LinearUnit, check_params, flatten_input
 from .linear import linear as _linear
@@ -850,6 +851,23 @@ class RetinaHeadFunction(torch.autograd.Function):
         return (None, None) + tuple(dxs) + tuple(grads)
 
 
+def _ghm_pair(loss_cls, loss_bbox):
+    """``RetinaHead``'s ``loss_cls`` / ``loss_bbox``: None for both (the focal / smooth-L1 default), or a ``GHMC`` / ``GHMR``
+    pair, each a module instance or mmdetection's ``dict(type='GHMC', ...)`` -> None or the two modules."""
+    if loss_cls is None and loss_bbox is None:
+        return None
+    pair = []
+    for cfg, kind, name in ((loss_cls, GHMC, "loss_cls"), (loss_bbox, GHMR, "loss_bbox")):
+        if isinstance(cfg, dict) and cfg.get('type') == kind.__name__:
+            cfg = kind(**{k: v for k, v in cfg.items() if k != 'type'})
+        if not isinstance(cfg, kind):
+            raise NotImplementedError("RetinaHead: %s must be a %s (a module or a dict with type=%r) when either loss is "
+                                      "configured, got %r; loss_cls=None with loss_bbox=None is focal + smooth L1"
+                                      % (name, kind.__name__, kind.__name__, cfg))
+        pair.append(cfg)
+    return pair
+
+
 @HEADS.register_module
 class RetinaHead(nn.Module):
     """``RetinaHead`` of mmdetection v1: two towers of ``stacked_convs`` 3x3 ``ConvModule``s (bias, ReLU), shared by all
@@ -858,13 +876,19 @@ class RetinaHead(nn.Module):
     (``cls_convs.0.conv.weight`` ... ``retina_reg.bias``); the predictors live in ``nn.Conv2d`` containers whose own
     forward is never called.  The whole head is one autograd node.  What the HIP path does not cover —
     ``norm_cfg`` / ``conv_cfg``, channel counts that are no multiples of 64 or above 512, more than 1024 predictor
-    channels, more than 8 levels — is accepted by the constructor and raises ``NotImplementedError`` in ``forward``."""
+    channels, more than 8 levels — is accepted by the constructor and raises ``NotImplementedError`` in ``forward``.
+    ``loss_cls`` / ``loss_bbox``: both None for the focal + smooth-L1 ``loss``, or ``GHMC`` and ``GHMR`` (modules, or
+    mmdetection's ``dict(type='GHMC', bins=30, momentum=0.75)`` / ``dict(type='GHMR', mu=0.02, bins=10, momentum=0.7)``)
+    for the gradient-harmonised one; any other value raises ``NotImplementedError`` here."""
 
     def __init__(self, num_classes, in_channels, feat_channels=256, stacked_convs=4, octave_base_scale=4,
                  scales_per_octave=3, anchor_ratios=(0.5, 1.0, 2.0), anchor_strides=(8, 16, 32, 64, 128),
                  anchor_base_sizes=None, target_means=(.0, .0, .0, .0), target_stds=(1.0, 1.0, 1.0, 1.0), conv_cfg=None,
-                 norm_cfg=None):
+                 norm_cfg=None, loss_cls=None, loss_bbox=None):
         super().__init__()
+        ghm = _ghm_pair(loss_cls, loss_bbox)
+        if ghm is not None:               # no parameters, no state-dict keys: the running averages are non-persistent
+            self.loss_cls, self.loss_bbox = ghm
         if num_classes < 2 or min(in_channels, feat_channels, scales_per_octave) < 1 or stacked_convs < 0 or \
                 not len(anchor_ratios) or not len(anchor_strides):
             raise ValueError("RetinaHead: num_classes >= 2 (background included), positive sizes and non-empty anchor "
@@ -988,13 +1012,23 @@ class RetinaHead(nn.Module):
              **target_cfg):
         """``anchor_target_all`` (pos_iou_thr 0.5, neg_iou_thr 0.4, min_pos_iou 0, the head's means / stds), then the focal
         ``anchor_head_loss`` (gamma 2, alpha 0.25, smooth-L1 ``beta``) averaged over the positives: -> losses (2,) =
-        [loss_cls, loss_bbox].  ``anchors`` / ``valid_flags``: what ``get_anchors`` returned or their concatenation."""
+        [loss_cls, loss_bbox].  ``anchors`` / ``valid_flags``: what ``get_anchors`` returned or their concatenation.  A head
+        built with ``loss_cls=GHMC`` / ``loss_bbox=GHMR`` calls ``ghm_head_loss`` (scope 'level') on the same targets
+        instead and multiplies the two terms by the modules' ``loss_weight``; ``beta`` is then not used."""
         cat = lambda t: torch.cat(list(t)) if isinstance(t, (list, tuple)) else t
         cfg = dict(pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, target_means=self.target_means,
                    target_stds=self.target_stds)
         cfg.update(target_cfg)
         labels, label_weights, bbox_targets, bbox_weights, num_pos, _, _ = anchor_target_all(
             cat(anchors), cat(valid_flags), gt_bboxes, gt_labels, gt_counts, img_shapes, **cfg)
+        lc, lb = getattr(self, 'loss_cls', None), getattr(self, 'loss_bbox', None)
+        if lc is not None:
+            losses = ghm_head_loss(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights, lc.acc_sum,
+                                   lb.acc_sum, self.cls_out_channels, bins_cls=lc.bins, bins_reg=lb.bins,
+                                   momentum_cls=lc.momentum, momentum_reg=lb.momentum, mu=lb.mu)
+            if lc.loss_weight == 1.0 and lb.loss_weight == 1.0:
+                return losses
+            return torch.stack((losses[0] * lc.loss_weight, losses[1] * lb.loss_weight))   # no host tensor: capturable
         return anchor_head_loss(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights,
                                 avg_factor=num_pos, num_classes=self.cls_out_channels, beta=beta, gamma=2.0, alpha=0.25)
 

@@ -53,28 +53,19 @@ def _avg(avg_factor, allow_none):
     return av, ()
 
 
-def _dense_setup(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights, num_classes, beta, gamma,
-                 alpha):
-    """Checks of a dense-head call -> (levels array, L, B, config, tensors to check for their device)."""
+def _head_levels(who, cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights, num_classes):
+    """The head outputs of 1..8 levels and ``anchor_target``'s tensors for them, as ``who`` (this module's dense loss,
+    ``ghm_ops.py``) takes them -> (levels array, L, B, A, C, dtype, tensors to check for their device)."""
     cls_scores, bbox_preds = list(cls_scores), list(bbox_preds)
     L = len(cls_scores)
     if not 1 <= L <= _lib.LOSS_MAX_LEVELS or len(bbox_preds) != L:
-        raise ValueError("anchor_head_loss takes 1..%d levels with one cls_score and one bbox_pred each"
-                         % _lib.LOSS_MAX_LEVELS)
-    cfg = _lib.LossConfig()
-    cfg.num_classes = C = integer(num_classes, "num_classes", 1, _lib.LOSS_MAX_CLASSES)
-    cfg.beta = number(beta, "beta", positive=True)
-    if gamma is not None:
-        cfg.focal = 1
-        cfg.gamma, cfg.alpha = number(gamma, "gamma"), number(alpha, "alpha")
-        if cfg.gamma < 0 or not 0 <= cfg.alpha <= 1:
-            raise ValueError("focal loss needs gamma >= 0 and alpha in [0, 1]")
+        raise ValueError("%s takes 1..%d levels with one cls_score and one bbox_pred each" % (who, _lib.LOSS_MAX_LEVELS))
+    C = integer(num_classes, "num_classes", 1, _lib.LOSS_MAX_CLASSES)
     B, ch, _, _ = tensor(cls_scores[0], "cls_scores[0]", tuple(CODES), ("B", "A*C", "H", "W"), contiguous=False)
     batch(B)
     if ch % C or ch == 0:
         raise ValueError("cls_scores have %d channels, no multiple of num_classes = %d" % (ch, C))
     A, dtype = ch // C, cls_scores[0].dtype
-    cfg.dtype, cfg.num_anchors = CODES[dtype], A
     levels = (_lib.LossLevel * L)()
     N = 0
     for l, (c, r) in enumerate(zip(cls_scores, bbox_preds)):
@@ -103,6 +94,22 @@ def _dense_setup(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bb
             [("bbox_preds[%d]" % l, t) for l, t in enumerate(bbox_preds)] + \
             [("labels", labels), ("label_weights", label_weights), ("bbox_targets", bbox_targets),
              ("bbox_weights", bbox_weights)]
+    return levels, L, B, A, C, dtype, named
+
+
+def _dense_setup(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights, num_classes, beta, gamma,
+                 alpha):
+    """Checks of a dense-head call -> (levels array, L, B, config, tensors to check for their device)."""
+    levels, L, B, A, C, dtype, named = _head_levels("anchor_head_loss", cls_scores, bbox_preds, labels, label_weights,
+                                                    bbox_targets, bbox_weights, num_classes)
+    cfg = _lib.LossConfig()
+    cfg.dtype, cfg.num_anchors, cfg.num_classes = CODES[dtype], A, C
+    cfg.beta = number(beta, "beta", positive=True)
+    if gamma is not None:
+        cfg.focal = 1
+        cfg.gamma, cfg.alpha = number(gamma, "gamma"), number(alpha, "alpha")
+        if cfg.gamma < 0 or not 0 <= cfg.alpha <= 1:
+            raise ValueError("focal loss needs gamma >= 0 and alpha in [0, 1]")
     return levels, L, B, cfg, named
 
 
