@@ -1030,6 +1030,98 @@ int tdn_ghm_bwd(const tdn_loss_level* levels, int num_levels, int B, const tdn_g
                 const float* label_weights, const float* bbox_targets, const float* bbox_weights, const float* g,
                 const float* table, void* stream);
 
+/* ---- Guided Anchoring: location targets, shape targets, the location + shape loss, the guided anchors (DESIGN.md §4w:
+ *      the project's own spec in the lineage of mmdetection v1's GuidedAnchorHead; tests/ga_ref.py restates it) ----
+ * A pyramid is 1..TDN_LOSS_MAX_LEVELS levels; locations are level-major, (y*W + x) within a level, N = sum H*W <=
+ * TDN_TARGET_MAX_BOXES.  Head outputs: loc (B, 1, H, W) logits, shape (B, 2, H, W) = (dw, dh), TDN_F32 / TDN_BF16 /
+ * TDN_F16, NCHW-contiguous or channels_last, read in place.  Boxes are fp32 '+1' xyxy; ground truths gt fp32 [B][G][4]
+ * with gt_counts int32 [B] (clamped to 0..G, rows past it never read), G <= TDN_TARGET_MAX_GT.  Nothing synchronises with
+ * the host; the only atomics are integer maxima / minima, every output is a pure function of the inputs. */
+#define TDN_GA_MAX_APPROX 16
+typedef struct tdn_ga_level {
+  const void* loc;             /* (B, 1, H, W) */
+  const void* shape;           /* (B, 2, H, W) */
+  void* dloc;                  /* backward only: gradients, laid out as loc / shape */
+  void* dshape;
+  int32_t H, W;
+  int32_t stride;              /* tdn_ga_loc_target only: 1..32768, H*stride and W*stride below 2^24 */
+  int32_t shape_nhwc;          /* 0: NCHW-contiguous memory, 1: channels_last */
+} tdn_ga_level;
+/* Location targets, one launch.  The level of a ground truth: #{k in 1..L-1 : area >= area_thr[k-1]}, area the fp32
+ * product of its '+1' sides.  A region of ratio pair (r, c) on level l: g = gt / stride_l, x1 = rint(c g.x1 + r g.x2),
+ * x2 = rint(r g.x1 + c g.x2), the same for y, fp32 with one rounding per operation, rint to even, clamped to the map.
+ * Per location, ground truths in ascending j, from t = 0, w = -1, ig = 0: j on the location's level: inside the ignore
+ * region w = 0, then inside the centre region t = 1, w = 1; j one level above or below: inside its ignore region at this
+ * level's stride ig = 1.  At the end w < 0 becomes ig ? 0 : 0.1.  loc_targets int64 [B][N], loc_weights fp32 [B][N]. */
+typedef struct tdn_ga_loc_config {
+  float area_thr[TDN_LOSS_MAX_LEVELS]; /* [0, L-1): finite, positive, ascending */
+  float center_r, center_c;    /* fp32((1 - center_ratio) / 2), fp32(1 - that) */
+  float ignore_r, ignore_c;    /* the same of ignore_ratio */
+} tdn_ga_loc_config;
+int tdn_ga_loc_target(const tdn_ga_level* levels, int nlevels, int B, const float* gt, const int32_t* gt_counts, int G,
+                      const tdn_ga_loc_config* cfg, int64_t* loc_targets, float* loc_weights, void* stream);
+/* Shape targets: tdn_anchor_target's assignment and sampling (cfg: its thresholds, gt_max_assign_all, num,
+ * num_pos_expected, neg_pos_ub, allowed_border, seed) with the overlap of location i and ground truth j = max over a of
+ * IoU(approxs[i][a], gt[j]), approxs fp32 [N][A][4], A <= TDN_GA_MAX_APPROX.  valid uint8 [N*A] (valid_stride 0) or
+ * [B][N*A] (valid_stride N*A) or NULL; a location takes part iff one of its approxs is flagged valid and, with
+ * allowed_border >= 0, inside the image by tdn_anchor_target's rule; the maximum runs over all A.  sampling == 0: every
+ * positive and every negative.  On sampled positives bbox_anchors fp32 [B][N][4] = squares[i] (squares fp32 [N][4]),
+ * bbox_gts = the assigned ground truth, bbox_weights = 1; zeros elsewhere.  num_pos / num_neg int32 [B], assigned int32
+ * [B][N], max_overlaps fp32 [B][N].  Launches: clear, two assign passes, the first-index pass (gt_max_assign_all = 0),
+ * select, fill.  workspace: tdn_ga_shape_target_workspace_bytes() bytes, 256-aligned. */
+int64_t tdn_ga_shape_target_workspace_bytes(int B, int N, int G);
+int tdn_ga_shape_target(const float* approxs, int A, const float* squares, const uint8_t* valid, int64_t valid_stride,
+                        const float* gt, const int32_t* gt_counts, const int32_t* img_shapes, int B, int N, int G,
+                        const tdn_target_config* cfg, int sampling, const int32_t* keys, float* bbox_anchors,
+                        float* bbox_gts, float* bbox_weights, int32_t* num_pos, int32_t* num_neg, int32_t* assigned,
+                        float* max_overlaps, void* workspace, int64_t workspace_bytes, void* stream);
+/* Guided anchors, one launch: anchors fp32 [B][N][4] = tdn_delta2bbox's decode of squares[i] with deltas (0, 0, dw, dh),
+ * wh_ratio_clip 1e-6, no clipping to an image; loc_mask uint8 [B][N] = 1, or with use_loc (loc logit >= loc_thr_logit). */
+int tdn_guided_anchors(const tdn_ga_level* levels, int nlevels, int B, int dtype, const float* squares,
+                       const float* means4, const float* stds4, int use_loc, float loc_thr_logit, float* anchors,
+                       uint8_t* loc_mask, void* stream);
+/* The loss.  losses fp32 [2] = (loss_loc, loss_shape); norm fp32 [2] = their divisors, which the backward takes back.
+ *   loss_loc    sum over (b, n) with loc_weights != 0 of loc_weights * focal(loc logit, loc_targets == 1) (the focal
+ *               element of tdn_loss_dense_fwd), divided by loc_avg_factor; a location of weight 0 is never evaluated
+ *   loss_shape  over the rows with bbox_weights[b][n][0] > 0: the box p = tdn_delta2bbox's decode of bbox_anchors with
+ *               (0, 0, dw, dh), means, stds and wh_ratio_clip 1e-6; per axis, with centres (x1 + x2) / 2 and sizes
+ *               x2 - x1 + 1 of p and of bbox_gts, D = 2 |ct - cp|:  l_c = 1 - max((st - D) / (st + D + eps), 0),
+ *               l_s = 1 - min(st / (sp + eps), sp / (st + eps)); each l shaped as l < beta ? 0.5 l l / beta :
+ *               l - 0.5 beta and weighted by its bbox_weights element (x, y, w, h); divided by avg (tdn_loss_avg mode 0
+ *               or 1).  Other rows never have their shape outputs, anchors or ground truths read.
+ * Gradients reach only dw, dh, through the size terms; min's tie takes half of each side and the clamp passes the
+ * gradient on [-R, R] inclusive, as torch does.  Forward: two launches, backward: one; sums are fp64 in an order fixed by
+ * the shapes.  workspace: tdn_ga_loss_workspace_bytes() bytes, 256-aligned. */
+typedef struct tdn_ga_loss_config {
+  int32_t dtype;               /* TDN_BF16 / TDN_F16 / TDN_F32, of every head output and gradient */
+  float gamma, alpha;          /* focal: gamma >= 0, alpha in [0, 1] */
+  float beta;                  /* the knee, > 0 */
+  float eps;                   /* in (0, 1) */
+  float loc_avg_factor;        /* finite and > 0 */
+  float means[4], stds[4];     /* the anchoring normalisation */
+} tdn_ga_loss_config;
+int64_t tdn_ga_loss_workspace_bytes(const tdn_ga_level* levels, int nlevels, int B, const tdn_ga_loss_config* cfg);
+int tdn_ga_loss_fwd(const tdn_ga_level* levels, int nlevels, int B, const tdn_ga_loss_config* cfg,
+                    const int64_t* loc_targets, const float* loc_weights, const float* bbox_anchors,
+                    const float* bbox_gts, const float* bbox_weights, const tdn_loss_avg* avg, float* losses, float* norm,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int tdn_ga_loss_bwd(const tdn_ga_level* levels, int nlevels, int B, const tdn_ga_loss_config* cfg,
+                    const int64_t* loc_targets, const float* loc_weights, const float* bbox_anchors,
+                    const float* bbox_gts, const float* bbox_weights, const float* g, const float* norm, void* stream);
+/* Guided RPN proposals: tdn_rpn_proposals (levels, cfg, outputs, padding rules, limits, launch count: its four, the
+ * first one replaced) with one anchor per location (every level's A must be 1; the levels' own anchors pointers are
+ * ignored), anchors fp32 [B][N][4] that differ per image and loc_mask uint8 [B][N], N = sum H*W over the levels in
+ * order, both as tdn_guided_anchors writes them.  A location whose mask byte is 0 is absent: level l of image b sends
+ * the min(nms_pre, locations in) highest logits of its locations that are in to NMS (all of them with nms_pre = 0).
+ * With anchors repeated for every image and a mask of ones the outputs are tdn_rpn_proposals' bit for bit.  NaN logits
+ * are unsupported.  workspace: tdn_ga_rpn_proposals_workspace_bytes() bytes (tdn_rpn_proposals' own size),
+ * 256-aligned. */
+int64_t tdn_ga_rpn_proposals_workspace_bytes(const tdn_rpn_level* levels, int nlevels, int B,
+                                             const tdn_rpn_config* cfg);
+int tdn_ga_rpn_proposals(const tdn_rpn_level* levels, int nlevels, int B, const float* anchors, const uint8_t* loc_mask,
+                         const int32_t* img_shapes, const tdn_rpn_config* cfg, float* proposals, int64_t* anchor_idx,
+                         int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- the mask branch of Mask R-CNN: polygon mask targets, mask loss, mask paste (the project's own
  *      spec in the mmdetection-v1 lineage of mask_target / FCNMaskHead.loss / get_seg_masks) ----
  * Polygons: poly_xy fp32 [P][2] vertices in the network-input frame; poly_offsets int32 [Q + 1]: polygon q owns vertices

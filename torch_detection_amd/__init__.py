@@ -18,7 +18,8 @@ conv ``conv_transpose2x2`` / ``FCNMaskHead`` between ``roi_align`` and the mask 
 ``refine_bboxes`` / ``cascade_detections`` / ``CascadeRoIHead``, and Libra R-CNN's ``BFP`` neck,
 ``sample_assigned_iou_balanced`` / ``sample_rois(neg_sampler='iou_balanced')`` and ``bbox_head_loss(reg_loss='balanced_l1')``,
 and Mask Scoring R-CNN's ``MaskIoUHead`` with ``mask_iou_stem`` / ``mask_iou_target`` / ``mask_iou_loss`` / ``mask_scores``, and CARAFE upsampling: the ``carafe`` op, ``CARAFEPack`` and the ``FPN_CARAFE`` neck, and the gradient-harmonised losses ``ghm_head_loss`` / ``GHMC`` / ``GHMR`` that
-``RetinaHead(loss_cls=..., loss_bbox=...)`` trains with).  Everything computes through libtdn.so
+``RetinaHead(loss_cls=..., loss_bbox=...)`` trains with, and the Guided Anchoring operations ``ga_loc_target`` /
+``ga_shape_target`` / ``ga_loss`` / ``guided_anchors`` / ``ga_rpn_proposals``).  Everything computes through libtdn.so
 (hand-written gfx950 HIP kernels, C ABI in include/tdn.h); there is no CPU or eager fallback.
 """
 __version__ = "0.1.0"
@@ -47,6 +48,8 @@ from .dense_detect import (anchor_head_detections, anchor_head_detections_plan, 
                            anchor_target_all)
 from .fcos import (FcosLossFunction, fcos_detections, fcos_detections_plan, fcos_loss,  # noqa: F401
                    fcos_points, fcos_target)
+from .guided import (GALossFunction, ga_loc_target, ga_loss, ga_rpn_proposals, ga_shape_target,  # noqa: F401
+                     guided_anchors)
 from .mask import (MaskHeadLossFunction, mask_head_loss, mask_head_masks, mask_target,  # noqa: F401
                    pack_polygons, rois_from_detections)
 from .mask_iou import (MaskIoULossFunction, MaskIoUStemFunction, mask_iou_loss, mask_iou_stem,  # noqa: F401

@@ -1,5 +1,5 @@
 """Argument checks shared by the host wrappers of the detection heads (``ops.py`` from the box ops on,
-``target_ops.py``, ``loss_ops.py``, ``detect_ops.py``, ``dense_detect_ops.py``, ``fcos_ops.py``, ``mask_ops.py``, ``cascade_ops.py``, ``mask_iou_ops.py``, ``carafe_ops.py``, ``ghm_ops.py``).  Checks only: nothing here
+``target_ops.py``, ``loss_ops.py``, ``detect_ops.py``, ``dense_detect_ops.py``, ``fcos_ops.py``, ``mask_ops.py``, ``cascade_ops.py``, ``mask_iou_ops.py``, ``carafe_ops.py``, ``ghm_ops.py``, ``guided_ops.py``).  Checks only: nothing here
 allocates a tensor, calls the library or reads a tensor's contents, so a wrapper built from these stays capturable in a
 graph.  Every refusal is a ValueError that names the argument and the requirement.
 """

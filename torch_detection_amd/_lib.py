@@ -355,6 +355,32 @@ class GhmConfig(ctypes.Structure):
 
 _GC = ctypes.POINTER(GhmConfig)
 
+GA_MAX_APPROX = 16
+
+
+class GaLevel(ctypes.Structure):
+    """Mirror of ``tdn_ga_level`` (include/tdn.h): one pyramid level of a Guided Anchoring head."""
+    _fields_ = [("loc", c_void_p), ("shape", c_void_p), ("dloc", c_void_p), ("dshape", c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("shape_nhwc", ctypes.c_int32)]
+
+
+class GaLocConfig(ctypes.Structure):
+    """Mirror of ``tdn_ga_loc_config`` (include/tdn.h)."""
+    _fields_ = [("area_thr", c_float * LOSS_MAX_LEVELS), ("center_r", c_float), ("center_c", c_float),
+                ("ignore_r", c_float), ("ignore_c", c_float)]
+
+
+class GaLossConfig(ctypes.Structure):
+    """Mirror of ``tdn_ga_loss_config`` (include/tdn.h)."""
+    _fields_ = [("dtype", ctypes.c_int32), ("gamma", c_float), ("alpha", c_float), ("beta", c_float),
+                ("eps", c_float), ("loc_avg_factor", c_float), ("means", c_float * 4), ("stds", c_float * 4)]
+
+
+_GaL = ctypes.POINTER(GaLevel)
+_GaLC = ctypes.POINTER(GaLocConfig)
+_GaSC = ctypes.POINTER(GaLossConfig)
+
 # name -> (restype, argtypes); must list every symbol of include/tdn.h (tests/test_abi.py checks this)
 SIGNATURES = {
     "tdn_last_error": (ctypes.c_char_p, []),
@@ -489,6 +515,19 @@ SIGNATURES = {
     "tdn_fcos_detections_soft_workspace_bytes": (c_i64, [_FL, c_int, c_int, _FDC]),
     "tdn_fcos_detections_soft": (c_int, [_FL, c_int, c_int, c_void_p, c_void_p, c_void_p, _FDC, _SNC] +
                                  [c_void_p] * 10 + [c_i64, c_void_p]),
+    "tdn_ga_loc_target": (c_int, [_GaL, c_int, c_int, c_void_p, c_void_p, c_int, _GaLC, c_void_p, c_void_p, c_void_p]),
+    "tdn_ga_shape_target_workspace_bytes": (c_i64, [c_int] * 3),
+    "tdn_ga_shape_target": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_int, c_int, _TC, c_int] + [c_void_p] * 9 + [c_i64, c_void_p]),
+    "tdn_guided_anchors": (c_int, [_GaL, c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_float),
+                                   ctypes.POINTER(c_float), c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "tdn_ga_loss_workspace_bytes": (c_i64, [_GaL, c_int, c_int, _GaSC]),
+    "tdn_ga_loss_fwd": (c_int, [_GaL, c_int, c_int, _GaSC] + [c_void_p] * 5 + [_LA, c_void_p, c_void_p, c_void_p, c_i64,
+                                                                              c_void_p]),
+    "tdn_ga_loss_bwd": (c_int, [_GaL, c_int, c_int, _GaSC] + [c_void_p] * 8),
+    "tdn_ga_rpn_proposals_workspace_bytes": (c_i64, [_RL, c_int, c_int, _RC]),
+    "tdn_ga_rpn_proposals": (c_int, [_RL, c_int, c_int, c_void_p, c_void_p, c_void_p, _RC] + [c_void_p] * 4 +
+                             [c_i64, c_void_p]),
     "tdn_mask_target": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p]),
     "tdn_mask_loss_workspace_bytes": (c_i64, [c_int]),

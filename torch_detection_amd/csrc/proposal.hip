@@ -383,6 +383,40 @@ extern "C" int tdn_rpn_proposals(const tdn_rpn_level* levels, int nlevels, int B
   return 0;
 }
 
+// ---- hooks for guided.hip (proposal_host.h): the workspace and launches 2-4 on their own --------------------------
+#include "proposal_host.h"
+
+int tdn_rpn_ws_layout(const tdn_rpn_level* levels, int nlevels, int B, const tdn_rpn_config* cfg, void* base,
+                      tdn_rpn_ws* out) {
+  RpnPlan p;
+  if (rpn_plan(levels, nlevels, B, cfg, &p) != 0) return -1;
+  const RpnWs w = rpn_layout(p, base);
+  *out = {w.seg_box, w.seg_key, w.seg_aidx, w.kept, w.seg_start, w.seg_count, w.num_kept, w.mask, w.bytes};
+  return 0;
+}
+
+int tdn_rpn_nms_merge(const tdn_rpn_level* levels, int nlevels, int B, const tdn_rpn_config* cfg, const tdn_rpn_ws* w,
+                      float* proposals, int64_t* anchor_idx, int32_t* counts, void* stream) {
+  RpnPlan p;
+  if (rpn_plan(levels, nlevels, B, cfg, &p) != 0) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const int pitch = p.P.pitch;
+  TDN_LAUNCH(nms_mask_seg_kernel, dim3(pitch, pitch, p.S), dim3(64), 0, st, (const float*)w->seg_box,
+             (const int*)w->seg_start, (const int*)w->seg_count, cfg->nms_thr, pitch, w->mask);
+  TDN_LAUNCH_CHECK();
+  if (tdn_allow_lds<nms_scan_seg_kernel>(160 * 1024, "nms_scan_seg") < 0) return -1;
+  TDN_LAUNCH(nms_scan_seg_kernel, dim3(p.S), dim3(BLK), nms_scan_block_lds(pitch), st,
+             (const unsigned long long*)w->mask, (const int*)nullptr, (const int*)w->seg_start, (const int*)w->seg_count,
+             pitch, (uint8_t*)nullptr, w->kept, w->num_kept);
+  TDN_LAUNCH_CHECK();
+  if (tdn_allow_lds<rpn_merge_kernel>(160 * 1024, "rpn_merge") < 0) return -1;
+  TDN_LAUNCH(rpn_merge_kernel, dim3(p.B), dim3(BLK), MERGE_LDS, st, p.P, (const f32x4_t*)w->seg_box,
+             (const uint32_t*)w->seg_key, (const int*)w->seg_aidx, (const int*)w->seg_start, (const int64_t*)w->kept,
+             (const int*)w->num_kept, proposals, anchor_idx, counts);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---- batched NMS ------------------------------------------------------------------------------------------------
 // one workgroup per segment: (score key, ~row) sorted descending -> order (input index) and the boxes in that order
 __global__ __launch_bounds__(1024) void nms_seg_sort_kernel(const float* __restrict__ boxes,

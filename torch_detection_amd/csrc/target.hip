@@ -896,3 +896,20 @@ int tdn_target_anchor_assign(const char* who, const float* anchors, int64_t box_
   const BoxSrc S = anchor_src(anchors, box_stride, valid, valid_stride, gt, G, img_shapes, cfg->allowed_border);
   return run_assign(S, gt_counts, B, N, G, cfg, assigned, nullptr, w, (hipStream_t)stream);
 }
+
+// ---- hooks for guided.hip (target_host.h): launches 0 and 2b of the assignment on their own -------------------------
+int tdn_target_clear(uint32_t* colmax, int* first, int64_t words, void* stream) {
+  TDN_CHECK(words >= 1 && words <= 64ll * TDN_TARGET_MAX_GT, "tdn_target_clear: %lld words (1..B*G <= %d)",
+            (long long)words, 64 * TDN_TARGET_MAX_GT);
+  TDN_LAUNCH(target_clear_kernel, dim3((int)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, colmax, first,
+             (int)words);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
+
+int tdn_target_assign_first(const int* first, const int32_t* gt_counts, int B, int N, int G, int32_t* assigned,
+                            void* stream) {
+  TDN_LAUNCH(assign_first_kernel, dim3(B), dim3(MAXG), 0, (hipStream_t)stream, first, gt_counts, N, G, assigned);
+  TDN_LAUNCH_CHECK();
+  return 0;
+}
